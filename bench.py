@@ -1,6 +1,6 @@
 """bench.py -- headline benchmark of the ray-marching hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--mode f32|f16x3]
+    python bench.py --gpus N --steps K --warmup W [--mode f32|f16x3] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot path over one batch of synthetic input: one
 512x512 frame (262 144 rays that all hit the canonical bbox, 128 samples/ray --
@@ -10,10 +10,18 @@ outputs rgb/alpha/depth).  Inputs and weights are resident in HBM before the
 timed region.  With N > 1 every rank renders its own frames (frame-sharded,
 no data-path collective): weak scaling.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line (headline
+`value`, `ms_per_step` and the roofline below, all from the timed steps).
+--dump-outputs DIR writes what the last timed step returned (rank 0) as float32
+DIR/<key>.npy: per-ray outputs whole, per-sample outputs at a fixed seeded
+subset of DUMP_RAYS rays (rows in ascending ray order); under 64 MB in all.
+
 Extra objects on that line:
   roofline     -- dominant kernel (canonical MLP): algorithmic FLOP per launch /
                   average launch duration measured here with HIP events on the
                   launch stream, against the MFMA peak of the arithmetic used.
+With --full, after the timed region: lean_outputs, other_mode, culled,
+terminated, frame_loop, train and
   cpu_baseline -- the CPU oracle (port of the reference path, parity-pinned by
                   tests/test_oracle_golden.py) timed on this host on a bounded
                   sample of the same frame: one warm-up, median of 3, at 8 threads
@@ -44,6 +52,9 @@ CNL_MAC_PER_SAMPLE = 492032
 NR_MAC_PER_SAMPLE = 100352           # row a11
 PMC_FILE = 'r03_pmc_canonical.json'
 PEAK_TFLOPS = {'f32': 157.3, 'f16x3': 2500.0 / 3.0}   # MI355X_MICROARCH.md; f16x3 issues 3 f16 MFMAs per fp32-equivalent MAC
+DUMP_RAYS = 2048                     # --dump-outputs: rays kept of every per-sample output
+DUMP_WHOLE_BYTES = 4 << 20           # outputs up to this size are written whole
+DUMP_MAX_BYTES = 64 << 20
 
 
 def launch_ranks(n):
@@ -65,6 +76,24 @@ def launch_ranks(n):
     return max(abs(c) for c in codes)
 
 
+def dump_outputs(out, d):
+    """The dict one timed step returned -> d/<key>.npy (float32).  Outputs larger than DUMP_WHOLE_BYTES (the per-sample
+    ones) keep the rows of a fixed seeded subset of the rays, the same rows for every key."""
+    os.makedirs(d, exist_ok=True)
+    idx, total = None, 0
+    for k in sorted(out):
+        v = out[k].detach()
+        if v.numel() * 4 > DUMP_WHOLE_BYTES:
+            if idx is None:
+                rows = np.sort(np.random.RandomState(0).choice(v.shape[0], DUMP_RAYS, replace=False))
+                idx = torch.from_numpy(rows).to(v.device)
+            v = v.index_select(0, idx)
+        a = v.float().cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_MAX_BYTES, 'outputs to dump exceed %d bytes' % DUMP_MAX_BYTES
+        np.save(os.path.join(d, k + '.npy'), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -78,6 +107,11 @@ def main():
     ap.add_argument('--main-only', action='store_true',
                     help='only the headline loop (no other-mode / culled / training / CPU legs): the profiling form, '
                          'so that a rocprofv3 --stats average covers exactly the launches behind `roofline`')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline, also run the other legs (lean outputs, other MLP mode, culling, early '
+                         'termination, frame loop, training, eager PyTorch-ROCm and CPU baselines)')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write the outputs of the last timed step as DIR/<key>.npy (float32, rank 0)')
     args = ap.parse_args()
 
     if 'HNRF_BENCH_DEVICE' not in os.environ and torch.cuda.device_count() < args.gpus:
@@ -160,6 +194,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(out['rgb']).all()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     # roofline of the dominant kernel from the HIP events recorded around every launch
     ev = net.mlp_event_log
@@ -214,7 +250,7 @@ def main():
                                     / elapsed / 1e12, 2),
     }
 
-    extras = not args.main_only
+    extras = args.full and not args.main_only
     if extras and not args.lean:
         # the lean path (what run.py's image writers and the trainer actually read: rgb, alpha, depth)
         cfg.amd.diagnostics = False

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 cd /tmp && export TMPDIR=/tmp
 step() { echo "== $1 ($(date +%T))"; }
-step "default bench";      (cd $R && python3 bench.py > $O/r03_bench_default.json 2> $O/r03_bench_default.err) || exit 1
+step "default bench";      (cd $R && python3 bench.py --full > $O/r03_bench_default.json 2> $O/r03_bench_default.err) || exit 1
 step "kernel stats f16x3"; rocprofv3 --kernel-trace --stats --output-format csv -d $O/r03_main -- python3 $R/bench.py --steps 5 --warmup 1 --main-only > $O/r03_bench_f16x3.json 2> /dev/null || exit 1
 step "kernel stats f32";   rocprofv3 --kernel-trace --stats --output-format csv -d $O/r03_main32 -- python3 $R/bench.py --steps 3 --warmup 1 --main-only --mode f32 > $O/r03_bench_f32.json 2> /dev/null || exit 1
 step "pmc fetch";          rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/r03_pmc_fetch -- python3 $R/bench.py --steps 2 --warmup 1 --main-only > /dev/null 2>&1 || exit 1
