@@ -64,6 +64,12 @@ SIGNATURES = {
     'hnrf_render_term_workspace_bytes': (_sz, [_i64, _int]),
     'hnrf_render_rays_term_fwd': (_int, [_vp] * 14 + [_int, ctypes.c_float, ctypes.c_float, _i64, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
     'hnrf_render_rays_fwd': (_int, [_vp] * 14 + [_int, ctypes.c_float, _i64, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'hnrf_density_grid_workspace_bytes': (_sz, [_int]),
+    'hnrf_density_grid': (_int, [_vp, _int, _vp, _int, _int, _vp, _vp, _vp, _int, _vp, _sz, _vp, _vp, _vp, _vp]),
+    'hnrf_mesh_workspace_bytes': (_sz, [_int]),
+    'hnrf_mesh_count': (_int, [_vp, _int, ctypes.c_float, _vp, _sz, _vp, _vp]),
+    'hnrf_mesh_emit': (_int, [_vp, _int, ctypes.c_float, _vp, _vp, _vp, _sz, _i64, _i64, _vp, _vp, _vp]),
+    'hnrf_forward_skin': (_int, [_vp, _i64, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

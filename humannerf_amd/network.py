@@ -848,3 +848,99 @@ class Network(nn.Module):
         out = ops.composite(raw, mask, z, rays_d, xyz, bg, diagnostics=True, out=dst)
         out.update(xyz_on_rays=xyz, backward_motion_weights=bmw, offsets=offsets)
         return out
+
+    # mesh extraction (no counterpart in the reference) ------------------------------------------------------------
+    # Density at which the canonical surface is cut.  NOT checked on a trained checkpoint (none can be obtained
+    # here): a density of 20 per unit length absorbs about a quarter of the light over 1.6 cm, the sample spacing of
+    # 128 samples along a 2 m ray.  Pick the level per checkpoint.
+    MESH_LEVEL = 20.0
+
+    def _mesh_device(self):
+        return next(self.parameters()).device
+
+    def _mesh_bbox(self, cnl_bbox_min_xyz, cnl_bbox_max_xyz, cnl_bbox_scale_xyz=None):
+        dev = self._mesh_device()
+        f32 = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(3).contiguous()
+        bmin, bmax = f32(cnl_bbox_min_xyz), f32(cnl_bbox_max_xyz)
+        # the datasets' cnl_bbox_scale_xyz = 2 / (max - min) in float32 (dataset.Subject._skeleton_entries)
+        scale = f32(cnl_bbox_scale_xyz) if cnl_bbox_scale_xyz is not None else (2.0 / (bmax - bmin)).contiguous()
+        return bmin, bmax, scale
+
+    def _f16_rerun(self, packed, mode):
+        """After a canonical-MLP pass outside forward: act on its status word exactly as forward does
+        (cfg.amd.on_f16_range: raise, warn and switch to 'f32', or ignore).  True when the pass must run again in the
+        mode just forced."""
+        if mode != 'f16x3':
+            return False
+        self._watch_f16_range(packed, None, mode)
+        return self.check_f16_range(wait=True) and self._mlp_mode() != mode
+
+    def canonical_density_grid(self, cnl_bbox_min_xyz, cnl_bbox_max_xyz, motion_weights_priors, resolution=256,
+                               cnl_bbox_scale_xyz=None, return_parts=False):
+        """The canonical density relu(sigma) * fg on a resolution^3 lattice over [cnl_bbox_min_xyz, cnl_bbox_max_xyz]
+        (hnrf_density_grid): (N, N, N) indexed [z][y][x].  fg is the foreground gate rendering applies to alpha -- the
+        summed bone weights of the weight volume -- under the identity motion.  ``return_parts``: (density, sigma,
+        fg)."""
+        with torch.no_grad():
+            dev = self._mesh_device()
+            bmin, bmax, scale = self._mesh_bbox(cnl_bbox_min_xyz, cnl_bbox_max_xyz, cnl_bbox_scale_xyz)
+            vol = self._weight_volume(torch.as_tensor(motion_weights_priors).to(device=dev, dtype=torch.float32))
+            while True:
+                mode = self._mlp_mode()
+                packed = self._canonical_packed()
+                out = ops.density_grid(packed, vol, bmin, bmax, scale, int(resolution), mode, want_parts=return_parts)
+                if not self._f16_rerun(packed, mode):
+                    return out
+
+    def vertex_colors(self, verts):
+        """sigmoid(raw[:3]) of the canonical MLP at the vertices (V, 3) -- the activation of _raw2outputs."""
+        with torch.no_grad():
+            verts = verts.to(device=self._mesh_device(), dtype=torch.float32).contiguous()
+            if verts.shape[0] == 0:
+                return verts.new_zeros(0, 3)
+            while True:
+                mode = self._mlp_mode()
+                packed = self._canonical_packed()
+                raw = ops.canonical(verts, packed, mode)
+                if not self._f16_rerun(packed, mode):
+                    return torch.sigmoid(raw[:, :3])
+
+    def extract_canonical_mesh(self, cnl_bbox_min_xyz, cnl_bbox_max_xyz, motion_weights_priors, resolution=256,
+                               level=MESH_LEVEL, cnl_bbox_scale_xyz=None):
+        """The canonical body as a coloured triangle mesh: marching tetrahedra (humannerf_amd.mesh) of
+        canonical_density_grid at ``level`` (default MESH_LEVEL, not checked on a trained checkpoint), colours from
+        vertex_colors.  Returns verts (V, 3) fp32, faces (F, 3) int32, colors (V, 3) fp32 in [0, 1], on the device.
+        The surface is open where it meets the bbox."""
+        from . import mesh
+        density = self.canonical_density_grid(cnl_bbox_min_xyz, cnl_bbox_max_xyz, motion_weights_priors, resolution,
+                                              cnl_bbox_scale_xyz)
+        verts, faces = mesh.mesh_from_density(density, cnl_bbox_min_xyz, cnl_bbox_max_xyz, level)
+        return verts, faces, self.vertex_colors(verts)
+
+    def frame_motion(self, frame, iter_val=1e7):
+        """The motion basis (B,3,3), (B,3) and weight volume forward computes for a frame dict (dst_Rs, dst_Ts,
+        cnl_gtfms, motion_weights_priors, dst_posevec), the pose refiner applied when iter_val >= its kick_in_iter."""
+        dev = self._mesh_device()
+        t = lambda k: torch.as_tensor(frame[k]).to(device=dev, dtype=torch.float32)
+        with torch.no_grad():
+            dst_Rs, dst_Ts, cnl_gtfms = t('dst_Rs'), t('dst_Ts'), t('cnl_gtfms')
+            rvec = None
+            if float(iter_val) >= cfg.pose_decoder.get('kick_in_iter', 0) and not cfg.get('pose_decoder_off', False):
+                rvec = self.pose_decoder.rvec(t('dst_posevec')[None])
+            motion_Rs, motion_Ts = motion_basis(dst_Rs, dst_Ts, cnl_gtfms, rvec)
+            vol = self._weight_volume(t('motion_weights_priors'))
+        return motion_Rs.contiguous(), motion_Ts.contiguous(), vol
+
+    def pose_vertices(self, verts, frame, iter_val=1e7):
+        """Canonical vertices (V, 3) -> the frame's pose by forward linear blend skinning (hnrf_forward_skin):
+        x_o = sum_b w_b(x_c) A_b^-1(x_c) / max(sum_b w_b, 1e-4) with the frame's motion basis A_b and the bone weights
+        of the weight volume at the canonical vertex -- the counterpart of the inverse warp rendering applies.  The
+        non-rigid offsets are not inverted: the posed mesh is the skinned canonical surface.  ``frame``: a
+        dataset.Subject.movement_frame dict (or any dict with forward's per-frame inputs)."""
+        motion_Rs, motion_Ts, vol = self.frame_motion(frame, iter_val)
+        dev = self._mesh_device()
+        f32 = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(3).contiguous()
+        bmin, scale = f32(frame['cnl_bbox_min_xyz']), f32(frame['cnl_bbox_scale_xyz'])
+        with torch.no_grad():
+            verts = verts.to(device=self._mesh_device(), dtype=torch.float32).contiguous()
+            return ops.forward_skin(verts, motion_Rs, motion_Ts, vol, bmin, scale)

@@ -768,3 +768,72 @@ def deconv_fold(col, bias, cout, D, H, W):
     out = torch.empty(1, cout, 2 * D, 2 * H, 2 * W, device=col.device)
     _lib.check(lib.hnrf_deconv_fold(_ptr(col), _ptr(bias), cout, D, H, W, _ptr(out), _stream()), 'hnrf_deconv_fold')
     return out
+
+
+def density_grid(packed, vol, bbox_min, bbox_max, bbox_scale, N, mode='f32', want_parts=False):
+    """hnrf_density_grid: relu(sigma) * fg on the N^3 lattice over [bbox_min, bbox_max], (N, N, N) indexed [z][y][x].
+    ``vol`` (B+1, G, G, G) with the background channel last (fg sums the B bone channels).  ``want_parts``: also
+    return sigma and fg, each (N, N, N)."""
+    lib = _lib.load()
+    _chk(packed, vol, bbox_min, bbox_max, bbox_scale)
+    N = int(N)
+    B, G = vol.shape[0] - 1, vol.shape[-1]
+    assert vol.dim() == 4 and vol.shape[1] == vol.shape[2] == G and B >= 1
+    dev = vol.device
+    need = lib.hnrf_density_grid_workspace_bytes(N)
+    if need == 0:
+        raise _lib.HnrfError(f'density grid resolution {N} out of range [8, 512]')
+    ws = torch.empty(need // 4 + 64, device=dev)
+    density = torch.empty(N, N, N, device=dev)
+    sigma = torch.empty(N, N, N, device=dev) if want_parts else None
+    fg = torch.empty(N, N, N, device=dev) if want_parts else None
+    _lib.check(lib.hnrf_density_grid(_ptr(packed), _mode_arg(mode), _ptr(vol), B, G, _ptr(bbox_min), _ptr(bbox_max),
+                                     _ptr(bbox_scale), N, _ptr(ws), ws.numel() * 4, _ptr(density), _ptr(sigma), _ptr(fg),
+                                     _stream()), 'hnrf_density_grid')
+    return (density, sigma, fg) if want_parts else density
+
+
+def mesh_workspace(N, device):
+    need = _lib.load().hnrf_mesh_workspace_bytes(int(N))
+    if need == 0:
+        raise _lib.HnrfError(f'mesh lattice resolution {N} out of range [8, 512]')
+    return torch.empty(need // 4 + 64, device=device)
+
+
+def mesh_count(density, level, workspace):
+    """hnrf_mesh_count: density (N, N, N) -> (V, F) on the host (one synchronisation); fills ``workspace``."""
+    lib = _lib.load()
+    _chk(density, workspace)
+    N = density.shape[0]
+    assert density.shape == (N, N, N)
+    counts = torch.empty(2, dtype=torch.int64, device=density.device)
+    _lib.check(lib.hnrf_mesh_count(_ptr(density), N, float(level), _ptr(workspace), workspace.numel() * 4, _ptr(counts),
+                                   _stream()), 'hnrf_mesh_count')
+    V, F = (int(v) for v in counts.cpu())
+    return V, F
+
+
+def mesh_emit(density, level, bbox_min, bbox_max, workspace, V, F):
+    """hnrf_mesh_emit after mesh_count on the same density / level / workspace: verts (V, 3) fp32, faces (F, 3) int32."""
+    lib = _lib.load()
+    _chk(density, bbox_min, bbox_max, workspace)
+    N = density.shape[0]
+    if V >= 2 ** 31:
+        raise _lib.HnrfError(f'{V} mesh vertices: int32 vertex ids hold at most 2^31 - 1')
+    verts = torch.empty(V, 3, device=density.device)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=density.device)
+    _lib.check(lib.hnrf_mesh_emit(_ptr(density), N, float(level), _ptr(bbox_min), _ptr(bbox_max), _ptr(workspace),
+                                  workspace.numel() * 4, V, F, _ptr(verts), _ptr(faces), _stream()), 'hnrf_mesh_emit')
+    return verts, faces
+
+
+def forward_skin(verts, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale):
+    """hnrf_forward_skin: canonical verts (V, 3) -> posed (V, 3) under the motion basis (B,3,3), (B,3)."""
+    lib = _lib.load()
+    _chk(verts, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale)
+    B, G = motion_Rs.shape[0], vol.shape[-1]
+    assert vol.shape[0] >= B and verts.shape[-1] == 3
+    out = torch.empty_like(verts)
+    _lib.check(lib.hnrf_forward_skin(_ptr(verts), verts.shape[0], _ptr(motion_Rs), _ptr(motion_Ts), _ptr(vol), B, G,
+                                     _ptr(bbox_min), _ptr(bbox_scale), _ptr(out), _stream()), 'hnrf_forward_skin')
+    return out

@@ -9,6 +9,7 @@ render.ImageWriter / MetricsWriter on worker threads.
                                   side by side, PSNR (SSIM, LPIPS) per image and averaged
   run_freeview   run.py:67-170    one training frame seen from a camera orbiting the subject
   run_tpose      run.py:178-183   the canonical pose on a turntable, non-rigid motion off
+  run_mesh       (no counterpart) the canonical body as a coloured triangle mesh, and that mesh skinned into frames
 
 Output layout as in the reference: ``<logdir>/<load_net><eval_output_tag>/<folder>/NAME.png`` plus
 ``<folder>-metrics.perimg.txt / .average.txt`` (movement) and the stacked frames (MP4 when imageio is importable).
@@ -119,3 +120,27 @@ def run_tpose(network, subject, total_frames=None, render_folder_name=None, logd
                             folder, logdir, rank, world, device)
     finally:
         cfg.ignore_non_rigid_motions = old
+
+
+def run_mesh(network, subject, frames=(), resolution=256, level=None, logdir=None):
+    """Network.extract_canonical_mesh over the subject's canonical bbox, written as ``<out>/mesh/canonical.ply``, and
+    for every entry of ``frames`` (index into subject.framelist, or frame name) that mesh posed with
+    Network.pose_vertices, written as ``<out>/mesh/<frame_name>.ply`` (vertex colours of the canonical mesh; the
+    non-rigid offsets are not inverted).  ``level``: None = Network.MESH_LEVEL.  Returns {name: path}."""
+    from . import mesh
+    out_dir = os.path.join(_output_dir(logdir), 'mesh')
+    os.makedirs(out_dir, exist_ok=True)
+    bbox = subject.canonical_bbox
+    verts, faces, colors = network.extract_canonical_mesh(
+        bbox['min_xyz'], bbox['max_xyz'], subject.motion_weights_priors, resolution=resolution,
+        level=network.MESH_LEVEL if level is None else level)
+    faces_h, colors_h = faces.cpu().numpy(), colors.cpu().numpy()
+    written = {'canonical': os.path.join(out_dir, 'canonical.ply')}
+    mesh.write_ply(written['canonical'], verts.cpu().numpy(), faces_h, colors_h)
+    for f in frames:
+        idx = subject.framelist.index(f) if isinstance(f, str) else int(f)
+        frame = subject.movement_frame(idx, image_size=(1, 1))          # (the camera entries are not used)
+        name = str(frame['frame_name']).replace('/', '-')
+        written[name] = os.path.join(out_dir, name + '.ply')
+        mesh.write_ply(written[name], network.pose_vertices(verts, frame).cpu().numpy(), faces_h, colors_h)
+    return written

@@ -408,6 +408,43 @@ int hnrf_resize_mask(const uint8_t* alpha, int Hs, int Ws, int channel, int mode
  *  written as a gather per output voxel (deterministic, no atomics). */
 int hnrf_deconv_fold(const float* col, const float* bias, int cout, int D, int H, int W, float* out, void* stream);
 
+/* ---- mesh extraction of the canonical body (no counterpart in the reference; humannerf_amd/mesh.py) ----
+ * hnrf_density_grid: the canonical density on an N^3 lattice (8 <= N <= 512) over [bbox_min, bbox_max] [3] each,
+ *  indexed [z][y][x], x fastest; point (x,y,z) at bbox_min + (float)i * step, step = (bbox_max - bbox_min) / (N - 1),
+ *  each operation rounded on its own.  density [N^3] = relu(sigma) * fg: sigma = channel 3 of the canonical MLP
+ *  (cnl_packed, mode as hnrf_canonical_fwd), fg = sum over the B bone channels of vol [>= B, G, G, G] sampled like
+ *  K1 (bbox_min / bbox_scale [3], align_corners, zero padding) under the identity motion.  Nullable: sigma [N^3],
+ *  fg [N^3].  Runs in chunks of hnrf_canonical_fwd through `workspace` (hnrf_density_grid_workspace_bytes(N),
+ *  256-byte aligned); every chunk is guarded (HNRF_STATUS_F16_RANGE in cnl_packed's status word, mode f16x3).
+ * hnrf_mesh_count / hnrf_mesh_emit: marching tetrahedra (Kuhn decomposition: 6 tetrahedra per cell around its main
+ *  diagonal) of density [N^3] at `level` (inside: density > level).  Each lattice point owns its edges to the +x, +y,
+ *  +z, +xy, +xz, +yz, +xyz neighbour (slots 0..6); one vertex per edge that crosses the level, at pa + t (pb - pa),
+ *  t = (level - da) / (db - da), a = the owning point; vertices ordered by (point, slot), triangles by (cell,
+ *  tetrahedron 0..5, triangle 0..1), wound counter-clockwise seen from outside ((v1 - v0) x (v2 - v0) points toward
+ *  lower density).  Watertight and edge-manifold except where the surface meets the lattice boundary: it stays open
+ *  there.  Bit-reproducible (integer block scans, no atomics).
+ *  hnrf_mesh_count writes counts [2] = {V, F} (int64, device) and fills `workspace` (hnrf_mesh_workspace_bytes(N),
+ *  256-byte aligned); the caller reads the counts, allocates verts [V,3] fp32 and faces [F,3] int32 (vertex ids,
+ *  V < 2^31) and passes the same density, level and workspace to hnrf_mesh_emit (bbox_max > bbox_min on every axis,
+ *  or the winding flips).  Writes past V / F are dropped. */
+size_t hnrf_density_grid_workspace_bytes(int N);
+int hnrf_density_grid(const void* cnl_packed, int mode, const float* vol, int B, int G, const float* bbox_min,
+                      const float* bbox_max, const float* bbox_scale, int N, void* workspace, size_t workspace_bytes,
+                      float* density, float* sigma, float* fg, void* stream);
+size_t hnrf_mesh_workspace_bytes(int N);
+int hnrf_mesh_count(const float* density, int N, float level, void* workspace, size_t workspace_bytes, int64_t* counts,
+                    void* stream);
+int hnrf_mesh_emit(const float* density, int N, float level, const float* bbox_min, const float* bbox_max,
+                   const void* workspace, size_t workspace_bytes, int64_t V, int64_t F, float* verts, int* faces,
+                   void* stream);
+/* hnrf_forward_skin: canonical vertices verts [V,3] -> posed out [V,3],
+ *  x_o = sum_b w_b(x_c) A_b^-1(x_c) / max(sum_b w_b, 1e-4), A_b(x) = R_b x + T_b the frame's motion basis
+ *  (motion_Rs [B,3,3], motion_Ts [B,3], B <= 128), w_b = the trilinear weight of bone b of vol at the canonical
+ *  vertex (bbox_min / bbox_scale as K1).  The forward counterpart of K1's inverse warp; the non-rigid offsets are not
+ *  inverted. */
+int hnrf_forward_skin(const float* verts, int64_t V, const float* motion_Rs, const float* motion_Ts, const float* vol,
+                      int B, int G, const float* bbox_min, const float* bbox_scale, float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
