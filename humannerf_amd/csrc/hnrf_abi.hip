@@ -1,4 +1,7 @@
-// Error channel, version, and the whole-path entry point (K1 -> K2 -> K3 -> K4).
+// Error channel, version, and the inference entry points.  hnrf_render_rays_fwd (one ray chunk, rgb / alpha /
+// depth) and hnrf_render_frame_fwd (every chunk of a frame, lean or with the eight diagnostic outputs) run K1 and
+// then the same per-chunk body, render_chunk: K2 -> K3 -> K4.  Early ray termination (hnrf_term.hip) walks depth
+// slabs instead and shares only the workspace carve (render_carve, hnrf_common.h).
 #include <stdarg.h>
 #include <string.h>
 
@@ -12,7 +15,6 @@ void set_error(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 }  // namespace hnrf
 
 using namespace hnrf;
@@ -20,12 +22,58 @@ using namespace hnrf;
 extern "C" int hnrf_abi_version(void) { return 13; }
 extern "C" const char* hnrf_last_error(void) { return g_err; }
 
-// workspace carve: z_vals[P] | mask[P] | x_skel[3P] | xyz[3P] | raw[4P] | idx[P] | count
 extern "C" size_t hnrf_render_workspace_bytes(int64_t R, int S) {
     if (R < 0 || S < 0) return 0;
-    const size_t P = (size_t)R * (size_t)S;
-    return align256(P * 4) * 2 + align256(P * 12) * 2 + align256(P * 16) + align256(P * 4) + 256;
+    return render_carve(nullptr, R, S).bytes;
 }
+
+// a failed HIP runtime call (only hnrf_render_frame_fwd makes them, render_chunk in its diagnostic form included)
+#define HNRF_HIP(call)                                                          \
+    do {                                                                        \
+        if ((call) != hipSuccess) {                                             \
+            set_error("hnrf_render_frame_fwd: %s failed", #call);               \
+            return HNRF_E_LAUNCH;                                               \
+        }                                                                       \
+    } while (0)
+
+namespace {
+// The chunk's rows of hnrf_render_frame_fwd's eight diagnostic outputs; all null = the lean form (rgb / alpha / depth).
+// (backward_motion_weights is K1's and written before render_chunk.)
+struct DiagRows {
+    float *weights, *rgb_on_rays, *cnl_xyz, *cnl_rgb, *cnl_weight, *xyz, *offsets;
+};
+
+// K2 -> K3 -> K4 of one ray chunk whose K1 results are in `c`: the whole of hnrf_render_rays_fwd after K1, and the body
+// of every chunk of hnrf_render_frame_fwd.  cull_eps > 0: the MLPs run only on the compacted samples.  ev_start /
+// ev_stop (hipEvent_t, nullable) are recorded right before / after the canonical-MLP launch.
+int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w, const void* nr_packed,
+                 const void* cnl_packed, const float* bgcolor, int mode, float cull_eps, int64_t R, int S, float* rgb,
+                 float* alpha, float* depth, const DiagRows& d, void* ev_start, void* ev_stop, hipStream_t st) {
+    const size_t P = (size_t)R * (size_t)S;
+    const bool cull = cull_eps > 0.f, diag = d.weights != nullptr;
+    int rc;
+    if (cull && (rc = hnrf_compact_samples(c.mask, cull_eps, (int64_t)P, c.idx, c.count, st))) return rc;
+    const int* ci = cull ? c.idx : nullptr;
+    const int* cc = cull ? c.count : nullptr;
+    float* xyz = diag ? d.xyz : c.xyz;
+    const float* cnl_in = c.x_skel;
+    if (nr_packed) {
+        if ((rc = hnrf_nonrigid_fwd_sparse(c.x_skel, hann_w, nr_packed, mode, (int64_t)P, ci, cc, xyz, d.offsets, st)))
+            return rc;
+        cnl_in = xyz;
+    } else if (diag) {                                            // network.py:276-277: xyz = x_skel, offsets = 0
+        HNRF_HIP(hipMemcpyAsync(xyz, c.x_skel, P * 12, hipMemcpyDeviceToDevice, st));
+        HNRF_HIP(hipMemsetAsync(d.offsets, 0, P * 12, st));
+    }
+    if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
+    rc = hnrf_canonical_fwd_sparse(cnl_in, cnl_packed, mode, (int64_t)P, ci, cc, c.raw, st);
+    if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
+    if (rc) return rc;
+    return hnrf_composite_fwd(c.raw, c.mask, c.z_vals, rays_d, diag ? cnl_in : nullptr, bgcolor, R, S,
+                              cull ? cull_eps : 0.f, rgb, alpha, depth, d.weights, d.rgb_on_rays, d.cnl_xyz, d.cnl_rgb,
+                              d.cnl_weight, st);
+}
+}  // namespace
 
 extern "C" int hnrf_render_rays_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
                                     const float* t_rand, const float* motion_Rs, const float* motion_Ts,
@@ -39,37 +87,12 @@ extern "C" int hnrf_render_rays_fwd(const float* rays_o, const float* rays_d, co
     HNRF_REQUIRE(workspace_bytes >= hnrf_render_workspace_bytes(R, S), HNRF_E_WORKSPACE,
                  "hnrf_render_rays_fwd: workspace %zu < %zu bytes", workspace_bytes, hnrf_render_workspace_bytes(R, S));
     HNRF_REQUIRE(nr_packed == nullptr || hann_w != nullptr, HNRF_E_ARG, "hnrf_render_rays_fwd: hann_w missing");
-    const size_t P = (size_t)R * (size_t)S;
-    char* w = (char*)workspace;
-    float* z_vals = (float*)w;  w += align256(P * 4);
-    float* mask = (float*)w;    w += align256(P * 4);
-    float* x_skel = (float*)w;  w += align256(P * 12);
-    float* xyz = (float*)w;     w += align256(P * 12);
-    float* raw = (float*)w;     w += align256(P * 16);
-    int* idx = (int*)w;         w += align256(P * 4);
-    int* count = (int*)w;
-    const bool cull = cull_eps > 0.f;
+    const RenderCarve c = render_carve(workspace, R, S);
     int rc = hnrf_sample_warp_fwd(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
-                                  R, S, B, G, z_vals, x_skel, mask, nullptr, stream);
+                                  R, S, B, G, c.z_vals, c.x_skel, c.mask, nullptr, stream);
     if (rc) return rc;
-    if (cull) {
-        rc = hnrf_compact_samples(mask, cull_eps, (int64_t)P, idx, count, stream);
-        if (rc) return rc;
-    }
-    const int* ci = cull ? idx : nullptr;
-    const int* cc = cull ? count : nullptr;
-    const float* cnl_in = x_skel;
-    if (nr_packed) {
-        rc = hnrf_nonrigid_fwd_sparse(x_skel, hann_w, nr_packed, mode, (int64_t)P, ci, cc, xyz, nullptr, stream);
-        if (rc) return rc;
-        cnl_in = xyz;
-    }
-    if (ev_mlp_start) (void)hipEventRecord((hipEvent_t)ev_mlp_start, (hipStream_t)stream);
-    rc = hnrf_canonical_fwd_sparse(cnl_in, cnl_packed, mode, (int64_t)P, ci, cc, raw, stream);
-    if (ev_mlp_stop) (void)hipEventRecord((hipEvent_t)ev_mlp_stop, (hipStream_t)stream);
-    if (rc) return rc;
-    return hnrf_composite_fwd(raw, mask, z_vals, rays_d, nullptr, bgcolor, R, S, cull ? cull_eps : 0.f, rgb, alpha,
-                              depth, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
+    return render_chunk(c, rays_d, hann_w, nr_packed, cnl_packed, bgcolor, mode, cull_eps, R, S, rgb, alpha, depth,
+                        DiagRows{}, ev_mlp_start, ev_mlp_stop, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -105,35 +128,14 @@ extern "C" int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, c
     hipStream_t st = (hipStream_t)stream, sd = side_stream ? (hipStream_t)side_stream : st;
     const bool two = side_stream != nullptr && side_stream != stream;
     const int64_t nchunk = (N + chunk - 1) / chunk;
-    const bool cull = cull_eps > 0.f;
-    struct Carve { float *z, *mask, *x_skel, *xyz, *raw; int *idx, *count; };
-    auto carve = [&](int slot, int64_t R) {
-        const size_t P = (size_t)R * (size_t)S;
-        char* w = (char*)workspace + (size_t)slot * ws_one;
-        Carve c;
-        c.z = (float*)w;       w += align256(P * 4);
-        c.mask = (float*)w;    w += align256(P * 4);
-        c.x_skel = (float*)w;  w += align256(P * 12);
-        c.xyz = (float*)w;     w += align256(P * 12);
-        c.raw = (float*)w;     w += align256(P * 16);
-        c.idx = (int*)w;       w += align256(P * 4);
-        c.count = (int*)w;
-        return c;
-    };
+    auto carve = [&](int64_t i, int64_t R) { return render_carve((char*)workspace + (size_t)(i & 1) * ws_one, R, S); };
     auto warp = [&](int64_t i) {                                  // K1 of chunk i on the side stream
         const int64_t r0 = i * chunk, R = (N - r0 < chunk) ? N - r0 : chunk;
-        const Carve c = carve((int)(i & 1), R);
+        const RenderCarve c = carve(i, R);
         return hnrf_sample_warp_fwd(rays_o + 3 * r0, rays_d + 3 * r0, near + r0, far + r0, t_rand ? t_rand + r0 * S : nullptr,
-                                    motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, R, S, B, G, c.z, c.x_skel, c.mask,
+                                    motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, R, S, B, G, c.z_vals, c.x_skel, c.mask,
                                     bmw ? bmw + r0 * S * B : nullptr, sd);
     };
-#define HNRF_HIP(call)                                                          \
-    do {                                                                        \
-        if ((call) != hipSuccess) {                                             \
-            set_error("hnrf_render_frame_fwd: %s failed", #call);               \
-            return HNRF_E_LAUNCH;                                               \
-        }                                                                       \
-    } while (0)
     hipEvent_t ev_in = nullptr, ev_k1[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
     if (two) {
         ev_in = (hipEvent_t)events[0];
@@ -147,8 +149,6 @@ extern "C" int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, c
     if (two) HNRF_HIP(hipEventRecord(ev_k1[0], sd));
     for (int64_t i = 0; i < nchunk; ++i) {
         const int64_t r0 = i * chunk, R = (N - r0 < chunk) ? N - r0 : chunk;
-        const size_t P = (size_t)R * (size_t)S;
-        const Carve c = carve((int)(i & 1), R);
         if (i + 1 < nchunk) {                                     // next chunk's K1: its workspace was last read by chunk i-1
             if (two && i >= 1) HNRF_HIP(hipStreamWaitEvent(sd, ev_done[(i + 1) & 1], 0));
             if (two) {
@@ -157,31 +157,15 @@ extern "C" int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, c
             }
         }
         if (two) HNRF_HIP(hipStreamWaitEvent(st, ev_k1[i & 1], 0));
-        if (cull && (rc = hnrf_compact_samples(c.mask, cull_eps, (int64_t)P, c.idx, c.count, st))) return rc;
-        const int* ci = cull ? c.idx : nullptr;
-        const int* cc = cull ? c.count : nullptr;
-        float* xyz = diag ? xyz_on_rays + r0 * S * 3 : c.xyz;
-        const float* cnl_in = c.x_skel;
         // f16-range guard (hnrf.h): every chunk, none, or the one chunk the caller's rotating index names
         int cmode = mode & (HNRF_MLP_ARITH_MASK | HNRF_MLP_NO_RANGE_GUARD);
         if ((mode & HNRF_MLP_GUARD_ONE_CHUNK) && (int64_t)((unsigned)mode >> 16) % nchunk != i) cmode |= HNRF_MLP_NO_RANGE_GUARD;
-        if (nr_packed) {
-            if ((rc = hnrf_nonrigid_fwd_sparse(c.x_skel, hann_w, nr_packed, cmode, (int64_t)P, ci, cc, xyz,
-                                               diag ? offsets + r0 * S * 3 : nullptr, st))) return rc;
-            cnl_in = xyz;
-        } else if (diag) {                                        // network.py:276-277: xyz = x_skel, offsets = 0
-            HNRF_HIP(hipMemcpyAsync(xyz, c.x_skel, P * 12, hipMemcpyDeviceToDevice, st));
-            HNRF_HIP(hipMemsetAsync(offsets + r0 * S * 3, 0, P * 12, st));
-        }
-        if (mlp_events) (void)hipEventRecord((hipEvent_t)mlp_events[2 * i], st);
-        rc = hnrf_canonical_fwd_sparse(cnl_in, cnl_packed, cmode, (int64_t)P, ci, cc, c.raw, st);
-        if (mlp_events) (void)hipEventRecord((hipEvent_t)mlp_events[2 * i + 1], st);
-        if (rc) return rc;
-        if ((rc = hnrf_composite_fwd(c.raw, c.mask, c.z, rays_d + 3 * r0, diag ? cnl_in : nullptr, bgcolor, R, S,
-                                     cull ? cull_eps : 0.f, rgb + 3 * r0, alpha + r0, depth + r0,
-                                     diag ? weights_on_rays + r0 * S : nullptr, diag ? rgb_on_rays + r0 * S * 3 : nullptr,
-                                     diag ? cnl_xyz + 3 * r0 : nullptr, diag ? cnl_rgb + 3 * r0 : nullptr,
-                                     diag ? cnl_weight + r0 : nullptr, st))) return rc;
+        const DiagRows d = diag ? DiagRows{weights_on_rays + r0 * S, rgb_on_rays + r0 * S * 3, cnl_xyz + 3 * r0,
+                                           cnl_rgb + 3 * r0, cnl_weight + r0, xyz_on_rays + r0 * S * 3, offsets + r0 * S * 3}
+                                : DiagRows{};
+        if ((rc = render_chunk(carve(i, R), rays_d + 3 * r0, hann_w, nr_packed, cnl_packed, bgcolor, cmode, cull_eps, R, S,
+                               rgb + 3 * r0, alpha + r0, depth + r0, d, mlp_events ? mlp_events[2 * i] : nullptr,
+                               mlp_events ? mlp_events[2 * i + 1] : nullptr, st))) return rc;
         if (two) HNRF_HIP(hipEventRecord(ev_done[i & 1], st));
         if (!two && i + 1 < nchunk && (rc = warp(i + 1))) return rc;   // single stream: plain sequence
     }

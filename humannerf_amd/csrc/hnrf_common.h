@@ -28,6 +28,37 @@ static inline int check_launch(const char* what) {
 
 constexpr int kWave = 64;
 
+static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// Workspace of one ray chunk of R rays x S samples (P = R S), every part 256-byte aligned:
+// z_vals[P] | mask[P] | x_skel[3P] | xyz[3P] | raw[4P] | idx[P] | count.  hnrf_render_rays_fwd, each of the two
+// slots of hnrf_render_frame_fwd and hnrf_render_rays_term_fwd carve it; `bytes` is its size
+// (hnrf_render_workspace_bytes carves from a null base).
+struct RenderCarve {
+    float *z_vals, *mask, *x_skel, *xyz, *raw;
+    int *idx, *count;
+    size_t bytes;
+};
+static inline RenderCarve render_carve(void* base, int64_t R, int S) {
+    const size_t P = (size_t)R * (size_t)S;
+    size_t o = 0;
+    auto take = [&](size_t n) {
+        void* p = (void*)((uintptr_t)base + o);
+        o += align256(n);
+        return p;
+    };
+    RenderCarve c;
+    c.z_vals = (float*)take(P * 4);
+    c.mask = (float*)take(P * 4);
+    c.x_skel = (float*)take(P * 12);
+    c.xyz = (float*)take(P * 12);
+    c.raw = (float*)take(P * 16);
+    c.idx = (int*)take(P * 4);
+    c.count = (int*)take(sizeof(int));
+    c.bytes = o;
+    return c;
+}
+
 // Opt a kernel into > 64 KiB of dynamic LDS, once per device of this process (`done`: one bit per device id;
 // the attribute is per device, and a process may drive more than one).
 static inline int reserve_lds(const void* fn, int bytes, unsigned long long& done, const char* what) {

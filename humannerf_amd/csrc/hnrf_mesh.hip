@@ -28,7 +28,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int64_t kDensityChunk = 1 << 21;     // lattice points per canonical-MLP launch (56 MiB of workspace)
 constexpr int kMaxSkinBones = 128;
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // Cell corner c: bit 0 = +x, bit 1 = +y, bit 2 = +z.  Slot s of a point is the edge to its corner kSlotCorner[s].
 __constant__ unsigned char c_slot_corner[7] = {1, 2, 4, 3, 5, 6, 7};

@@ -448,8 +448,6 @@ extern "C" int hnrf_nonrigid_pack(const float* const* weights, const float* cons
     return launch_pack(d, cond, out, st);
 }
 
-extern "C" int hnrf_canonical_fwd_sparse(const float* xyz, const void* packed, int mode, int64_t P, const int* idx,
-                                         const int* count, float* raw, void* stream);
 extern "C" int hnrf_canonical_fwd(const float* xyz, const void* packed, int mode, int64_t P, float* raw,
                                   void* stream) {
     return hnrf_canonical_fwd_sparse(xyz, packed, mode, P, nullptr, nullptr, raw, stream);
@@ -489,9 +487,6 @@ extern "C" int hnrf_canonical_fwd_train(const float* xyz, const void* packed, in
     return check_launch("hnrf_canonical_fwd_train");
 }
 
-extern "C" int hnrf_nonrigid_fwd_sparse(const float* x_skel, const float* hann_w, const void* packed, int mode,
-                                        int64_t P, const int* idx, const int* count, float* xyz, float* offsets,
-                                        void* stream);
 extern "C" int hnrf_nonrigid_fwd(const float* x_skel, const float* hann_w, const void* packed, int mode, int64_t P,
                                  float* xyz, float* offsets, void* stream) {
     return hnrf_nonrigid_fwd_sparse(x_skel, hann_w, packed, mode, P, nullptr, nullptr, xyz, offsets, stream);

@@ -127,22 +127,14 @@ __global__ void term_finish_kernel(const float* __restrict__ st, const float* __
 
 __global__ void term_add_count_kernel(const int* __restrict__ c, int* __restrict__ e) { *e += *c; }
 
-static inline size_t align256t(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace hnrf
 
 using namespace hnrf;
 
-extern "C" int hnrf_nonrigid_fwd_sparse(const float* x_skel, const float* hann_w, const void* packed, int mode,
-                                        int64_t P, const int* idx, const int* count, float* xyz, float* offsets,
-                                        void* stream);
-extern "C" int hnrf_canonical_fwd_sparse(const float* xyz, const void* packed, int mode, int64_t P, const int* idx,
-                                         const int* count, float* raw, void* stream);
-
-// workspace: the carve of hnrf_render_rays_fwd + the per-ray state
+// workspace: the per-chunk carve (render_carve) followed by the per-ray state (RayState[R])
 extern "C" size_t hnrf_render_term_workspace_bytes(int64_t R, int S) {
     if (R < 0 || S < 0) return 0;
-    return hnrf_render_workspace_bytes(R, S) + align256t((size_t)R * 6 * sizeof(float)) + 256;
+    return hnrf_render_workspace_bytes(R, S) + align256((size_t)R * sizeof(RayState)) + 256;
 }
 
 extern "C" int hnrf_render_rays_term_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
@@ -162,19 +154,11 @@ extern "C" int hnrf_render_rays_term_fwd(const float* rays_o, const float* rays_
     HNRF_REQUIRE(nr_packed == nullptr || hann_w != nullptr, HNRF_E_ARG, "hnrf_render_rays_term_fwd: hann_w missing");
     HNRF_REQUIRE(R >= 0 && S >= 2 && (int64_t)R * 32 < 2147483647LL, HNRF_E_ARG, "hnrf_render_rays_term_fwd: bad dims");
     if (R == 0) return HNRF_OK;
-    const size_t P = (size_t)R * (size_t)S;
-    char* w = (char*)workspace;
-    float* z_vals = (float*)w;  w += align256t(P * 4);
-    float* mask = (float*)w;    w += align256t(P * 4);
-    float* x_skel = (float*)w;  w += align256t(P * 12);
-    float* xyz = (float*)w;     w += align256t(P * 12);
-    float* raw = (float*)w;     w += align256t(P * 16);
-    int* idx = (int*)w;         w += align256t(P * 4);
-    int* count = (int*)w;       w += 256;
-    float* st = (float*)w;
+    const RenderCarve c = render_carve(workspace, R, S);
+    float* st = (float*)((char*)workspace + c.bytes);
     hipStream_t stq = (hipStream_t)stream;
     int rc = hnrf_sample_warp_fwd(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
-                                  R, S, B, G, z_vals, x_skel, mask, nullptr, stream);
+                                  R, S, B, G, c.z_vals, c.x_skel, c.mask, nullptr, stream);
     if (rc) return rc;
     hipLaunchKernelGGL(term_init_kernel, dim3((unsigned)((R * 6 + 255) / 256)), dim3(256), 0, stq, st, R);
     if (evaluated && hipMemsetAsync(evaluated, 0, sizeof(int), stq) != hipSuccess) {
@@ -185,24 +169,24 @@ extern "C" int hnrf_render_rays_term_fwd(const float* rays_o, const float* rays_
     for (int s0 = 0; s0 < S; s0 += SS) {
         const int ss = S - s0 < SS ? S - s0 : SS;
         const int64_t cap = R * (int64_t)ss;
-        if (hipMemsetAsync(count, 0, sizeof(int), stq) != hipSuccess) {
+        if (hipMemsetAsync(c.count, 0, sizeof(int), stq) != hipSuccess) {
             set_error("hnrf_render_rays_term_fwd: memset failed");
             return HNRF_E_LAUNCH;
         }
-        hipLaunchKernelGGL(compact_slab_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, stq, mask, st, cull_eps,
-                           term_eps, R, S, s0, ss, idx, count);
-        const float* cnl_in = x_skel;
+        hipLaunchKernelGGL(compact_slab_kernel, dim3((unsigned)((cap + 255) / 256)), dim3(256), 0, stq, c.mask, st, cull_eps,
+                           term_eps, R, S, s0, ss, c.idx, c.count);
+        const float* cnl_in = c.x_skel;
         if (nr_packed) {
-            rc = hnrf_nonrigid_fwd_sparse(x_skel, hann_w, nr_packed, mode, cap, idx, count, xyz, nullptr, stream);
+            rc = hnrf_nonrigid_fwd_sparse(c.x_skel, hann_w, nr_packed, mode, cap, c.idx, c.count, c.xyz, nullptr, stream);
             if (rc) return rc;
-            cnl_in = xyz;
+            cnl_in = c.xyz;
         }
-        rc = hnrf_canonical_fwd_sparse(cnl_in, cnl_packed, mode, cap, idx, count, raw, stream);
+        rc = hnrf_canonical_fwd_sparse(cnl_in, cnl_packed, mode, cap, c.idx, c.count, c.raw, stream);
         if (rc) return rc;
-        hipLaunchKernelGGL(composite_slab_kernel, dim3((unsigned)((R + 7) / 8)), dim3(256), 0, stq, (const float4*)raw,
-                           mask, z_vals, rays_d, cull_eps, term_eps, R, S, s0, ss, st);
+        hipLaunchKernelGGL(composite_slab_kernel, dim3((unsigned)((R + 7) / 8)), dim3(256), 0, stq, (const float4*)c.raw,
+                           c.mask, c.z_vals, rays_d, cull_eps, term_eps, R, S, s0, ss, st);
         if (evaluated)     // running total of evaluated samples (diagnostic), kept on the device
-            hipLaunchKernelGGL(term_add_count_kernel, dim3(1), dim3(1), 0, stq, count, evaluated);
+            hipLaunchKernelGGL(term_add_count_kernel, dim3(1), dim3(1), 0, stq, c.count, evaluated);
     }
     hipLaunchKernelGGL(term_finish_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stq, st, bgcolor, R, rgb,
                        alpha, depth);

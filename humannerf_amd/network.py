@@ -730,10 +730,11 @@ class Network(nn.Module):
             return {k: v.reshape(list(rays_shape[:-1]) + list(v.shape[1:])) for k, v in out.items()}
 
         term_eps = float(amd_option('term_eps', 0.0))
-        if not train_path and term_eps == 0.0:
-            # the whole frame in one library call: chunk loop of network.py:330-352, results straight into whole-frame
-            # tensors (the reference concatenates per-chunk results: one more pass over 17 KB per ray); optionally K1 of
-            # the next chunk on a side stream under the MLP kernels of the current one (cfg.amd.overlap_warp)
+        if not train_path and (diag or term_eps == 0.0):
+            # inference: the whole frame in one library call -- chunk loop of network.py:330-352, results straight into
+            # whole-frame tensors (the reference concatenates per-chunk results: one more pass over 17 KB per ray);
+            # optionally K1 of the next chunk on a side stream under the MLP kernels of the current one
+            # (cfg.amd.overlap_warp).  With diagnostics on, term_eps is ignored: early termination has no 11-output form
             gmode, guarded = self._guard_plan(mode, -(-N // int(cfg.chunk)))
             out, self._workspace = ops.render_frame(
                 rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w, nr_packed,
@@ -743,23 +744,29 @@ class Network(nn.Module):
             if mode == 'f16x3' and guarded != set():
                 self._watch_f16_range(cnl_packed, nr_packed, mode)
         else:
+            # per ray chunk (network.py:333): training (autograd.RenderRays), or the lean inference path with early ray
+            # termination (hnrf_render_rays_term_fwd, one workspace for every chunk)
+            chunk = int(cfg.chunk)
             chunks = []
             guarded = None
             if not train_path:
-                _, guarded = self._guard_plan(mode, -(-N // int(cfg.chunk)))
-            for ci, i in enumerate(range(0, N, int(cfg.chunk))):           # network.py:333
-                sl = slice(i, min(i + int(cfg.chunk), N))
+                _, guarded = self._guard_plan(mode, -(-N // chunk))
+                need = ops.render_term_workspace_bytes(min(chunk, N), S) // 4 + 64
+                if self._workspace is None or self._workspace.numel() < need or self._workspace.device != rays_o.device:
+                    self._workspace = torch.empty(need, device=rays_o.device)
+            for ci, i in enumerate(range(0, N, chunk)):
+                sl = slice(i, min(i + chunk, N))
+                tr = None if t_rand is None else t_rand[sl]
                 if train_path:
-                    chunks.append(self._render_rays_train(rays_o[sl], rays_d[sl], near[sl], far[sl],
-                                                          None if t_rand is None else t_rand[sl], motion_Rs, motion_Ts,
-                                                          vol, bbox_min, bbox_scale, hann_w, cond, bg, S, not ignore_nr,
-                                                          diag))
+                    chunks.append(self._render_rays_train(rays_o[sl], rays_d[sl], near[sl], far[sl], tr, motion_Rs,
+                                                          motion_Ts, vol, bbox_min, bbox_scale, hann_w, cond, bg, S,
+                                                          not ignore_nr, diag))
                     continue
-                chunks.append(self._render_rays(rays_o[sl], rays_d[sl], near[sl], far[sl],
-                                                None if t_rand is None else t_rand[sl],
-                                                motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w,
-                                                nr_packed, cnl_packed, bg, S,
-                                                mode if guarded is None or ci in guarded else mode + '+noguard', diag, None))
+                chunks.append(ops.render_rays_term(rays_o[sl], rays_d[sl], near[sl], far[sl], tr, motion_Rs, motion_Ts,
+                                                   vol, bbox_min, bbox_scale, hann_w, nr_packed, cnl_packed, bg, S,
+                                                   mode if guarded is None or ci in guarded else mode + '+noguard',
+                                                   term_eps=term_eps, cull_eps=float(amd_option('cull_eps', 0.0)),
+                                                   workspace=self._workspace))
             out = {k: (torch.cat([c[k] for c in chunks], 0) if len(chunks) > 1 else chunks[0][k]) for k in chunks[0]}
             if not train_path and mode == 'f16x3' and guarded != set():
                 self._watch_f16_range(cnl_packed, nr_packed, mode)
@@ -803,51 +810,6 @@ class Network(nn.Module):
                                cond.detach().contiguous(), bg, S, use_nonrigid, diag, const_offset, motion_Rs, motion_Ts, vol,
                                *params)
         return dict(zip(RenderRays.OUTPUT_KEYS if diag else RenderRays.OUTPUT_KEYS[:3], res))
-
-    def _render_rays(self, rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
-                     hann_w, nr_packed, cnl_packed, bg, S, mode, diag, dst=None):
-        """network.py:474-602 for one ray chunk.  ``dst``: this chunk's row range of the whole-frame output buffers
-        (full-signature path), written in place."""
-        if not diag:
-            term_eps = float(amd_option('term_eps', 0.0))
-            need = (ops.render_term_workspace_bytes if term_eps > 0.0 else ops.render_workspace_bytes)(rays_o.shape[0], S) // 4 + 64
-            if self._workspace is None or self._workspace.numel() < need or self._workspace.device != rays_o.device:
-                self._workspace = torch.empty(need, device=rays_o.device)
-            if term_eps > 0.0:
-                return ops.render_rays_term(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min,
-                                            bbox_scale, hann_w, nr_packed, cnl_packed, bg, S, mode, term_eps=term_eps,
-                                            cull_eps=float(amd_option('cull_eps', 0.0)), workspace=self._workspace)
-            events = None
-            if self.mlp_event_log is not None:
-                events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-                self.mlp_event_log.append(events)
-            return ops.render_rays(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min,
-                                   bbox_scale, hann_w, nr_packed, cnl_packed, bg, S, mode,
-                                   workspace=self._workspace, mlp_events=events,
-                                   cull_eps=float(amd_option('cull_eps', 0.0)))
-        g = (lambda k: None) if dst is None else dst.get
-        z, x_skel, mask, bmw = ops.sample_warp(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol,
-                                               bbox_min, bbox_scale, S, want_bmw=True,
-                                               bmw_out=g('backward_motion_weights'))
-        if nr_packed is not None:
-            xyz, offsets = ops.nonrigid(x_skel, hann_w, nr_packed, mode, want_offsets=True,
-                                        xyz_out=g('xyz_on_rays'), offsets_out=g('offsets'))
-        else:
-            xyz, offsets = x_skel, torch.zeros_like(x_skel)                 # network.py:276-277
-            if dst is not None:
-                dst['xyz_on_rays'].copy_(xyz)
-                dst['offsets'].zero_()
-        if self.mlp_event_log is not None:
-            events = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-            self.mlp_event_log.append(events)
-            events[0].record()
-            raw = ops.canonical(xyz, cnl_packed, mode)
-            events[1].record()
-        else:
-            raw = ops.canonical(xyz, cnl_packed, mode)
-        out = ops.composite(raw, mask, z, rays_d, xyz, bg, diagnostics=True, out=dst)
-        out.update(xyz_on_rays=xyz, backward_motion_weights=bmw, offsets=offsets)
-        return out
 
     # mesh extraction (no counterpart in the reference) ------------------------------------------------------------
     # Density at which the canonical surface is cut.  NOT checked on a trained checkpoint (none can be obtained

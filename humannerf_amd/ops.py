@@ -198,22 +198,34 @@ def render_term_workspace_bytes(R, S):
     return _lib.load().hnrf_render_term_workspace_bytes(int(R), int(S))
 
 
+def _render_args(operands, workspace, need, grow=True):
+    """Shared by the render wrappers.  Returns ``operands`` -- their 14 leading tensors, rays_o .. bgcolor -- checked
+    and with near / far flattened, and a workspace of at least ``need`` bytes on the rays' device: ``workspace`` itself
+    when it is one, else ``need // 4 + 64`` fresh floats (``grow=False``: a caller's workspace that is not one raises)."""
+    args = operands[:2] + (operands[2].reshape(-1), operands[3].reshape(-1)) + operands[4:]
+    _chk(*args)
+    dev = args[0].device
+    if workspace is None or workspace.numel() * workspace.element_size() < need or workspace.device != dev:
+        if workspace is not None and not grow:
+            raise _lib.HnrfError(f'workspace: {workspace.numel() * workspace.element_size()} bytes on '
+                                 f'{workspace.device}, need {need} bytes on {dev}')
+        workspace = torch.empty(need // 4 + 64, device=dev)
+    return args, workspace
+
+
 def render_rays(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
                 hann_w, nr_packed, cnl_packed, bgcolor, n_samples, mode='f32', workspace=None, out=None,
                 mlp_events=None, cull_eps=0.0):
     """The whole path for one ray chunk (network.py:474-602) with only the
-    rgb/alpha/depth outputs; intermediates live in ``workspace``.  ``mlp_events``:
+    rgb/alpha/depth outputs; intermediates live in ``workspace`` (one given must hold
+    render_workspace_bytes(R, S) on the rays' device: it is not replaced).  ``mlp_events``:
     optional pair of torch.cuda.Event(enable_timing=True), recorded around the
     canonical-MLP launch."""
     lib = _lib.load()
-    near, far = near.reshape(-1), far.reshape(-1)
-    _chk(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w,
-         nr_packed, cnl_packed, bgcolor)
     R, S = rays_o.shape[0], int(n_samples)
-    need = lib.hnrf_render_workspace_bytes(R, S)
-    if workspace is None:
-        workspace = torch.empty(need // 4 + 64, device=rays_o.device)
-    assert workspace.numel() * workspace.element_size() >= need
+    args, workspace = _render_args((rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
+                                    hann_w, nr_packed, cnl_packed, bgcolor), workspace,
+                                   lib.hnrf_render_workspace_bytes(R, S), grow=False)
     dev = rays_o.device
     if out is None:
         out = {'rgb': torch.empty(R, 3, device=dev), 'alpha': torch.empty(R, device=dev),
@@ -224,14 +236,10 @@ def render_rays(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bb
             if not e.cuda_event:
                 e.record()            # forces creation of the hipEvent_t
         ev = (mlp_events[0].cuda_event, mlp_events[1].cuda_event)
-    _lib.check(lib.hnrf_render_rays_fwd(_ptr(rays_o), _ptr(rays_d), _ptr(near), _ptr(far), _ptr(t_rand),
-                                        _ptr(motion_Rs), _ptr(motion_Ts), _ptr(vol), _ptr(bbox_min),
-                                        _ptr(bbox_scale), _ptr(hann_w), _ptr(nr_packed), _ptr(cnl_packed),
-                                        _ptr(bgcolor), _mode_arg(mode), float(cull_eps), R, S, motion_Rs.shape[0], vol.shape[-1],
-                                        _ptr(workspace), workspace.numel() * workspace.element_size(),
-                                        _ptr(out['rgb']), _ptr(out['alpha']), _ptr(out['depth']),
-                                        ev[0], ev[1], _stream()),
-               'hnrf_render_rays_fwd')
+    _lib.check(lib.hnrf_render_rays_fwd(*map(_ptr, args), _mode_arg(mode), float(cull_eps), R, S, motion_Rs.shape[0],
+                                        vol.shape[-1], _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                        _ptr(out['rgb']), _ptr(out['alpha']), _ptr(out['depth']), ev[0], ev[1],
+                                        _stream()), 'hnrf_render_rays_fwd')
     return out
 
 
@@ -257,15 +265,12 @@ def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, b
     K1 of the next chunk on a side stream while the MLP kernels of the current one run.  Returns (dict of outputs,
     workspace).  ``mlp_event_log``: list that receives one (start, stop) torch.cuda.Event pair per chunk."""
     lib = _lib.load()
-    near, far = near.reshape(-1), far.reshape(-1)
-    _chk(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w, nr_packed, cnl_packed,
-         bgcolor)
     N, S, B, G = rays_o.shape[0], int(n_samples), motion_Rs.shape[0], vol.shape[-1]
     dev = rays_o.device
     chunk = int(chunk)
-    need = lib.hnrf_render_frame_workspace_bytes(min(chunk, max(N, 1)), S)
-    if workspace is None or workspace.numel() * 4 < need or workspace.device != dev:
-        workspace = torch.empty(need // 4 + 64, device=dev)
+    args, workspace = _render_args((rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
+                                    hann_w, nr_packed, cnl_packed, bgcolor), workspace,
+                                   lib.hnrf_render_frame_workspace_bytes(min(chunk, max(N, 1)), S))
     shp = {'rgb': (3,), 'alpha': (), 'depth': ()}
     if diagnostics:
         shp.update(weights_on_rays=(S,), rgb_on_rays=(S, 3), cnl_xyz=(3,), cnl_rgb=(3,), cnl_weight=(), xyz_on_rays=(S, 3),
@@ -285,17 +290,15 @@ def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, b
             b.record()
         mlp_arr = (ctypes.c_void_p * (2 * nchunk))(*[e.cuda_event for p in pairs for e in p])
     _lib.check(lib.hnrf_render_frame_fwd(
-        _ptr(rays_o), _ptr(rays_d), _ptr(near), _ptr(far), _ptr(t_rand), _ptr(motion_Rs), _ptr(motion_Ts), _ptr(vol),
-        _ptr(bbox_min), _ptr(bbox_scale), _ptr(hann_w), _ptr(nr_packed), _ptr(cnl_packed), _ptr(bgcolor), _mode_arg(mode),
-        float(cull_eps), N, S, B, G, chunk, _ptr(workspace), workspace.numel() * 4, g('rgb'), g('alpha'), g('depth'),
+        *map(_ptr, args), _mode_arg(mode), float(cull_eps), N, S, B, G, chunk, _ptr(workspace),
+        workspace.numel() * workspace.element_size(), g('rgb'), g('alpha'), g('depth'),
         g('weights_on_rays'), g('rgb_on_rays'), g('cnl_xyz'), g('cnl_rgb'), g('cnl_weight'), g('xyz_on_rays'),
         g('backward_motion_weights'), g('offsets'), side.cuda_stream if side is not None else None, ev_arr, mlp_arr,
         _stream()), 'hnrf_render_frame_fwd')
     if side is not None:
         # the side stream read the inputs and wrote backward_motion_weights / the workspace: keep the allocator from
         # handing those blocks out again before it is done (everything it did is also ordered on the main stream)
-        for t in (rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, workspace,
-                  out.get('backward_motion_weights')):
+        for t in args[:10] + (workspace, out.get('backward_motion_weights')):      # rays_o .. bbox_scale: K1's inputs
             if t is not None:
                 t.record_stream(side)
     if mlp_event_log is not None:
@@ -309,20 +312,14 @@ def render_rays_term(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vo
     """Lean path with early ray termination (opt-in approximation, |d rgb|, |d alpha| <= term_eps): see
     hnrf_render_rays_term_fwd.  Returns the rgb/alpha/depth dict (+ 'evaluated': device int tensor when asked)."""
     lib = _lib.load()
-    near, far = near.reshape(-1), far.reshape(-1)
-    _chk(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w,
-         nr_packed, cnl_packed, bgcolor)
     R, S = rays_o.shape[0], int(n_samples)
-    need = lib.hnrf_render_term_workspace_bytes(R, S)
-    if workspace is None or workspace.numel() * workspace.element_size() < need:
-        workspace = torch.empty(need // 4 + 64, device=rays_o.device)
+    args, workspace = _render_args((rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
+                                    hann_w, nr_packed, cnl_packed, bgcolor), workspace,
+                                   lib.hnrf_render_term_workspace_bytes(R, S))
     dev = rays_o.device
     out = {'rgb': torch.empty(R, 3, device=dev), 'alpha': torch.empty(R, device=dev), 'depth': torch.empty(R, device=dev)}
     ev = torch.empty(1, dtype=torch.int32, device=dev) if want_count else None
-    _lib.check(lib.hnrf_render_rays_term_fwd(_ptr(rays_o), _ptr(rays_d), _ptr(near), _ptr(far), _ptr(t_rand),
-                                             _ptr(motion_Rs), _ptr(motion_Ts), _ptr(vol), _ptr(bbox_min),
-                                             _ptr(bbox_scale), _ptr(hann_w), _ptr(nr_packed), _ptr(cnl_packed),
-                                             _ptr(bgcolor), _mode_arg(mode), float(cull_eps), float(term_eps), R, S,
+    _lib.check(lib.hnrf_render_rays_term_fwd(*map(_ptr, args), _mode_arg(mode), float(cull_eps), float(term_eps), R, S,
                                              motion_Rs.shape[0], vol.shape[-1], _ptr(workspace),
                                              workspace.numel() * workspace.element_size(), _ptr(out['rgb']),
                                              _ptr(out['alpha']), _ptr(out['depth']),

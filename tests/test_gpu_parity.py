@@ -196,21 +196,43 @@ def test_f16_range_guard_of_inference(which, diag, gpu_net, golden_frame, seeded
         gpu_net._forced_mode, gpu_net._range_watch, gpu_net._cnl_pack = None, None, None
 
 
-def test_lean_path_equals_diagnostic_path(gpu_net, golden_frame):
-    """hnrf_render_rays_fwd (workspace path, 3 outputs) == the 11-output path."""
-    from humannerf_amd import config
+def test_lean_path_equals_diagnostic_path(gpu_net, golden_frame, monkeypatch):
+    """hnrf_render_rays_fwd (workspace path, 3 outputs) == the 11-output path.  And the routing of Network.forward:
+    with diagnostics on, term_eps changes nothing; ops.render_rays on one ray chunk of the frame gives the lean
+    forward's rows of that chunk."""
+    from humannerf_amd import config, ops
+    frames, render_frame, chunk = [], ops.render_frame, config.cfg.chunk
+
+    def spy(*a, **k):                                             # keeps the positional arguments of every frame
+        frames.append(a)
+        return render_frame(*a, **k)
+    monkeypatch.setattr(ops, 'render_frame', spy)
     config.cfg.perturb = 0.
     try:
         with torch.no_grad():
             full = gpu_net(**frame_to_gpu(golden_frame), iter_val=1e7)
+            config.cfg.amd.term_eps = 1e-3
+            full_term = gpu_net(**frame_to_gpu(golden_frame), iter_val=1e7)
+            config.cfg.amd.term_eps = 0.0
             config.cfg.amd.diagnostics = False
             lean = gpu_net(**frame_to_gpu(golden_frame), iter_val=1e7)
+            config.cfg.chunk = 96                                 # 256 rays: chunks of 96, 96, 64
+            lean_chunked = gpu_net(**frame_to_gpu(golden_frame), iter_val=1e7)
+            a = frames[-1]
+            r0, r1 = 96, 192
+            rows = lambda t: None if t is None else t[r0:r1].contiguous()
+            one = ops.render_rays(*map(rows, a[:5]), *a[5:15], a[16].partition('+')[0])
     finally:
-        config.cfg.amd.diagnostics = True
+        config.cfg.amd.diagnostics, config.cfg.amd.term_eps, config.cfg.chunk = True, 0.0, chunk
         config.cfg.perturb = 1.0
     assert set(lean) == {'rgb', 'alpha', 'depth'}
     for k in lean:
         assert torch.equal(lean[k], full[k])
+    assert set(full_term) == set(full) and len(full) == 11
+    for k in full:
+        assert torch.equal(full_term[k], full[k]), k
+    for k in lean:
+        assert torch.equal(one[k], lean_chunked[k][r0:r1]), k
 
 
 # ------------------------------------------------------------------ per-kernel vs the oracle
