@@ -349,8 +349,8 @@ __device__ __forceinline__ void epi_pair(const f32x16& a1, const f32x16& a2, int
 // products wh . xl then carry no 2^11 and go into the FIRST accumulator; wl keeps its lift (weights are packed
 // offline and 2^-12 |w| would sit far down in the subnormals).
 // f16-range guard of the inference kernels.  The split v = hi + lo holds below the f16 range; the epilogue clamps
-// post-ReLU activations at 65504, and a checkpoint whose hidden activations get there would render a wrong image without
-// any error.  GUARDED kernel instances (template parameter GUARD, Pipe::guard) therefore look at every finished
+// post-ReLU activations at 65504, and a checkpoint whose hidden activations get there -- or only past 128, where the
+// un-lifted weights stop being fp32-accurate (SAT_HALF below) -- would render a wrong image without any error.  GUARDED kernel instances (template parameter GUARD, Pipe::guard) therefore look at every finished
 // B-operand fragment (every fourth pair): its 8 non-negative halves are folded with three v_pk_max_u16 and compared --
 // as integers, which order like the values and put +inf / NaN on top -- against SAT_HALF; the verdict lands in an SGPR
 // pair (no VGPR lives on: these kernels sit at the 256 + 256 register limit, one more live VGPR sent the two-group
@@ -363,7 +363,12 @@ __device__ __forceinline__ void epi_pair(const f32x16& a1, const f32x16& a2, int
 // v_max_f32 drops NaN); (2) a v_max3_f32 running maximum: 4 VALU per 8 values but one more live VGPR (see above).
 // The inline asm needs its "scc" clobber: s_or_b64 writes SCC, and without it hipcc scheduled the block between an
 // s_add_u32 / s_addc_u32 pair -- a hit then added a carry, i.e. 4 GiB, to a weight pointer (memory fault).
-constexpr unsigned SAT_HALF = 0x7B53u;      // f16(60000)
+// The threshold is the edge of the ACCURACY envelope, not of the f16 range: the forward images keep a weight's low part
+// un-lifted (WLO_UNLIFTED above), so |w| < 0.25 carries an absolute error of up to 2^-25, and an activation a multiplies
+// it into up to |a| 2^-25 per product.  Measured (tests/test_gpu_f16_range.py, an activation carried into the output by
+// weights c / a): fp32-class up to a = 100 (1.5e-6 relative, 4x CPU fp32 + 1e-6 allowed), 2.3e-5 at 1e3, 6.8e-4 at
+// 5e4 -- the old threshold of 6e4 let all of that through unreported.  Reporting from 128 on costs no instruction.
+constexpr unsigned SAT_HALF = 0x5800u;      // f16(128)
 __device__ __forceinline__ void sat_check_frag(const h16x8& hi, unsigned long long& sflag) {
     typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
     typedef unsigned short u16x8 __attribute__((ext_vector_type(8)));

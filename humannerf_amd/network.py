@@ -481,8 +481,9 @@ def check_config_is_built(config):
 
 
 class ActivationRangeError(RuntimeError):
-    """A hidden activation of one of the two MLPs left the range of the split-f16 arithmetic (|x| >= 6e4; the kernels
-    clamp at 65504): the frames rendered with these weights in mlp_mode 'f16x3' are not the network's output."""
+    """A hidden activation of one of the two MLPs left the range in which the split-f16 arithmetic is fp32-accurate
+    (|x| >= 128, hnrf.h; the kernels clamp at 65504): the frames rendered with these weights in mlp_mode 'f16x3' are not
+    the network's output."""
 
 
 class Network(nn.Module):
@@ -603,8 +604,9 @@ class Network(nn.Module):
         self.f16_range_hits += 1
         self._cnl_pack = None                                   # (a fresh pack clears the canonical image's word)
         policy = amd_option('on_f16_range', 'raise')
-        msg = ("a hidden activation of the %s MLP reached the f16 range (|x| >= 6e4) in mlp_mode 'f16x3': the frames "
-               "rendered with these weights are clamped, not the network's output; render with cfg.amd.mlp_mode = 'f32'"
+        msg = ("a hidden activation of the %s MLP left the range of the split-f16 arithmetic (|x| >= 128) in mlp_mode "
+               "'f16x3': the frames rendered with these weights are not the network's output to fp32 accuracy; render "
+               "with cfg.amd.mlp_mode = 'f32'"
                % (' and the '.join(n for n, h in (('canonical', cnl_hit), ('non-rigid', nr_hit)) if h)))
         if policy == 'ignore':
             return True

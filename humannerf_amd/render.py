@@ -518,10 +518,14 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
             ev.record(copy_stream)
         return [item['idx'], hosts, ev, item, wid]
 
+    def mlp_mode():
+        return network._mlp_mode() if hasattr(network, '_mlp_mode') else None
+
     def rerender_pending():
         """A range hit with cfg.amd.on_f16_range = 'f32' has switched the network to the exact kernels: every frame not
         yet handed over was rendered with the clamped ones (or has no verdict yet) and is rendered again; frames
-        handed over earlier had their verdict and were fine."""
+        handed over earlier had their verdict and were fine.  A hit that left the mode as it was ('ignore') renders
+        nothing again: the frames are delivered as they are."""
         for k, entry in enumerate(pending):
             if entry[2] is not None:
                 entry[2].synchronize()
@@ -532,9 +536,9 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
 
     def verdicts(wait, upto=None):
         if guard:
-            hits = network.f16_range_hits
+            hits, mode = network.f16_range_hits, mlp_mode()
             network.check_f16_range(wait=wait, upto=upto)
-            if network.f16_range_hits != hits:
+            if network.f16_range_hits != hits and mlp_mode() != mode:
                 rerender_pending()
 
     def known(entry):
@@ -548,11 +552,11 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
                           workers=workers)
     try:
         for item in pre:
-            hits = network.f16_range_hits if guard else 0
+            hits, mode = (network.f16_range_hits, mlp_mode()) if guard else (0, None)
             t0 = time.perf_counter()
             pending.append(render(item))                                 # (forward looks at the verdicts that have arrived)
             t_submit.append(time.perf_counter() - t0)
-            if guard and network.f16_range_hits != hits:
+            if guard and network.f16_range_hits != hits and mlp_mode() != mode:
                 rerender_pending()
             # a frame is handed over once its verdict is known and its copy has landed; at most three in flight
             while pending and (len(pending) > 3 or (known(pending[0]) and (pending[0][2] is None or pending[0][2].query()))):

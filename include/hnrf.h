@@ -53,10 +53,14 @@ const char* hnrf_last_error(void);
  * chains, mlp_rgb_sigma.py:163-198 / mlp_offset.py:74-84, have no such limit).  Every packed image therefore carries a
  * STATUS WORD (uint32 at byte offset hnrf_*_status_offset(mode) of the caller's `packed` buffer; zeroed by every
  * hnrf_*_pack): hnrf_canonical_fwd / hnrf_nonrigid_fwd, their sparse forms and the hnrf_render_* entries OR
- * HNRF_STATUS_F16_RANGE into it when any activation reached 6e4.  This is the one place where a forward call
+ * HNRF_STATUS_F16_RANGE into it when any activation reached 128.  This is the one place where a forward call
  * writes into `packed`.  The caller reads the word when it likes (no call synchronises) and re-renders with
  * HNRF_MLP_F32, which has no such limit (offset 0 = the mode has no status word).  Training has its own guard on
- * the saved activations (humannerf_amd/autograd.py OperandRangeGuard). */
+ * the saved activations (humannerf_amd/autograd.py OperandRangeGuard).
+ * Why 128 and not the f16 range: the forward images store a weight's low part un-lifted, w = hi + f16(w - hi), so a
+ * weight below 0.25 keeps an absolute error of up to 2^-25 and an activation a turns it into up to |a| 2^-25 per
+ * product.  An activation carried into the output by small weights (tests/test_gpu_f16_range.py) stays fp32-accurate
+ * up to 100 and is off by 2.3e-5 of the output at 1e3, 6.8e-4 at 5e4.  The contract: no report -> fp32 accuracy. */
 #define HNRF_STATUS_F16_RANGE 1u
 size_t hnrf_canonical_status_offset(int mode);
 size_t hnrf_nonrigid_status_offset(int mode);

@@ -199,9 +199,10 @@ def fourier_pe(x, multires):
 
 
 # -------------------------------------------------------------- a11 / a13
-def non_rigid_mlp(state, pe, cond, x_skel):
+def non_rigid_mlp(state, pe, cond, x_skel, hidden=None):
     """NonRigidMotionMLP.forward, non_rigid_motion_mlps/mlp_offset.py:74-114
-    (default branch).  Skip input order is [h, pe]."""
+    (default branch).  Skip input order is [h, pe].  ``hidden``: list that
+    receives every post-ReLU activation (P, 128), first layer first."""
     p = 'non_rigid_mlp.module.block_mlps.'
     idx = sorted(int(k[len(p):].split('.')[0]) for k in state if k.startswith(p) and k.endswith('.weight'))
     h = torch.cat([cond.expand(pe.shape[0], -1), pe], dim=-1)
@@ -212,12 +213,15 @@ def non_rigid_mlp(state, pe, cond, x_skel):
         h = _lin(state, p + str(i), h)
         if n < len(idx) - 1:
             h = torch.relu(h)
+            if hidden is not None:
+                hidden.append(h)
     return x_skel + h, h
 
 
-def canonical_mlp(state, pe):
+def canonical_mlp(state, pe, hidden=None):
     """CanonicalMLP.forward default branch, canonical_mlps/mlp_rgb_sigma.py:
-    132-198.  Skip input order is [pe, h]."""
+    132-198.  Skip input order is [pe, h].  ``hidden``: list that receives
+    every post-ReLU activation (P, 256), first layer first."""
     p = 'cnl_mlp.module.pts_linears.'
     idx = sorted(int(k[len(p):].split('.')[0]) for k in state if k.startswith(p) and k.endswith('.weight'))
     h = pe
@@ -226,6 +230,8 @@ def canonical_mlp(state, pe):
         if n > 0 and W.shape[1] == h.shape[1] + pe.shape[1]:
             h = torch.cat([pe, h], dim=-1)             # layers_to_cat_input
         h = torch.relu(_lin(state, p + str(i), h))
+        if hidden is not None:
+            hidden.append(h)
     return _lin(state, 'cnl_mlp.module.output_linear.0', h)
 
 
