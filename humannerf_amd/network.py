@@ -908,3 +908,24 @@ class Network(nn.Module):
         with torch.no_grad():
             verts = verts.to(device=self._mesh_device(), dtype=torch.float32).contiguous()
             return ops.forward_skin(verts, motion_Rs, motion_Ts, vol, bmin, scale)
+
+    def render_mesh(self, verts, faces, colors, frame, iter_val=1e7, posed=False, **raster_options):
+        """A picture of the mesh in a frame's pose and camera (humannerf_amd.raster, hnrf_raster_mesh): the canonical
+        vertices are posed with pose_vertices unless ``posed``; ``K``, ``E``, ``img_height``, ``img_width`` and
+        ``bgcolor`` (0..255 in frame dicts) come from the frame -- a camera frame (dataset.Subject frames,
+        scene.synthetic_frame(camera_only=True)); host-ray frames carry no camera.  ``raster_options``: cull, shade,
+        z_near.  Returns dict(rgb (H, W, 3), alpha, depth (H, W), tri_id (H, W) int32) on the device."""
+        import numpy as np
+        from . import raster
+        from ._lib import HnrfError
+        for k in ('K', 'E', 'img_height', 'img_width', 'bgcolor'):
+            if k not in frame:
+                raise HnrfError('render_mesh: the frame has no %r (a camera frame is needed, not a host-ray frame)' % k)
+        dev = self._mesh_device()
+        verts = verts.to(device=dev, dtype=torch.float32).contiguous()
+        if not posed:
+            verts = self.pose_vertices(verts, frame, iter_val)
+        host = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else a
+        bg = np.asarray(host(frame['bgcolor']), dtype=np.float32).reshape(3) / np.float32(255.)
+        return raster.rasterize(verts, faces, colors, host(frame['K']), host(frame['E']), int(frame['img_height']),
+                                int(frame['img_width']), bgcolor=bg, **raster_options)

@@ -834,3 +834,43 @@ def forward_skin(verts, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale):
     _lib.check(lib.hnrf_forward_skin(_ptr(verts), verts.shape[0], _ptr(motion_Rs), _ptr(motion_Ts), _ptr(vol), B, G,
                                      _ptr(bbox_min), _ptr(bbox_scale), _ptr(out), _stream()), 'hnrf_forward_skin')
     return out
+
+
+_raster_ws = {}                       # (V, F, H, W, device) -> workspace of the last call of that shape
+
+
+def raster_workspace(V, F, H, W, device):
+    """Workspace of hnrf_raster_mesh, kept per shape (a frame loop rasterises one mesh into one image size)."""
+    key = (int(V), int(F), int(H), int(W), torch.device(device))
+    ws = _raster_ws.get(key)
+    if ws is None:
+        need = _lib.load().hnrf_raster_workspace_bytes(int(V), int(F), int(H), int(W))
+        if need == 0:
+            raise _lib.HnrfError(f'raster: V={V} F={F} image {H}x{W} out of range')
+        if len(_raster_ws) >= 8:
+            _raster_ws.clear()
+        ws = _raster_ws[key] = torch.empty(need // 4 + 64, device=device)
+    return ws
+
+
+def raster_mesh(verts, faces, colors, cam, H, W, z_near, flags):
+    """hnrf_raster_mesh: verts (V, 3) fp32, faces (F, 3) int32, colors (V, 3) fp32 or None (shade normal), ``cam`` the
+    24 floats K | R | T | bgcolor on the device, ``flags`` cull | shade (hnrf.h).  Returns dict(rgb (H, W, 3), alpha,
+    depth (H, W), tri_id (H, W) int32).  No synchronisation."""
+    lib = _lib.load()
+    _chk(verts, colors, cam)
+    if not (faces.is_cuda and faces.dtype == torch.int32 and faces.is_contiguous()):
+        raise _lib.HnrfError('raster_mesh: faces must be a contiguous int32 tensor on the GPU')
+    assert verts.dim() == 2 and verts.shape[1] == 3 and faces.dim() == 2 and faces.shape[1] == 3 and cam.numel() == 24
+    assert colors is None or colors.shape == verts.shape
+    dev = verts.device
+    V, F = verts.shape[0], faces.shape[0]
+    ws = raster_workspace(V, F, H, W, dev)
+    out = {'rgb': torch.empty(H, W, 3, device=dev), 'alpha': torch.empty(H, W, device=dev),
+           'depth': torch.empty(H, W, device=dev), 'tri_id': torch.empty(H, W, dtype=torch.int32, device=dev)}
+    base = cam.data_ptr()
+    _lib.check(lib.hnrf_raster_mesh(_ptr(verts), V, faces.data_ptr(), F, _ptr(colors), base, base + 36, base + 72,
+                                    base + 84, H, W, float(z_near), int(flags), _ptr(out['rgb']), _ptr(out['alpha']),
+                                    _ptr(out['depth']), out['tri_id'].data_ptr(), _ptr(ws), ws.numel() * 4, _stream()),
+               'hnrf_raster_mesh')
+    return out

@@ -10,6 +10,7 @@ render.ImageWriter / MetricsWriter on worker threads.
   run_freeview   run.py:67-170    one training frame seen from a camera orbiting the subject
   run_tpose      run.py:178-183   the canonical pose on a turntable, non-rigid motion off
   run_mesh       (no counterpart) the canonical body as a coloured triangle mesh, and that mesh skinned into frames
+  run_mesh_render (no counterpart) the movement / freeview / tpose sequences as rasterised pictures of that mesh: a preview
 
 Output layout as in the reference: ``<logdir>/<load_net><eval_output_tag>/<folder>/NAME.png`` plus
 ``<folder>-metrics.perimg.txt / .average.txt`` (movement) and the stacked frames (MP4 when imageio is importable).
@@ -144,3 +145,81 @@ def run_mesh(network, subject, frames=(), resolution=256, level=None, logdir=Non
         written[name] = os.path.join(out_dir, name + '.ply')
         mesh.write_ply(written[name], network.pose_vertices(verts, frame).cpu().numpy(), faces_h, colors_h)
     return written
+
+
+def run_mesh_render(network, subject, kind='movement', resolution=256, level=None, logdir=None, render_folder_name=None,
+                    test_num=-1, frame_idx=None, total_frames=None, image_size=None, shade='color', cull='back'):
+    """The movement / freeview / tpose sequences as pictures of the posed canonical mesh instead of volume renders: a
+    preview (Network.render_mesh: forward skinning, the non-rigid offsets are not inverted; no anti-aliasing).  The mesh
+    is extracted once (Network.extract_canonical_mesh as in run_mesh), then every frame of the loop -- camera only, no
+    image is loaded -- is posed, rasterised, quantised on the device and written by render.ImageWriter under
+    ``<out>/mesh_<kind>/`` (freeview: ``mesh_freeview_<frame_idx>``) with the volume loops' frame names.  Single rank.
+    Returns {'frames', 'images', 'image_dir', 'stack'} like the volume loops."""
+    import torch
+    if kind not in ('movement', 'freeview', 'tpose'):
+        raise ValueError("kind must be 'movement', 'freeview' or 'tpose'")
+    bbox = subject.canonical_bbox
+    verts, faces, colors = network.extract_canonical_mesh(
+        bbox['min_xyz'], bbox['max_xyz'], subject.motion_weights_priors, resolution=resolution,
+        level=network.MESH_LEVEL if level is None else level)
+    if kind == 'movement':
+        n = len(subject) if test_num < 0 else min(test_num, len(subject))
+        size = lambda i: image_size if image_size is not None else subject.image_size(subject.framelist[i])
+        frames = _Frames(n, lambda i: subject.movement_frame(i, image_size=size(i)))
+        names = [str(subject.framelist[i]).replace('/', '-') for i in range(n)]
+        folder = render_folder_name or 'mesh_movement'
+    elif kind == 'freeview':
+        frame_idx = int(cfg.get('freeview', {}).get('frame_idx', 0)) if frame_idx is None else int(frame_idx)
+        n = int(cfg.get('render_frames', 100)) if total_frames is None else int(total_frames)
+        if image_size is None:
+            image_size = subject.image_size(subject.framelist_all[frame_idx])
+        frames = _Frames(n, lambda i: subject.freeview_frame(i, n, train_frame_idx=frame_idx, image_size=image_size,
+                                                             bgcolor=cfg.bgcolor))
+        names = [None] * n
+        folder = render_folder_name or 'mesh_freeview_%d' % frame_idx
+    else:
+        n = int(cfg.get('render_frames', 100)) if total_frames is None else int(total_frames)
+        size = None if image_size is None else int(np.max(image_size))           # (the T-pose camera is square)
+        frames = _Frames(n, lambda i: subject.tpose_frame(i, n, image_size=size, bgcolor=cfg.bgcolor))
+        names = [None] * n
+        folder = render_folder_name or 'mesh_tpose'
+    writer = render.ImageWriter(_output_dir(logdir), folder)
+    device = verts.device
+    copy_stream = torch.cuda.Stream(device=device)
+    pool = render._PinnedPool()
+    images, pending = {}, []                        # pending: [idx, pinned rgb, pinned alpha, event], oldest first
+
+    def deliver(entry):
+        i, h_rgb, h_alpha, ev = entry
+        ev.synchronize()                            # the one wait per frame: its copy has landed
+        rgb8, alpha8 = h_rgb.numpy().copy(), h_alpha.numpy().copy()
+        pool.give(h_rgb)
+        pool.give(h_alpha)
+        images[i] = rgb8
+        writer.append(_panels(rgb8, alpha8), img_name=names[i])
+
+    network.eval()
+    # the subject's priors, uploaded once: Network keeps the weight volume of a resident tensor without comparing it
+    priors = torch.as_tensor(subject.motion_weights_priors).to(device=device, dtype=torch.float32)
+    for i in range(n):
+        frame = dict(frames[i], motion_weights_priors=priors)
+        out = network.render_mesh(verts, faces, colors, frame, iter_val=float(cfg.get('eval_iter', 1e7)),
+                                  shade=shade, cull=cull)
+        imgs = [render.to_8b_image(out['rgb']), render.to_8b3ch_image(out['alpha']).contiguous()]
+        copy_stream.wait_stream(torch.cuda.current_stream(device))
+        hosts = []
+        with torch.cuda.stream(copy_stream):
+            for im in imgs:
+                h = pool.take(im.shape)
+                h.copy_(im, non_blocking=True)
+                im.record_stream(copy_stream)
+                hosts.append(h)
+            ev = torch.cuda.Event()
+            ev.record(copy_stream)
+        pending.append([i] + hosts + [ev])
+        while len(pending) > 2:                     # two frames in flight: the copy of one overlaps the next raster
+            deliver(pending.pop(0))
+    while pending:
+        deliver(pending.pop(0))
+    stack = writer.finalize()
+    return {'frames': list(range(n)), 'images': images, 'image_dir': writer.image_dir, 'stack': stack}

@@ -449,6 +449,46 @@ int hnrf_mesh_emit(const float* density, int N, float level, const float* bbox_m
 int hnrf_forward_skin(const float* verts, int64_t V, const float* motion_Rs, const float* motion_Ts, const float* vol,
                       int B, int G, const float* bbox_min, const float* bbox_scale, float* out, void* stream);
 
+/* ---- rasteriser for vertex-coloured triangle meshes (no counterpart in the reference; humannerf_amd/raster.py) ----
+ * hnrf_raster_mesh: verts [V,3] fp32 world positions, faces [F,3] int32, colors [V,3] fp32 (nullable when the shade
+ *  is the normal), camera K [9], R [9] (row-major 3x3), T [3], bgcolor [3] (0..1): device pointers, nothing is read
+ *  on the host.  Every float operation rounded on its own, sums associated left to right as written (raster.py
+ *  restates all of it in numpy, bit for bit):
+ *  - projection in fp32: xc_i = ((R_i0 x + R_i1 y) + R_i2 z) + T_i, p_i = (K_i0 xc_0 + K_i1 xc_1) + K_i2 xc_2,
+ *    u = p_0 / p_2, v = p_1 / p_2, z = xc_2, w = 1 / z; pixel (i, j) is sampled at screen position (i, j) exactly;
+ *  - positions snapped to 1/256 pixel, X = rint(256 u) (half to even); coverage is 64-bit integer arithmetic: with
+ *    a = (X1 - X0)(Y2 - Y0) - (Y1 - Y0)(X2 - X0), s = sign(a), the edge values E0 = s cross(P2 - P1, S - P1),
+ *    E1 = s cross(P0 - P2, S - P2), E2 = s cross(P1 - P0, S - P0) at S = (256 i, 256 j), cross(d, q) = d_x q_y - d_y q_x;
+ *  - a triangle is dropped whole when an index is outside [0, V) (nothing is read there), when a vertex fails
+ *    z >= z_near && |u| <= 16384 && |v| <= 16384 && w > 0 (NaN fails; no clipping), or when a = 0;
+ *  - top-left fill rule in the triangle's own positive orientation (independent of the winding): inside iff for every
+ *    edge E_k > 0, or E_k = 0 and the oriented edge vector d has d_y < 0 or (d_y = 0 and d_x > 0); triangles sharing an
+ *    edge never both own a sample on it and never both miss it;
+ *  - flags & HNRF_RASTER_CULL_MASK: NONE (two-sided) | BACK | FRONT; front-facing (the winding normal
+ *    (v1 - v0) x (v2 - v0) faces the camera) is (a < 0) != (det(K R) < 0), the determinant in fp32 on the device;
+ *  - inverse depth per sample in fp64: b_k = E_k / |a|, w = (w0 + b1 (w1 - w0)) + b2 (w2 - w0), rounded to fp32; the
+ *    visible triangle has the largest w, among equal w the lowest index: key = bits(w) << 32 | 0xFFFFFFFF - index is
+ *    folded into a 64-bit-per-pixel buffer with an atomic maximum, so the result does not depend on the order of
+ *    processing and is bit-reproducible;
+ *  - outputs [H,W] (each nullable): tri_id int32 (-1 = background), depth = 1 / w (0 on background), alpha 1 / 0,
+ *    rgb [H,W,3] = bgcolor on background, else q_k = b_k w_k, ((q0 c0 + q1 c1) + q2 c2) / ((q0 + q1) + q2) in fp64
+ *    rounded to fp32 (perspective-correct), or with HNRF_RASTER_SHADE_NORMAL 0.5 + 0.5 n, n = R m, m = the normalised
+ *    winding normal of the fp32 world positions in fp32 (0 when its length is 0 or not finite), not flipped toward
+ *    the viewer.
+ *  1 <= H, W <= 8192, V, F < 2^31, z_near > 0, known flags (HNRF_E_UNSUPPORTED otherwise; null pointers HNRF_E_ARG);
+ *  V == 0 or F == 0 renders the background.  `workspace`: hnrf_raster_workspace_bytes(V, F, H, W), 256-byte aligned
+ *  (0 for arguments out of range).  No allocation, no synchronisation. */
+#define HNRF_RASTER_CULL_NONE    0
+#define HNRF_RASTER_CULL_BACK    1
+#define HNRF_RASTER_CULL_FRONT   2
+#define HNRF_RASTER_CULL_MASK    3
+#define HNRF_RASTER_SHADE_NORMAL 4
+size_t hnrf_raster_workspace_bytes(int64_t V, int64_t F, int H, int W);
+int hnrf_raster_mesh(const float* verts, int64_t V, const int* faces, int64_t F, const float* colors, const float* K,
+                     const float* R, const float* T, const float* bgcolor, int H, int W, float z_near, int flags,
+                     float* rgb, float* alpha, float* depth, int* tri_id, void* workspace, size_t workspace_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif
