@@ -80,14 +80,17 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
         if (s >= S) { gw[i] = 0.f; wv[i] = 0.f; }
         loc += gw[i] * wv[i];
     }
-    // exclusive suffix sum over lanes of `loc`
+    // exclusive suffix sum over lanes of `loc`: the inclusive sum of the NEXT lane.  (Not `suf - loc`: behind an opaque
+    // sample the later lanes' terms are ~1e-10 of this lane's, the subtraction would keep none of their bits, and the
+    // division by t = 1e-10 below brings them back to the size of the result.)
     float suf = loc;
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) {
         const float o = __shfl_down(suf, off, 64);
         if (lane + off < 64) suf += o;
     }
-    float after = suf - loc;   // sum over later lanes
+    float after = __shfl_down(suf, 1, 64);   // sum over later lanes
+    if (lane == 63) after = 0.f;
 #pragma unroll
     for (int i = SPL - 1; i >= 0; --i) {
         const int s = lane * SPL + i;

@@ -191,9 +191,18 @@ __global__ __launch_bounds__(256) void mlp_dw16_kernel(const float* __restrict__
     // power-of-two scale of dZ: largest magnitude -> [2^7, 2^8)
     int ex = 0;
     float amax = 0.f;
-    for (int i = 0; i < n_amax; ++i) amax = fmaxf(amax, dz_amax[i]);   // uniform address: scalar loads
-    if (amax > 0.f) (void)frexpf(amax, &ex);
-    const float scale = ldexpf(1.0f, 8 - ex), descale = ldexpf(1.0f, ex - 8);
+    // (maximum of the words: the same order as the floats for magnitudes, and a NaN, which fmaxf would drop, is the largest)
+    unsigned int amax_u = 0u;
+    for (int i = 0; i < n_amax; ++i) {                                   // uniform address: scalar loads
+        const unsigned int u = __float_as_uint(dz_amax[i]) & 0x7fffffffu;
+        amax_u = u > amax_u ? u : amax_u;
+    }
+    amax = __uint_as_float(amax_u);
+    const bool finite = amax < 3.0e38f;
+    if (amax > 0.f && finite) (void)frexpf(amax, &ex);
+    // a non-finite bound (the chain kernels store NaN maxima for a non-finite incoming gradient): NaN out, as from
+    // the fp32 kernels -- the operand clamp of split_pair would turn NaN operands into finite numbers
+    const float scale = ldexpf(1.0f, 8 - ex), descale = finite ? ldexpf(1.0f, ex - 8) : __builtin_nanf("");
 
     f32x16 acc[OT][IT];
 #pragma unroll
@@ -1396,6 +1405,22 @@ extern "C" int hnrf_nonrigid_bwd_pack(const float* const* weights, int mode, voi
     return launch_pack_bwd(PackBwd{weights[0], 128, 105, 2, 16, PE_NONRIGID, 69, 0, NB_L0P}, out, st);
 }
 
+// dz_amax before a chain: zeros for the atomicMax of the stages -- or, when the bound of the incoming gradient is not
+// finite (an overflowed loss: the split-f16 chain's scale is NaN and so is every dZ it stores), NaN: the stages' fmaxf drops
+// NaNs and would leave a maximum of 0, while a NaN word wins every unsigned atomicMax against a finite maximum and makes
+// hnrf_mlp_dw's split-f16 kernel return NaN (its operand clamp would otherwise turn NaN operands into finite gradients).
+__global__ void amax_init_kernel(float* __restrict__ dz_amax, int n, const float* __restrict__ amax_in) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool finite = amax_in == nullptr || *amax_in < 3.0e38f;
+    if (i < n) dz_amax[i] = finite ? 0.f : __builtin_nanf("");
+}
+
+static int init_dz_amax(float* dz_amax, int layers, const float* amax_in, hipStream_t st, const char* what) {
+    const int n = layers * HNRF_AMAX_SLOTS;
+    hipLaunchKernelGGL(amax_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dz_amax, n, amax_in);
+    return check_launch(what);
+}
+
 extern "C" int hnrf_canonical_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed,
                                   int mode, const float* d_raw_amax, int64_t P, float* dZ, float* d_xyz,
                                   float* dz_amax, void* stream) {
@@ -1413,10 +1438,8 @@ extern "C" int hnrf_canonical_bwd(const float* xyz, const float* d_raw, const ui
     HNRF_REQUIRE(blocks < 2147483647LL, HNRF_E_ARG, "hnrf_canonical_bwd: too many samples");
     if (mode == HNRF_MLP_F16X3_H)
         return canonical16_bwd(xyz, d_raw, relu_bits, packed, P, d_raw_amax, dZ, d_xyz, dz_amax, 1, (hipStream_t)stream);
-    if (dz_amax && hipMemsetAsync(dz_amax, 0, 8 * HNRF_AMAX_SLOTS * sizeof(float), (hipStream_t)stream) != hipSuccess) {
-        set_error("hnrf_canonical_bwd: memset failed");
-        return HNRF_E_LAUNCH;
-    }
+    if (dz_amax)
+        if (int rc = init_dz_amax(dz_amax, 8, mode == HNRF_MLP_F16X3 ? d_raw_amax : nullptr, (hipStream_t)stream, "hnrf_canonical_bwd (maxima)")) return rc;
     if (mode == HNRF_MLP_F16X3)
         return canonical16_bwd(xyz, d_raw, relu_bits, packed, P, d_raw_amax, dZ, d_xyz, dz_amax, 0, (hipStream_t)stream);
     hipLaunchKernelGGL(canonical_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, xyz,
@@ -1443,10 +1466,8 @@ extern "C" int hnrf_nonrigid_bwd(const float* x_skel, const float* hann_w, const
     if (mode == HNRF_MLP_F16X3_H)
         return nonrigid16_bwd(x_skel, hann_w, d_xyz, relu_bits, packed, P, d_xyz_amax, dZ, d_x_skel, dz_amax, 1,
                               (hipStream_t)stream);
-    if (dz_amax && hipMemsetAsync(dz_amax, 0, 6 * HNRF_AMAX_SLOTS * sizeof(float), (hipStream_t)stream) != hipSuccess) {
-        set_error("hnrf_nonrigid_bwd: memset failed");
-        return HNRF_E_LAUNCH;
-    }
+    if (dz_amax)
+        if (int rc = init_dz_amax(dz_amax, 6, mode == HNRF_MLP_F16X3 ? d_xyz_amax : nullptr, (hipStream_t)stream, "hnrf_nonrigid_bwd (maxima)")) return rc;
     if (mode == HNRF_MLP_F16X3)
         return nonrigid16_bwd(x_skel, hann_w, d_xyz, relu_bits, packed, P, d_xyz_amax, dZ, d_x_skel, dz_amax, 0,
                               (hipStream_t)stream);

@@ -235,7 +235,15 @@ int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, const float*
 int hnrf_canonical_fwd_train(const float* xyz, const void* packed, int mode, int64_t P,
                              float* raw, float* pe_out, float* acts, uint32_t* relu_bits, void* stream);
 /* pe_out [P,36] (hannw_fourier.py order, window weights applied), acts [6][P][128],
- * relu_bits [6][P][4] uint32. */
+ * relu_bits [6][P][4] uint32.
+ * Both entry points write EVERY element of their outputs that a later kernel reads, whatever the buffers held before
+ * (nothing is accumulated into, nothing needs to be cleared): rows 0 .. P-1 of raw / xyz / offsets, pe_out, acts and
+ * relu_bits, and in HNRF_MLP_F16X3_H also
+ *   - the padding columns of pe_out (63 of the canonical, 36..63 of the non-rigid matrix): zeros;
+ *   - the padding rows P .. ceil(P / 128) * 128 - 1 of every blocked acts layer: a copy of row P-1 (finite values; the
+ *     weight-gradient kernel multiplies them by the zero rows of dZ).
+ * The non-rigid forward runs eight waves per workgroup when P is a multiple of 256 and four otherwise; the two forms
+ * return the same bits for the same sample. */
 int hnrf_nonrigid_fwd_train(const float* x_skel, const float* hann_w, const void* packed,
                             int mode, int64_t P, float* xyz, float* offsets,
                             float* pe_out, float* acts, uint32_t* relu_bits, void* stream);
@@ -352,8 +360,23 @@ int hnrf_nonrigid_bwd_pack(const float* const* weights, int mode, void* packed, 
 /* dz_amax (nullable): [L][HNRF_AMAX_SLOTS] floats; max over row l bounds |dZ_l| (the scale input of
  * hnrf_mlp_dw in HNRF_MLP_F16X3 mode). */
 #define HNRF_AMAX_SLOTS 64
-/* mode HNRF_MLP_F16X3: the chain on the split-f16 matrix pipe; d_raw_amax / d_xyz_amax = device scalar >= the
- * largest magnitude of the incoming gradient (sets its power-of-two scale), ignored in HNRF_MLP_F32. */
+/* mode HNRF_MLP_F16X3 / HNRF_MLP_F16X3_H: the chain on the split-f16 matrix pipe; d_raw_amax / d_xyz_amax = device
+ * scalar >= the largest magnitude of the incoming gradient, ignored in HNRF_MLP_F32.  The amax contract:
+ *   - it only sets a power-of-two scale (the incoming gradient is brought to |g| < 4), so the results do not depend on
+ *     the size of the gradient: g x 2^-24 and g x 2^10 give the same relative accuracy as g;
+ *   - it need not be tight.  Every factor of two of slack costs one bit of the range below the largest value: of the
+ *     22-bit split operands' 2^-14 floor in HNRF_MLP_F16X3 (harmless), of the f16 dZ stored by HNRF_MLP_F16X3_H (small
+ *     dZ reach f16 subnormals earlier).  A bound 1000 x the true maximum (10 bits) keeps dW / db within the 1e-3 the
+ *     f16 operands are specified to; keep it within that factor;
+ *   - 0 (an all-zero incoming gradient) is valid: the scale is then 4, every dZ, d_xyz and weight gradient comes out
+ *     exactly 0, d_x_skel = d_xyz bit for bit, and the per-layer scales returned in HNRF_MLP_F16X3_H are finite and > 0;
+ *   - inf or NaN (an overflowed loss; the caller's maximum of a gradient with a non-finite element) makes the scale NaN:
+ *     d_xyz / d_x_skel, dZ and every weight gradient computed from them by hnrf_mlp_dw / hnrf_mlp_dw_h contain NaN (in
+ *     HNRF_MLP_F16X3 the maxima in dz_amax are NaN, in HNRF_MLP_F16X3_H the scales are), so that a finite check of
+ *     ANY gradient tensor sees it.  Units whose ReLU is dead are masked by select and may stay 0.
+ * The padding contract: rows 0 .. P-1 of dZ and d_xyz / d_x_skel and all of dz_amax are written whatever the buffers
+ * held before; in HNRF_MLP_F16X3_H the padding rows P .. ceil(P / 128) * 128 - 1 of every blocked dZ layer are written
+ * with ZEROS (hnrf_mlp_dw_h reads whole 128-sample blocks).  Nothing is read before it is written. */
 int hnrf_canonical_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed,
                        int mode, const float* d_raw_amax, int64_t P, float* dZ, float* d_xyz, float* dz_amax,
                        void* stream);
