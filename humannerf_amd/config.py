@@ -150,6 +150,13 @@ _DEFAULTS = {
         # cache the motion-weight volume across eval-mode frames while the
         # decoder parameters and the priors tensor are unchanged.
         'cache_weight_volume': True,
+        # inference only: where a sample's raw (r, g, b, sigma) comes from.  'mlp' = the canonical MLP (the reference).
+        # 'baked' = an opt-in approximation: the MLP tabulated once per checkpoint on a bake_resolution^3 f16 lattice over
+        # the canonical bbox and interpolated trilinearly per sample (Network.bake_canonical / set_baked_grid,
+        # DESIGN.md section 4 "Baked canonical grid"); everything else of the frame stays exact.  Training ignores it;
+        # term_eps > 0 in the lean form is refused with it
+        'canonical': 'mlp',
+        'bake_resolution': 256,
         # lean rendering only: skip the MLPs for samples whose foreground likelihood (sum of
         # skinning weights) is below this; bounds |d rgb|, |d alpha| by ~2 * N_samples * cull_eps.
         # 0 = evaluate every sample exactly like the reference.  1e-9 already drops ~55 % of the

@@ -1,7 +1,8 @@
 // Error channel, version, and the inference entry points.  hnrf_render_rays_fwd (one ray chunk, rgb / alpha /
 // depth) and hnrf_render_frame_fwd (every chunk of a frame, lean or with the eight diagnostic outputs) run K1 and
 // then the same per-chunk body, render_chunk: K2 -> K3 -> K4.  Early ray termination (hnrf_term.hip) walks depth
-// slabs instead and shares only the workspace carve (render_carve, hnrf_common.h).
+// slabs instead and shares only the workspace carve (render_carve, hnrf_common.h).  The *_baked_* entries run the
+// same two bodies with the baked grid's sampler (hnrf_baked.hip) in K3's place.
 #include <stdarg.h>
 #include <string.h>
 
@@ -31,7 +32,7 @@ extern "C" size_t hnrf_render_workspace_bytes(int64_t R, int S) {
 #define HNRF_HIP(call)                                                          \
     do {                                                                        \
         if ((call) != hipSuccess) {                                             \
-            set_error("hnrf_render_frame_fwd: %s failed", #call);               \
+            set_error("hnrf_render_frame_fwd / _baked_fwd: %s failed", #call);  \
             return HNRF_E_LAUNCH;                                               \
         }                                                                       \
     } while (0)
@@ -43,11 +44,19 @@ struct DiagRows {
     float *weights, *rgb_on_rays, *cnl_xyz, *cnl_rgb, *cnl_weight, *xyz, *offsets;
 };
 
+// Where a chunk's raw comes from: the canonical MLP on `packed`, or -- grid != null -- the baked grid's sampler.
+struct CnlSource {
+    const void* packed;
+    const void* grid;
+    int N;
+    const float *bmin, *bmax;
+};
+
 // K2 -> K3 -> K4 of one ray chunk whose K1 results are in `c`: the whole of hnrf_render_rays_fwd after K1, and the body
 // of every chunk of hnrf_render_frame_fwd.  cull_eps > 0: the MLPs run only on the compacted samples.  ev_start /
-// ev_stop (hipEvent_t, nullable) are recorded right before / after the canonical-MLP launch.
+// ev_stop (hipEvent_t, nullable) are recorded right before / after the canonical-MLP (or grid sampler) launch.
 int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w, const void* nr_packed,
-                 const void* cnl_packed, const float* bgcolor, int mode, float cull_eps, int64_t R, int S, float* rgb,
+                 const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t R, int S, float* rgb,
                  float* alpha, float* depth, const DiagRows& d, void* ev_start, void* ev_stop, hipStream_t st) {
     const size_t P = (size_t)R * (size_t)S;
     const bool cull = cull_eps > 0.f, diag = d.weights != nullptr;
@@ -66,12 +75,45 @@ int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w,
         HNRF_HIP(hipMemsetAsync(d.offsets, 0, P * 12, st));
     }
     if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-    rc = hnrf_canonical_fwd_sparse(cnl_in, cnl_packed, mode, (int64_t)P, ci, cc, c.raw, st);
+    rc = cnl.grid ? baked_sample(cnl_in, cnl.grid, cnl.N, cnl.bmin, cnl.bmax, (int64_t)P, ci, cc, c.raw, st)
+                  : hnrf_canonical_fwd_sparse(cnl_in, cnl.packed, mode, (int64_t)P, ci, cc, c.raw, st);
     if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
     if (rc) return rc;
     return hnrf_composite_fwd(c.raw, c.mask, c.z_vals, rays_d, diag ? cnl_in : nullptr, bgcolor, R, S,
                               cull ? cull_eps : 0.f, rgb, alpha, depth, d.weights, d.rgb_on_rays, d.cnl_xyz, d.cnl_rgb,
                               d.cnl_weight, st);
+}
+// the baked entries' grid arguments (the sampler launches from inside render_chunk without further checks)
+int check_source(const char* who, const CnlSource& cnl) {
+    if (cnl.grid == nullptr && cnl.N == 0) {
+        HNRF_REQUIRE(cnl.packed, HNRF_E_ARG, "%s: null canonical weights", who);
+        return HNRF_OK;
+    }
+    HNRF_REQUIRE(cnl.grid && cnl.bmin && cnl.bmax, HNRF_E_ARG, "%s: null grid / grid bbox pointer", who);
+    HNRF_REQUIRE(cnl.N >= 8 && cnl.N <= 512, HNRF_E_ARG, "%s: grid N=%d out of range [8, 512]", who, cnl.N);
+    HNRF_REQUIRE(((uintptr_t)cnl.grid & 7) == 0, HNRF_E_ARG, "%s: grid must be 8-byte aligned", who);
+    return HNRF_OK;
+}
+
+int render_rays(const char* who, const float* rays_o, const float* rays_d, const float* near, const float* far,
+                const float* t_rand, const float* motion_Rs, const float* motion_Ts, const float* vol,
+                const float* bbox_min, const float* bbox_scale, const float* hann_w, const void* nr_packed,
+                const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t R, int S, int B, int G,
+                void* workspace, size_t workspace_bytes, float* rgb, float* alpha, float* depth, void* ev_mlp_start,
+                void* ev_mlp_stop, void* stream) {
+    HNRF_REQUIRE(workspace, HNRF_E_ARG, "%s: null workspace / canonical weights", who);
+    int src = check_source(who, cnl);
+    if (src) return src;
+    HNRF_REQUIRE(((uintptr_t)workspace & 255) == 0, HNRF_E_ARG, "%s: workspace must be 256-byte aligned", who);
+    HNRF_REQUIRE(workspace_bytes >= hnrf_render_workspace_bytes(R, S), HNRF_E_WORKSPACE,
+                 "%s: workspace %zu < %zu bytes", who, workspace_bytes, hnrf_render_workspace_bytes(R, S));
+    HNRF_REQUIRE(nr_packed == nullptr || hann_w != nullptr, HNRF_E_ARG, "%s: hann_w missing", who);
+    const RenderCarve c = render_carve(workspace, R, S);
+    int rc = hnrf_sample_warp_fwd(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
+                                  R, S, B, G, c.z_vals, c.x_skel, c.mask, nullptr, stream);
+    if (rc) return rc;
+    return render_chunk(c, rays_d, hann_w, nr_packed, cnl, bgcolor, mode, cull_eps, R, S, rgb, alpha, depth,
+                        DiagRows{}, ev_mlp_start, ev_mlp_stop, (hipStream_t)stream);
 }
 }  // namespace
 
@@ -82,17 +124,25 @@ extern "C" int hnrf_render_rays_fwd(const float* rays_o, const float* rays_d, co
                                     const float* bgcolor, int mode, float cull_eps, int64_t R, int S, int B, int G,
                                     void* workspace, size_t workspace_bytes, float* rgb, float* alpha, float* depth,
                                     void* ev_mlp_start, void* ev_mlp_stop, void* stream) {
-    HNRF_REQUIRE(workspace && cnl_packed, HNRF_E_ARG, "hnrf_render_rays_fwd: null workspace / canonical weights");
-    HNRF_REQUIRE(((uintptr_t)workspace & 255) == 0, HNRF_E_ARG, "hnrf_render_rays_fwd: workspace must be 256-byte aligned");
-    HNRF_REQUIRE(workspace_bytes >= hnrf_render_workspace_bytes(R, S), HNRF_E_WORKSPACE,
-                 "hnrf_render_rays_fwd: workspace %zu < %zu bytes", workspace_bytes, hnrf_render_workspace_bytes(R, S));
-    HNRF_REQUIRE(nr_packed == nullptr || hann_w != nullptr, HNRF_E_ARG, "hnrf_render_rays_fwd: hann_w missing");
-    const RenderCarve c = render_carve(workspace, R, S);
-    int rc = hnrf_sample_warp_fwd(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
-                                  R, S, B, G, c.z_vals, c.x_skel, c.mask, nullptr, stream);
-    if (rc) return rc;
-    return render_chunk(c, rays_d, hann_w, nr_packed, cnl_packed, bgcolor, mode, cull_eps, R, S, rgb, alpha, depth,
-                        DiagRows{}, ev_mlp_start, ev_mlp_stop, (hipStream_t)stream);
+    return render_rays("hnrf_render_rays_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min,
+                       bbox_scale, hann_w, nr_packed, CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor, mode,
+                       cull_eps, R, S, B, G, workspace, workspace_bytes, rgb, alpha, depth, ev_mlp_start, ev_mlp_stop,
+                       stream);
+}
+
+extern "C" int hnrf_render_rays_baked_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                          const float* t_rand, const float* motion_Rs, const float* motion_Ts,
+                                          const float* vol, const float* bbox_min, const float* bbox_scale,
+                                          const float* hann_w, const void* nr_packed, const void* grid, int grid_N,
+                                          const float* grid_bbox_min, const float* grid_bbox_max, const float* bgcolor,
+                                          int mode, float cull_eps, int64_t R, int S, int B, int G, void* workspace,
+                                          size_t workspace_bytes, float* rgb, float* alpha, float* depth,
+                                          void* ev_mlp_start, void* ev_mlp_stop, void* stream) {
+    HNRF_REQUIRE(grid, HNRF_E_ARG, "hnrf_render_rays_baked_fwd: null grid");
+    return render_rays("hnrf_render_rays_baked_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol,
+                       bbox_min, bbox_scale, hann_w, nr_packed, CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max},
+                       bgcolor, mode, cull_eps, R, S, B, G, workspace, workspace_bytes, rgb, alpha, depth, ev_mlp_start,
+                       ev_mlp_stop, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -102,28 +152,30 @@ extern "C" int hnrf_render_rays_fwd(const float* rays_o, const float* rays_d, co
 // the critical path (3 % of a 512x512x128 frame).  Two workspaces alternate; the caller provides the events.
 extern "C" size_t hnrf_render_frame_workspace_bytes(int64_t chunk, int S) { return 2 * hnrf_render_workspace_bytes(chunk, S); }
 
-extern "C" int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
-                                     const float* t_rand, const float* motion_Rs, const float* motion_Ts,
-                                     const float* vol, const float* bbox_min, const float* bbox_scale,
-                                     const float* hann_w, const void* nr_packed, const void* cnl_packed,
-                                     const float* bgcolor, int mode, float cull_eps, int64_t N, int S, int B, int G,
-                                     int64_t chunk, void* workspace, size_t workspace_bytes, float* rgb, float* alpha,
-                                     float* depth, float* weights_on_rays, float* rgb_on_rays, float* cnl_xyz,
-                                     float* cnl_rgb, float* cnl_weight, float* xyz_on_rays, float* bmw, float* offsets,
-                                     void* side_stream, void* const* events, void* const* mlp_events, void* stream) {
-    HNRF_REQUIRE(workspace && cnl_packed && rgb && alpha && depth, HNRF_E_ARG, "hnrf_render_frame_fwd: null pointer");
-    HNRF_REQUIRE(N >= 0 && chunk >= 1 && S >= 2, HNRF_E_ARG, "hnrf_render_frame_fwd: bad dims");
-    HNRF_REQUIRE(((uintptr_t)workspace & 255) == 0, HNRF_E_ARG, "hnrf_render_frame_fwd: workspace must be 256-byte aligned");
+namespace {
+int render_frame(const char* who, const float* rays_o, const float* rays_d, const float* near, const float* far,
+                 const float* t_rand, const float* motion_Rs, const float* motion_Ts, const float* vol,
+                 const float* bbox_min, const float* bbox_scale, const float* hann_w, const void* nr_packed,
+                 const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t N, int S, int B, int G,
+                 int64_t chunk, void* workspace, size_t workspace_bytes, float* rgb, float* alpha, float* depth,
+                 float* weights_on_rays, float* rgb_on_rays, float* cnl_xyz, float* cnl_rgb, float* cnl_weight,
+                 float* xyz_on_rays, float* bmw, float* offsets, void* side_stream, void* const* events,
+                 void* const* mlp_events, void* stream) {
+    HNRF_REQUIRE(workspace && rgb && alpha && depth, HNRF_E_ARG, "%s: null pointer", who);
+    int src = check_source(who, cnl);
+    if (src) return src;
+    HNRF_REQUIRE(N >= 0 && chunk >= 1 && S >= 2, HNRF_E_ARG, "%s: bad dims", who);
+    HNRF_REQUIRE(((uintptr_t)workspace & 255) == 0, HNRF_E_ARG, "%s: workspace must be 256-byte aligned", who);
     const int64_t cr = chunk < N ? chunk : (N > 0 ? N : 1);
     const size_t ws_one = hnrf_render_workspace_bytes(cr, S);
-    HNRF_REQUIRE(workspace_bytes >= 2 * ws_one, HNRF_E_WORKSPACE, "hnrf_render_frame_fwd: workspace %zu < %zu bytes",
+    HNRF_REQUIRE(workspace_bytes >= 2 * ws_one, HNRF_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who,
                  workspace_bytes, 2 * ws_one);
-    HNRF_REQUIRE(nr_packed == nullptr || hann_w != nullptr, HNRF_E_ARG, "hnrf_render_frame_fwd: hann_w missing");
+    HNRF_REQUIRE(nr_packed == nullptr || hann_w != nullptr, HNRF_E_ARG, "%s: hann_w missing", who);
     const bool diag = weights_on_rays != nullptr;
     HNRF_REQUIRE(!diag || (rgb_on_rays && cnl_xyz && cnl_rgb && cnl_weight && xyz_on_rays && bmw && offsets), HNRF_E_ARG,
-                 "hnrf_render_frame_fwd: the eight diagnostic outputs go together");
-    HNRF_REQUIRE(!diag || cull_eps == 0.f, HNRF_E_UNSUPPORTED, "hnrf_render_frame_fwd: sample culling exists in the lean form only");
-    HNRF_REQUIRE(side_stream == nullptr || events != nullptr, HNRF_E_ARG, "hnrf_render_frame_fwd: a side stream needs 5 events");
+                 "%s: the eight diagnostic outputs go together", who);
+    HNRF_REQUIRE(!diag || cull_eps == 0.f, HNRF_E_UNSUPPORTED, "%s: sample culling exists in the lean form only", who);
+    HNRF_REQUIRE(side_stream == nullptr || events != nullptr, HNRF_E_ARG, "%s: a side stream needs 5 events", who);
     if (N == 0) return HNRF_OK;
     hipStream_t st = (hipStream_t)stream, sd = side_stream ? (hipStream_t)side_stream : st;
     const bool two = side_stream != nullptr && side_stream != stream;
@@ -163,7 +215,7 @@ extern "C" int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, c
         const DiagRows d = diag ? DiagRows{weights_on_rays + r0 * S, rgb_on_rays + r0 * S * 3, cnl_xyz + 3 * r0,
                                            cnl_rgb + 3 * r0, cnl_weight + r0, xyz_on_rays + r0 * S * 3, offsets + r0 * S * 3}
                                 : DiagRows{};
-        if ((rc = render_chunk(carve(i, R), rays_d + 3 * r0, hann_w, nr_packed, cnl_packed, bgcolor, cmode, cull_eps, R, S,
+        if ((rc = render_chunk(carve(i, R), rays_d + 3 * r0, hann_w, nr_packed, cnl, bgcolor, cmode, cull_eps, R, S,
                                rgb + 3 * r0, alpha + r0, depth + r0, d, mlp_events ? mlp_events[2 * i] : nullptr,
                                mlp_events ? mlp_events[2 * i + 1] : nullptr, st))) return rc;
         if (two) HNRF_HIP(hipEventRecord(ev_done[i & 1], st));
@@ -171,4 +223,40 @@ extern "C" int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, c
     }
 #undef HNRF_HIP
     return HNRF_OK;
+}
+}  // namespace
+
+extern "C" int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                     const float* t_rand, const float* motion_Rs, const float* motion_Ts,
+                                     const float* vol, const float* bbox_min, const float* bbox_scale,
+                                     const float* hann_w, const void* nr_packed, const void* cnl_packed,
+                                     const float* bgcolor, int mode, float cull_eps, int64_t N, int S, int B, int G,
+                                     int64_t chunk, void* workspace, size_t workspace_bytes, float* rgb, float* alpha,
+                                     float* depth, float* weights_on_rays, float* rgb_on_rays, float* cnl_xyz,
+                                     float* cnl_rgb, float* cnl_weight, float* xyz_on_rays, float* bmw, float* offsets,
+                                     void* side_stream, void* const* events, void* const* mlp_events, void* stream) {
+    return render_frame("hnrf_render_frame_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min,
+                        bbox_scale, hann_w, nr_packed, CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor, mode,
+                        cull_eps, N, S, B, G, chunk, workspace, workspace_bytes, rgb, alpha, depth, weights_on_rays,
+                        rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays, bmw, offsets, side_stream, events,
+                        mlp_events, stream);
+}
+
+extern "C" int hnrf_render_frame_baked_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                           const float* t_rand, const float* motion_Rs, const float* motion_Ts,
+                                           const float* vol, const float* bbox_min, const float* bbox_scale,
+                                           const float* hann_w, const void* nr_packed, const void* grid, int grid_N,
+                                           const float* grid_bbox_min, const float* grid_bbox_max, const float* bgcolor,
+                                           int mode, float cull_eps, int64_t N, int S, int B, int G, int64_t chunk,
+                                           void* workspace, size_t workspace_bytes, float* rgb, float* alpha,
+                                           float* depth, float* weights_on_rays, float* rgb_on_rays, float* cnl_xyz,
+                                           float* cnl_rgb, float* cnl_weight, float* xyz_on_rays, float* bmw,
+                                           float* offsets, void* side_stream, void* const* events,
+                                           void* const* mlp_events, void* stream) {
+    HNRF_REQUIRE(grid, HNRF_E_ARG, "hnrf_render_frame_baked_fwd: null grid");
+    return render_frame("hnrf_render_frame_baked_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol,
+                        bbox_min, bbox_scale, hann_w, nr_packed, CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max},
+                        bgcolor, mode, cull_eps, N, S, B, G, chunk, workspace, workspace_bytes, rgb, alpha, depth,
+                        weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays, bmw, offsets,
+                        side_stream, events, mlp_events, stream);
 }

@@ -74,6 +74,17 @@ static inline int reserve_lds(const void* fn, int bytes, unsigned long long& don
     return HNRF_OK;
 }
 
+// The N^3 lattice of hnrf_density_grid and hnrf_bake_canonical (hnrf_mesh.hip): positions of the lattice points
+// p0 .. p0 + cnt - 1 ([z][y][x], x fastest) -> xyz [cnt,3]; both walk it in chunks of kLatticeChunk points per
+// canonical-MLP launch (56 MiB of workspace).
+constexpr int64_t kLatticeChunk = 1 << 21;
+int lattice_points(const float* bmin, const float* bmax, int N, int64_t p0, int64_t cnt, float* xyz, hipStream_t st);
+
+// Baked canonical grid (hnrf_baked.hip): raw[p] = the grid sampled at xyz[p]; idx / count null = every p < P, else
+// the samples idx[0 .. *count).  Arguments are the caller's to check.
+int baked_sample(const float* xyz, const void* grid, int N, const float* bmin, const float* bmax, int64_t P,
+                 const int* idx, const int* count, float* raw, hipStream_t st);
+
 // HNRF_MLP_F16X3 back end (hnrf_mlp_f16.hip)
 size_t canonical16_bytes();
 size_t nonrigid16_bytes();

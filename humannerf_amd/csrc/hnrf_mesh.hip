@@ -26,7 +26,7 @@ namespace hnrf {
 namespace {
 
 constexpr int kThreads = 256;
-constexpr int64_t kDensityChunk = 1 << 21;     // lattice points per canonical-MLP launch (56 MiB of workspace)
+constexpr int64_t kDensityChunk = kLatticeChunk;
 constexpr int kMaxSkinBones = 128;
 
 // Cell corner c: bit 0 = +x, bit 1 = +y, bit 2 = +z.  Slot s of a point is the edge to its corner kSlotCorner[s].
@@ -377,6 +377,12 @@ MeshCarve carve_mesh(void* ws, int64_t M) {
 }
 
 }  // namespace
+
+int lattice_points(const float* bmin, const float* bmax, int N, int64_t p0, int64_t cnt, float* xyz, hipStream_t st) {
+    hipLaunchKernelGGL(lattice_points_kernel, dim3((unsigned)((cnt + kThreads - 1) / kThreads)), dim3(kThreads), 0, st,
+                       bmin, bmax, N, p0, cnt, xyz);
+    return check_launch("lattice_points");
+}
 }  // namespace hnrf
 
 using namespace hnrf;
@@ -407,8 +413,7 @@ extern "C" int hnrf_density_grid(const void* cnl_packed, int mode, const float* 
     for (int64_t p0 = 0; p0 < M; p0 += C) {
         const int64_t cnt = (M - p0 < C) ? M - p0 : C;
         const unsigned blocks = (unsigned)((cnt + kThreads - 1) / kThreads);
-        hipLaunchKernelGGL(lattice_points_kernel, dim3(blocks), dim3(kThreads), 0, st, bbox_min, bbox_max, N, p0, cnt, xyz);
-        int rc = check_launch("hnrf_density_grid");
+        int rc = lattice_points(bbox_min, bbox_max, N, p0, cnt, xyz, st);
         if (rc) return rc;
         // every chunk guarded: a hit ORs HNRF_STATUS_F16_RANGE into the packed image's status word
         if ((rc = hnrf_canonical_fwd(xyz, cnl_packed, arith, cnt, raw, stream))) return rc;

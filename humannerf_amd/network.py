@@ -515,6 +515,10 @@ class Network(nn.Module):
         self._forced_mode = None
         self.f16_range_hits = self.f16_range_watched = self.f16_range_checked = 0
         self._vol_cache = None    # (key, priors, volume)
+        # baked canonical grid (cfg.amd.canonical = 'baked'): dict(grid, bmin, bmax, key, injected, refs) or None;
+        # bake_count counts the bakes this network ran
+        self._baked = None
+        self.bake_count = 0
         self._workspace = None
         # set by train.Trainer when world_size > 1: dist.GradientSync whose volume_hook averages the weight-volume
         # gradient over the ranks in front of the decoder backward
@@ -732,6 +736,15 @@ class Network(nn.Module):
             return {k: v.reshape(list(rays_shape[:-1]) + list(v.shape[1:])) for k, v in out.items()}
 
         term_eps = float(amd_option('term_eps', 0.0))
+        canonical = amd_option('canonical', 'mlp')
+        if canonical not in ('mlp', 'baked'):
+            raise ValueError("cfg.amd.canonical must be 'mlp' or 'baked', got %r" % (canonical,))
+        baked = None
+        if canonical == 'baked' and not train_path:          # (training ignores the option: _render_rays_train)
+            if not diag and term_eps > 0.0:
+                raise NotImplementedError("cfg.amd.term_eps > 0 with cfg.amd.canonical = 'baked': early ray termination "
+                                          "has no baked form (hnrf_render_rays_term_fwd runs the canonical MLP)")
+            baked = self._baked_for_frame(cnl_bbox_min_xyz, kwargs.get('cnl_bbox_max_xyz'), cnl_bbox_scale_xyz)
         if not train_path and (diag or term_eps == 0.0):
             # inference: the whole frame in one library call -- chunk loop of network.py:330-352, results straight into
             # whole-frame tensors (the reference concatenates per-chunk results: one more pass over 17 KB per ray);
@@ -742,7 +755,7 @@ class Network(nn.Module):
                 rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w, nr_packed,
                 cnl_packed, bg, S, int(cfg.chunk), gmode, diagnostics=diag,
                 cull_eps=0.0 if diag else float(amd_option('cull_eps', 0.0)), workspace=self._workspace,
-                overlap=bool(amd_option('overlap_warp', False)), mlp_event_log=self.mlp_event_log)
+                overlap=bool(amd_option('overlap_warp', False)), mlp_event_log=self.mlp_event_log, baked=baked)
             if mode == 'f16x3' and guarded != set():
                 self._watch_f16_range(cnl_packed, nr_packed, mode)
         else:
@@ -793,7 +806,8 @@ class Network(nn.Module):
                            hann_w, cond, bg, S, use_nonrigid, diag):
         """Differentiable chunk: autograd.RenderRays (activation-saving MLP kernels).  rgb / alpha / depth carry
         gradient (the trainer's loss reads rgb, trainer.py:121); with ``cfg.amd.diagnostics`` the other eight keys of
-        the reference's return dict (network.py:776-789) are returned too, detached."""
+        the reference's return dict (network.py:776-789) are returned too, detached.  cfg.amd.canonical = 'baked' is
+        ignored here: training always evaluates the canonical MLP (the grid has no gradient)."""
         nr = self.non_rigid_mlp.module.linears()
         cn = self.cnl_mlp.module.linears()
         if hann_w is None:
@@ -812,6 +826,93 @@ class Network(nn.Module):
                                cond.detach().contiguous(), bg, S, use_nonrigid, diag, const_offset, motion_Rs, motion_Ts, vol,
                                *params)
         return dict(zip(RenderRays.OUTPUT_KEYS if diag else RenderRays.OUTPUT_KEYS[:3], res))
+
+    # baked canonical grid (no counterpart in the reference; humannerf_amd/baked.py) --------------------------------
+    def _cnl_tensors(self):
+        lin = self.cnl_mlp.module.linears()
+        return [t for l in lin for t in (l.weight, l.bias)]
+
+    def canonical_weights_hash(self):
+        """sha256 of the canonical MLP's weights (baked.weights_hash): what save_grid stores with a grid."""
+        from . import baked
+        return baked.weights_hash(self._cnl_tensors())
+
+    def bake_canonical(self, cnl_bbox_min_xyz, cnl_bbox_max_xyz=None, resolution=None, cnl_bbox_scale_xyz=None):
+        """Tabulate the canonical MLP on a resolution^3 lattice (default cfg.amd.bake_resolution) over
+        [cnl_bbox_min_xyz, cnl_bbox_max_xyz] (max absent: min + 2 / cnl_bbox_scale_xyz) with hnrf_bake_canonical, in
+        the current mlp_mode, with the f16-range re-run of canonical_density_grid.  Returns the grid (N, N, N, 4)
+        float16 on the device and caches it for forward (cfg.amd.canonical = 'baked').  Warns when an output left the
+        f16 range and was saturated.  One host synchronisation (the verdicts): call it once per checkpoint."""
+        from . import baked as baked_mod
+        with torch.no_grad():
+            N = baked_mod.check_resolution(amd_option('bake_resolution', 256) if resolution is None else resolution)
+            dev = self._mesh_device()
+            f32 = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(3).contiguous()
+            bmin = f32(cnl_bbox_min_xyz)
+            bmax = f32(cnl_bbox_max_xyz) if cnl_bbox_max_xyz is not None else (bmin + 2.0 / f32(cnl_bbox_scale_xyz)).contiguous()
+            while True:
+                mode = self._mlp_mode()
+                packed = self._canonical_packed()
+                grid, sat = ops.bake_canonical(packed, bmin, bmax, N, mode, want_saturated=True)
+                if not self._f16_rerun(packed, mode):
+                    break
+            n_sat = int(sat)
+            if n_sat:
+                import warnings
+                warnings.warn('bake_canonical: %d canonical-MLP outputs beyond +-65504 were saturated in the f16 grid: '
+                              'the baked render differs from the exact one there' % n_sat)
+            self.bake_count += 1
+            self._baked = {'grid': grid, 'bmin': bmin, 'bmax': bmax, 'key': (_versions(self._cnl_tensors()), mode, N),
+                           'injected': False, 'refs': None}
+            return grid
+
+    def set_baked_grid(self, grid, bbox_min, bbox_max, weights_hash=None):
+        """Use ``grid`` (float16 (N, N, N, 4), array or tensor; baked.load_grid, or any field on the lattice) over
+        [bbox_min, bbox_max] where cfg.amd.canonical = 'baked' asks for one.  An injected grid is never re-baked, whatever
+        happens to the weights; ``weights_hash`` (the one stored with a saved grid), when given, must be this network's
+        canonical_weights_hash().  ``grid`` None drops the cached grid."""
+        if grid is None:
+            self._baked = None
+            return
+        if weights_hash is not None and weights_hash != self.canonical_weights_hash():
+            raise ValueError('set_baked_grid: the grid was baked from other canonical weights (hash %s..., this network '
+                             '%s...)' % (str(weights_hash)[:12], self.canonical_weights_hash()[:12]))
+        from . import baked as baked_mod
+        dev = self._mesh_device()
+        g = torch.as_tensor(grid)
+        N = baked_mod.check_resolution(g.shape[0])
+        if tuple(g.shape) != (N, N, N, 4) or g.dtype != torch.float16:
+            raise ValueError('set_baked_grid: grid must be float16 (N, N, N, 4), got %s %s' % (g.dtype, tuple(g.shape)))
+        f32 = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(3).contiguous()
+        self._baked = {'grid': g.to(dev).contiguous(), 'bmin': f32(bbox_min), 'bmax': f32(bbox_max), 'key': None,
+                       'injected': True, 'refs': None}
+
+    def _baked_for_frame(self, bbox_min, bbox_max, bbox_scale):
+        """(grid, bmin, bmax) for an inference frame: the injected grid; else the cached one when its key (canonical
+        weight versions, mode, N) and box match; else a fresh bake over the frame's box.  The box is compared like the
+        priors of _weight_volume: the same tensor objects as last frame hit without a look at their values (a render
+        loop keeps them resident), fresh tensors are compared by value once (a device round trip) and remembered."""
+        b = self._baked
+        if b is not None and b['injected']:
+            return b['grid'], b['bmin'], b['bmax']
+        other = bbox_max if bbox_max is not None else bbox_scale
+        refs = lambda: tuple((weakref.ref(t), t._version) for t in (bbox_min, other))
+        key = (_versions(self._cnl_tensors()), self._mlp_mode(), int(amd_option('bake_resolution', 256)))
+        if b is not None and b['key'] == key:
+            if b['refs'] is not None and all(r() is t and v == t._version
+                                             for (r, v), t in zip(b['refs'], (bbox_min, other))):
+                return b['grid'], b['bmin'], b['bmax']
+            dev = b['bmin'].device
+            f32 = lambda t: t.to(device=dev, dtype=torch.float32).reshape(3)
+            bmin = f32(bbox_min)
+            bmax = f32(bbox_max) if bbox_max is not None else bmin + 2.0 / f32(bbox_scale)
+            if torch.equal(bmin, b['bmin']) and torch.equal(bmax, b['bmax']):
+                b['refs'] = refs()
+                return b['grid'], b['bmin'], b['bmax']
+        self.bake_canonical(bbox_min, bbox_max, key[2], bbox_scale)
+        b = self._baked
+        b['refs'] = refs()
+        return b['grid'], b['bmin'], b['bmax']
 
     # mesh extraction (no counterpart in the reference) ------------------------------------------------------------
     # Density at which the canonical surface is cut.  NOT checked on a trained checkpoint (none can be obtained

@@ -215,12 +215,13 @@ def _render_args(operands, workspace, need, grow=True):
 
 def render_rays(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
                 hann_w, nr_packed, cnl_packed, bgcolor, n_samples, mode='f32', workspace=None, out=None,
-                mlp_events=None, cull_eps=0.0):
+                mlp_events=None, cull_eps=0.0, baked=None):
     """The whole path for one ray chunk (network.py:474-602) with only the
     rgb/alpha/depth outputs; intermediates live in ``workspace`` (one given must hold
     render_workspace_bytes(R, S) on the rays' device: it is not replaced).  ``mlp_events``:
     optional pair of torch.cuda.Event(enable_timing=True), recorded around the
-    canonical-MLP launch."""
+    canonical-MLP launch.  ``baked``: (grid, bbox_min, bbox_max) of bake_canonical -- raw then comes from the grid
+    sampler (hnrf_render_rays_baked_fwd) and ``cnl_packed`` is not used (may be None)."""
     lib = _lib.load()
     R, S = rays_o.shape[0], int(n_samples)
     args, workspace = _render_args((rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
@@ -236,10 +237,13 @@ def render_rays(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bb
             if not e.cuda_event:
                 e.record()            # forces creation of the hipEvent_t
         ev = (mlp_events[0].cuda_event, mlp_events[1].cuda_event)
-    _lib.check(lib.hnrf_render_rays_fwd(*map(_ptr, args), _mode_arg(mode), float(cull_eps), R, S, motion_Rs.shape[0],
-                                        vol.shape[-1], _ptr(workspace), workspace.numel() * workspace.element_size(),
-                                        _ptr(out['rgb']), _ptr(out['alpha']), _ptr(out['depth']), ev[0], ev[1],
-                                        _stream()), 'hnrf_render_rays_fwd')
+    fn, name, ptrs = lib.hnrf_render_rays_fwd, 'hnrf_render_rays_fwd', list(map(_ptr, args))
+    if baked is not None:
+        fn, name = lib.hnrf_render_rays_baked_fwd, 'hnrf_render_rays_baked_fwd'
+        ptrs[12:13] = _baked_args(baked, dev)
+    _lib.check(fn(*ptrs, _mode_arg(mode), float(cull_eps), R, S, motion_Rs.shape[0],
+                  vol.shape[-1], _ptr(workspace), workspace.numel() * workspace.element_size(),
+                  _ptr(out['rgb']), _ptr(out['alpha']), _ptr(out['depth']), ev[0], ev[1], _stream()), name)
     return out
 
 
@@ -260,10 +264,12 @@ def _frame_streams(device):
 
 def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w, nr_packed,
                  cnl_packed, bgcolor, n_samples, chunk, mode='f16x3', diagnostics=True, cull_eps=0.0, workspace=None,
-                 overlap=True, mlp_event_log=None):
+                 overlap=True, mlp_event_log=None, baked=None):
     """The whole frame in one call (hnrf_render_frame_fwd): all ray chunks through K1..K4, results in whole-frame tensors;
     K1 of the next chunk on a side stream while the MLP kernels of the current one run.  Returns (dict of outputs,
-    workspace).  ``mlp_event_log``: list that receives one (start, stop) torch.cuda.Event pair per chunk."""
+    workspace).  ``mlp_event_log``: list that receives one (start, stop) torch.cuda.Event pair per chunk.  ``baked``:
+    (grid, bbox_min, bbox_max) of bake_canonical -- raw then comes from the grid sampler (hnrf_render_frame_baked_fwd,
+    the event pairs around its launches) and ``cnl_packed`` is not used (may be None)."""
     lib = _lib.load()
     N, S, B, G = rays_o.shape[0], int(n_samples), motion_Rs.shape[0], vol.shape[-1]
     dev = rays_o.device
@@ -289,12 +295,16 @@ def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, b
             a.record()
             b.record()
         mlp_arr = (ctypes.c_void_p * (2 * nchunk))(*[e.cuda_event for p in pairs for e in p])
-    _lib.check(lib.hnrf_render_frame_fwd(
-        *map(_ptr, args), _mode_arg(mode), float(cull_eps), N, S, B, G, chunk, _ptr(workspace),
+    fn, name, ptrs = lib.hnrf_render_frame_fwd, 'hnrf_render_frame_fwd', list(map(_ptr, args))
+    if baked is not None:
+        fn, name = lib.hnrf_render_frame_baked_fwd, 'hnrf_render_frame_baked_fwd'
+        ptrs[12:13] = _baked_args(baked, dev)
+    _lib.check(fn(
+        *ptrs, _mode_arg(mode), float(cull_eps), N, S, B, G, chunk, _ptr(workspace),
         workspace.numel() * workspace.element_size(), g('rgb'), g('alpha'), g('depth'),
         g('weights_on_rays'), g('rgb_on_rays'), g('cnl_xyz'), g('cnl_rgb'), g('cnl_weight'), g('xyz_on_rays'),
         g('backward_motion_weights'), g('offsets'), side.cuda_stream if side is not None else None, ev_arr, mlp_arr,
-        _stream()), 'hnrf_render_frame_fwd')
+        _stream()), name)
     if side is not None:
         # the side stream read the inputs and wrote backward_motion_weights / the workspace: keep the allocator from
         # handing those blocks out again before it is done (everything it did is also ordered on the main stream)
@@ -788,6 +798,71 @@ def density_grid(packed, vol, bbox_min, bbox_max, bbox_scale, N, mode='f32', wan
                                      _ptr(bbox_scale), N, _ptr(ws), ws.numel() * 4, _ptr(density), _ptr(sigma), _ptr(fg),
                                      _stream()), 'hnrf_density_grid')
     return (density, sigma, fg) if want_parts else density
+
+
+# ------------------------------------------------------------------------------------------------ baked canonical grid
+def _chk_grid(grid, bbox_min, bbox_max):
+    """-> N of a baked grid: contiguous float16 (N, N, N, 4) on the GPU, with its fp32 box."""
+    if not (torch.is_tensor(grid) and grid.is_cuda and grid.dtype == torch.float16 and grid.is_contiguous()
+            and grid.dim() == 4 and grid.shape[0] == grid.shape[1] == grid.shape[2] and grid.shape[3] == 4):
+        raise _lib.HnrfError('baked grid must be a contiguous float16 (N, N, N, 4) tensor on the GPU')
+    _chk(bbox_min, bbox_max)
+    assert bbox_min.numel() == 3 and bbox_max.numel() == 3
+    return int(grid.shape[0])
+
+
+def _baked_args(baked, device):
+    """The four arguments that stand for cnl_packed in the *_baked_fwd entries."""
+    grid, bbox_min, bbox_max = baked
+    N = _chk_grid(grid, bbox_min, bbox_max)
+    if grid.device != device:
+        raise _lib.HnrfError(f'baked grid on {grid.device}, rays on {device}')
+    return [grid.data_ptr(), N, _ptr(bbox_min), _ptr(bbox_max)]
+
+
+def bake_canonical(packed, bbox_min, bbox_max, N, mode='f32', want_saturated=False):
+    """hnrf_bake_canonical: the canonical MLP (``packed``, ``mode``) on the N^3 lattice over [bbox_min, bbox_max] ->
+    grid (N, N, N, 4) float16 indexed [z][y][x][c], c = (r, g, b, sigma) pre-activation, values beyond +-65504
+    saturated.  ``want_saturated``: also return their count, a (1,) int32 device tensor (no synchronisation)."""
+    lib = _lib.load()
+    _chk(packed, bbox_min, bbox_max)
+    N = int(N)
+    need = lib.hnrf_bake_canonical_workspace_bytes(N)
+    if need == 0:
+        raise _lib.HnrfError(f'baked grid resolution {N} out of range [8, 512]')
+    dev = packed.device
+    ws = torch.empty(need // 4 + 64, device=dev)
+    grid = torch.empty(N, N, N, 4, dtype=torch.float16, device=dev)
+    sat = torch.zeros(1, dtype=torch.int32, device=dev)
+    _lib.check(lib.hnrf_bake_canonical(_ptr(packed), _mode_arg(mode), _ptr(bbox_min), _ptr(bbox_max), N, _ptr(ws),
+                                       ws.numel() * 4, grid.data_ptr(), sat.data_ptr(), _stream()), 'hnrf_bake_canonical')
+    return (grid, sat) if want_saturated else grid
+
+
+def baked_sample(xyz, grid, bbox_min, bbox_max):
+    """hnrf_baked_sample: xyz (..., 3) -> raw (..., 4), the grid interpolated where ``canonical`` runs the MLP."""
+    lib = _lib.load()
+    _chk(xyz)
+    N = _chk_grid(grid, bbox_min, bbox_max)
+    raw = torch.empty(*xyz.shape[:-1], 4, device=xyz.device)
+    _lib.check(lib.hnrf_baked_sample(_ptr(xyz), grid.data_ptr(), N, _ptr(bbox_min), _ptr(bbox_max), xyz.numel() // 3,
+                                     _ptr(raw), _stream()), 'hnrf_baked_sample')
+    return raw
+
+
+def baked_sample_sparse(xyz, grid, bbox_min, bbox_max, idx, count, raw=None):
+    """hnrf_baked_sample_sparse: only the samples idx[0 .. count) are read and written; ``raw`` (default zeros) keeps
+    its other rows."""
+    lib = _lib.load()
+    _chk(xyz, raw)
+    N = _chk_grid(grid, bbox_min, bbox_max)
+    if raw is None:
+        raw = torch.zeros(*xyz.shape[:-1], 4, device=xyz.device)
+    assert raw.numel() // 4 == xyz.numel() // 3
+    _lib.check(lib.hnrf_baked_sample_sparse(_ptr(xyz), grid.data_ptr(), N, _ptr(bbox_min), _ptr(bbox_max),
+                                            xyz.numel() // 3, _ptr(idx), _ptr(count), _ptr(raw), _stream()),
+               'hnrf_baked_sample_sparse')
+    return raw
 
 
 def mesh_workspace(N, device):

@@ -335,14 +335,15 @@ class FramePrefetcher:
             return t.pin_memory().to(self.device, non_blocking=True)
         return t.to(self.device)
 
-    def _priors(self, pri):
+    def _priors(self, pri, name='priors'):
         # per-subject constant: keep it on the device while the host copy is unchanged, so that the network's
-        # weight-volume cache hits by identity (no per-frame comparison / synchronisation)
+        # weight-volume cache hits by identity (no per-frame comparison / synchronisation); the same for the canonical
+        # bbox, which keys the network's baked canonical grid (cfg.amd.canonical = 'baked')
         with self._lock:
-            return self._priors_locked(pri)
+            return self._priors_locked(pri, name)
 
-    def _priors_locked(self, pri):
-        hit = self._resident.get('priors')
+    def _priors_locked(self, pri, name):
+        hit = self._resident.get(name)
         if hit is not None and (hit[0] is pri or (isinstance(pri, np.ndarray) and isinstance(hit[0], np.ndarray)
                                                   and hit[0].shape == pri.shape and np.array_equal(hit[0], pri))):
             if hit[2] is not None:                                       # uploaded on another worker's stream
@@ -353,7 +354,7 @@ class FramePrefetcher:
         if self.on_gpu:
             ev = torch.cuda.Event()
             ev.record()
-        self._resident['priors'] = (pri, t, ev)
+        self._resident[name] = (pri, t, ev)
         return t
 
     def build(self, idx):
@@ -368,6 +369,10 @@ class FramePrefetcher:
                                    int(fr['img_height']), int(fr['img_width']), device=self.device))
         data = {k: self._up(fr[k]) for k in ('rays', 'near', 'far') + _FRAME_KEYS}
         data['motion_weights_priors'] = self._priors(fr['motion_weights_priors'])
+        if cfg.get('amd', {}).get('canonical', 'mlp') == 'baked':
+            for k in ('cnl_bbox_min_xyz', 'cnl_bbox_scale_xyz', 'cnl_bbox_max_xyz'):
+                if k in fr:
+                    data[k] = self._priors(fr[k], k)
         mask = self._up(fr['ray_mask']).reshape(-1)
         index = torch.nonzero(mask).reshape(-1)                          # (the one read-back of the frame: on this stream)
         truth = None

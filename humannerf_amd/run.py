@@ -53,6 +53,23 @@ def _panels(rgb8, alpha8, truth8=None):
     return np.concatenate(imgs, axis=1)
 
 
+def _baked_folder(network, subject, folder):
+    """cfg.amd.canonical = 'baked': bake the canonical grid over the subject's canonical bbox before the first frame
+    (so that no frame of the loop pays for it) and mark the folder ``<folder>_baked_<N>`` -- approximate pictures are
+    never written where exact ones go.  An injected grid (Network.set_baked_grid) is used as it is."""
+    from .config import amd_option
+    if amd_option('canonical', 'mlp') != 'baked':
+        return folder
+    b = getattr(network, '_baked', None)
+    if b is None or not b['injected']:
+        bbox = subject.canonical_bbox
+        mn, mx = bbox['min_xyz'].astype('float32'), bbox['max_xyz'].astype('float32')
+        import torch
+        with torch.no_grad():
+            network._baked_for_frame(torch.from_numpy(mn), torch.from_numpy(mx), None)
+    return '%s_baked_%d' % (folder, network._baked['grid'].shape[0])
+
+
 def _render_loop(network, frames, names, folder, logdir, rank, world, device, metrics=None):
     out_dir = _output_dir(logdir)
     writer = render.ImageWriter(out_dir, folder)
@@ -87,6 +104,7 @@ def run_movement(network, subject, render_folder_name='movement', logdir=None, r
     # the device when there is one)
     frames = _Frames(n, lambda i: subject.movement_frame(i, load_image=True, device=device))
     names = [str(subject.framelist[i]).replace('/', '-') for i in range(n)]
+    render_folder_name = _baked_folder(network, subject, render_folder_name)
     suffix = '' if world == 1 else '.rank%d' % rank
     mw = render.MetricsWriter(_output_dir(logdir), render_folder_name + suffix, dataset=subject.dataset_path,
                               metrics=metrics, lpips_fn=lpips_fn)
@@ -104,6 +122,7 @@ def run_freeview(network, subject, frame_idx=None, total_frames=None, render_fol
     frames = _Frames(total, lambda i: subject.freeview_frame(i, total, train_frame_idx=frame_idx, src_type=src_type,
                                                              image_size=image_size, bgcolor=cfg.bgcolor))
     folder = render_folder_name or cfg.get('render_folder_name', '') or 'freeview_%d' % frame_idx
+    folder = _baked_folder(network, subject, folder)
     return _render_loop(network, frames, [None] * total if world == 1 else ['%06d' % i for i in range(total)], folder,
                         logdir, rank, world, device)
 
@@ -117,6 +136,7 @@ def run_tpose(network, subject, total_frames=None, render_folder_name=None, logd
     cfg.ignore_non_rigid_motions = True
     try:
         folder = render_folder_name or cfg.get('render_folder_name', '') or 'tpose'
+        folder = _baked_folder(network, subject, folder)
         return _render_loop(network, frames, [None] * total if world == 1 else ['%06d' % i for i in range(total)],
                             folder, logdir, rank, world, device)
     finally:

@@ -472,6 +472,58 @@ int hnrf_mesh_emit(const float* density, int N, float level, const float* bbox_m
 int hnrf_forward_skin(const float* verts, int64_t V, const float* motion_Rs, const float* motion_Ts, const float* vol,
                       int B, int G, const float* bbox_min, const float* bbox_scale, float* out, void* stream);
 
+/* ---- baked canonical grid (no counterpart in the reference; humannerf_amd/baked.py) ----
+ * In the configuration this library builds (no view direction, no pose colour, no condition code) the canonical MLP is
+ * a pure function of the canonical position: raw = f(xyz), the same for every frame, pose and camera until the weights
+ * change.  It can be tabulated once per checkpoint and interpolated afterwards -- an opt-in APPROXIMATION like
+ * cull_eps / term_eps (not the reference arithmetic): K1, K2, K4, culling and all 11 outputs stay exact, only raw
+ * comes from interpolation.
+ * grid [N][N][N][4] f16, indexed [z][y][x][c], c = (r, g, b, sigma) PRE-activation, 8 bytes per lattice point
+ *  (hnrf_baked_grid_bytes(N); 8-byte aligned), 8 <= N <= 512.  Lattice exactly as hnrf_density_grid's: point i on an
+ *  axis at bbox_min + (float)i * step, step = (bbox_max - bbox_min) / (N - 1), each operation rounded on its own.
+ * hnrf_bake_canonical: value = hnrf_canonical_fwd at the lattice point in `mode`, converted to f16 with round to
+ *  nearest even; values beyond +-65504 (infinities included) are stored as +-65504 and counted into *saturated
+ *  (nullable device counter, ADDED to: the caller zeroes it); NaN stays NaN.  Runs in chunks through `workspace`
+ *  (hnrf_bake_canonical_workspace_bytes(N), 256-byte aligned); every chunk is range-guarded (HNRF_STATUS_F16_RANGE in
+ *  cnl_packed's status word, mode f16x3).
+ * hnrf_baked_sample: xyz [P,3] -> raw [P,4] fp32 (16-byte aligned), what hnrf_canonical_fwd writes.  Per axis, with
+ *  n = N - 1: inv_step = (float)n / (bbox_max - bbox_min); u = (x - bbox_min) * inv_step; u = min(max(u, 0), n) --
+ *  border replicate: points outside the box sample the clamped point, a NaN coordinate samples index 0 --;
+ *  i0 = min((int)floor(u), n - 1); t = u - (float)i0.  Blend in fp32, every channel on its own, every operation
+ *  rounded on its own (no fma), a + t * (b - a) first along x (4 times), then along y (twice), then along z.
+ *  humannerf_amd/baked.py:sample_host restates it in numpy float32, bit for bit.
+ * hnrf_baked_sample_sparse: only the samples idx[0 .. *count) are read and written (semantics of
+ *  hnrf_canonical_fwd_sparse). */
+size_t hnrf_baked_grid_bytes(int N);
+size_t hnrf_bake_canonical_workspace_bytes(int N);
+int hnrf_bake_canonical(const void* cnl_packed, int mode, const float* bbox_min, const float* bbox_max, int N,
+                        void* workspace, size_t workspace_bytes, void* grid, unsigned* saturated, void* stream);
+int hnrf_baked_sample(const float* xyz, const void* grid, int N, const float* bbox_min, const float* bbox_max, int64_t P,
+                      float* raw, void* stream);
+int hnrf_baked_sample_sparse(const float* xyz, const void* grid, int N, const float* bbox_min, const float* bbox_max,
+                             int64_t P, const int* idx, const int* count, float* raw, void* stream);
+/* hnrf_render_rays_fwd / hnrf_render_frame_fwd with the grid sampler in the canonical MLP's place: the arguments of
+ * those entries with cnl_packed replaced by grid, grid_N, grid_bbox_min, grid_bbox_max (the box the grid was baked
+ * over: device pointers [3]).  Lean and 11-output forms, cull_eps, the side stream and the event pairs (recorded
+ * around the sampler launch) as there; `mode` is the non-rigid MLP's, whose image is still guarded.  There is no
+ * canonical status word in this form, and no early-termination form. */
+int hnrf_render_rays_baked_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                               const float* t_rand, const float* motion_Rs, const float* motion_Ts, const float* vol,
+                               const float* bbox_min, const float* bbox_scale, const float* hann_w, const void* nr_packed,
+                               const void* grid, int grid_N, const float* grid_bbox_min, const float* grid_bbox_max,
+                               const float* bgcolor, int mode, float cull_eps, int64_t R, int S, int B, int G,
+                               void* workspace, size_t workspace_bytes, float* rgb, float* alpha, float* depth,
+                               void* ev_mlp_start, void* ev_mlp_stop, void* stream);
+int hnrf_render_frame_baked_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                const float* t_rand, const float* motion_Rs, const float* motion_Ts, const float* vol,
+                                const float* bbox_min, const float* bbox_scale, const float* hann_w, const void* nr_packed,
+                                const void* grid, int grid_N, const float* grid_bbox_min, const float* grid_bbox_max,
+                                const float* bgcolor, int mode, float cull_eps, int64_t N, int S, int B, int G,
+                                int64_t chunk, void* workspace, size_t workspace_bytes, float* rgb, float* alpha,
+                                float* depth, float* weights_on_rays, float* rgb_on_rays, float* cnl_xyz, float* cnl_rgb,
+                                float* cnl_weight, float* xyz_on_rays, float* bmw, float* offsets, void* side_stream,
+                                void* const* events, void* const* mlp_events, void* stream);
+
 /* ---- rasteriser for vertex-coloured triangle meshes (no counterpart in the reference; humannerf_amd/raster.py) ----
  * hnrf_raster_mesh: verts [V,3] fp32 world positions, faces [F,3] int32, colors [V,3] fp32 (nullable when the shade
  *  is the normal), camera K [9], R [9] (row-major 3x3), T [3], bgcolor [3] (0..1): device pointers, nothing is read
