@@ -18,7 +18,8 @@ namespace hnrf {
 struct __attribute__((packed, aligned(4))) f32x2u { float x, y; };
 
 // torch.linspace(0, 1, S)[s] in fp32 (start + step*i below the midpoint,
-// end - step*(S-1-i) above it), then the reference's lerp (network.py:457-458).
+// end - step*(S-1-i) from it on; torch's own kernels differ from these two forms
+// by an ulp on some elements), then the reference's lerp (network.py:457-458).
 __device__ __forceinline__ float z_at(float nr, float fr, int s, int S) {
 #pragma clang fp contract(off)
     const float step = 1.0f / (float)(S - 1);

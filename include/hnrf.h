@@ -89,7 +89,14 @@ size_t hnrf_nonrigid_status_offset(int mode);
  *  B == 24 16-byte aligned -- it is then written in 16-byte pieces --,
  *  HNRF_E_ARG otherwise).
  * Every operation of the reference's tensor expressions is rounded on its own
- * (no compiler-chosen fma), so all forms of the kernel agree bit for bit. */
+ * (no compiler-chosen fma), so all forms of the kernel agree bit for bit.
+ * z_vals: torch.linspace's element in its two forms, step * s below the midpoint
+ * S / 2 and 1 - step * (S - 1 - s) from it on, step = 1 / (S - 1) in fp32; equal
+ * bit for bit to that statement (tests/test_render_kernel_refs.py::
+ * z_statement_fp32), within an ulp of torch.linspace's own kernels.
+ * Limits, checked before any launch (HNRF_E_ARG): S >= 2, B >= 1, 2 <= G <= 1024,
+ * bmw 16-byte aligned when B == 24 (any other B: 4-byte stores, no requirement).
+ * R == 0 returns HNRF_OK without a launch and leaves every output untouched. */
 int hnrf_sample_warp_fwd(const float* rays_o, const float* rays_d,
                          const float* near, const float* far, const float* t_rand,
                          const float* motion_Rs, const float* motion_Ts,
@@ -102,7 +109,8 @@ int hnrf_sample_warp_fwd(const float* rays_o, const float* rays_d,
  * idx[0 .. *count) = indices p with fg_mask[p] >= eps, count written on the device (no host
  * sync).  alpha = (1 - exp(-sigma delta)) * fg_mask (network.py:369) < eps for a dropped sample,
  * so a ray's rgb / alpha / depth move by at most ~2 S eps; eps == 0 keeps every sample and the
- * path is exactly the reference's.  idx must hold P ints. */
+ * path is exactly the reference's.  idx must hold P ints; idx[*count .. P) is NOT written (it keeps what it
+ * held); a NaN fg_mask is never kept, also at eps == 0; P < 2^31 - 1; P == 0 sets *count = 0 without a launch. */
 int hnrf_compact_samples(const float* fg_mask, float eps, int64_t P, int* idx, int* count, void* stream);
 
 /* ---- K2: non-rigid motion MLP ---------------------------------------------
@@ -124,6 +132,7 @@ int hnrf_nonrigid_pack(const float* const* weights, const float* const* biases,
  *  26-40).  Outputs xyz = x_skel + offset [P,3]; offsets [P,3] or NULL. */
 int hnrf_nonrigid_fwd(const float* x_skel, const float* hann_w, const void* packed,
                       int mode, int64_t P, float* xyz, float* offsets, void* stream);
+/*  Sparse form, as hnrf_canonical_fwd_sparse below: xyz (and offsets) are written at the listed samples only. */
 int hnrf_nonrigid_fwd_sparse(const float* x_skel, const float* hann_w, const void* packed,
                              int mode, int64_t P, const int* idx, const int* count,
                              float* xyz, float* offsets, void* stream);
@@ -141,8 +150,9 @@ int hnrf_canonical_pack(const float* const* weights, const float* const* biases,
 int hnrf_canonical_fwd(const float* xyz, const void* packed, int mode, int64_t P,
                        float* raw, void* stream);
 /*  Sparse form: only the samples idx[0 .. *count) are evaluated (xyz read at and raw written to
- *  those indices; everything else untouched).  idx, count: device pointers from
- *  hnrf_compact_samples; P = capacity of idx (grid size). */
+ *  those indices; everything else untouched, and the listed rows equal the dense launch bit for bit).  idx, count:
+ *  device pointers from hnrf_compact_samples; P = capacity of idx (grid size), *count <= P is read on the device;
+ *  idx[*count .. P) is not read; *count == 0 writes nothing. */
 int hnrf_canonical_fwd_sparse(const float* xyz, const void* packed, int mode, int64_t P,
                               const int* idx, const int* count, float* raw, void* stream);
 
@@ -153,7 +163,9 @@ int hnrf_canonical_fwd_sparse(const float* xyz, const void* packed, int mode, in
  *  cull_eps: samples with fg_mask < cull_eps get weight 0 and their raw is not interpreted
  *  (0 = reference behaviour).
  * Outputs: rgb [R,3], alpha [R], depth [R]; nullable: weights [R,S],
- *  rgb_on_rays [R,S,3], cnl_xyz [R,3], cnl_rgb [R,3], cnl_weight [R]. */
+ *  rgb_on_rays [R,S,3] (0 at culled samples), cnl_xyz [R,3], cnl_rgb [R,3], cnl_weight [R]: gathered at the
+ *  largest weight of the ray, of equal weights at the first (a ray without any weight: sample 0).
+ * Limits: 2 <= S <= 512 (HNRF_E_UNSUPPORTED above 512), raw 16-byte aligned (HNRF_E_ARG). */
 int hnrf_composite_fwd(const float* raw, const float* fg_mask, const float* z_vals,
                        const float* rays_d, const float* xyz, const float* bgcolor,
                        int64_t R, int S, float cull_eps,
@@ -189,7 +201,10 @@ int hnrf_render_rays_fwd(const float* rays_o, const float* rays_d,
 /* Opt-in variant with early ray termination (NOT the reference arithmetic): the samples are walked front to back
  * in slabs of 32; a ray whose transmittance has fallen below term_eps (0 < term_eps < 1) is not evaluated further,
  * which moves rgb / alpha by at most term_eps; cull_eps as above (may be 0).  evaluated (nullable): device int that
- * receives the number of samples that went through the MLPs.  workspace: hnrf_render_term_workspace_bytes. */
+ * receives the number of samples that went through the MLPs.  workspace: hnrf_render_term_workspace_bytes.
+ * Exactly: a ray is alive for a slab iff its transmittance BEFORE that slab is >= term_eps (so the slab in which it
+ * falls under the threshold is still composited whole); a sample is evaluated iff its ray is alive and fg_mask >=
+ * cull_eps (at cull_eps == 0 that includes fg_mask == 0); every other sample enters with alpha = 0. */
 size_t hnrf_render_term_workspace_bytes(int64_t R, int S);
 int hnrf_render_rays_term_fwd(const float* rays_o, const float* rays_d,
                               const float* near, const float* far, const float* t_rand,
@@ -391,7 +406,8 @@ int hnrf_nonrigid_bwd(const float* x_skel, const float* hann_w, const float* d_x
  *  Kinv [3,3] = inverse intrinsics, R [3,3], T [3] = extrinsics, bbox_min / bbox_max [3] (unpadded; the 1 cm pad
  *  is applied inside), all float32 device pointers.  Outputs, in pixel order: ray_mask [H*W] (1 = the ray crosses
  *  the box), and for the *count kept rays rays_o / rays_d [count,3] (direction un-normalised, components clamped
- *  to 1e-5 like the reference), near / far [count].  Size the ray buffers for H*W. */
+ *  to 1e-5 like the reference), near / far [count].  Size the ray buffers for H*W; their entries from *count on
+ *  are not written. */
 size_t hnrf_gen_rays_workspace_bytes(int H, int W);
 int hnrf_gen_rays(const float* Kinv, const float* R, const float* T, const float* bbox_min, const float* bbox_max,
                   int H, int W, float* rays_o, float* rays_d, float* near, float* far, uint8_t* ray_mask,
