@@ -381,23 +381,13 @@ extern "C" int hnrf_sample_warp_bwd(const float* rays_o, const float* rays_d, co
         // 16 waves per block (four per SIMD): with ONE wave per SIMD every one of the ~350 instructions per (sample, bone)
         // pair costs ~5 cycles of issue (profiles/r03_mfma_issue.txt); 0.529 ms (256 threads) -> 0.357 (512) -> 0.295 (1024).
         // (Before the atomics were folded, more waves lost to LDS-atomic contention: 0.90 -> 1.00 ms, round 2.)
-        static const int nth = getenv("HNRF_K1B_THREADS") ? atoi(getenv("HNRF_K1B_THREADS")) : 1024;
-#define HNRF_K1B(NTH_)                                                                                                   \
-    do {                                                                                                                 \
-        static unsigned long long lds_done = 0;                                                                          \
-        if (int rc = reserve_lds((const void*)sample_warp_bwd_kernel<true, NTH_>, 150 * 1024, lds_done, "hnrf_sample_warp_bwd")) \
-            return rc;                                                                                                   \
-        hipLaunchKernelGGL((sample_warp_bwd_kernel<true, NTH_>), dim3((unsigned)bx, (unsigned)B), dim3(NTH_), lds, st, rays_o, \
-                           rays_d, z_vals, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, x_skel, fg_mask, g_x_skel,  \
-                           g_mask, P, S, G, d_vol, d_Rs, d_Ts);                                                          \
-    } while (0)
-        if (nth == 512) HNRF_K1B(512); else if (nth == 1024) HNRF_K1B(1024); else HNRF_K1B(256);
-#undef HNRF_K1B
-    } else {
-        if (blocks > 1024) blocks = 1024;     // grid-stride: few, long blocks keep the 12-value reduction cheap
-        hipLaunchKernelGGL((sample_warp_bwd_kernel<false, 256>), dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, st,
-                           rays_o, rays_d, z_vals, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, x_skel, fg_mask,
-                           g_x_skel, g_mask, P, S, G, d_vol, d_Rs, d_Ts);
+        return launch_lds<sample_warp_bwd_kernel<true, 1024>, 150 * 1024>(
+            "hnrf_sample_warp_bwd", dim3((unsigned)bx, (unsigned)B), dim3(1024), lds, st, rays_o, rays_d, z_vals, motion_Rs,
+            motion_Ts, vol, bbox_min, bbox_scale, x_skel, fg_mask, g_x_skel, g_mask, P, S, G, d_vol, d_Rs, d_Ts);
     }
+    if (blocks > 1024) blocks = 1024;         // grid-stride: few, long blocks keep the 12-value reduction cheap
+    hipLaunchKernelGGL((sample_warp_bwd_kernel<false, 256>), dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, st, rays_o,
+                       rays_d, z_vals, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, x_skel, fg_mask, g_x_skel, g_mask, P, S,
+                       G, d_vol, d_Rs, d_Ts);
     return check_launch("hnrf_sample_warp_bwd");
 }

@@ -74,6 +74,16 @@ static inline int reserve_lds(const void* fn, int bytes, unsigned long long& don
     return HNRF_OK;
 }
 
+// Launch of kernel K with `lds` bytes of dynamic LDS, > 64 KiB allowed: owns K's per-device mask for reserve_lds (one per
+// kernel instance: a function-local static of the template).  LDS_MAX: the size reserved where launches differ in size.
+template <auto K, int LDS_MAX = 0, typename... Args>
+static inline int launch_lds(const char* what, dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    static unsigned long long done = 0;
+    if (int rc = reserve_lds((const void*)K, LDS_MAX ? LDS_MAX : (int)lds, done, what)) return rc;
+    hipLaunchKernelGGL(K, grid, block, lds, st, args...);
+    return check_launch(what);
+}
+
 // The N^3 lattice of hnrf_density_grid and hnrf_bake_canonical (hnrf_mesh.hip): positions of the lattice points
 // p0 .. p0 + cnt - 1 ([z][y][x], x fastest) -> xyz [cnt,3]; both walk it in chunks of kLatticeChunk points per
 // canonical-MLP launch (56 MiB of workspace).

@@ -21,6 +21,7 @@
 #include "hnrf_common.h"
 #include "hnrf_sincos.h"
 #include "hnrf_mlp_layout.h"
+#include "hnrf_lds_dma.h"
 
 namespace hnrf {
 
@@ -469,13 +470,13 @@ __device__ __forceinline__ h16x8 dwh_frag2(unsigned addr_lo, unsigned addr_hi) {
 }
 
 // OT: 32-row tiles of dZ columns per wave (n_out = 128 OT); IT: 32-column tiles of X (n_in padded to 32 IT: 2, 4, 8).
-// ZBLK / XBLK: the matrix arrives in the BLOCKED layout the training kernels write (hnrf_mlp_f16.hip, save_pair_bh):
+// ZBLK: dZ arrives in the BLOCKED layout the training kernels write (hnrf_mlp_f16.hip, save_pair_bh):
 // 32-sample blocks of [32-feature tile][k = 8 groups of 4 features][32 sample slots][4 halves], sample c in slot
 // c ^ 4 k.  A stage is then ONE contiguous block, copied to LDS as it is (linear 16-byte chunks), and the slot swizzle
 // is what makes the transposed reads conflict-free: a read takes 4 samples x 8 groups per lane half, whose 8-byte
 // granules (k 32 + (c ^ 4 k)) 8 cover the 64 banks once.  Rows past P are zero in a blocked dZ (the chain kernels
 // store zeros there), so padded blocks need no masking.
-template <int OT, int IT, bool ZBLK, bool XBLK>
+template <int OT, int IT, bool ZBLK>
 __global__ __launch_bounds__(256) void mlp_dwh_kernel(const _Float16* __restrict__ dZ, int64_t ldz,
                                                       const _Float16* __restrict__ X, int64_t ldx, int64_t P,
                                                       int64_t per_wg, const float* __restrict__ dz_scale,
@@ -484,7 +485,6 @@ __global__ __launch_bounds__(256) void mlp_dwh_kernel(const _Float16* __restrict
     constexpr int ZB = 32 * NOW * 2, XB = 32 * NIP * 2;          // bytes per stage
     constexpr int ZC = NOW / 64, XC = NIP / 64;                   // 16-byte chunks per thread and stage
     constexpr int ZROW = NOW >= 128 ? 256 : 128, XROW = NIP >= 128 ? 256 : 128;
-    static_assert(!XBLK || NIP >= 128, "blocked X: hidden layers only");
     __shared__ __attribute__((aligned(16))) char lds[2][ZB + XB];
     const unsigned lbase = (unsigned)(size_t)(__attribute__((address_space(3))) char*)&lds[0][0];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -534,12 +534,8 @@ __global__ __launch_bounds__(256) void mlp_dwh_kernel(const _Float16* __restrict
 #pragma unroll
         for (int i = 0; i < XC; ++i) {
             const int id = tid + 256 * i;
-            if (XBLK) {
-                rx[slot][i] = sb < s1 ? *reinterpret_cast<const u32x4*>(X + (sb >> 5) * (int64_t)(NIP * 32) + 8 * id) : u32x4{0u, 0u, 0u, 0u};
-            } else {
-                const int row = id / (NIP / 8), ch = id % (NIP / 8);
-                rx[slot][i] = sb + row < s1 ? *reinterpret_cast<const u32x4*>(X + (sb + row) * ldx + 8 * ch) : u32x4{0u, 0u, 0u, 0u};
-            }
+            const int row = id / (NIP / 8), ch = id % (NIP / 8);
+            rx[slot][i] = sb + row < s1 ? *reinterpret_cast<const u32x4*>(X + (sb + row) * ldx + 8 * ch) : u32x4{0u, 0u, 0u, 0u};
         }
     };
     auto stage_in = [&](int slot, int buf) {
@@ -551,7 +547,7 @@ __global__ __launch_bounds__(256) void mlp_dwh_kernel(const _Float16* __restrict
 #pragma unroll
         for (int i = 0; i < XC; ++i) {
             const int id = tid + 256 * i, row = id / (NIP / 8), ch = id % (NIP / 8);
-            *reinterpret_cast<u32x4*>(&lds[buf][ZB + (XBLK ? 16 * id : dwh_off<NIP>(row, 8 * ch))]) = rx[slot][i];
+            *reinterpret_cast<u32x4*>(&lds[buf][ZB + dwh_off<NIP>(row, 8 * ch)]) = rx[slot][i];
         }
     };
     auto compute = [&](int buf) {
@@ -569,12 +565,8 @@ __global__ __launch_bounds__(256) void mlp_dwh_kernel(const _Float16* __restrict
             }
 #pragma unroll
             for (int it = 0; it < IT; ++it) {
-                h16x8 bf;
-                if (XBLK) bf = dwh_frag2(lb + ZB + it * 2048 + bpos[ks][0], lb + ZB + it * 2048 + bpos[ks][1]);
-                else {
-                    const unsigned ba = lb + boff[it & 3] + (it >> 2) * (32 * 256) + 16 * ks * XROW;
-                    bf = dwh_frag2(ba, ba + 4 * XROW);
-                }
+                const unsigned ba = lb + boff[it & 3] + (it >> 2) * (32 * 256) + 16 * ks * XROW;
+                const h16x8 bf = dwh_frag2(ba, ba + 4 * XROW);
 #pragma unroll
                 for (int a = 0; a < OT; ++a) acc[a][it] = __builtin_amdgcn_mfma_f32_32x32x16_f16(af[a], bf, acc[a][it], 0, 0, 0);
             }
@@ -625,26 +617,11 @@ __global__ __launch_bounds__(256) void mlp_dwh_kernel(const _Float16* __restrict
 // (2-KiB) run of the dZ part and one of the X part per stage: one source base and one M0 per run, the pieces through the
 // instruction's immediate offset (which applies to both addresses, profiles/tools/dma_offset.hip).  Stage order, and with it
 // the summation order, is that of mlp_dwh_kernel: the results are bit-identical.
-template <int R>
-__device__ __forceinline__ void dwh_dma_piece(const char* gbase, unsigned voff, unsigned lds_addr) {
-    // a scalar write of M0 needs one wait state before an LDS-DMA instruction reads it (gfx9 hazard), and hipcc, which
-    // places the write, cannot see into the asm to insert it: hence the s_nop inside the statement.  In EVERY piece, not
-    // only a run's first: where the pieces of a run sit in different basic blocks (runtime piece counts at layer
-    // boundaries) the compiler writes M0 again in front of later pieces (the same value, so a stale read would be
-    // harmless -- but that is an argument about today's code generation, not a guarantee)
-    asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3" : : "v"(voff), "s"(gbase), "{m0}"(lds_addr), "n"(R * 1024) : "memory");
-}
-template <int NP>
-__device__ __forceinline__ void dwh_dma_run(const char* gbase, unsigned voff, unsigned lds_addr) {
-    static_assert(NP == 2 || NP == 4, "pieces per wave and operand");
-    dwh_dma_piece<0>(gbase, voff, lds_addr);
-    dwh_dma_piece<1>(gbase, voff, lds_addr);
-    if (NP == 4) {
-        dwh_dma_piece<2>(gbase, voff, lds_addr);
-        dwh_dma_piece<3>(gbase, voff, lds_addr);
-    }
-}
-__device__ __forceinline__ void dwh_wait_keep(int keep) {               // at most `keep` DMA pieces of this wave still in flight
+// At most `keep` DMA pieces of this wave still in flight.  Not wait_dma_keep() of hnrf_lds_dma.h: here `keep` is a RUNTIME
+// value (stages left x pieces per stage), the switch is lowered to a compare chain over its case list, and a longer list
+// is other code (checked: profiles/refactor_f16_epilogue.txt).  Stages of 6 pieces (<2,4>, <1,8>) have no case for
+// keep = 6 and drain the queue there, as they always did.
+__device__ __forceinline__ void dwh_wait_keep(int keep) {
 #define HNRF_VM(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
     switch (keep) {
         HNRF_VM(4) HNRF_VM(8) HNRF_VM(12) HNRF_VM(16) HNRF_VM(20) HNRF_VM(24) HNRF_VM(28) HNRF_VM(32)
@@ -699,8 +676,8 @@ __global__ __launch_bounds__(256) void mlp_dwh_dma_kernel(const _Float16* __rest
     auto issue = [&](int64_t stage) {                                   // wave-uniform
         const int64_t blk = (s0 >> 5) + stage;
         const unsigned dst = lbase + (unsigned)(stage % NBUF) * SB;
-        dwh_dma_run<ZP>(reinterpret_cast<const char*>(dZ + blk * (int64_t)(NOW * 32)) + w * (ZP * 1024), voff, dst + w * (ZP * 1024));
-        dwh_dma_run<XP>(reinterpret_cast<const char*>(X + blk * (int64_t)(NIP * 32)) + w * (XP * 1024), voff, dst + ZB + w * (XP * 1024));
+        dma_run<ZP>(reinterpret_cast<const char*>(dZ + blk * (int64_t)(NOW * 32)) + w * (ZP * 1024), voff, dst + w * (ZP * 1024));
+        dma_run<XP>(reinterpret_cast<const char*>(X + blk * (int64_t)(NIP * 32)) + w * (XP * 1024), voff, dst + ZB + w * (XP * 1024));
     };
     auto compute = [&](int buf) {
         const unsigned lb = lbase + buf * SB;
@@ -754,7 +731,10 @@ __global__ __launch_bounds__(256) void mlp_dwh_dma_kernel(const _Float16* __rest
     }
 }
 
-// head layers with f16 activations: mlp_dw_head_kernel reading X as halves (XBLK: blocked layout, see mlp_dwh_kernel)
+// head layers with f16 activations: mlp_dw_head_kernel reading X as halves (XBLK: blocked layout, see mlp_dwh_kernel).
+// Only XBLK = false is instantiated (blocked X takes mlp_dwh_head_blk_kernel below).  The parameter stays: without the
+// dead arm hipcc orders two register moves of the row-major instances differently (seven spellings tried, see
+// profiles/refactor_f16_epilogue.txt), and these kernels are pinned instruction by instruction.
 template <int NI, bool XBLK>
 __global__ __launch_bounds__(NI) void mlp_dwh_head_kernel(const float* __restrict__ dY, int64_t ldy, int n_out,
                                                            const _Float16* __restrict__ X, int64_t ldx, int64_t P,
@@ -1314,25 +1294,24 @@ extern "C" int hnrf_mlp_dw_h(const void* dZ, int64_t ldz, const void* X, int64_t
         HNRF_REQUIRE((((uintptr_t)dZ | (uintptr_t)X) & 15) == 0 && (zb || ldz % 8 == 0) && (xb || ldx % 8 == 0), HNRF_E_ARG,
                      "hnrf_mlp_dw_h: dZ and X must be 16-byte aligned with row strides that are multiples of 8 halves");
         HNRF_REQUIRE(!xb || pl.nip >= 128, HNRF_E_UNSUPPORTED, "hnrf_mlp_dw_h: blocked X needs n_in 128 | 256");
-#define HNRF_DWH1(OT, IT, ZB_, XB_)                                                                                    \
-    hipLaunchKernelGGL((mlp_dwh_kernel<OT, IT, ZB_, XB_>), dim3(pl.nsplit), dim3(256), 0, st, (const _Float16*)dZ, ldz, \
+#define HNRF_DWH1(OT, IT, ZB_)                                                                                    \
+    hipLaunchKernelGGL((mlp_dwh_kernel<OT, IT, ZB_>), dim3(pl.nsplit), dim3(256), 0, st, (const _Float16*)dZ, ldz, \
                        (const _Float16*)X, ldx, P, pl.per_wg, dz_scale, part, db ? dbpart : nullptr)
 #define HNRF_DWH_DMA(OT, IT)                                                                                         \
     do {                                                                                                             \
         constexpr int lds = dwh_dma_bufs(32 * 128 * OT * 2 + 32 * 32 * IT * 2) * (32 * 128 * OT * 2 + 32 * 32 * IT * 2);  \
-        static unsigned long long done = 0;                                                                          \
-        if (int rc_ = reserve_lds((const void*)mlp_dwh_dma_kernel<OT, IT>, lds, done, "hnrf_mlp_dw_h")) return rc_;   \
-        hipLaunchKernelGGL((mlp_dwh_dma_kernel<OT, IT>), dim3(pl.nsplit), dim3(256), lds, st, (const _Float16*)dZ,    \
-                           (const _Float16*)X, P, pl.per_wg, dz_scale, part, db ? dbpart : nullptr);                  \
+        if (int rc_ = launch_lds<mlp_dwh_dma_kernel<OT, IT>>("hnrf_mlp_dw_h", dim3(pl.nsplit), dim3(256), lds, st,   \
+                                                             (const _Float16*)dZ, (const _Float16*)X, P, pl.per_wg,  \
+                                                             dz_scale, part, db ? dbpart : nullptr))                 \
+            return rc_;                                                                                              \
     } while (0)
+    // both operands blocked (hidden layers only: IT >= 4): the LDS-DMA kernel
 #define HNRF_DWH(OT, IT)                                                       \
     do {                                                                       \
-        if (zb && xb) { if (IT >= 4) { if (use_dma) HNRF_DWH_DMA(OT, (IT >= 4 ? IT : 4)); else HNRF_DWH1(OT, (IT >= 4 ? IT : 4), true, true); } } \
-        else if (zb) HNRF_DWH1(OT, IT, true, false);                           \
-        else HNRF_DWH1(OT, IT, false, false);                                  \
+        if (zb && xb) { if (IT >= 4) HNRF_DWH_DMA(OT, (IT >= 4 ? IT : 4)); }   \
+        else if (zb) HNRF_DWH1(OT, IT, true);                                  \
+        else HNRF_DWH1(OT, IT, false);                                         \
     } while (0)
-        // (HNRF_DWH_NO_DMA in the environment: the register-staged form, for A/B runs)
-        static const bool use_dma = getenv("HNRF_DWH_NO_DMA") == nullptr;
         HNRF_REQUIRE(zb || !xb, HNRF_E_UNSUPPORTED, "hnrf_mlp_dw_h: blocked X with row-major dZ is not built");
         if (n_out == 256) { if (pl.nip == 256) HNRF_DWH(2, 8); else if (pl.nip == 128) HNRF_DWH(2, 4); else HNRF_DWH(2, 2); }
         else { if (pl.nip == 256) HNRF_DWH(1, 8); else if (pl.nip == 128) HNRF_DWH(1, 4); else HNRF_DWH(1, 2); }

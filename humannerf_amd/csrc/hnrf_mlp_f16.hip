@@ -26,6 +26,7 @@
 // [k-step][hi|lo][lane][8 halves]).  All biases sit in a small LDS table loaded once.
 #include "hnrf_common.h"
 #include "hnrf_sincos.h"
+#include "hnrf_lds_dma.h"
 
 namespace hnrf {
 
@@ -38,20 +39,15 @@ constexpr int RING = 3;                    // slabs resident in LDS
 constexpr float LO_SCALE = 2048.0f;        // 2^11
 constexpr float LO_INV = 1.0f / 2048.0f;
 // Forward images (inference and activation-saving kernels): the weights' low parts are stored UN-lifted, lo = f16(w - hi),
-// like the activations' (epi_pair_u), so that all three products of a k-step -- wh.xh, wh.xl, wl.xh -- go into ONE fp32
+// like the activations' (epi_pair), so that all three products of a k-step -- wh.xh, wh.xl, wl.xh -- go into ONE fp32
 // accumulator: no second accumulator (32 VGPRs), no `acc1 + acc2 / 2^11` in the epilogue (2 of its 8 VALU per value
 // pair), and the third MFMA multiplies tiny operands (the matrix pipe's energy depends on its operands' bits, and these
 // kernels run at the package power limit).  The price: w - hi ~ 2^-12 |w| sits in f16's subnormal range for |w| < 0.25,
 // so a weight is represented to max(2^-25, 2^-23 |w|) instead of 2^-23 |w| -- an ABSOLUTE floor of 3e-8 against layers
 // whose largest weights are 0.1 .. 0.3; a dot product over 256 activations of order 0.5 sees 1.4e-7 of it, below the
 // 6e-7 of fp32 accumulation itself (measured: tests/test_gpu_parity.py -s).  Layers with abnormally small weights are
-// lifted as a whole by an exact power of two (layer_exponent), as before.  The dX chains keep the lifted form.
-// -DHNRF_WLO_LIFTED builds the round-2 scheme (two accumulators) for A/B through HNRF_LIB_PATH.
-#ifdef HNRF_WLO_LIFTED
-constexpr bool WLO_UNLIFTED = false;
-#else
-constexpr bool WLO_UNLIFTED = true;
-#endif
+// lifted as a whole by an exact power of two (layer_exponent), as before.  The dX chains keep the lifted form (weights'
+// low parts x 2^11, products wh.xl and wl.xh in a second accumulator that the epilogue folds in as acc1 + acc2 / 2^11).
 
 enum { PE16_NONE = 0, PE16_CANONICAL = 1, PE16_NONRIGID = 2 };
 
@@ -65,6 +61,8 @@ enum { SV_NONE = 0,
 __host__ __device__ constexpr bool sv_fwd(int s) { return s == SV_ACT || s == SV_ACT_H; }
 __host__ __device__ constexpr bool sv_bwd(int s) { return s == SV_DZ || s == SV_DZ_H; }
 __host__ __device__ constexpr bool sv_has_bias(int s) { return s == SV_NONE || sv_fwd(s); }
+// the chain stages keep lifted low parts and two accumulators (top of the file); every forward form: one, un-lifted
+__host__ __device__ constexpr bool sv_lifted(int s) { return sv_bwd(s) || s == SV_PE; }
 
 // hidden feature contracted by element j of k-step ks on lane half h
 __host__ __device__ inline int hid_feat16(int ks, int j, int h) {
@@ -162,7 +160,7 @@ __global__ void pack_layer16_kernel(PackSet16 set, const float* __restrict__ con
         float w = 0.f;
         if (row < d.n_out && col >= 0 && col < d.n_in) w = ldexpf(d.W[(int64_t)row * d.n_in + col], kexp);
         const _Float16 hi = (_Float16)w;
-        const _Float16 lo = WLO_UNLIFTED ? (_Float16)(w - (float)hi) : (_Float16)((w - (float)hi) * LO_SCALE);
+        const _Float16 lo = (_Float16)(w - (float)hi);               // un-lifted, see above
         outv[e] = part ? lo : hi;
     }
     *reinterpret_cast<h16x2*>(dst) = h16x2{outv[0], outv[1]};
@@ -208,77 +206,11 @@ __device__ __forceinline__ h16x8 lds_ld8(unsigned addr) { return *reinterpret_ca
 __device__ __forceinline__ f32x4 lds_ld4f(unsigned addr) { return *reinterpret_cast<const lds_f32x4*>((size_t)addr); }
 __device__ __forceinline__ void lds_st8(unsigned addr, h16x8 v) { *reinterpret_cast<lds_h16x8*>((size_t)addr) = v; }
 
-// Lane id recomputed where it is needed (2 VALU).  Volatile on purpose: addresses derived
-// from a lane id hoisted to kernel entry get spilled, and the reload's compiler-inserted
-// s_waitcnt vmcnt(0) would drain the hand-counted DMA queue on every tile.
-__device__ __forceinline__ unsigned lane_now() {
-    unsigned l;
-    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-    return l;
-}
-
-// One 1-KiB LDS-DMA piece: lane l's 16 bytes at gbase + voff(l) land at LDS byte lds_addr + 16 l.
-// Inline asm so that hipcc does not count it (its own bookkeeping would put
-// s_waitcnt vmcnt(0) in front of the next ds_read); retired by wait_dma_keep().
-__device__ __forceinline__ void dma_piece(const char* gbase, unsigned voff, unsigned lds_addr) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2\n\ts_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(voff), "s"(gbase), "s"(lds_addr)
-        : "memory");
-}
-
-// The same inside the k-loops, where every instruction of the one wave per SIMD costs ~5 cycles of issue next to the
-// MFMAs' 32 (profiles/tools/mfma_issue.hip: 8 + 5 n cycles per MFMA with n other instructions of ANY kind, scalar ones
-// included): the form above is 8 instructions per piece (m0 saved / set / restored, s_nop, two-word source add, LDS
-// address add), 1.3 per MFMA of the canonical kernel.  The instruction's immediate offset applies to BOTH addresses
-// (LDS address = M0 + offset + 16 lane, measured: profiles/tools/dma_offset.hip), so four consecutive 1-KiB pieces
-// share one source base and one M0 value (offsets 0 / 1024 / 2048 / 3072); M0 is handed to the compiler as an operand
-// ("{m0}": it materialises the value and the hazard wait itself, and nothing else in these kernels uses M0).
-// Wave w therefore moves the CONTIGUOUS pieces [w n, (w + 1) n) of a slab (n = pieces per wave), not w, w+4, ...
-template <int R>
-__device__ __forceinline__ void dma_piece_g(const char* gbase, unsigned voff, unsigned lds_addr) {
-    // a scalar write of M0 needs one wait state before an LDS-DMA instruction reads it (gfx9 hazard), and hipcc, which
-    // places the write, cannot see into the asm to insert it: hence the s_nop inside the statement.  In EVERY piece, not
-    // only a run's first: where the pieces of a run sit in different basic blocks (runtime piece counts at layer
-    // boundaries) the compiler writes M0 again in front of later pieces (the same value, so a stale read would be
-    // harmless -- but that is an argument about today's code generation, not a guarantee)
-    asm volatile("s_nop 0\n\tglobal_load_lds_dwordx4 %0, %1 offset:%3" : : "v"(voff), "s"(gbase), "{m0}"(lds_addr), "n"(R * 1024) : "memory");
-}
-// piece i (compile-time after unrolling) of this wave's run: base addresses of the wave's run in, group of four out
-__device__ __forceinline__ void dma_run_piece(const char* run_src, unsigned voff, unsigned run_dst, int i) {
-    const char* g = run_src + (i >> 2) * 4096;
-    const unsigned d = run_dst + (i >> 2) * 4096;
-    switch (i & 3) {
-        case 0: dma_piece_g<0>(g, voff, d); break;
-        case 1: dma_piece_g<1>(g, voff, d); break;
-        case 2: dma_piece_g<2>(g, voff, d); break;
-        default: dma_piece_g<3>(g, voff, d); break;
-    }
-}
-
 // DMA of nblocks 1-KiB blocks: wave w moves blocks w, w+4, ...  (nblocks % 4 == 0
 // wherever a counted wait follows, so that every wave has the same count in flight)
 __device__ __forceinline__ void slab_issue(const char* gsrc, unsigned lds_addr, int nblocks, int wave, int nw = 4) {
     const unsigned voff = lane_now() * 16;
     for (int b = wave; b < nblocks; b += nw) dma_piece(gsrc + b * 1024, voff, lds_addr + b * 1024);
-}
-
-// wait until at most `keep` of this wave's DMA pieces are still in flight
-__device__ __forceinline__ void wait_dma_keep(int keep) {
-#define HNRF_VMCNT_CASE(N) case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
-    switch (keep) {
-        // (even counts: four waves per workgroup; the odd ones: eight, 2 or 3 pieces per wave and slab.  Training variants:
-        // the 4 activation stores per finished tile sit in the same in-order queue)
-        HNRF_VMCNT_CASE(1) HNRF_VMCNT_CASE(2) HNRF_VMCNT_CASE(3) HNRF_VMCNT_CASE(4) HNRF_VMCNT_CASE(5) HNRF_VMCNT_CASE(6)
-        HNRF_VMCNT_CASE(7) HNRF_VMCNT_CASE(8) HNRF_VMCNT_CASE(9) HNRF_VMCNT_CASE(10) HNRF_VMCNT_CASE(11) HNRF_VMCNT_CASE(12)
-        HNRF_VMCNT_CASE(13) HNRF_VMCNT_CASE(14) HNRF_VMCNT_CASE(15) HNRF_VMCNT_CASE(16) HNRF_VMCNT_CASE(18) HNRF_VMCNT_CASE(20)
-        HNRF_VMCNT_CASE(22) HNRF_VMCNT_CASE(24) HNRF_VMCNT_CASE(26) HNRF_VMCNT_CASE(28) HNRF_VMCNT_CASE(30)
-        HNRF_VMCNT_CASE(32) HNRF_VMCNT_CASE(34) HNRF_VMCNT_CASE(36) HNRF_VMCNT_CASE(38) HNRF_VMCNT_CASE(40)
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-#undef HNRF_VMCNT_CASE
 }
 
 __device__ __forceinline__ void tile_sync(int keep) {
@@ -287,13 +219,15 @@ __device__ __forceinline__ void tile_sync(int keep) {
     asm volatile("" ::: "memory");
 }
 
-// hi/lo split of 8 fp32 values into two f16x8 B-operand fragments
+// hi/lo split of 8 fp32 values into two f16x8 B-operand fragments; ULO: un-scaled low parts (see epi_core)
+template <bool ULO>
 __device__ __forceinline__ void split8(const float (&v)[8], h16x8& hi, h16x8& lo) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const f32x2 p = {v[2 * i], v[2 * i + 1]};
         const h16x2 hh = __builtin_convertvector(p, h16x2);
-        const f32x2 rem = {fmaf((float)hh[0], -LO_SCALE, p[0] * LO_SCALE), fmaf((float)hh[1], -LO_SCALE, p[1] * LO_SCALE)};
+        const f32x2 rem = ULO ? f32x2{p[0] - (float)hh[0], p[1] - (float)hh[1]}
+                              : f32x2{fmaf((float)hh[0], -LO_SCALE, p[0] * LO_SCALE), fmaf((float)hh[1], -LO_SCALE, p[1] * LO_SCALE)};
         const h16x2 ll = __builtin_convertvector(rem, h16x2);
         hi[2 * i] = hh[0];
         hi[2 * i + 1] = hh[1];
@@ -319,35 +253,6 @@ struct Pipe {
 #endif
 };
 
-// Epilogue of one PAIR of accumulator registers (2i, 2i+1) of a finished tile: combine the
-// two accumulators, ReLU + f16-range clamp, hi/lo split, and drop the two halves into the
-// next layer's B-operand fragment (k-step 2t + (i>>2), elements 2(i&3), 2(i&3)+1).
-template <bool RELU>
-__device__ __forceinline__ void epi_pair(const f32x16& a1, const f32x16& a2, int i, h16x8& hi, h16x8& lo) {
-    // scalar f32 ops on purpose: beside MFMAs the packed forms (v_pk_add/mul_f32) cost more issue time
-    float x0 = fmaf(a2[2 * i], LO_INV, a1[2 * i]);
-    float x1 = fmaf(a2[2 * i + 1], LO_INV, a1[2 * i + 1]);
-    if (RELU) {
-        x0 = __builtin_amdgcn_fmed3f(x0, 0.f, 65504.f);
-        x1 = __builtin_amdgcn_fmed3f(x1, 0.f, 65504.f);
-    }
-    const h16x2 hh = __builtin_convertvector(f32x2{x0, x1}, h16x2);
-    // (x - hi) * 2^11, exact; written so that hipcc folds the f16 -> f32 conversion into v_fma_mix_f32
-    const float r0 = fmaf((float)hh[0], -LO_SCALE, x0 * LO_SCALE);
-    const float r1 = fmaf((float)hh[1], -LO_SCALE, x1 * LO_SCALE);
-    const h16x2 ll = __builtin_convertvector(f32x2{r0, r1}, h16x2);
-    const int e = 2 * (i & 3);
-    hi[e] = hh[0];
-    hi[e + 1] = hh[1];
-    lo[e] = ll[0];
-    lo[e + 1] = ll[1];
-}
-
-// Un-scaled low part (two-group K2 kernel): lo = f16(x - hi) without the 2^11 lift, one VALU less per value.  lo then
-// drops into f16 subnormals for |x| < 2^-3 and x is represented to max(2^-25, 2^-22 |x|) instead of 2^-22 |x|: an
-// ABSOLUTE floor of 3e-8 on activations of order 0.1 .. 1 -- what a dot product over them sees is the same.  The
-// products wh . xl then carry no 2^11 and go into the FIRST accumulator; wl keeps its lift (weights are packed
-// offline and 2^-12 |w| would sit far down in the subnormals).
 // f16-range guard of the inference kernels.  The split v = hi + lo holds below the f16 range; the epilogue clamps
 // post-ReLU activations at 65504, and a checkpoint whose hidden activations get there -- or only past 128, where the
 // un-lifted weights stop being fp32-accurate (SAT_HALF below) -- would render a wrong image without any error.  GUARDED kernel instances (template parameter GUARD, Pipe::guard) therefore look at every finished
@@ -364,7 +269,7 @@ __device__ __forceinline__ void epi_pair(const f32x16& a1, const f32x16& a2, int
 // The inline asm needs its "scc" clobber: s_or_b64 writes SCC, and without it hipcc scheduled the block between an
 // s_add_u32 / s_addc_u32 pair -- a hit then added a carry, i.e. 4 GiB, to a weight pointer (memory fault).
 // The threshold is the edge of the ACCURACY envelope, not of the f16 range: the forward images keep a weight's low part
-// un-lifted (WLO_UNLIFTED above), so |w| < 0.25 carries an absolute error of up to 2^-25, and an activation a multiplies
+// un-lifted (top of the file), so |w| < 0.25 carries an absolute error of up to 2^-25, and an activation a multiplies
 // it into up to |a| 2^-25 per product.  Measured (tests/test_gpu_f16_range.py, an activation carried into the output by
 // weights c / a): fp32-class up to a = 100 (1.5e-6 relative, 4x CPU fp32 + 1e-6 allowed), 2.3e-5 at 1e3, 6.8e-4 at
 // 5e4 -- the old threshold of 6e4 let all of that through unreported.  Reporting from 128 on costs no instruction.
@@ -386,61 +291,48 @@ __device__ __forceinline__ void raise_f16_range(const char* packed, int64_t off,
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-template <bool RELU>
-__device__ __forceinline__ void epi_pair_u(const f32x16& a1, const f32x16& a2, int i, h16x8& hi, h16x8& lo,
-                                           unsigned long long& sflag, bool guard) {
-    float x0 = WLO_UNLIFTED ? a1[2 * i] : fmaf(a2[2 * i], LO_INV, a1[2 * i]);
-    float x1 = WLO_UNLIFTED ? a1[2 * i + 1] : fmaf(a2[2 * i + 1], LO_INV, a1[2 * i + 1]);
-    if (RELU) {
+// Epilogue of one PAIR of accumulator registers (2i, 2i+1) of a finished tile: combine the accumulators, activation,
+// hi/lo split, and drop the two halves into the next layer's B-operand fragment (k-step 2t + (i>>2), elements 2(i&3),
+// 2(i&3)+1).  Hands back the pair's hi parts and the two values (the training variants store them).
+//   ACT_RELU      forward: ReLU + f16-range clamp
+//   ACT_MASK_SEL  backward chain, fp32 dZ: relu' from bit 2i / 2i+1 of m (the tile's 16 bits of the sign mask)
+//   ACT_MASK_AND  backward chain, f16 dZ: relu' from the whole mask word m as push_pair_bits built it (n = 8 (tile & 1)
+//                 + pair): a 1-bit signed field extract gives 0 / -1, one AND applies it (2 VALU per value)
+// ULO (all forward forms): ONE accumulator (a2 is not read, see the top of the file) and an UN-scaled low part,
+// lo = f16(x - hi) without the 2^11 lift, one VALU less per value.  lo then drops into f16 subnormals for |x| < 2^-3 and
+// x is represented to max(2^-25, 2^-22 |x|) instead of 2^-22 |x|: an ABSOLUTE floor of 3e-8 on activations of order
+// 0.1 .. 1 -- what a dot product over them sees is the same.  Otherwise (the chains) x = a1 + a2 / 2^11 and
+// lo = f16((x - hi) 2^11).
+enum { ACT_NONE = 0, ACT_RELU = 1, ACT_MASK_SEL = 2, ACT_MASK_AND = 3 };
+template <int ACT, bool ULO>
+__device__ __forceinline__ h16x2 epi_core(const f32x16& a1, const f32x16& a2, int i, uint32_t m, int n, h16x8& hi, h16x8& lo,
+                                          float& x0, float& x1) {
+    // scalar f32 ops on purpose: beside MFMAs the packed forms (v_pk_add/mul_f32) cost more issue time
+    x0 = ULO ? a1[2 * i] : fmaf(a2[2 * i], LO_INV, a1[2 * i]);
+    x1 = ULO ? a1[2 * i + 1] : fmaf(a2[2 * i + 1], LO_INV, a1[2 * i + 1]);
+    if (ACT == ACT_RELU) {
         x0 = __builtin_amdgcn_fmed3f(x0, 0.f, 65504.f);
         x1 = __builtin_amdgcn_fmed3f(x1, 0.f, 65504.f);
-    }
-    const h16x2 hh = __builtin_convertvector(f32x2{x0, x1}, h16x2);
-    // x - hi in ONE v_fma_mix_f32 (f16 operand converted inside): with a literal -1 hipcc rewrites the fma as
-    // v_cvt_f32_f16 + v_sub_f32, so the factor is made opaque
-    float m1 = -1.0f;
-    asm("" : "+v"(m1));
-    const float r0 = fmaf((float)hh[0], m1, x0);
-    const float r1 = fmaf((float)hh[1], m1, x1);
-    const h16x2 ll = __builtin_convertvector(f32x2{r0, r1}, h16x2);
-    const int e = 2 * (i & 3);
-    hi[e] = hh[0];
-    hi[e + 1] = hh[1];
-    lo[e] = ll[0];
-    lo[e + 1] = ll[1];
-    if (RELU && guard && (i & 3) == 3) sat_check_frag(hi, sflag);
-}
-__device__ __forceinline__ void split8_u(const float (&v)[8], h16x8& hi, h16x8& lo) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x2 p = {v[2 * i], v[2 * i + 1]};
-        const h16x2 hh = __builtin_convertvector(p, h16x2);
-        const h16x2 ll = __builtin_convertvector(f32x2{p[0] - (float)hh[0], p[1] - (float)hh[1]}, h16x2);
-        hi[2 * i] = hh[0];
-        hi[2 * i + 1] = hh[1];
-        lo[2 * i] = ll[0];
-        lo[2 * i + 1] = ll[1];
-    }
-}
-
-// epi_pair that also hands back the two activations (training variant stores them)
-template <bool RELU, bool ULO = false>
-__device__ __forceinline__ h16x2 epi_pair_x(const f32x16& a1, const f32x16& a2, int i, h16x8& hi, h16x8& lo, float& x0o,
-                                            float& x1o) {
-    float x0 = (ULO && WLO_UNLIFTED) ? a1[2 * i] : fmaf(a2[2 * i], LO_INV, a1[2 * i]);
-    float x1 = (ULO && WLO_UNLIFTED) ? a1[2 * i + 1] : fmaf(a2[2 * i + 1], LO_INV, a1[2 * i + 1]);
-    if (RELU) {
-        x0 = __builtin_amdgcn_fmed3f(x0, 0.f, 65504.f);
-        x1 = __builtin_amdgcn_fmed3f(x1, 0.f, 65504.f);
+    } else if (ACT == ACT_MASK_SEL) {
+        x0 = (m >> (2 * i)) & 1u ? __builtin_amdgcn_fmed3f(x0, -65504.f, 65504.f) : 0.f;
+        x1 = (m >> (2 * i + 1)) & 1u ? __builtin_amdgcn_fmed3f(x1, -65504.f, 65504.f) : 0.f;
+    } else if (ACT == ACT_MASK_AND) {
+        x0 = __builtin_amdgcn_fmed3f(x0, -65504.f, 65504.f);
+        x1 = __builtin_amdgcn_fmed3f(x1, -65504.f, 65504.f);
+        x0 = __uint_as_float(__float_as_uint(x0) & (uint32_t)__builtin_amdgcn_sbfe((int)m, 15 - n, 1));
+        x1 = __uint_as_float(__float_as_uint(x1) & (uint32_t)__builtin_amdgcn_sbfe((int)m, 31 - n, 1));
     }
     const h16x2 hh = __builtin_convertvector(f32x2{x0, x1}, h16x2);
     float r0, r1;
-    if (ULO) {                  // un-scaled low part, see epi_pair_u
+    if (ULO) {
+        // x - hi in ONE v_fma_mix_f32 (f16 operand converted inside): with a literal -1 hipcc rewrites the fma as
+        // v_cvt_f32_f16 + v_sub_f32, so the factor is made opaque
         float m1 = -1.0f;
         asm("" : "+v"(m1));
         r0 = fmaf((float)hh[0], m1, x0);
         r1 = fmaf((float)hh[1], m1, x1);
-    } else {                    // (x - hi) * 2^11, exact; written so that hipcc folds the f16 -> f32 conversion into v_fma_mix_f32
+    } else {
+        // (x - hi) * 2^11, exact; written so that hipcc folds the f16 -> f32 conversion into v_fma_mix_f32
         r0 = fmaf((float)hh[0], -LO_SCALE, x0 * LO_SCALE);
         r1 = fmaf((float)hh[1], -LO_SCALE, x1 * LO_SCALE);
     }
@@ -450,9 +342,14 @@ __device__ __forceinline__ h16x2 epi_pair_x(const f32x16& a1, const f32x16& a2, 
     hi[e + 1] = hh[1];
     lo[e] = ll[0];
     lo[e + 1] = ll[1];
-    x0o = x0;
-    x1o = x1;
     return hh;
+}
+// inference form: nothing handed back, the range guard looks at every finished fragment (every fourth pair)
+template <bool RELU>
+__device__ __forceinline__ void epi_pair(const f32x16& a, int i, h16x8& hi, h16x8& lo, unsigned long long& sflag, bool guard) {
+    float x0, x1;
+    epi_core<RELU ? ACT_RELU : ACT_NONE, true>(a, a, i, 0u, 0, hi, lo, x0, x1);
+    if (RELU && guard && (i & 3) == 3) sat_check_frag(hi, sflag);
 }
 
 // Training variant (SAVE): where this lane's activations go.  row = the lane's row of the layer's [P, width]
@@ -473,28 +370,6 @@ struct SaveCtx {
     float descale, amax;
     float fout[32];
 };
-
-// Backward epilogue of one accumulator pair: x = (acc1 + acc2 / 2^11) * relu'(mask bit), split for the next stage;
-// hands back the two (still scaled) values.
-__device__ __forceinline__ void epi_pair_m(const f32x16& a1, const f32x16& a2, int i, uint32_t mbits, h16x8& hi,
-                                           h16x8& lo, float& x0o, float& x1o) {
-    float x0 = fmaf(a2[2 * i], LO_INV, a1[2 * i]);
-    float x1 = fmaf(a2[2 * i + 1], LO_INV, a1[2 * i + 1]);
-    x0 = (mbits >> (2 * i)) & 1u ? __builtin_amdgcn_fmed3f(x0, -65504.f, 65504.f) : 0.f;
-    x1 = (mbits >> (2 * i + 1)) & 1u ? __builtin_amdgcn_fmed3f(x1, -65504.f, 65504.f) : 0.f;
-    const h16x2 hh = __builtin_convertvector(f32x2{x0, x1}, h16x2);
-    // (x - hi) * 2^11, exact; written so that hipcc folds the f16 -> f32 conversion into v_fma_mix_f32
-    const float r0 = fmaf((float)hh[0], -LO_SCALE, x0 * LO_SCALE);
-    const float r1 = fmaf((float)hh[1], -LO_SCALE, x1 * LO_SCALE);
-    const h16x2 ll = __builtin_convertvector(f32x2{r0, r1}, h16x2);
-    const int e = 2 * (i & 3);
-    hi[e] = hh[0];
-    hi[e + 1] = hh[1];
-    lo[e] = ll[0];
-    lo[e + 1] = ll[1];
-    x0o = x0;
-    x1o = x1;
-}
 
 // dZ store of the backward chain: un-scaled fp32, 4 values per store like save_pair; tracks max |dZ|
 __device__ __forceinline__ void save_pair_b(SaveCtx& sc, int t, int i, float x0, float x1) {
@@ -563,26 +438,35 @@ __device__ __forceinline__ void push_pair_bits(uint32_t& acc, h16x2 hh) {
     asm("v_pk_min_u16 %1, %2, %3\n\tv_pk_mad_u16 %0, %0, %4, %1" : "+v"(acc), "=&v"(tmp) : "v"(u), "s"(0x00010001u), "s"(0x00020002u));
 }
 
-// Backward epilogue of the f16 form: relu' from that mask (the whole word; n = 8 (tile & 1) + pair as pushed): a 1-bit
-// signed field extract gives 0 / -1, one AND applies it (2 VALU per value).
-__device__ __forceinline__ h16x2 epi_pair_mh(const f32x16& a1, const f32x16& a2, int i, uint32_t mword, int n, h16x8& hi, h16x8& lo) {
-    float x0 = fmaf(a2[2 * i], LO_INV, a1[2 * i]);
-    float x1 = fmaf(a2[2 * i + 1], LO_INV, a1[2 * i + 1]);
-    x0 = __builtin_amdgcn_fmed3f(x0, -65504.f, 65504.f);
-    x1 = __builtin_amdgcn_fmed3f(x1, -65504.f, 65504.f);
-    x0 = __uint_as_float(__float_as_uint(x0) & (uint32_t)__builtin_amdgcn_sbfe((int)mword, 15 - n, 1));
-    x1 = __uint_as_float(__float_as_uint(x1) & (uint32_t)__builtin_amdgcn_sbfe((int)mword, 31 - n, 1));
-    const h16x2 hh = __builtin_convertvector(f32x2{x0, x1}, h16x2);
-    const float r0 = fmaf((float)hh[0], -LO_SCALE, x0 * LO_SCALE);
-    const float r1 = fmaf((float)hh[1], -LO_SCALE, x1 * LO_SCALE);
-    const h16x2 ll = __builtin_convertvector(f32x2{r0, r1}, h16x2);
-    const int e = 2 * (i & 3);
-    hi[e] = hh[0];
-    hi[e + 1] = hh[1];
-    lo[e] = ll[0];
-    lo[e + 1] = ll[1];
-    return hh;
-}
+// Epilogue of pair I of finished tile T, by what the layer saves (layer16 runs it in two places: for tile t - 1 inside
+// the k-loop of tile t, and for the last tile behind the loop).  A macro, not a function: as a capturing lambda or a
+// function template the same text changes the register allocation of the training-forward kernels
+// (canonical_f16x3_kernel<SV_ACT_H>: 4 431 -> 4 494 VALU instructions, profiles/refactor_f16_epilogue.txt).
+#define HNRF_TILE_EPILOGUE_PAIR(T, I)                                                                                          \
+    if constexpr (SAVE == SV_ACT) {                                                                                            \
+        float x0, x1;                                                                                                          \
+        epi_core<ACT, ULO>(pacc1, pacc2, I, 0u, 0, oh[2 * (T) + ((I) >> 2)], ol[2 * (T) + ((I) >> 2)], x0, x1);                \
+        save_pair(*sc, bw, T, I, x0, x1);                                                                                      \
+    } else if constexpr (SAVE == SV_ACT_H) {                                                                                   \
+        float x0, x1;                                                                                                          \
+        const h16x2 hh = epi_core<ACT, ULO>(pacc1, pacc2, I, 0u, 0, oh[2 * (T) + ((I) >> 2)], ol[2 * (T) + ((I) >> 2)], x0, x1); \
+        push_pair_bits(bw[(T) >> 1], hh);                                                                                      \
+        if ((I) & 1) store_frag_h(rowh, cxh, T, I, oh[2 * (T) + ((I) >> 2)]);                                                  \
+    } else if constexpr (SAVE == SV_DZ) {                                                                                      \
+        float x0, x1;                                                                                                          \
+        epi_core<ACT_MASK_SEL, ULO>(pacc1, pacc2, I, sc->mask[(T) >> 1] >> (16 * ((T) & 1)), 0, oh[2 * (T) + ((I) >> 2)],      \
+                                    ol[2 * (T) + ((I) >> 2)], x0, x1);                                                         \
+        save_pair_b(*sc, T, I, x0, x1);                                                                                        \
+    } else if constexpr (SAVE == SV_DZ_H) {                                                                                    \
+        float x0, x1;                                                                                                          \
+        const h16x2 hh = epi_core<ACT_MASK_AND, ULO>(pacc1, pacc2, I, sc->mask[(T) >> 1], 8 * ((T) & 1) + (I),                 \
+                                                     oh[2 * (T) + ((I) >> 2)], ol[2 * (T) + ((I) >> 2)], x0, x1);              \
+        store_pair_h(rowh, cxh, svu, T, I, hh);                                                                                \
+    } else if constexpr (SAVE == SV_PE) {                                                                                      \
+        sc->fout[16 * (T) + 2 * (I)] = fmaf(pacc2[2 * (I)], LO_INV, pacc1[2 * (I)]);                                           \
+        sc->fout[16 * (T) + 2 * (I) + 1] = fmaf(pacc2[2 * (I) + 1], LO_INV, pacc1[2 * (I) + 1]);                               \
+    } else                                                                                                                     \
+        epi_pair<RELU>(pacc1, I, oh[2 * (T) + ((I) >> 2)], ol[2 * (T) + ((I) >> 2)], p.sat, p.guard);
 
 // One layer.  K order = [PE part (NKA k-steps, B operand from the LDS stash) | hidden part
 // (NKB k-steps, B operand from registers)].  The layer's NT tiles travel TPS per slab.
@@ -595,13 +479,13 @@ __device__ __forceinline__ h16x2 epi_pair_mh(const f32x16& a1, const f32x16& a2,
 //   * the VALU epilogue of tile t-1 (8 pair-units) is spread over the k-steps of tile t,
 //     so it runs in the shadow of the MFMAs; only the last tile's epilogue is exposed.
 //   * PEND_IN / DEFER (inference): the epilogue of a layer's LAST tile has no next tile of its own layer to hide
-//     behind; with DEFER it is left pending in (pend1, pend2) and the next layer (PEND_IN) runs it inside its first
+//     behind; with DEFER it is left pending in *pend and the next layer (PEND_IN) runs it inside its first
 //     tile, writing the last two fragments of its own input just before the k-steps that consume them.
 template <int NT, int TPS, int NKA, int NKB, bool RELU, int SAVE = 0, bool PEND_IN = false, bool DEFER = false,
-          bool ULO = false, int NW = 4, int NB, int NO>
+          int NW = 4, int NB, int NO>
 __device__ __forceinline__ void layer16(Pipe& p, int nb1, int nb2, h16x8 (&bh)[NB], h16x8 (&bl)[NB],
                                         h16x8 (&oh)[NO], h16x8 (&ol)[NO], float (&last)[16], SaveCtx* sc = nullptr,
-                                        f32x16* pend1 = nullptr, f32x16* pend2 = nullptr) {
+                                        f32x16* pend = nullptr) {
     static_assert(!(PEND_IN || DEFER) || SAVE == SV_NONE, "deferred epilogues exist in the inference form only");
     static_assert(!PEND_IN || NKB >= 2, "a pending tile fills the last two hidden fragments");
     static_assert(NB >= (NKB > 0 ? NKB : 1) && NO >= 2 * NT && NT % TPS == 0, "bad layer shape");
@@ -610,7 +494,9 @@ __device__ __forceinline__ void layer16(Pipe& p, int nb1, int nb2, h16x8 (&bh)[N
     constexpr int NS = NT / TPS;             // slabs of this layer
     constexpr int PFK = NK < 4 ? NK : 4;
     static_assert((NBLK * TPS) % NW == 0, "every wave must issue the same number of DMA pieces per slab");
-    static_assert(!ULO || SAVE == SV_NONE || sv_fwd(SAVE), "un-scaled activation low parts exist in the forward kernels only");
+    constexpr bool ULO = !sv_lifted(SAVE);   // un-scaled low parts, one accumulator (epi_core)
+    constexpr int ACT = RELU ? ACT_RELU : ACT_NONE;
+    static_assert(ULO || NT > 1, "the head layers exist in the forward kernels only");
     f32x16 pacc1 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     f32x16 pacc2 = pacc1;                    // accumulators of the previous tile (epilogue pending)
     f32x16 nbias = pacc1;                    // bias of the NEXT tile: the table is resident in LDS, so it is read
@@ -697,7 +583,7 @@ __device__ __forceinline__ void layer16(Pipe& p, int nb1, int nb2, h16x8 (&bh)[N
                 acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh, acc1, 0, 0, 0);
                 if (ULO) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, acc1, 0, 0, 0);
                 else acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl, acc2, 0, 0, 0);
-                if (ULO && WLO_UNLIFTED) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, acc1, 0, 0, 0);
+                if (ULO) acc1 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, acc1, 0, 0, 0);
                 else acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh, acc2, 0, 0, 0);
                 if (NT > 1 && sv_has_bias(SAVE) && ks == NK - 1 && t + 1 < NT) {
                     const unsigned bn = p.lds_base + p.bias_off + (tt + 1) * 128 + (lane >> 5) * 16;   // (tt + 1 == TPS: next slab's first)
@@ -722,7 +608,7 @@ __device__ __forceinline__ void layer16(Pipe& p, int nb1, int nb2, h16x8 (&bh)[N
 #pragma unroll
                     for (int i = 0; i < 8; ++i)
                         if ((i * (NK - 1)) / 8 == ks) {
-                            epi_pair_u<true>(*pend1, *pend2, i, bh[NKB - 2 + (i >> 2)], bl[NKB - 2 + (i >> 2)], p.sat, p.guard);
+                            epi_pair<true>(*pend, i, bh[NKB - 2 + (i >> 2)], bl[NKB - 2 + (i >> 2)], p.sat, p.guard);
                             asm volatile("" : "+v"(bh[NKB - 2 + (i >> 2)]), "+v"(bl[NKB - 2 + (i >> 2)]));
                         }
                 }
@@ -730,30 +616,7 @@ __device__ __forceinline__ void layer16(Pipe& p, int nb1, int nb2, h16x8 (&bh)[N
 #pragma unroll
                     for (int i = 0; i < 8; ++i)
                         if ((i * NK) / 8 == ks) {
-                            if constexpr (SAVE == SV_ACT) {
-                                float x0, x1;
-                                epi_pair_x<RELU, ULO>(pacc1, pacc2, i, oh[2 * (t - 1) + (i >> 2)], ol[2 * (t - 1) + (i >> 2)],
-                                                 x0, x1);
-                                save_pair(*sc, bw, t - 1, i, x0, x1);
-                            } else if constexpr (SAVE == SV_ACT_H) {
-                                float x0, x1;
-                                const h16x2 hh = epi_pair_x<RELU, ULO>(pacc1, pacc2, i, oh[2 * (t - 1) + (i >> 2)], ol[2 * (t - 1) + (i >> 2)], x0, x1);
-                                push_pair_bits(bw[(t - 1) >> 1], hh);
-                                if (i & 1) store_frag_h(rowh, cxh, t - 1, i, oh[2 * (t - 1) + (i >> 2)]);
-                            } else if constexpr (SAVE == SV_DZ) {
-                                float x0, x1;
-                                epi_pair_m(pacc1, pacc2, i, sc->mask[(t - 1) >> 1] >> (16 * ((t - 1) & 1)),
-                                           oh[2 * (t - 1) + (i >> 2)], ol[2 * (t - 1) + (i >> 2)], x0, x1);
-                                save_pair_b(*sc, t - 1, i, x0, x1);
-                            } else if constexpr (SAVE == SV_DZ_H) {
-                                const h16x2 hh = epi_pair_mh(pacc1, pacc2, i, sc->mask[(t - 1) >> 1], 8 * ((t - 1) & 1) + i,
-                                                             oh[2 * (t - 1) + (i >> 2)], ol[2 * (t - 1) + (i >> 2)]);
-                                store_pair_h(rowh, cxh, svu, t - 1, i, hh);
-                            } else if constexpr (SAVE == SV_PE) {
-                                sc->fout[16 * (t - 1) + 2 * i] = fmaf(pacc2[2 * i], LO_INV, pacc1[2 * i]);
-                                sc->fout[16 * (t - 1) + 2 * i + 1] = fmaf(pacc2[2 * i + 1], LO_INV, pacc1[2 * i + 1]);
-                            } else
-                            epi_pair_u<RELU>(pacc1, pacc2, i, oh[2 * (t - 1) + (i >> 2)], ol[2 * (t - 1) + (i >> 2)], p.sat, p.guard);
+                            HNRF_TILE_EPILOGUE_PAIR(t - 1, i)
                             // pin the result here: without a use in this block hipcc sinks the whole
                             // epilogue to the first consumer (the next layer), out of the MFMA shadow
                             if constexpr (SAVE != SV_PE)
@@ -788,36 +651,13 @@ __device__ __forceinline__ void layer16(Pipe& p, int nb1, int nb2, h16x8 (&bh)[N
     }
     if (NT == 1) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) last[r] = (ULO && WLO_UNLIFTED) ? pacc1[r] : pacc1[r] + pacc2[r] * LO_INV;
+        for (int r = 0; r < 16; ++r) last[r] = pacc1[r];
     } else if (DEFER) {
-        *pend1 = pacc1;
-        *pend2 = pacc2;
+        *pend = pacc1;
     } else {
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            if constexpr (SAVE == SV_ACT) {
-                float x0, x1;
-                epi_pair_x<RELU, ULO>(pacc1, pacc2, i, oh[2 * (NT - 1) + (i >> 2)], ol[2 * (NT - 1) + (i >> 2)], x0, x1);
-                save_pair(*sc, bw, NT - 1, i, x0, x1);
-            } else if constexpr (SAVE == SV_ACT_H) {
-                float x0, x1;
-                const h16x2 hh = epi_pair_x<RELU, ULO>(pacc1, pacc2, i, oh[2 * (NT - 1) + (i >> 2)], ol[2 * (NT - 1) + (i >> 2)], x0, x1);
-                push_pair_bits(bw[(NT - 1) >> 1], hh);
-                if (i & 1) store_frag_h(rowh, cxh, NT - 1, i, oh[2 * (NT - 1) + (i >> 2)]);
-            } else if constexpr (SAVE == SV_DZ) {
-                float x0, x1;
-                epi_pair_m(pacc1, pacc2, i, sc->mask[(NT - 1) >> 1] >> (16 * ((NT - 1) & 1)), oh[2 * (NT - 1) + (i >> 2)],
-                           ol[2 * (NT - 1) + (i >> 2)], x0, x1);
-                save_pair_b(*sc, NT - 1, i, x0, x1);
-            } else if constexpr (SAVE == SV_DZ_H) {
-                const h16x2 hh = epi_pair_mh(pacc1, pacc2, i, sc->mask[(NT - 1) >> 1], 8 * ((NT - 1) & 1) + i,
-                                             oh[2 * (NT - 1) + (i >> 2)], ol[2 * (NT - 1) + (i >> 2)]);
-                store_pair_h(rowh, cxh, svu, NT - 1, i, hh);
-            } else if constexpr (SAVE == SV_PE) {
-                sc->fout[16 * (NT - 1) + 2 * i] = fmaf(pacc2[2 * i], LO_INV, pacc1[2 * i]);
-                sc->fout[16 * (NT - 1) + 2 * i + 1] = fmaf(pacc2[2 * i + 1], LO_INV, pacc1[2 * i + 1]);
-            } else
-            epi_pair_u<RELU>(pacc1, pacc2, i, oh[2 * (NT - 1) + (i >> 2)], ol[2 * (NT - 1) + (i >> 2)], p.sat, p.guard);
+            HNRF_TILE_EPILOGUE_PAIR(NT - 1, i)
         }
         if constexpr (sv_fwd(SAVE)) {
 #pragma unroll
@@ -825,6 +665,8 @@ __device__ __forceinline__ void layer16(Pipe& p, int nb1, int nb2, h16x8 (&bh)[N
         }
     }
 }
+
+#undef HNRF_TILE_EPILOGUE_PAIR
 
 // Two sample groups per wave (64 samples): every weight fragment read from LDS feeds six MFMAs instead of three
 // and the per-tile fixed costs (barrier, operand-queue priming, DMA issue) are paid once for twice the work.
@@ -842,7 +684,7 @@ __device__ __forceinline__ void layer16x2(Pipe& p, unsigned stash_per_wave, int 
     constexpr int PFK = NK < 4 ? NK : 4;
     static_assert((NBLK * TPS) % 4 == 0, "every wave must issue the same number of DMA pieces per slab");
     const f32x16 zero = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    f32x16 pacc1[2] = {zero, zero}, pacc2[2] = {zero, zero};
+    f32x16 pacc[2] = {zero, zero};           // accumulators of the previous tile (epilogue pending)
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         const int nissue = (s + 2 < NS) ? NBLK * TPS : (s + 2 == NS ? nb1 : nb2);
@@ -858,13 +700,13 @@ __device__ __forceinline__ void layer16x2(Pipe& p, unsigned stash_per_wave, int 
             unsigned cur = p.lds_base + p.ring_off + p.ph * p.slab_bytes + tt * (NBLK * 1024) + lane * 16;
             unsigned pe = p.lds_base + p.pe_off + p.wave * stash_per_wave + lane * 16;
             asm volatile("" : "+v"(cur), "+v"(pe));        // see layer16
-            f32x16 acc1[2] = {zero, zero}, acc2[2] = {zero, zero};
+            f32x16 acc[2] = {zero, zero};
             if (NT > 1) {
                 const unsigned bp = p.lds_base + p.bias_off + tt * 128 + (lane >> 5) * 16;
                 const f32x4 b0 = lds_ld4f(bp), b1 = lds_ld4f(bp + 32), b2 = lds_ld4f(bp + 64), b3 = lds_ld4f(bp + 96);
-                acc1[0] = f32x16{b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w,
+                acc[0] = f32x16{b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w,
                                  b2.x, b2.y, b2.z, b2.w, b3.x, b3.y, b3.z, b3.w};
-                acc1[1] = acc1[0];
+                acc[1] = acc[0];
             }
             h16x8 qwh[PFK], qwl[PFK], qxh[2][PFK], qxl[2][PFK];
 #pragma unroll
@@ -911,10 +753,9 @@ __device__ __forceinline__ void layer16x2(Pipe& p, unsigned stash_per_wave, int 
                 }
 #pragma unroll
                 for (int g = 0; g < 2; ++g) {
-                    acc1[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh[g], acc1[g], 0, 0, 0);
-                    acc1[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl[g], acc1[g], 0, 0, 0);     // (xl un-scaled: epi_pair_u)
-                    if (WLO_UNLIFTED) acc1[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh[g], acc1[g], 0, 0, 0);
-                    else acc2[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh[g], acc2[g], 0, 0, 0);
+                    acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xh[g], acc[g], 0, 0, 0);
+                    acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh, xl[g], acc[g], 0, 0, 0);     // (one accumulator: epi_core)
+                    acc[g] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl, xh[g], acc[g], 0, 0, 0);
                 }
                 {
                     constexpr int MAXP = (TPS * NK - 1) < 10 ? (TPS * NK - 1) : 10;
@@ -932,7 +773,7 @@ __device__ __forceinline__ void layer16x2(Pipe& p, unsigned stash_per_wave, int 
                     for (int j = 0; j < 16; ++j)
                         if ((j * NK) / 16 == ks) {
                             const int g = j >> 3, i = j & 7;
-                            epi_pair_u<RELU>(pacc1[g], pacc2[g], i, oh[g][2 * (t - 1) + (i >> 2)], ol[g][2 * (t - 1) + (i >> 2)], p.sat, p.guard);
+                            epi_pair<RELU>(pacc[g], i, oh[g][2 * (t - 1) + (i >> 2)], ol[g][2 * (t - 1) + (i >> 2)], p.sat, p.guard);
                             asm volatile("" : "+v"(oh[g][2 * (t - 1) + (i >> 2)]), "+v"(ol[g][2 * (t - 1) + (i >> 2)]));
                         }
                 }
@@ -954,7 +795,7 @@ __device__ __forceinline__ void layer16x2(Pipe& p, unsigned stash_per_wave, int 
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
-            for (int g = 0; g < 2; ++g) { pacc1[g] = acc1[g]; pacc2[g] = acc2[g]; }
+            for (int g = 0; g < 2; ++g) pacc[g] = acc[g];
         }
         tile_sync(nissue / 4);
         p.ph = p.ph == RING - 1 ? 0 : p.ph + 1;
@@ -964,11 +805,11 @@ __device__ __forceinline__ void layer16x2(Pipe& p, unsigned stash_per_wave, int 
     for (int g = 0; g < 2; ++g) {
         if (NT == 1) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) last[g][r] = WLO_UNLIFTED ? pacc1[g][r] : pacc1[g][r] + pacc2[g][r] * LO_INV;
+            for (int r = 0; r < 16; ++r) last[g][r] = pacc[g][r];
         } else {
 #pragma unroll
             for (int i = 0; i < 8; ++i)
-                epi_pair_u<RELU>(pacc1[g], pacc2[g], i, oh[g][2 * (NT - 1) + (i >> 2)], ol[g][2 * (NT - 1) + (i >> 2)], p.sat, p.guard);
+                epi_pair<RELU>(pacc[g], i, oh[g][2 * (NT - 1) + (i >> 2)], ol[g][2 * (NT - 1) + (i >> 2)], p.sat, p.guard);
         }
     }
 }
@@ -1000,8 +841,7 @@ __device__ __forceinline__ Pipe pipe_start(const char* packed, int64_t bias_img_
 template <bool ULO = false>
 __device__ __forceinline__ void stash_pe(const Pipe& p, int ks, const float (&v)[8]) {
     h16x8 hi, lo;
-    if (ULO) split8_u(v, hi, lo);
-    else split8(v, hi, lo);
+    split8<ULO>(v, hi, lo);
     const unsigned pe = p.lds_base + p.pe_off + p.wave * (PE_STASH / 4) + lane_now() * 16;
     lds_st8(pe + (2 * ks) * 1024, hi);
     lds_st8(pe + (2 * ks + 1) * 1024, lo);
@@ -1018,7 +858,6 @@ __global__ __launch_bounds__(256) void canonical_f16x3_kernel(const float* __res
                                                               const int* __restrict__ count,
                                                               float* __restrict__ pe_out, float* __restrict__ acts,
                                                               uint32_t* __restrict__ relu_bits) {
-    constexpr bool UL = true;                                    // un-scaled activation low parts (epi_pair_u): all forward forms
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // sparse launch: only the `*count` samples listed in idx are evaluated (hnrf_compact_samples)
     if (idx != nullptr) {
@@ -1043,7 +882,7 @@ __global__ __launch_bounds__(256) void canonical_f16x3_kernel(const float* __res
     for (int ks = 0; ks < 4; ++ks) {
         const float v[8] = {pev[8 * ks], pev[8 * ks + 1], pev[8 * ks + 2], pev[8 * ks + 3],
                             pev[8 * ks + 4], pev[8 * ks + 5], pev[8 * ks + 6], pev[8 * ks + 7]};
-        stash_pe<UL>(p, ks, v);
+        stash_pe<true>(p, ks, v);
     }
     SaveCtx sc;
     if constexpr (SAVE) {
@@ -1066,31 +905,31 @@ __global__ __launch_bounds__(256) void canonical_f16x3_kernel(const float* __res
 
     h16x8 hA_h[16], hA_l[16], hB_h[16], hB_l[16];
     float last[16];
-    f32x16 pend1, pend2;                          // inference: last-tile epilogues travel into the next layer
+    f32x16 pend;                                 // inference: last-tile epilogues travel into the next layer
     constexpr bool DF = SAVE == SV_NONE;
-    layer16<8, 4, 4, 0, true, SAVE, false, DF, UL>(p, CNL16_NB_MID, CNL16_NB_MID, hB_h, hB_l, hA_h, hA_l, last, &sc, &pend1, &pend2);   // (hB unused: NKB = 0)
+    layer16<8, 4, 4, 0, true, SAVE, false, DF>(p, CNL16_NB_MID, CNL16_NB_MID, hB_h, hB_l, hA_h, hA_l, last, &sc, &pend);   // (hB unused: NKB = 0)
     if constexpr (SAVE) { sc.row += act_stride; sc.rowh += acth_stride; sc.bits += bit_stride; }
 #pragma unroll 1
     for (int l = 1; l <= 4; ++l) {
         const int nb = l == 4 ? CNL16_NB_L5 : CNL16_NB_MID;
-        layer16<8, 1, 0, 16, true, SAVE, DF, DF, UL>(p, nb, nb, hA_h, hA_l, hB_h, hB_l, last, &sc, &pend1, &pend2);
+        layer16<8, 1, 0, 16, true, SAVE, DF, DF>(p, nb, nb, hA_h, hA_l, hB_h, hB_l, last, &sc, &pend);
         if constexpr (SAVE) { sc.row += act_stride; sc.rowh += acth_stride; sc.bits += bit_stride; }
 #pragma unroll
         for (int i = 0; i < 16; ++i) { hA_h[i] = hB_h[i]; hA_l[i] = hB_l[i]; }
     }
-    layer16<8, 1, 4, 16, true, SAVE, DF, DF, UL>(p, CNL16_NB_MID, CNL16_NB_MID, hA_h, hA_l, hB_h, hB_l, last, &sc, &pend1, &pend2);   // skip layer
+    layer16<8, 1, 4, 16, true, SAVE, DF, DF>(p, CNL16_NB_MID, CNL16_NB_MID, hA_h, hA_l, hB_h, hB_l, last, &sc, &pend);   // skip layer
     if constexpr (SAVE) { sc.row += act_stride; sc.rowh += acth_stride; sc.bits += bit_stride; }
 #pragma unroll
     for (int i = 0; i < 16; ++i) { hA_h[i] = hB_h[i]; hA_l[i] = hB_l[i]; }
 #pragma unroll 1
     for (int l = 6; l <= 7; ++l) {
-        layer16<8, 1, 0, 16, true, SAVE, DF, DF, UL>(p, CNL16_NB_MID, l == 7 ? 0 : CNL16_NB_MID, hA_h, hA_l, hB_h, hB_l, last, &sc, &pend1, &pend2);
+        layer16<8, 1, 0, 16, true, SAVE, DF, DF>(p, CNL16_NB_MID, l == 7 ? 0 : CNL16_NB_MID, hA_h, hA_l, hB_h, hB_l, last, &sc, &pend);
         if constexpr (SAVE) { sc.row += act_stride; sc.rowh += acth_stride; sc.bits += bit_stride; }
 #pragma unroll
         for (int i = 0; i < 16; ++i) { hA_h[i] = hB_h[i]; hA_l[i] = hB_l[i]; }
     }
     h16x8 dh[2], dl[2];
-    layer16<1, 1, 0, 16, false, 0, DF, false, UL>(p, 0, 0, hA_h, hA_l, dh, dl, last, nullptr, &pend1, &pend2);
+    layer16<1, 1, 0, 16, false, 0, DF, false>(p, 0, 0, hA_h, hA_l, dh, dl, last, nullptr, &pend);
     // head bias and the head's power-of-two descale (pack_layer16_kernel, head_scale): scalar loads
     const float* ob = reinterpret_cast<const float*>(packed + CNL16_BIAS + CNL16_BIAS_LDS);
     const float hs = ob[8];
@@ -1125,7 +964,6 @@ __global__ __launch_bounds__(64 * NW) void nonrigid_f16x3_kernel(const float* __
                                                              const int* __restrict__ count,
                                                              float* __restrict__ pe_out, float* __restrict__ acts,
                                                              uint32_t* __restrict__ relu_bits) {
-    constexpr bool UL = true;                                    // un-scaled activation low parts (epi_pair_u): all forward forms
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if (idx != nullptr) {
         P = *count;
@@ -1152,7 +990,7 @@ __global__ __launch_bounds__(64 * NW) void nonrigid_f16x3_kernel(const float* __
     for (int ks = 0; ks < 4; ++ks) {
         const float v[8] = {pev[8 * ks], pev[8 * ks + 1], pev[8 * ks + 2], pev[8 * ks + 3],
                             pev[8 * ks + 4], pev[8 * ks + 5], pev[8 * ks + 6], pev[8 * ks + 7]};
-        stash_pe<UL>(p, ks, v);
+        stash_pe<true>(p, ks, v);
     }
     SaveCtx sc;
     if constexpr (SAVE) {
@@ -1181,34 +1019,34 @@ __global__ __launch_bounds__(64 * NW) void nonrigid_f16x3_kernel(const float* __
     if constexpr (W8) {
         constexpr int MID = NR16_NB_MID, L4B = NR16_NB_L4;      // blocks per tile: 16 / 24
 #define HNRF_NEXT_LAYER if constexpr (SAVE) { sc.row += act_stride; sc.rowh += acth_stride; sc.bits += bit_stride; }
-        layer16<4, 2, 4, 0, true, SAVE, false, false, UL, 8>(p, MID, MID, hB_h, hB_l, hA_h, hA_l, last, &sc);        // L0
+        layer16<4, 2, 4, 0, true, SAVE, false, false, 8>(p, MID, MID, hB_h, hB_l, hA_h, hA_l, last, &sc);        // L0
         HNRF_NEXT_LAYER
-        layer16<4, 1, 0, 8, true, SAVE, false, false, UL, 8>(p, MID, MID, hA_h, hA_l, hB_h, hB_l, last, &sc);        // L1
+        layer16<4, 1, 0, 8, true, SAVE, false, false, 8>(p, MID, MID, hA_h, hA_l, hB_h, hB_l, last, &sc);        // L1
         HNRF_NEXT_LAYER
-        layer16<4, 1, 0, 8, true, SAVE, false, false, UL, 8>(p, MID, MID, hB_h, hB_l, hA_h, hA_l, last, &sc);        // L2
+        layer16<4, 1, 0, 8, true, SAVE, false, false, 8>(p, MID, MID, hB_h, hB_l, hA_h, hA_l, last, &sc);        // L2
         HNRF_NEXT_LAYER
-        layer16<4, 1, 0, 8, true, SAVE, false, false, UL, 8>(p, L4B, L4B, hA_h, hA_l, hB_h, hB_l, last, &sc);        // L3
+        layer16<4, 1, 0, 8, true, SAVE, false, false, 8>(p, L4B, L4B, hA_h, hA_l, hB_h, hB_l, last, &sc);        // L3
         HNRF_NEXT_LAYER
-        layer16<4, 1, 4, 8, true, SAVE, false, false, UL, 8>(p, MID, MID, hB_h, hB_l, hA_h, hA_l, last, &sc);        // skip layer
+        layer16<4, 1, 4, 8, true, SAVE, false, false, 8>(p, MID, MID, hB_h, hB_l, hA_h, hA_l, last, &sc);        // skip layer
         HNRF_NEXT_LAYER
-        layer16<4, 1, 0, 8, true, SAVE, false, false, UL, 8>(p, MID, 0, hA_h, hA_l, hB_h, hB_l, last, &sc);
+        layer16<4, 1, 0, 8, true, SAVE, false, false, 8>(p, MID, 0, hA_h, hA_l, hB_h, hB_l, last, &sc);
 #undef HNRF_NEXT_LAYER
-        layer16<1, 1, 0, 8, false, 0, false, false, UL, 8>(p, 0, 0, hB_h, hB_l, dh, dl, last);
+        layer16<1, 1, 0, 8, false, 0, false, false, 8>(p, 0, 0, hB_h, hB_l, dh, dl, last);
     } else {
-    layer16<4, 4, 4, 0, true, SAVE, false, false, UL>(p, 0 /*already in flight*/, 2 * NR16_NB_MID, hB_h, hB_l, hA_h, hA_l, last, &sc);
+    layer16<4, 4, 4, 0, true, SAVE>(p, 0 /*already in flight*/, 2 * NR16_NB_MID, hB_h, hB_l, hA_h, hA_l, last, &sc);
     if constexpr (SAVE) { sc.row += act_stride; sc.rowh += acth_stride; sc.bits += bit_stride; }
     // 128-wide tiles have only 8 k-steps: two tiles per slab halve the barriers per MFMA.  The layers alternate
     // between the two fragment arrays (no loop with a copy-back: this kernel's time follows its instruction count)
-    layer16<4, 2, 0, 8, true, SAVE, false, false, UL>(p, 2 * NR16_NB_MID, 2 * NR16_NB_MID, hA_h, hA_l, hB_h, hB_l, last, &sc);     // L1
+    layer16<4, 2, 0, 8, true, SAVE>(p, 2 * NR16_NB_MID, 2 * NR16_NB_MID, hA_h, hA_l, hB_h, hB_l, last, &sc);     // L1
     if constexpr (SAVE) { sc.row += act_stride; sc.rowh += acth_stride; sc.bits += bit_stride; }
-    layer16<4, 2, 0, 8, true, SAVE, false, false, UL>(p, 2 * NR16_NB_MID, 2 * NR16_NB_MID, hB_h, hB_l, hA_h, hA_l, last, &sc);     // L2
+    layer16<4, 2, 0, 8, true, SAVE>(p, 2 * NR16_NB_MID, 2 * NR16_NB_MID, hB_h, hB_l, hA_h, hA_l, last, &sc);     // L2
     if constexpr (SAVE) { sc.row += act_stride; sc.rowh += acth_stride; sc.bits += bit_stride; }
-    layer16<4, 2, 0, 8, true, SAVE, false, false, UL>(p, NR16_NB_L4, NR16_NB_L4, hA_h, hA_l, hB_h, hB_l, last, &sc);               // L3
+    layer16<4, 2, 0, 8, true, SAVE>(p, NR16_NB_L4, NR16_NB_L4, hA_h, hA_l, hB_h, hB_l, last, &sc);               // L3
     if constexpr (SAVE) { sc.row += act_stride; sc.rowh += acth_stride; sc.bits += bit_stride; }
-    layer16<4, 1, 4, 8, true, SAVE, false, false, UL>(p, 2 * NR16_NB_MID, 2 * NR16_NB_MID, hB_h, hB_l, hA_h, hA_l, last, &sc);    // skip layer
+    layer16<4, 1, 4, 8, true, SAVE>(p, 2 * NR16_NB_MID, 2 * NR16_NB_MID, hB_h, hB_l, hA_h, hA_l, last, &sc);    // skip layer
     if constexpr (SAVE) { sc.row += act_stride; sc.rowh += acth_stride; sc.bits += bit_stride; }
-    layer16<4, 2, 0, 8, true, SAVE, false, false, UL>(p, NR16_NB_MID, 0, hA_h, hA_l, hB_h, hB_l, last, &sc);
-    layer16<1, 1, 0, 8, false, 0, false, false, UL>(p, 0, 0, hB_h, hB_l, dh, dl, last);
+    layer16<4, 2, 0, 8, true, SAVE>(p, NR16_NB_MID, 0, hA_h, hA_l, hB_h, hB_l, last, &sc);
+    layer16<1, 1, 0, 8, false, 0>(p, 0, 0, hB_h, hB_l, dh, dl, last);
     }
     const float* ob = reinterpret_cast<const float*>(packed + NR16_BIAS + NR16_BIAS_LDS);
     const float hs = ob[8];                                     // head descale (pack_layer16_kernel, head_scale)
@@ -1276,7 +1114,7 @@ __global__ __launch_bounds__(256) void nonrigid_f16x3_x2_kernel(const float* __r
             const float v[8] = {pev[8 * ks], pev[8 * ks + 1], pev[8 * ks + 2], pev[8 * ks + 3],
                                 pev[8 * ks + 4], pev[8 * ks + 5], pev[8 * ks + 6], pev[8 * ks + 7]};
             h16x8 hi, lo;
-            split8_u(v, hi, lo);
+            split8<true>(v, hi, lo);
             lds_st8(pe + (2 * ks) * 1024, hi);
             lds_st8(pe + (2 * ks + 1) * 1024, lo);
         }
@@ -1552,9 +1390,8 @@ constexpr int64_t NB16_BYTES = NB16_L0P + NB16_PE;            // followed by flo
 
 // Non-rigid MLP, split-f16 (xyz = x_skel + offset): d_x_skel = d_xyz + J_offset^T d_xyz, dZ [6][P][128].
 // HALF: see canonical_bwd16_kernel.
-// NW = 8: eight waves per workgroup as in nonrigid_f16x3_kernel (one tile per slab, 16-KiB ring slots; P a multiple of 256)
-template <bool HALF, int NW = 4>
-__global__ __launch_bounds__(64 * NW) void nonrigid_bwd16_kernel(const float* __restrict__ x_skel,
+template <bool HALF>
+__global__ __launch_bounds__(256) void nonrigid_bwd16_kernel(const float* __restrict__ x_skel,
                                                              const float* __restrict__ hann_w,
                                                              const float* __restrict__ d_xyz,
                                                              const uint32_t* __restrict__ relu_bits,
@@ -1564,14 +1401,12 @@ __global__ __launch_bounds__(64 * NW) void nonrigid_bwd16_kernel(const float* __
                                                              float* __restrict__ dz_amax) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int SV = HALF ? SV_DZ_H : SV_DZ;
-    constexpr bool W8 = NW == 8;
-    constexpr int SLAB = W8 ? 16 * 1024 : NR16_SLAB, SB = W8 ? 16 : 32;         // ring slot bytes; blocks per mid-layer slab
-    constexpr int TP = W8 ? 1 : 2;                                               // tiles per slab of the 128-wide stages
-    Pipe p = pipe_start(packed, 0, NR16_BIAS_LDS, SLAB, 8, SB, smem, W8 ? NR16W8_STASH : PE_STASH, NW);
-    slab_issue(p.gi, p.lds_base + p.ring_off + 2 * SLAB, SB, p.wave, NW);       // third slab: see canonical_bwd16_kernel
+    constexpr int SB = 32;                                                       // blocks per mid-layer slab (two tiles)
+    Pipe p = pipe_start(packed, 0, NR16_BIAS_LDS, NR16_SLAB, 8, SB, smem);
+    slab_issue(p.gi, p.lds_base + p.ring_off + 2 * NR16_SLAB, SB, p.wave);      // third slab: see canonical_bwd16_kernel
     p.gi += SB * 1024;
     const int lane = threadIdx.x & 63, h = lane >> 5;
-    const int64_t slot = ((int64_t)blockIdx.x * NW + p.wave) * 32 + (lane & 31);
+    const int64_t slot = ((int64_t)blockIdx.x * 4 + p.wave) * 32 + (lane & 31);
     const int64_t sample = slot < P ? slot : P - 1;
     const int64_t stride = P * 128, bstride = P * 4;
     const float* wmax = reinterpret_cast<const float*>(packed + NB16_BYTES);
@@ -1593,7 +1428,7 @@ __global__ __launch_bounds__(64 * NW) void nonrigid_bwd16_kernel(const float* __
     sc.amax = 0.f;
     sc.mask[2] = sc.mask[3] = 0u;
     sc.row = dZ + 5 * stride + sample * 128 + 4 * h;
-    const int64_t strideh = (int64_t)gridDim.x * (32 * NW) * 128;
+    const int64_t strideh = (int64_t)gridDim.x * 128 * 128;
     sc.rowh = reinterpret_cast<_Float16*>(dZ) + 5 * strideh + (slot >> 5) * (128 * 32) + h * 128;
     sc.cx = (lane & 31) ^ (4 * h);
     const uint32_t* mrow = relu_bits + 5 * bstride + sample * 4 + 2 * h;
@@ -1620,29 +1455,29 @@ __global__ __launch_bounds__(64 * NW) void nonrigid_bwd16_kernel(const float* __
     h16x8 dh[4], dl[4];
     float last[16];
     load_mask();
-    layer16<4, 4, 1, 0, false, SV, false, false, false, NW>(p, 0, 0, hB_h, hB_l, hA_h, hA_l, last, &sc);   // dZ5
+    layer16<4, 4, 1, 0, false, SV>(p, 0, 0, hB_h, hB_l, hA_h, hA_l, last, &sc);   // dZ5
     next_stage(5);
     load_mask();
-    layer16<4, TP, 0, 8, false, SV, false, false, false, NW>(p, SB, SB, hA_h, hA_l, hB_h, hB_l, last, &sc);             // dZ4 (the skip layer's)
+    layer16<4, 2, 0, 8, false, SV>(p, SB, SB, hA_h, hA_l, hB_h, hB_l, last, &sc);             // dZ4 (the skip layer's)
     next_stage(4);
     load_mask();
-    layer16<4, TP, 0, 8, false, SV, false, false, false, NW>(p, SB, SB, hB_h, hB_l, hA_h, hA_l, last, &sc);             // skip [h | PE]: dZ3 ...
+    layer16<4, 2, 0, 8, false, SV>(p, SB, SB, hB_h, hB_l, hA_h, hA_l, last, &sc);             // skip [h | PE]: dZ3 ...
     const float inv_skip = sc.descale;                                                         // (W4^T: hidden and PE rows share kt[4])
     next_stage(3);
-    layer16<2, TP, 0, 8, false, SV_PE, false, false, false, NW>(p, SB, SB, hB_h, hB_l, dh, dl, last, &sc);              // ... and its d PE
+    layer16<2, 2, 0, 8, false, SV_PE>(p, SB, SB, hB_h, hB_l, dh, dl, last, &sc);              // ... and its d PE
     float dpe[18];
 #pragma unroll
     for (int j = 0; j < 18; ++j) dpe[j] = sc.fout[j] * inv_skip;
     load_mask();
-    layer16<4, TP, 0, 8, false, SV, false, false, false, NW>(p, SB, SB, hA_h, hA_l, hB_h, hB_l, last, &sc);             // dZ2
+    layer16<4, 2, 0, 8, false, SV>(p, SB, SB, hA_h, hA_l, hB_h, hB_l, last, &sc);             // dZ2
     next_stage(2);
     load_mask();
-    layer16<4, TP, 0, 8, false, SV, false, false, false, NW>(p, SB, SB, hB_h, hB_l, hA_h, hA_l, last, &sc);             // dZ1
+    layer16<4, 2, 0, 8, false, SV>(p, SB, SB, hB_h, hB_l, hA_h, hA_l, last, &sc);             // dZ1
     next_stage(1);
     load_mask();
-    layer16<4, TP, 0, 8, false, SV, false, false, false, NW>(p, SB, W8 ? SB : 0, hA_h, hA_l, hB_h, hB_l, last, &sc);   // dZ0
+    layer16<4, 2, 0, 8, false, SV>(p, SB, 0, hA_h, hA_l, hB_h, hB_l, last, &sc);   // dZ0
     next_stage(0);                                                                             // (scale of layer 0's d PE)
-    layer16<2, TP, 0, 8, false, SV_PE, false, false, false, NW>(p, 0, 0, hB_h, hB_l, dh, dl, last, &sc);   // layer 0's d PE
+    layer16<2, 2, 0, 8, false, SV_PE>(p, 0, 0, hB_h, hB_l, dh, dl, last, &sc);   // layer 0's d PE
 #pragma unroll
     for (int j = 0; j < 18; ++j) dpe[j] = fmaf(sc.fout[j], sc.descale, dpe[j]);
 
@@ -1687,12 +1522,10 @@ size_t nonrigid16_status_offset() { return (size_t)NR16_STATUS; }
 
 int canonical16_pack(const float* const* w, const float* const* b, void* packed, hipStream_t st) {
     char* out = (char*)packed;
-    int rc;
     if (hipMemsetAsync(out + CNL16_BIAS, 0, 9 * 1024, st) != hipSuccess) {
         set_error("hnrf_canonical_pack: memset failed");
         return HNRF_E_LAUNCH;
     }
-    (void)rc;
     PackLayer16 d[9];
     d[0] = PackLayer16{w[0], b[0], 256, 63, 8, 4, 0, PE16_CANONICAL, 0, 0, 0, CNL16_L0, CNL16_BIAS, 0};
     for (int l = 1; l <= 4; ++l)
@@ -1708,12 +1541,10 @@ int canonical16_pack(const float* const* w, const float* const* b, void* packed,
 
 int nonrigid16_pack(const float* const* w, const float* const* b, const float* cond, void* packed, hipStream_t st) {
     char* out = (char*)packed;
-    int rc;
     if (hipMemsetAsync(out + NR16_BIAS, 0, 4 * 1024, st) != hipSuccess) {
         set_error("hnrf_nonrigid_pack: memset failed");
         return HNRF_E_LAUNCH;
     }
-    (void)rc;
     PackLayer16 d[7];
     d[0] = PackLayer16{w[0], b[0], 128, 105, 4, 4, 0, PE16_NONRIGID, 69, 0, 69, NR16_L0, NR16_BIAS, 0};
     for (int l = 1; l <= 3; ++l)
@@ -1729,79 +1560,57 @@ int nonrigid16_pack(const float* const* w, const float* const* b, const float* c
 int canonical16_fwd(const float* xyz, const void* packed, int64_t P, float* raw, const int* idx, const int* count,
                     bool guard, hipStream_t st) {
     constexpr int lds = CNL16_BIAS_LDS + PE_STASH + RING * CNL16_SLAB;
-    static unsigned long long lds_done = 0, lds_done_g = 0;
     const dim3 grid((unsigned)((P + 127) / 128));
-    if (guard) {
-        if (int rc = reserve_lds((const void*)canonical_f16x3_kernel<SV_NONE, true>, lds, lds_done_g, "hnrf_canonical_fwd (f16x3)")) return rc;
-        hipLaunchKernelGGL((canonical_f16x3_kernel<SV_NONE, true>), grid, dim3(256), lds, st, xyz, (const char*)packed, P,
-                           (float4*)raw, idx, count, nullptr, nullptr, nullptr);
-    } else {
-        if (int rc = reserve_lds((const void*)canonical_f16x3_kernel<SV_NONE, false>, lds, lds_done, "hnrf_canonical_fwd (f16x3)")) return rc;
-        hipLaunchKernelGGL((canonical_f16x3_kernel<SV_NONE, false>), grid, dim3(256), lds, st, xyz, (const char*)packed, P,
-                           (float4*)raw, idx, count, nullptr, nullptr, nullptr);
-    }
-    return check_launch("hnrf_canonical_fwd (f16x3)");
+    const char* what = "hnrf_canonical_fwd (f16x3)";
+    if (guard)
+        return launch_lds<canonical_f16x3_kernel<SV_NONE, true>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
+                                                                 (float4*)raw, idx, count, nullptr, nullptr, nullptr);
+    return launch_lds<canonical_f16x3_kernel<SV_NONE, false>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
+                                                              (float4*)raw, idx, count, nullptr, nullptr, nullptr);
 }
 
 int canonical16_fwd_train(const float* xyz, const void* packed, int64_t P, float* raw, float* pe_out, float* acts,
                           uint32_t* relu_bits, int half, hipStream_t st) {
     constexpr int lds = CNL16_BIAS_LDS + PE_STASH + RING * CNL16_SLAB;
-    static unsigned long long lds_done = 0, lds_done_h = 0;
     const dim3 grid((unsigned)((P + 127) / 128));
-    if (half) {
-        if (int rc = reserve_lds((const void*)canonical_f16x3_kernel<SV_ACT_H>, lds, lds_done_h, "hnrf_canonical_fwd_train (f16x3, f16 operands)")) return rc;
-        hipLaunchKernelGGL(canonical_f16x3_kernel<SV_ACT_H>, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
-                           (float4*)raw, nullptr, nullptr, pe_out, acts, relu_bits);
-    } else {
-        if (int rc = reserve_lds((const void*)canonical_f16x3_kernel<SV_ACT>, lds, lds_done, "hnrf_canonical_fwd_train (f16x3)")) return rc;
-        hipLaunchKernelGGL(canonical_f16x3_kernel<SV_ACT>, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
-                           (float4*)raw, nullptr, nullptr, pe_out, acts, relu_bits);
-    }
-    return check_launch("hnrf_canonical_fwd_train (f16x3)");
+    const char* what = "hnrf_canonical_fwd_train (f16x3)";
+    if (half)
+        return launch_lds<canonical_f16x3_kernel<SV_ACT_H>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
+                                                            (float4*)raw, nullptr, nullptr, pe_out, acts, relu_bits);
+    return launch_lds<canonical_f16x3_kernel<SV_ACT>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P, (float4*)raw,
+                                                      nullptr, nullptr, pe_out, acts, relu_bits);
 }
 
 int nonrigid16_fwd(const float* x_skel, const float* hann_w, const void* packed, int64_t P, float* xyz,
                    float* offsets, const int* idx, const int* count, bool guard, hipStream_t st) {
     constexpr int lds2 = NR16_BIAS_LDS + NR16X2_STASH + RING * NR16X2_SLAB;
-    static unsigned long long lds2_done = 0, lds2_done_g = 0;
     const dim3 grid((unsigned)((P + 255) / 256));
-    if (guard) {
-        if (int rc = reserve_lds((const void*)nonrigid_f16x3_x2_kernel<true>, lds2, lds2_done_g, "hnrf_nonrigid_fwd (f16x3)")) return rc;
-        hipLaunchKernelGGL(nonrigid_f16x3_x2_kernel<true>, grid, dim3(256), lds2, st, x_skel, hann_w, (const char*)packed, P, xyz,
-                           offsets, idx, count);
-    } else {
-        if (int rc = reserve_lds((const void*)nonrigid_f16x3_x2_kernel<false>, lds2, lds2_done, "hnrf_nonrigid_fwd (f16x3)")) return rc;
-        hipLaunchKernelGGL(nonrigid_f16x3_x2_kernel<false>, grid, dim3(256), lds2, st, x_skel, hann_w, (const char*)packed, P, xyz,
-                           offsets, idx, count);
-    }
-    return check_launch("hnrf_nonrigid_fwd (f16x3)");
+    const char* what = "hnrf_nonrigid_fwd (f16x3)";
+    if (guard)
+        return launch_lds<nonrigid_f16x3_x2_kernel<true>>(what, grid, dim3(256), lds2, st, x_skel, hann_w, (const char*)packed, P,
+                                                          xyz, offsets, idx, count);
+    return launch_lds<nonrigid_f16x3_x2_kernel<false>>(what, grid, dim3(256), lds2, st, x_skel, hann_w, (const char*)packed, P,
+                                                       xyz, offsets, idx, count);
 }
 
 int nonrigid16_fwd_train(const float* x_skel, const float* hann_w, const void* packed, int64_t P, float* xyz,
                          float* offsets, float* pe_out, float* acts, uint32_t* relu_bits, int half, hipStream_t st) {
     constexpr int lds = NR16_BIAS_LDS + PE_STASH + RING * NR16_SLAB;
-    static unsigned long long lds_done = 0, lds_done_h = 0;
     const dim3 grid((unsigned)((P + 127) / 128));
+    const char* what = "hnrf_nonrigid_fwd_train (f16x3)";
     // eight waves per workgroup where the sample count allows it (whole 256-sample workgroups: the blocked activation
-    // layers are padded to whole workgroups, and the chain / weight-gradient kernels pad to 128); HNRF_K2T_W4: the
-    // four-wave form, for A/B runs
-    static const bool w8_ok = getenv("HNRF_K2T_W4") == nullptr;
-    if (half && w8_ok && P % 256 == 0) {
+    // layers are padded to whole workgroups, and the chain / weight-gradient kernels pad to 128)
+    if (half && P % 256 == 0) {
         constexpr int lds8 = NR16_BIAS_LDS + NR16W8_STASH + RING * NR16W8_SLAB;
-        static unsigned long long lds_done_8 = 0;
-        if (int rc = reserve_lds((const void*)nonrigid_f16x3_kernel<SV_ACT_H, 8>, lds8, lds_done_8, "hnrf_nonrigid_fwd_train (f16x3, f16 operands, 8 waves)")) return rc;
-        hipLaunchKernelGGL((nonrigid_f16x3_kernel<SV_ACT_H, 8>), dim3((unsigned)(P / 256)), dim3(512), lds8, st, x_skel, hann_w,
-                           (const char*)packed, P, xyz, offsets, nullptr, nullptr, pe_out, acts, relu_bits);
-    } else if (half) {
-        if (int rc = reserve_lds((const void*)nonrigid_f16x3_kernel<SV_ACT_H>, lds, lds_done_h, "hnrf_nonrigid_fwd_train (f16x3, f16 operands)")) return rc;
-        hipLaunchKernelGGL(nonrigid_f16x3_kernel<SV_ACT_H>, grid, dim3(256), lds, st, x_skel, hann_w, (const char*)packed, P,
-                           xyz, offsets, nullptr, nullptr, pe_out, acts, relu_bits);
-    } else {
-        if (int rc = reserve_lds((const void*)nonrigid_f16x3_kernel<SV_ACT>, lds, lds_done, "hnrf_nonrigid_fwd_train (f16x3)")) return rc;
-        hipLaunchKernelGGL(nonrigid_f16x3_kernel<SV_ACT>, grid, dim3(256), lds, st, x_skel, hann_w, (const char*)packed, P,
-                           xyz, offsets, nullptr, nullptr, pe_out, acts, relu_bits);
+        return launch_lds<nonrigid_f16x3_kernel<SV_ACT_H, 8>>(what, dim3((unsigned)(P / 256)), dim3(512), lds8, st, x_skel, hann_w,
+                                                              (const char*)packed, P, xyz, offsets, nullptr, nullptr, pe_out,
+                                                              acts, relu_bits);
     }
-    return check_launch("hnrf_nonrigid_fwd_train (f16x3)");
+    if (half)
+        return launch_lds<nonrigid_f16x3_kernel<SV_ACT_H>>(what, grid, dim3(256), lds, st, x_skel, hann_w, (const char*)packed, P,
+                                                           xyz, offsets, nullptr, nullptr, pe_out, acts, relu_bits);
+    return launch_lds<nonrigid_f16x3_kernel<SV_ACT>>(what, grid, dim3(256), lds, st, x_skel, hann_w, (const char*)packed, P, xyz,
+                                                     offsets, nullptr, nullptr, pe_out, acts, relu_bits);
 }
 
 size_t canonical16_bwd_bytes() { return (size_t)CB16_BYTES + 256; }
@@ -1850,18 +1659,13 @@ int canonical16_bwd_pack(const float* const* w, void* packed, hipStream_t st) {
 int canonical16_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed, int64_t P,
                     const float* d_raw_amax, float* dZ, float* d_xyz, float* dz_amax, int half, hipStream_t st) {
     constexpr int lds = CNL16_BIAS_LDS + PE_STASH + RING * CNL16_SLAB;
-    static unsigned long long lds_done = 0, lds_done_h = 0;
     const dim3 grid((unsigned)((P + 127) / 128));
-    if (half) {
-        if (int rc = reserve_lds((const void*)canonical_bwd16_kernel<true>, lds, lds_done_h, "hnrf_canonical_bwd (f16x3, f16 operands)")) return rc;
-        hipLaunchKernelGGL(canonical_bwd16_kernel<true>, grid, dim3(256), lds, st, xyz, (const float4*)d_raw, relu_bits,
-                           (const char*)packed, P, d_raw_amax, dZ, d_xyz, dz_amax);
-    } else {
-        if (int rc = reserve_lds((const void*)canonical_bwd16_kernel<false>, lds, lds_done, "hnrf_canonical_bwd (f16x3)")) return rc;
-        hipLaunchKernelGGL(canonical_bwd16_kernel<false>, grid, dim3(256), lds, st, xyz, (const float4*)d_raw, relu_bits,
-                           (const char*)packed, P, d_raw_amax, dZ, d_xyz, dz_amax);
-    }
-    return check_launch("hnrf_canonical_bwd (f16x3)");
+    const char* what = "hnrf_canonical_bwd (f16x3)";
+    if (half)
+        return launch_lds<canonical_bwd16_kernel<true>>(what, grid, dim3(256), lds, st, xyz, (const float4*)d_raw, relu_bits,
+                                                        (const char*)packed, P, d_raw_amax, dZ, d_xyz, dz_amax);
+    return launch_lds<canonical_bwd16_kernel<false>>(what, grid, dim3(256), lds, st, xyz, (const float4*)d_raw, relu_bits,
+                                                     (const char*)packed, P, d_raw_amax, dZ, d_xyz, dz_amax);
 }
 
 size_t nonrigid16_bwd_bytes() { return (size_t)NB16_BYTES + 256; }
@@ -1887,20 +1691,15 @@ int nonrigid16_bwd(const float* x_skel, const float* hann_w, const float* d_xyz,
                    const void* packed, int64_t P, const float* d_xyz_amax, float* dZ, float* d_x_skel, float* dz_amax,
                    int half, hipStream_t st) {
     constexpr int lds = NR16_BIAS_LDS + PE_STASH + RING * NR16_SLAB;
-    static unsigned long long lds_done = 0, lds_done_h = 0;
     const dim3 grid((unsigned)((P + 127) / 128));
-    // (an eight-wave instance as in nonrigid16_fwd_train -- nonrigid_bwd16_kernel<true, 8> -- was built and measured: the chain
-    // needs 292 registers per lane, at 256 it spills 260 bytes and runs 0.659 instead of 0.605 ms; not dispatched)
-    if (half) {
-        if (int rc = reserve_lds((const void*)nonrigid_bwd16_kernel<true>, lds, lds_done_h, "hnrf_nonrigid_bwd (f16x3, f16 operands)")) return rc;
-        hipLaunchKernelGGL(nonrigid_bwd16_kernel<true>, grid, dim3(256), lds, st, x_skel, hann_w, d_xyz, relu_bits,
-                           (const char*)packed, P, d_xyz_amax, dZ, d_x_skel, dz_amax);
-    } else {
-        if (int rc = reserve_lds((const void*)nonrigid_bwd16_kernel<false>, lds, lds_done, "hnrf_nonrigid_bwd (f16x3)")) return rc;
-        hipLaunchKernelGGL(nonrigid_bwd16_kernel<false>, grid, dim3(256), lds, st, x_skel, hann_w, d_xyz, relu_bits,
-                           (const char*)packed, P, d_xyz_amax, dZ, d_x_skel, dz_amax);
-    }
-    return check_launch("hnrf_nonrigid_bwd (f16x3)");
+    const char* what = "hnrf_nonrigid_bwd (f16x3)";
+    // (an eight-wave instance as in nonrigid16_fwd_train was built and measured: the chain needs 292 registers per lane, at
+    // 256 it spills 260 bytes and runs 0.659 instead of 0.605 ms; removed)
+    if (half)
+        return launch_lds<nonrigid_bwd16_kernel<true>>(what, grid, dim3(256), lds, st, x_skel, hann_w, d_xyz, relu_bits,
+                                                       (const char*)packed, P, d_xyz_amax, dZ, d_x_skel, dz_amax);
+    return launch_lds<nonrigid_bwd16_kernel<false>>(what, grid, dim3(256), lds, st, x_skel, hann_w, d_xyz, relu_bits,
+                                                    (const char*)packed, P, d_xyz_amax, dZ, d_x_skel, dz_amax);
 }
 
 }  // namespace hnrf
