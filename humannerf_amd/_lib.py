@@ -77,6 +77,12 @@ SIGNATURES = {
     'hnrf_baked_sample_sparse': (_int, [_vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
     'hnrf_render_rays_baked_fwd': (_int, [_vp] * 13 + [_int, _vp, _vp, _vp, _int, ctypes.c_float, _i64, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
     'hnrf_render_frame_baked_fwd': (_int, [_vp] * 13 + [_int, _vp, _vp, _vp, _int, ctypes.c_float, _i64, _int, _int, _int, _i64, _vp, _sz] + [_vp] * 11 + [_vp, _vp, _vp, _vp]),
+    'hnrf_bake_nonrigid_workspace_bytes': (_sz, [_int]),
+    'hnrf_bake_nonrigid': (_int, [_vp, _vp, _int, _vp, _vp, _int, _vp, _sz, _vp, _vp, _vp]),
+    'hnrf_baked_warp_sample': (_int, [_vp, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
+    'hnrf_baked_warp_sample_sparse': (_int, [_vp, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'hnrf_render_rays_baked_nr_fwd': (_int, [_vp] * 11 + [_int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int, ctypes.c_float, _i64, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'hnrf_render_frame_baked_nr_fwd': (_int, [_vp] * 11 + [_int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int, ctypes.c_float, _i64, _int, _int, _int, _i64, _vp, _sz] + [_vp] * 11 + [_vp, _vp, _vp, _vp]),
     'hnrf_raster_workspace_bytes': (_sz, [_i64, _i64, _int, _int]),
     'hnrf_raster_mesh': (_int, [_vp, _i64, _vp, _i64] + [_vp] * 5 + [_int, _int, ctypes.c_float, _int] + [_vp] * 4 + [_vp, _sz, _vp]),
 }

@@ -4,7 +4,9 @@ trilinear interpolation (hnrf_baked_sample) where the volume renderer would run 
 
 This module is the host side: ``sample_host`` restates the device sampler in numpy float32, bit for bit (the
 host/device idiom of ``mesh`` and ``imageproc``); ``lattice_points`` are the positions the bake evaluates;
-``save_grid`` / ``load_grid`` ship a baked avatar without re-baking.  The conventions:
+``save_grid`` / ``load_grid`` ship a baked avatar without re-baking.  ``warp_sample_host`` is the twin of the fused
+sampler of the per-frame offset grid (``cfg.amd.nonrigid = 'baked'``, hnrf_bake_nonrigid / hnrf_baked_warp_sample): a
+grid of the same layout with c = (dx, dy, dz, +0).  The conventions:
 
 - ``grid`` (N, N, N, 4) float16 indexed [z][y][x][c], c = (r, g, b, sigma) pre-activation, 8 <= N <= 512, on the
   lattice of ``mesh.lattice_axes``;
@@ -70,6 +72,22 @@ def sample_host(grid, xyz, bbox_min, bbox_max):
             d.append(e[0] + ty * (e[1] - e[0]))
         out = d[0] + tz * (d[1] - d[0])
     return out.astype(np.float32).reshape(lead + (4,))
+
+
+def warp_sample_host(off_grid, cnl_grid, x_skel, boxes):
+    """The fused device sampler (hnrf_baked_warp_sample) in numpy float32: ``off = sample_host(off_grid, x_skel)[:3]``,
+    ``xyz = x_skel + off`` (one float32 add per coordinate), ``raw = sample_host(cnl_grid, xyz)``.  ``boxes`` =
+    ((off_bbox_min, off_bbox_max), (cnl_bbox_min, cnl_bbox_max)), or one (bbox_min, bbox_max) pair for both grids.
+    x_skel (..., 3) -> (raw (..., 4), xyz (..., 3), offsets (..., 3)), all float32."""
+    boxes = tuple(boxes)
+    if len(boxes) == 2 and np.ndim(boxes[0][0]) == 0:
+        boxes = (boxes, boxes)
+    (olo, ohi), (clo, chi) = boxes
+    x_skel = np.asarray(x_skel, dtype=np.float32)
+    off = sample_host(off_grid, x_skel, olo, ohi)[..., :3]
+    with np.errstate(invalid='ignore', over='ignore'):
+        xyz = (x_skel + off).astype(np.float32)
+    return sample_host(cnl_grid, xyz, clo, chi), xyz, np.ascontiguousarray(off)
 
 
 def weights_hash(tensors):

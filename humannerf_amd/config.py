@@ -157,6 +157,14 @@ _DEFAULTS = {
         # term_eps > 0 in the lean form is refused with it
         'canonical': 'mlp',
         'bake_resolution': 256,
+        # inference only, and only with canonical = 'baked': where a sample's non-rigid offset comes from.  'mlp' = the
+        # non-rigid motion MLP (the reference).  'baked' = an opt-in approximation: within a frame the offset is a
+        # function of x_skel alone, so it is tabulated once per FRAME on a nonrigid_bake_resolution^3 f16 lattice over the
+        # canonical bbox (Network.bake_nonrigid) and interpolated trilinearly per sample in one kernel with the canonical
+        # grid's look-up (DESIGN.md section 4 "Baked non-rigid offset field").  Training and ignore_non_rigid_motions
+        # ignore it; with canonical = 'mlp' it is refused
+        'nonrigid': 'mlp',
+        'nonrigid_bake_resolution': 128,
         # lean rendering only: skip the MLPs for samples whose foreground likelihood (sum of
         # skinning weights) is below this; bounds |d rgb|, |d alpha| by ~2 * N_samples * cull_eps.
         # 0 = evaluate every sample exactly like the reference.  1e-9 already drops ~55 % of the
@@ -213,6 +221,24 @@ def _resolve_cfg():
 
 
 cfg = _resolve_cfg()
+
+
+def check_amd_options(node=None):
+    """Validate the options of the two baked approximations that go together (``node``: an ``amd`` mapping, default
+    cfg.amd) and return (canonical, nonrigid, nonrigid_bake_resolution).  ValueError: a value that is not 'mlp' or
+    'baked', a resolution that is no integer in [8, 512], or nonrigid = 'baked' without canonical = 'baked'."""
+    get = amd_option if node is None else (lambda k: node.get(k, _DEFAULTS['amd'][k]))
+    canonical, nonrigid, M = get('canonical'), get('nonrigid'), get('nonrigid_bake_resolution')
+    if canonical not in ('mlp', 'baked'):
+        raise ValueError("cfg.amd.canonical must be 'mlp' or 'baked', got %r" % (canonical,))
+    if nonrigid not in ('mlp', 'baked'):
+        raise ValueError("cfg.amd.nonrigid must be 'mlp' or 'baked', got %r" % (nonrigid,))
+    if isinstance(M, bool) or not isinstance(M, int) or not 8 <= M <= 512:
+        raise ValueError('cfg.amd.nonrigid_bake_resolution must be an integer in [8, 512], got %r' % (M,))
+    if nonrigid == 'baked' and canonical != 'baked':
+        raise ValueError("cfg.amd.nonrigid = 'baked' needs cfg.amd.canonical = 'baked' (got cfg.amd.canonical = %r): "
+                         "the offset grid is sampled in one kernel with the canonical grid" % (canonical,))
+    return canonical, nonrigid, M
 
 
 def amd_option(name, default=None):

@@ -2,7 +2,8 @@
 // depth) and hnrf_render_frame_fwd (every chunk of a frame, lean or with the eight diagnostic outputs) run K1 and
 // then the same per-chunk body, render_chunk: K2 -> K3 -> K4.  Early ray termination (hnrf_term.hip) walks depth
 // slabs instead and shares only the workspace carve (render_carve, hnrf_common.h).  The *_baked_* entries run the
-// same two bodies with the baked grid's sampler (hnrf_baked.hip) in K3's place.
+// same two bodies with the baked grid's sampler (hnrf_baked.hip) in K3's place, the *_baked_nr_* entries with the
+// fused offset-grid + canonical-grid sampler in the place of K2 and K3.
 #include <stdarg.h>
 #include <string.h>
 
@@ -52,12 +53,18 @@ struct CnlSource {
     const float *bmin, *bmax;
 };
 
+// no offset grid: xyz comes from K2 (nr_packed) or is x_skel
+constexpr BakedGrid kNoOffGrid{nullptr, 0, nullptr, nullptr};
+
 // K2 -> K3 -> K4 of one ray chunk whose K1 results are in `c`: the whole of hnrf_render_rays_fwd after K1, and the body
 // of every chunk of hnrf_render_frame_fwd.  cull_eps > 0: the MLPs run only on the compacted samples.  ev_start /
 // ev_stop (hipEvent_t, nullable) are recorded right before / after the canonical-MLP (or grid sampler) launch.
+// off.grid != null (with cnl.grid): xyz and raw both come from the fused sampler of the two grids, which stands for
+// K2 and K3; the lean form then writes no xyz at all.
 int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w, const void* nr_packed,
-                 const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t R, int S, float* rgb,
-                 float* alpha, float* depth, const DiagRows& d, void* ev_start, void* ev_stop, hipStream_t st) {
+                 const BakedGrid& off, const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t R,
+                 int S, float* rgb, float* alpha, float* depth, const DiagRows& d, void* ev_start, void* ev_stop,
+                 hipStream_t st) {
     const size_t P = (size_t)R * (size_t)S;
     const bool cull = cull_eps > 0.f, diag = d.weights != nullptr;
     int rc;
@@ -66,6 +73,16 @@ int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w,
     const int* cc = cull ? c.count : nullptr;
     float* xyz = diag ? d.xyz : c.xyz;
     const float* cnl_in = c.x_skel;
+    if (off.grid) {
+        if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
+        rc = baked_warp_sample(c.x_skel, off, BakedGrid{cnl.grid, cnl.N, cnl.bmin, cnl.bmax}, (int64_t)P, ci, cc, c.raw,
+                               diag ? d.xyz : nullptr, d.offsets, st);
+        if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
+        if (rc) return rc;
+        return hnrf_composite_fwd(c.raw, c.mask, c.z_vals, rays_d, diag ? d.xyz : nullptr, bgcolor, R, S,
+                                  cull ? cull_eps : 0.f, rgb, alpha, depth, d.weights, d.rgb_on_rays, d.cnl_xyz,
+                                  d.cnl_rgb, d.cnl_weight, st);
+    }
     if (nr_packed) {
         if ((rc = hnrf_nonrigid_fwd_sparse(c.x_skel, hann_w, nr_packed, mode, (int64_t)P, ci, cc, xyz, d.offsets, st)))
             return rc;
@@ -95,15 +112,26 @@ int check_source(const char* who, const CnlSource& cnl) {
     return HNRF_OK;
 }
 
+// the *_baked_nr_* entries' offset grid; it goes with a canonical grid only
+int check_off_source(const char* who, const BakedGrid& off, const CnlSource& cnl) {
+    if (off.grid == nullptr && off.N == 0) return HNRF_OK;
+    HNRF_REQUIRE(off.grid && off.bmin && off.bmax, HNRF_E_ARG, "%s: null offset grid / offset grid bbox pointer", who);
+    HNRF_REQUIRE(off.N >= 8 && off.N <= 512, HNRF_E_ARG, "%s: offset grid M=%d out of range [8, 512]", who, off.N);
+    HNRF_REQUIRE(((uintptr_t)off.grid & 7) == 0, HNRF_E_ARG, "%s: offset grid must be 8-byte aligned", who);
+    HNRF_REQUIRE(cnl.grid, HNRF_E_ARG, "%s: an offset grid needs a canonical grid", who);
+    return HNRF_OK;
+}
+
 int render_rays(const char* who, const float* rays_o, const float* rays_d, const float* near, const float* far,
                 const float* t_rand, const float* motion_Rs, const float* motion_Ts, const float* vol,
                 const float* bbox_min, const float* bbox_scale, const float* hann_w, const void* nr_packed,
-                const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t R, int S, int B, int G,
-                void* workspace, size_t workspace_bytes, float* rgb, float* alpha, float* depth, void* ev_mlp_start,
-                void* ev_mlp_stop, void* stream) {
+                const BakedGrid& off, const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t R,
+                int S, int B, int G, void* workspace, size_t workspace_bytes, float* rgb, float* alpha, float* depth,
+                void* ev_mlp_start, void* ev_mlp_stop, void* stream) {
     HNRF_REQUIRE(workspace, HNRF_E_ARG, "%s: null workspace / canonical weights", who);
     int src = check_source(who, cnl);
     if (src) return src;
+    if ((src = check_off_source(who, off, cnl))) return src;
     HNRF_REQUIRE(((uintptr_t)workspace & 255) == 0, HNRF_E_ARG, "%s: workspace must be 256-byte aligned", who);
     HNRF_REQUIRE(workspace_bytes >= hnrf_render_workspace_bytes(R, S), HNRF_E_WORKSPACE,
                  "%s: workspace %zu < %zu bytes", who, workspace_bytes, hnrf_render_workspace_bytes(R, S));
@@ -112,7 +140,7 @@ int render_rays(const char* who, const float* rays_o, const float* rays_d, const
     int rc = hnrf_sample_warp_fwd(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
                                   R, S, B, G, c.z_vals, c.x_skel, c.mask, nullptr, stream);
     if (rc) return rc;
-    return render_chunk(c, rays_d, hann_w, nr_packed, cnl, bgcolor, mode, cull_eps, R, S, rgb, alpha, depth,
+    return render_chunk(c, rays_d, hann_w, nr_packed, off, cnl, bgcolor, mode, cull_eps, R, S, rgb, alpha, depth,
                         DiagRows{}, ev_mlp_start, ev_mlp_stop, (hipStream_t)stream);
 }
 }  // namespace
@@ -125,8 +153,8 @@ extern "C" int hnrf_render_rays_fwd(const float* rays_o, const float* rays_d, co
                                     void* workspace, size_t workspace_bytes, float* rgb, float* alpha, float* depth,
                                     void* ev_mlp_start, void* ev_mlp_stop, void* stream) {
     return render_rays("hnrf_render_rays_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min,
-                       bbox_scale, hann_w, nr_packed, CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor, mode,
-                       cull_eps, R, S, B, G, workspace, workspace_bytes, rgb, alpha, depth, ev_mlp_start, ev_mlp_stop,
+                       bbox_scale, hann_w, nr_packed, kNoOffGrid, CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor,
+                       mode, cull_eps, R, S, B, G, workspace, workspace_bytes, rgb, alpha, depth, ev_mlp_start, ev_mlp_stop,
                        stream);
 }
 
@@ -140,9 +168,26 @@ extern "C" int hnrf_render_rays_baked_fwd(const float* rays_o, const float* rays
                                           void* ev_mlp_start, void* ev_mlp_stop, void* stream) {
     HNRF_REQUIRE(grid, HNRF_E_ARG, "hnrf_render_rays_baked_fwd: null grid");
     return render_rays("hnrf_render_rays_baked_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol,
-                       bbox_min, bbox_scale, hann_w, nr_packed, CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max},
-                       bgcolor, mode, cull_eps, R, S, B, G, workspace, workspace_bytes, rgb, alpha, depth, ev_mlp_start,
-                       ev_mlp_stop, stream);
+                       bbox_min, bbox_scale, hann_w, nr_packed, kNoOffGrid,
+                       CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max}, bgcolor, mode, cull_eps, R, S, B, G,
+                       workspace, workspace_bytes, rgb, alpha, depth, ev_mlp_start, ev_mlp_stop, stream);
+}
+
+extern "C" int hnrf_render_rays_baked_nr_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                             const float* t_rand, const float* motion_Rs, const float* motion_Ts,
+                                             const float* vol, const float* bbox_min, const float* bbox_scale,
+                                             const void* off_grid, int off_M, const float* off_bbox_min,
+                                             const float* off_bbox_max, const void* grid, int grid_N,
+                                             const float* grid_bbox_min, const float* grid_bbox_max, const float* bgcolor,
+                                             int mode, float cull_eps, int64_t R, int S, int B, int G, void* workspace,
+                                             size_t workspace_bytes, float* rgb, float* alpha, float* depth,
+                                             void* ev_mlp_start, void* ev_mlp_stop, void* stream) {
+    HNRF_REQUIRE(off_grid, HNRF_E_ARG, "hnrf_render_rays_baked_nr_fwd: null offset grid");
+    HNRF_REQUIRE(grid, HNRF_E_ARG, "hnrf_render_rays_baked_nr_fwd: null grid");
+    return render_rays("hnrf_render_rays_baked_nr_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol,
+                       bbox_min, bbox_scale, nullptr, nullptr, BakedGrid{off_grid, off_M, off_bbox_min, off_bbox_max},
+                       CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max}, bgcolor, mode, cull_eps, R, S, B, G,
+                       workspace, workspace_bytes, rgb, alpha, depth, ev_mlp_start, ev_mlp_stop, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -156,14 +201,15 @@ namespace {
 int render_frame(const char* who, const float* rays_o, const float* rays_d, const float* near, const float* far,
                  const float* t_rand, const float* motion_Rs, const float* motion_Ts, const float* vol,
                  const float* bbox_min, const float* bbox_scale, const float* hann_w, const void* nr_packed,
-                 const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t N, int S, int B, int G,
-                 int64_t chunk, void* workspace, size_t workspace_bytes, float* rgb, float* alpha, float* depth,
+                 const BakedGrid& off, const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t N,
+                 int S, int B, int G, int64_t chunk, void* workspace, size_t workspace_bytes, float* rgb, float* alpha, float* depth,
                  float* weights_on_rays, float* rgb_on_rays, float* cnl_xyz, float* cnl_rgb, float* cnl_weight,
                  float* xyz_on_rays, float* bmw, float* offsets, void* side_stream, void* const* events,
                  void* const* mlp_events, void* stream) {
     HNRF_REQUIRE(workspace && rgb && alpha && depth, HNRF_E_ARG, "%s: null pointer", who);
     int src = check_source(who, cnl);
     if (src) return src;
+    if ((src = check_off_source(who, off, cnl))) return src;
     HNRF_REQUIRE(N >= 0 && chunk >= 1 && S >= 2, HNRF_E_ARG, "%s: bad dims", who);
     HNRF_REQUIRE(((uintptr_t)workspace & 255) == 0, HNRF_E_ARG, "%s: workspace must be 256-byte aligned", who);
     const int64_t cr = chunk < N ? chunk : (N > 0 ? N : 1);
@@ -215,7 +261,7 @@ int render_frame(const char* who, const float* rays_o, const float* rays_d, cons
         const DiagRows d = diag ? DiagRows{weights_on_rays + r0 * S, rgb_on_rays + r0 * S * 3, cnl_xyz + 3 * r0,
                                            cnl_rgb + 3 * r0, cnl_weight + r0, xyz_on_rays + r0 * S * 3, offsets + r0 * S * 3}
                                 : DiagRows{};
-        if ((rc = render_chunk(carve(i, R), rays_d + 3 * r0, hann_w, nr_packed, cnl, bgcolor, cmode, cull_eps, R, S,
+        if ((rc = render_chunk(carve(i, R), rays_d + 3 * r0, hann_w, nr_packed, off, cnl, bgcolor, cmode, cull_eps, R, S,
                                rgb + 3 * r0, alpha + r0, depth + r0, d, mlp_events ? mlp_events[2 * i] : nullptr,
                                mlp_events ? mlp_events[2 * i + 1] : nullptr, st))) return rc;
         if (two) HNRF_HIP(hipEventRecord(ev_done[i & 1], st));
@@ -236,8 +282,8 @@ extern "C" int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, c
                                      float* cnl_rgb, float* cnl_weight, float* xyz_on_rays, float* bmw, float* offsets,
                                      void* side_stream, void* const* events, void* const* mlp_events, void* stream) {
     return render_frame("hnrf_render_frame_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min,
-                        bbox_scale, hann_w, nr_packed, CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor, mode,
-                        cull_eps, N, S, B, G, chunk, workspace, workspace_bytes, rgb, alpha, depth, weights_on_rays,
+                        bbox_scale, hann_w, nr_packed, kNoOffGrid, CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor,
+                        mode, cull_eps, N, S, B, G, chunk, workspace, workspace_bytes, rgb, alpha, depth, weights_on_rays,
                         rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays, bmw, offsets, side_stream, events,
                         mlp_events, stream);
 }
@@ -255,8 +301,29 @@ extern "C" int hnrf_render_frame_baked_fwd(const float* rays_o, const float* ray
                                            void* const* mlp_events, void* stream) {
     HNRF_REQUIRE(grid, HNRF_E_ARG, "hnrf_render_frame_baked_fwd: null grid");
     return render_frame("hnrf_render_frame_baked_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol,
-                        bbox_min, bbox_scale, hann_w, nr_packed, CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max},
-                        bgcolor, mode, cull_eps, N, S, B, G, chunk, workspace, workspace_bytes, rgb, alpha, depth,
+                        bbox_min, bbox_scale, hann_w, nr_packed, kNoOffGrid,
+                        CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max}, bgcolor, mode, cull_eps, N, S, B, G, chunk, workspace, workspace_bytes, rgb, alpha, depth,
                         weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays, bmw, offsets,
                         side_stream, events, mlp_events, stream);
+}
+
+extern "C" int hnrf_render_frame_baked_nr_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                              const float* t_rand, const float* motion_Rs, const float* motion_Ts,
+                                              const float* vol, const float* bbox_min, const float* bbox_scale,
+                                              const void* off_grid, int off_M, const float* off_bbox_min,
+                                              const float* off_bbox_max, const void* grid, int grid_N,
+                                              const float* grid_bbox_min, const float* grid_bbox_max, const float* bgcolor,
+                                              int mode, float cull_eps, int64_t N, int S, int B, int G, int64_t chunk,
+                                              void* workspace, size_t workspace_bytes, float* rgb, float* alpha,
+                                              float* depth, float* weights_on_rays, float* rgb_on_rays, float* cnl_xyz,
+                                              float* cnl_rgb, float* cnl_weight, float* xyz_on_rays, float* bmw,
+                                              float* offsets, void* side_stream, void* const* events,
+                                              void* const* mlp_events, void* stream) {
+    HNRF_REQUIRE(off_grid, HNRF_E_ARG, "hnrf_render_frame_baked_nr_fwd: null offset grid");
+    HNRF_REQUIRE(grid, HNRF_E_ARG, "hnrf_render_frame_baked_nr_fwd: null grid");
+    return render_frame("hnrf_render_frame_baked_nr_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol,
+                        bbox_min, bbox_scale, nullptr, nullptr, BakedGrid{off_grid, off_M, off_bbox_min, off_bbox_max},
+                        CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max}, bgcolor, mode, cull_eps, N, S, B, G,
+                        chunk, workspace, workspace_bytes, rgb, alpha, depth, weights_on_rays, rgb_on_rays, cnl_xyz,
+                        cnl_rgb, cnl_weight, xyz_on_rays, bmw, offsets, side_stream, events, mlp_events, stream);
 }

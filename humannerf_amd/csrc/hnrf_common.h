@@ -95,6 +95,16 @@ int lattice_points(const float* bmin, const float* bmax, int N, int64_t p0, int6
 int baked_sample(const float* xyz, const void* grid, int N, const float* bmin, const float* bmax, int64_t P,
                  const int* idx, const int* count, float* raw, hipStream_t st);
 
+// Baked offset field + baked canonical grid in one kernel (hnrf_baked.hip): raw[p] = cnl sampled at x_skel[p] + the
+// offset grid sampled at x_skel[p]; xyz / offsets nullable; idx / count as above.  Arguments are the caller's to check.
+struct BakedGrid {
+    const void* grid;
+    int N;
+    const float *bmin, *bmax;
+};
+int baked_warp_sample(const float* x_skel, const BakedGrid& off, const BakedGrid& cnl, int64_t P, const int* idx,
+                      const int* count, float* raw, float* xyz, float* offsets, hipStream_t st);
+
 // HNRF_MLP_F16X3 back end (hnrf_mlp_f16.hip)
 size_t canonical16_bytes();
 size_t nonrigid16_bytes();

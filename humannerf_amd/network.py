@@ -28,7 +28,7 @@ import torch.nn.functional as F
 
 from . import ops
 from .autograd import RenderRays
-from .config import cfg, amd_option
+from .config import cfg, amd_option, check_amd_options
 
 SMPL_PARENT = [-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16,
                17, 18, 19, 20, 21]          # core/utils/network_util.py:91-94
@@ -519,6 +519,11 @@ class Network(nn.Module):
         # bake_count counts the bakes this network ran
         self._baked = None
         self.bake_count = 0
+        # baked non-rigid offset field of the current frame (cfg.amd.nonrigid = 'baked'): dict(grid, bmin, bmax, packed,
+        # key, refs) or None, the resident workspace of the bake, and the number of bakes this network ran
+        self._baked_nr = None
+        self._nr_bake_ws = None
+        self.nonrigid_bake_count = 0
         self._workspace = None
         # set by train.Trainer when world_size > 1: dist.GradientSync whose volume_hook averages the weight-volume
         # gradient over the ranks in front of the decoder backward
@@ -672,6 +677,7 @@ class Network(nn.Module):
         iter_val = float(iter_val)
         dev = dst_Rs.device
         f32 = lambda t: t.to(dtype=torch.float32)
+        posevec_arg = dst_posevec                  # (the caller's tensor: the per-frame offset grid is keyed by its identity)
         dst_Rs, dst_Ts, dst_posevec = f32(dst_Rs), f32(dst_Ts), f32(dst_posevec)
         cnl_gtfms, priors = f32(cnl_gtfms), f32(motion_weights_priors)
 
@@ -692,17 +698,21 @@ class Network(nn.Module):
             vol = self.grad_sync.volume_hook(vol, priors)
 
         mode = self._mlp_mode()
-        nr_packed, cnl_packed, hann_w = None, None, None
+        canonical, nonrigid, _ = check_amd_options()      # (ValueError: unknown values, 'baked' offsets without a grid)
+        # the offsets come from the frame's offset grid: no per-frame pack and no window upload unless it is (re)baked
+        nr_from_grid = nonrigid == 'baked' and not train_path and not ignore_nr
+        nr_packed, cnl_packed, hann_w, hann_host = None, None, None, None
         self._nr_inputs_are_zero = False
         if not ignore_nr:
-            hann_w = hann_window_weights(iter_val, nr_cfg.multires, nr_cfg.kick_in_iter, nr_cfg.full_band_iter)
-            self._nr_inputs_are_zero = iter_val < nr_cfg.kick_in_iter and float(hann_w.abs().max()) == 0.0
-            # through pinned memory: a pageable host-to-device copy waits for everything queued on the stream, i.e. it
-            # would synchronise host and GPU once per training step / frame
-            hann_w = hann_w.pin_memory().to(dev, non_blocking=True) if dev.type == 'cuda' else hann_w.to(dev)
+            hann_host = hann_window_weights(iter_val, nr_cfg.multires, nr_cfg.kick_in_iter, nr_cfg.full_band_iter)
+            self._nr_inputs_are_zero = iter_val < nr_cfg.kick_in_iter and float(hann_host.abs().max()) == 0.0
+            if not nr_from_grid:
+                # through pinned memory: a pageable host-to-device copy waits for everything queued on the stream, i.e.
+                # it would synchronise host and GPU once per training step / frame
+                hann_w = hann_host.pin_memory().to(dev, non_blocking=True) if dev.type == 'cuda' else hann_host.to(dev)
         if not train_path:
             cnl_packed = self._canonical_packed()
-            if not ignore_nr:
+            if not ignore_nr and not nr_from_grid:
                 nr_packed = self._nonrigid_packed(cond)
 
         rays_o, rays_d = rays[0], rays[1]
@@ -736,15 +746,16 @@ class Network(nn.Module):
             return {k: v.reshape(list(rays_shape[:-1]) + list(v.shape[1:])) for k, v in out.items()}
 
         term_eps = float(amd_option('term_eps', 0.0))
-        canonical = amd_option('canonical', 'mlp')
-        if canonical not in ('mlp', 'baked'):
-            raise ValueError("cfg.amd.canonical must be 'mlp' or 'baked', got %r" % (canonical,))
-        baked = None
+        baked, baked_nr = None, None
         if canonical == 'baked' and not train_path:          # (training ignores the option: _render_rays_train)
             if not diag and term_eps > 0.0:
                 raise NotImplementedError("cfg.amd.term_eps > 0 with cfg.amd.canonical = 'baked': early ray termination "
                                           "has no baked form (hnrf_render_rays_term_fwd runs the canonical MLP)")
             baked = self._baked_for_frame(cnl_bbox_min_xyz, kwargs.get('cnl_bbox_max_xyz'), cnl_bbox_scale_xyz)
+            if nr_from_grid:
+                # over the canonical grid's box; nr_baked_on: the image this frame's bake ran on (its status word is
+                # watched below), None when the grid of the last frame still holds
+                baked_nr, nr_baked_on = self._baked_nr_for_frame(posevec_arg, iter_val, hann_host, baked[1], baked[2])
         if not train_path and (diag or term_eps == 0.0):
             # inference: the whole frame in one library call -- chunk loop of network.py:330-352, results straight into
             # whole-frame tensors (the reference concatenates per-chunk results: one more pass over 17 KB per ray);
@@ -755,9 +766,10 @@ class Network(nn.Module):
                 rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w, nr_packed,
                 cnl_packed, bg, S, int(cfg.chunk), gmode, diagnostics=diag,
                 cull_eps=0.0 if diag else float(amd_option('cull_eps', 0.0)), workspace=self._workspace,
-                overlap=bool(amd_option('overlap_warp', False)), mlp_event_log=self.mlp_event_log, baked=baked)
+                overlap=bool(amd_option('overlap_warp', False)), mlp_event_log=self.mlp_event_log, baked=baked,
+                baked_nr=baked_nr)
             if mode == 'f16x3' and guarded != set():
-                self._watch_f16_range(cnl_packed, nr_packed, mode)
+                self._watch_f16_range(cnl_packed, nr_packed if baked_nr is None else nr_baked_on, mode)
         else:
             # per ray chunk (network.py:333): training (autograd.RenderRays), or the lean inference path with early ray
             # termination (hnrf_render_rays_term_fwd, one workspace for every chunk)
@@ -886,6 +898,61 @@ class Network(nn.Module):
         f32 = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(3).contiguous()
         self._baked = {'grid': g.to(dev).contiguous(), 'bmin': f32(bbox_min), 'bmax': f32(bbox_max), 'key': None,
                        'injected': True, 'refs': None}
+
+    # baked non-rigid offset field (no counterpart in the reference; humannerf_amd/baked.py) -------------------------
+    def _nr_tensors(self):
+        lin = self.non_rigid_mlp.module.linears()
+        return [t for l in lin for t in (l.weight, l.bias)]
+
+    def bake_nonrigid(self, dst_posevec, iter_val, box, resolution=None):
+        """Tabulate this frame's non-rigid offsets -- a function of x_skel alone once ``dst_posevec`` (the condition
+        code; zeroed below non_rigid_motion_mlp.kick_in_iter like in forward) and ``iter_val`` (the Hann window) are
+        fixed -- on a resolution^3 lattice (default cfg.amd.nonrigid_bake_resolution) over ``box`` = (bbox_min, bbox_max)
+        with hnrf_bake_nonrigid, in the current mlp_mode.  Returns the grid (M, M, M, 4) float16, c = (dx, dy, dz, 0), on
+        the device and keeps it for forward (cfg.amd.nonrigid = 'baked').  Nothing is read back: no host
+        synchronisation (forward calls this once per frame); the f16-range verdict of the packed image travels with
+        forward's watch, and offsets beyond +-65504 m are saturated uncounted."""
+        from . import baked as baked_mod
+        with torch.no_grad():
+            M = baked_mod.check_resolution(amd_option('nonrigid_bake_resolution', 128) if resolution is None else resolution)
+            dev = self._mesh_device()
+            f32 = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(3).contiguous()
+            bmin, bmax = f32(box[0]), f32(box[1])
+            nr_cfg = cfg.non_rigid_motion_mlp
+            iter_val = float(iter_val)
+            cond = torch.as_tensor(dst_posevec).to(device=dev, dtype=torch.float32).reshape(-1)
+            if iter_val < nr_cfg.kick_in_iter:
+                cond = torch.zeros_like(cond)                               # network.py:735-737
+            hann = hann_window_weights(iter_val, nr_cfg.multires, nr_cfg.kick_in_iter, nr_cfg.full_band_iter)
+            hann = hann.pin_memory().to(dev, non_blocking=True) if dev.type == 'cuda' else hann.to(dev)
+            mode = self._mlp_mode()
+            packed = self._nonrigid_packed(cond)
+            if self._nr_bake_ws is None or self._nr_bake_ws[0] != (M, dev):
+                self._nr_bake_ws = ((M, dev), ops.bake_nonrigid_workspace(M, dev))
+            grid = ops.bake_nonrigid(packed, hann, bmin, bmax, M, mode, workspace=self._nr_bake_ws[1])
+            self.nonrigid_bake_count += 1
+            self._baked_nr = {'grid': grid, 'bmin': bmin, 'bmax': bmax, 'packed': packed, 'mode': mode, 'key': None,
+                              'refs': None}
+            return grid
+
+    def _baked_nr_for_frame(self, dst_posevec, iter_val, hann_host, bmin, bmax):
+        """((off_grid, bmin, bmax), packed image or None) for an inference frame: the grid of the last frame when its
+        key -- non-rigid parameter versions, mlp_mode, M, the host-side Hann weights, whether the condition code is
+        zeroed -- is unchanged and box and ``dst_posevec`` are the same tensor objects at the same ``_version``; else a
+        fresh bake (whose packed image is returned for the f16-range watch).  Identity only: a fresh ``dst_posevec``
+        tensor re-bakes, nothing is compared by value, nothing synchronises."""
+        M = int(amd_option('nonrigid_bake_resolution', 128))
+        key = (_versions(self._nr_tensors()), self._mlp_mode(), M, tuple(hann_host.tolist()),
+               iter_val < cfg.non_rigid_motion_mlp.kick_in_iter)
+        watched = (dst_posevec, bmin, bmax)
+        b = self._baked_nr
+        if b is not None and b['key'] == key and b['refs'] is not None \
+                and all(r() is t and v == t._version for (r, v), t in zip(b['refs'], watched)):
+            return (b['grid'], b['bmin'], b['bmax']), None
+        self.bake_nonrigid(dst_posevec, iter_val, (bmin, bmax), M)
+        b = self._baked_nr
+        b['key'], b['refs'] = key, tuple((weakref.ref(t), t._version) for t in watched)
+        return (b['grid'], b['bmin'], b['bmax']), b['packed']
 
     def _baked_for_frame(self, bbox_min, bbox_max, bbox_scale):
         """(grid, bmin, bmax) for an inference frame: the injected grid; else the cached one when its key (canonical

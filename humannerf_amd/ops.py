@@ -215,14 +215,17 @@ def _render_args(operands, workspace, need, grow=True):
 
 def render_rays(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
                 hann_w, nr_packed, cnl_packed, bgcolor, n_samples, mode='f32', workspace=None, out=None,
-                mlp_events=None, cull_eps=0.0, baked=None):
+                mlp_events=None, cull_eps=0.0, baked=None, baked_nr=None):
     """The whole path for one ray chunk (network.py:474-602) with only the
     rgb/alpha/depth outputs; intermediates live in ``workspace`` (one given must hold
     render_workspace_bytes(R, S) on the rays' device: it is not replaced).  ``mlp_events``:
     optional pair of torch.cuda.Event(enable_timing=True), recorded around the
     canonical-MLP launch.  ``baked``: (grid, bbox_min, bbox_max) of bake_canonical -- raw then comes from the grid
-    sampler (hnrf_render_rays_baked_fwd) and ``cnl_packed`` is not used (may be None)."""
+    sampler (hnrf_render_rays_baked_fwd) and ``cnl_packed`` is not used (may be None).  ``baked_nr``: (off_grid, bbox_min,
+    bbox_max) of bake_nonrigid, with ``baked`` only -- xyz and raw then come from the fused sampler of the two grids
+    (hnrf_render_rays_baked_nr_fwd) and ``hann_w`` / ``nr_packed`` are not used (may be None)."""
     lib = _lib.load()
+    _chk_baked_nr(baked, baked_nr)
     R, S = rays_o.shape[0], int(n_samples)
     args, workspace = _render_args((rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
                                     hann_w, nr_packed, cnl_packed, bgcolor), workspace,
@@ -241,6 +244,9 @@ def render_rays(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bb
     if baked is not None:
         fn, name = lib.hnrf_render_rays_baked_fwd, 'hnrf_render_rays_baked_fwd'
         ptrs[12:13] = _baked_args(baked, dev)
+    if baked_nr is not None:
+        fn, name = lib.hnrf_render_rays_baked_nr_fwd, 'hnrf_render_rays_baked_nr_fwd'
+        ptrs[10:12] = _baked_args(baked_nr, dev)
     _lib.check(fn(*ptrs, _mode_arg(mode), float(cull_eps), R, S, motion_Rs.shape[0],
                   vol.shape[-1], _ptr(workspace), workspace.numel() * workspace.element_size(),
                   _ptr(out['rgb']), _ptr(out['alpha']), _ptr(out['depth']), ev[0], ev[1], _stream()), name)
@@ -264,13 +270,17 @@ def _frame_streams(device):
 
 def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w, nr_packed,
                  cnl_packed, bgcolor, n_samples, chunk, mode='f16x3', diagnostics=True, cull_eps=0.0, workspace=None,
-                 overlap=True, mlp_event_log=None, baked=None):
+                 overlap=True, mlp_event_log=None, baked=None, baked_nr=None):
     """The whole frame in one call (hnrf_render_frame_fwd): all ray chunks through K1..K4, results in whole-frame tensors;
     K1 of the next chunk on a side stream while the MLP kernels of the current one run.  Returns (dict of outputs,
     workspace).  ``mlp_event_log``: list that receives one (start, stop) torch.cuda.Event pair per chunk.  ``baked``:
     (grid, bbox_min, bbox_max) of bake_canonical -- raw then comes from the grid sampler (hnrf_render_frame_baked_fwd,
-    the event pairs around its launches) and ``cnl_packed`` is not used (may be None)."""
+    the event pairs around its launches) and ``cnl_packed`` is not used (may be None).  ``baked_nr``: (off_grid, bbox_min,
+    bbox_max) of bake_nonrigid, with ``baked`` only -- xyz and raw then come from the fused sampler of the two grids
+    (hnrf_render_frame_baked_nr_fwd; xyz_on_rays / offsets are the interpolated values) and ``hann_w`` / ``nr_packed``
+    are not used (may be None)."""
     lib = _lib.load()
+    _chk_baked_nr(baked, baked_nr)
     N, S, B, G = rays_o.shape[0], int(n_samples), motion_Rs.shape[0], vol.shape[-1]
     dev = rays_o.device
     chunk = int(chunk)
@@ -299,6 +309,9 @@ def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, b
     if baked is not None:
         fn, name = lib.hnrf_render_frame_baked_fwd, 'hnrf_render_frame_baked_fwd'
         ptrs[12:13] = _baked_args(baked, dev)
+    if baked_nr is not None:
+        fn, name = lib.hnrf_render_frame_baked_nr_fwd, 'hnrf_render_frame_baked_nr_fwd'
+        ptrs[10:12] = _baked_args(baked_nr, dev)
     _lib.check(fn(
         *ptrs, _mode_arg(mode), float(cull_eps), N, S, B, G, chunk, _ptr(workspace),
         workspace.numel() * workspace.element_size(), g('rgb'), g('alpha'), g('depth'),
@@ -820,6 +833,12 @@ def _baked_args(baked, device):
     return [grid.data_ptr(), N, _ptr(bbox_min), _ptr(bbox_max)]
 
 
+def _chk_baked_nr(baked, baked_nr):
+    if baked_nr is not None and baked is None:
+        raise _lib.HnrfError('baked_nr (the offset grid) needs baked (the canonical grid): the two are sampled in one '
+                             'kernel, and there is no offset grid in front of the canonical MLP')
+
+
 def bake_canonical(packed, bbox_min, bbox_max, N, mode='f32', want_saturated=False):
     """hnrf_bake_canonical: the canonical MLP (``packed``, ``mode``) on the N^3 lattice over [bbox_min, bbox_max] ->
     grid (N, N, N, 4) float16 indexed [z][y][x][c], c = (r, g, b, sigma) pre-activation, values beyond +-65504
@@ -862,6 +881,77 @@ def baked_sample_sparse(xyz, grid, bbox_min, bbox_max, idx, count, raw=None):
     _lib.check(lib.hnrf_baked_sample_sparse(_ptr(xyz), grid.data_ptr(), N, _ptr(bbox_min), _ptr(bbox_max),
                                             xyz.numel() // 3, _ptr(idx), _ptr(count), _ptr(raw), _stream()),
                'hnrf_baked_sample_sparse')
+    return raw
+
+
+# ---------------------------------------------------------------------------------- baked non-rigid offset field
+def bake_nonrigid_workspace(M, device):
+    """A workspace for bake_nonrigid at resolution M (a per-frame caller keeps it)."""
+    need = _lib.load().hnrf_bake_nonrigid_workspace_bytes(int(M))
+    if need == 0:
+        raise _lib.HnrfError(f'offset grid resolution {M} out of range [8, 512]')
+    return torch.empty(need // 4 + 64, device=device)
+
+
+def bake_nonrigid(nr_packed, hann_w, bbox_min, bbox_max, M, mode='f32', want_saturated=False, workspace=None, out=None):
+    """hnrf_bake_nonrigid: the offsets of the non-rigid MLP (``nr_packed`` -- one frame's condition code folded in --,
+    ``hann_w``, ``mode``) on the M^3 lattice over [bbox_min, bbox_max] -> grid (M, M, M, 4) float16 indexed
+    [z][y][x][c], c = (dx, dy, dz, +0), values beyond +-65504 saturated.  ``want_saturated``: also return their count, a
+    (1,) int32 device tensor (no synchronisation).  ``workspace`` (bake_nonrigid_workspace) / ``out`` (a grid tensor):
+    buffers of a per-frame caller to use instead of fresh ones."""
+    lib = _lib.load()
+    _chk(nr_packed, hann_w, bbox_min, bbox_max, workspace)
+    M = int(M)
+    dev = nr_packed.device
+    ws = workspace if workspace is not None else bake_nonrigid_workspace(M, dev)
+    grid = out if out is not None else torch.empty(M, M, M, 4, dtype=torch.float16, device=dev)
+    if _chk_grid(grid, bbox_min, bbox_max) != M or grid.device != dev or ws.device != dev:
+        raise _lib.HnrfError(f'bake_nonrigid: out must be a ({M}, {M}, {M}, 4) grid on {dev}')
+    sat = torch.zeros(1, dtype=torch.int32, device=dev) if want_saturated else None
+    _lib.check(lib.hnrf_bake_nonrigid(_ptr(nr_packed), _ptr(hann_w), _mode_arg(mode), _ptr(bbox_min), _ptr(bbox_max), M,
+                                      _ptr(ws), ws.numel() * 4, grid.data_ptr(), _ptr(sat), _stream()),
+               'hnrf_bake_nonrigid')
+    return (grid, sat) if want_saturated else grid
+
+
+def _warp_sample_args(x_skel, off, cnl, want_xyz, want_offsets):
+    _chk(x_skel)
+    M = _chk_grid(*off)
+    N = _chk_grid(*cnl)
+    dev = x_skel.device
+    if off[0].device != dev or cnl[0].device != dev:
+        raise _lib.HnrfError(f'baked grids on {off[0].device} / {cnl[0].device}, samples on {dev}')
+    xyz = torch.empty_like(x_skel) if want_xyz else None
+    offsets = torch.empty_like(x_skel) if want_offsets else None
+    args = [_ptr(x_skel), off[0].data_ptr(), M, _ptr(off[1]), _ptr(off[2]), cnl[0].data_ptr(), N, _ptr(cnl[1]),
+            _ptr(cnl[2]), x_skel.numel() // 3]
+    return args, xyz, offsets
+
+
+def baked_warp_sample(x_skel, off, cnl, want_xyz=False, want_offsets=False):
+    """hnrf_baked_warp_sample: x_skel (..., 3) -> raw (..., 4) = the canonical grid ``cnl`` = (grid, bbox_min, bbox_max)
+    sampled at xyz = x_skel + the offset grid ``off`` = (off_grid, bbox_min, bbox_max) sampled at x_skel: one kernel for
+    the chain baked_sample -> add -> baked_sample.  Returns raw, or (raw, xyz or None, offsets or None) when either is
+    asked for."""
+    lib = _lib.load()
+    args, xyz, offsets = _warp_sample_args(x_skel, off, cnl, want_xyz, want_offsets)
+    raw = torch.empty(*x_skel.shape[:-1], 4, device=x_skel.device)
+    _lib.check(lib.hnrf_baked_warp_sample(*args, _ptr(raw), _ptr(xyz), _ptr(offsets), _stream()), 'hnrf_baked_warp_sample')
+    return (raw, xyz, offsets) if (want_xyz or want_offsets) else raw
+
+
+def baked_warp_sample_sparse(x_skel, off, cnl, idx, count, raw=None, xyz=None, offsets=None):
+    """hnrf_baked_warp_sample_sparse: only the samples idx[0 .. count) are read and written; ``raw`` (default zeros)
+    and the optional ``xyz`` / ``offsets`` tensors (of x_skel's shape) keep their other rows.  Returns raw."""
+    lib = _lib.load()
+    _chk(raw, xyz, offsets)
+    args, _, _ = _warp_sample_args(x_skel, off, cnl, False, False)
+    if raw is None:
+        raw = torch.zeros(*x_skel.shape[:-1], 4, device=x_skel.device)
+    assert raw.numel() // 4 == x_skel.numel() // 3
+    assert all(t is None or t.numel() == x_skel.numel() for t in (xyz, offsets))
+    _lib.check(lib.hnrf_baked_warp_sample_sparse(*args, _ptr(idx), _ptr(count), _ptr(raw), _ptr(xyz), _ptr(offsets),
+                                                 _stream()), 'hnrf_baked_warp_sample_sparse')
     return raw
 
 

@@ -55,9 +55,11 @@ def _panels(rgb8, alpha8, truth8=None):
 
 def _baked_folder(network, subject, folder):
     """cfg.amd.canonical = 'baked': bake the canonical grid over the subject's canonical bbox before the first frame
-    (so that no frame of the loop pays for it) and mark the folder ``<folder>_baked_<N>`` -- approximate pictures are
-    never written where exact ones go.  An injected grid (Network.set_baked_grid) is used as it is."""
-    from .config import amd_option
+    (so that no frame of the loop pays for it) and mark the folder ``<folder>_baked_<N>`` -- ``<folder>_baked_<N>_nr<M>``
+    with cfg.amd.nonrigid = 'baked' where the non-rigid motions are on -- : approximate pictures are never written where
+    exact ones go.  An injected grid (Network.set_baked_grid) is used as it is."""
+    from .config import amd_option, check_amd_options
+    _, nonrigid, nr_M = check_amd_options()
     if amd_option('canonical', 'mlp') != 'baked':
         return folder
     b = getattr(network, '_baked', None)
@@ -67,7 +69,10 @@ def _baked_folder(network, subject, folder):
         import torch
         with torch.no_grad():
             network._baked_for_frame(torch.from_numpy(mn), torch.from_numpy(mx), None)
-    return '%s_baked_%d' % (folder, network._baked['grid'].shape[0])
+    folder = '%s_baked_%d' % (folder, network._baked['grid'].shape[0])
+    if nonrigid == 'baked' and not cfg.ignore_non_rigid_motions:
+        folder += '_nr%d' % nr_M                # the per-frame offset grid (cfg.amd.nonrigid = 'baked'): baked by forward
+    return folder
 
 
 def _render_loop(network, frames, names, folder, logdir, rank, world, device, metrics=None):

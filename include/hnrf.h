@@ -540,6 +540,62 @@ int hnrf_render_frame_baked_fwd(const float* rays_o, const float* rays_d, const 
                                 float* cnl_weight, float* xyz_on_rays, float* bmw, float* offsets, void* side_stream,
                                 void* const* events, void* const* mlp_events, void* stream);
 
+/* ---- baked non-rigid offset field (no counterpart in the reference; humannerf_amd/baked.py) ----
+ * Within one frame the condition code and the Hann window weights are constants, so K2's offset is a function of the
+ * three coordinates of x_skel alone: offset = g(x_skel).  It can be tabulated once per FRAME and interpolated -- an
+ * opt-in APPROXIMATION on the lines of the baked canonical grid, and only together with it.
+ * off_grid [M][M][M][4] f16, indexed [z][y][x][c], c = (dx, dy, dz, +0.0), 8 bytes per lattice point
+ *  (hnrf_baked_grid_bytes(M); 8-byte aligned), 8 <= M <= 512; the lattice and the layout are the canonical grid's, so
+ *  that one sampler serves both.
+ * hnrf_bake_nonrigid: value = the `offsets` output of hnrf_nonrigid_fwd (nr_packed, hann_w, mode) at the lattice point,
+ *  converted to f16 with round to nearest even; values beyond +-65504 (infinities included) are stored as +-65504 and
+ *  counted into *saturated (nullable device counter, ADDED to); NaN stays NaN; the pad lane is +0.  Runs in chunks
+ *  through `workspace` (hnrf_bake_nonrigid_workspace_bytes(M), 256-byte aligned); every chunk is range-guarded
+ *  (HNRF_STATUS_F16_RANGE in nr_packed's status word, mode f16x3).
+ * hnrf_baked_warp_sample: x_skel [P,3] -> raw [P,4] fp32 (16-byte aligned); nullable xyz [P,3], offsets [P,3].  With
+ *  `sample` = hnrf_baked_sample's arithmetic and every operation rounded on its own:
+ *      off = channels 0..2 of sample(off_grid, M, off_bbox) at x_skel
+ *      xyz = x_skel + off          (one fp32 add per coordinate)
+ *      raw = sample(grid, N, bbox) at xyz
+ *  bit for bit the chain hnrf_baked_sample -> add -> hnrf_baked_sample, in one kernel without the 24 B / sample round
+ *  trip of K2's output.  humannerf_amd/baked.py:warp_sample_host restates it in numpy float32.
+ * hnrf_baked_warp_sample_sparse: only the samples idx[0 .. *count) are read and written (raw, xyz and offsets alike;
+ *  semantics of hnrf_baked_sample_sparse). */
+size_t hnrf_bake_nonrigid_workspace_bytes(int M);
+int hnrf_bake_nonrigid(const void* nr_packed, const float* hann_w, int mode, const float* bbox_min, const float* bbox_max,
+                       int M, void* workspace, size_t workspace_bytes, void* grid, unsigned* saturated, void* stream);
+int hnrf_baked_warp_sample(const float* x_skel, const void* off_grid, int off_M, const float* off_bbox_min,
+                           const float* off_bbox_max, const void* grid, int grid_N, const float* grid_bbox_min,
+                           const float* grid_bbox_max, int64_t P, float* raw, float* xyz, float* offsets, void* stream);
+int hnrf_baked_warp_sample_sparse(const float* x_skel, const void* off_grid, int off_M, const float* off_bbox_min,
+                                  const float* off_bbox_max, const void* grid, int grid_N, const float* grid_bbox_min,
+                                  const float* grid_bbox_max, int64_t P, const int* idx, const int* count, float* raw,
+                                  float* xyz, float* offsets, void* stream);
+/* hnrf_render_rays_baked_fwd / hnrf_render_frame_baked_fwd with the fused sampler above in the place of K2 and the grid
+ * sampler: the arguments of those entries with hann_w, nr_packed replaced by off_grid, off_M, off_bbox_min,
+ * off_bbox_max.  Lean and 11-output forms, cull_eps, the side stream and the event pairs (recorded around the fused
+ * sampler's launch) as there.  In the 11-output form xyz_on_rays and offsets are the interpolated values actually used;
+ * backward_motion_weights stays exact.  No MLP runs: `mode` is checked and otherwise unused, and there is no status
+ * word in this form. */
+int hnrf_render_rays_baked_nr_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                  const float* t_rand, const float* motion_Rs, const float* motion_Ts, const float* vol,
+                                  const float* bbox_min, const float* bbox_scale, const void* off_grid, int off_M,
+                                  const float* off_bbox_min, const float* off_bbox_max, const void* grid, int grid_N,
+                                  const float* grid_bbox_min, const float* grid_bbox_max, const float* bgcolor, int mode,
+                                  float cull_eps, int64_t R, int S, int B, int G, void* workspace, size_t workspace_bytes,
+                                  float* rgb, float* alpha, float* depth, void* ev_mlp_start, void* ev_mlp_stop,
+                                  void* stream);
+int hnrf_render_frame_baked_nr_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                   const float* t_rand, const float* motion_Rs, const float* motion_Ts, const float* vol,
+                                   const float* bbox_min, const float* bbox_scale, const void* off_grid, int off_M,
+                                   const float* off_bbox_min, const float* off_bbox_max, const void* grid, int grid_N,
+                                   const float* grid_bbox_min, const float* grid_bbox_max, const float* bgcolor, int mode,
+                                   float cull_eps, int64_t N, int S, int B, int G, int64_t chunk, void* workspace,
+                                   size_t workspace_bytes, float* rgb, float* alpha, float* depth, float* weights_on_rays,
+                                   float* rgb_on_rays, float* cnl_xyz, float* cnl_rgb, float* cnl_weight,
+                                   float* xyz_on_rays, float* bmw, float* offsets, void* side_stream,
+                                   void* const* events, void* const* mlp_events, void* stream);
+
 /* ---- rasteriser for vertex-coloured triangle meshes (no counterpart in the reference; humannerf_amd/raster.py) ----
  * hnrf_raster_mesh: verts [V,3] fp32 world positions, faces [F,3] int32, colors [V,3] fp32 (nullable when the shade
  *  is the normal), camera K [9], R [9] (row-major 3x3), T [3], bgcolor [3] (0..1): device pointers, nothing is read
