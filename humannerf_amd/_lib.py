@@ -85,6 +85,17 @@ SIGNATURES = {
     'hnrf_render_frame_baked_nr_fwd': (_int, [_vp] * 11 + [_int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int, ctypes.c_float, _i64, _int, _int, _int, _i64, _vp, _sz] + [_vp] * 11 + [_vp, _vp, _vp, _vp]),
     'hnrf_raster_workspace_bytes': (_sz, [_i64, _i64, _int, _int]),
     'hnrf_raster_mesh': (_int, [_vp, _i64, _vp, _i64] + [_vp] * 5 + [_int, _int, ctypes.c_float, _int] + [_vp] * 4 + [_vp, _sz, _vp]),
+    'hnrf_lpips_packed_bytes': (_sz, []),
+    'hnrf_lpips_pack': (_int, [_vp, _vp, _vp, _vp, _vp]),
+    'hnrf_conv3x3_fwd': (_int, [_vp, _vp, _int, _int, _int, _int, _int, _vp, _vp]),
+    'hnrf_conv3x3_bwd_data': (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp]),
+    'hnrf_maxpool2_fwd': (_int, [_vp, _int, _int, _int, _int, _vp, _vp]),
+    'hnrf_maxpool2_bwd': (_int, [_vp, _vp, _int, _int, _int, _int, _vp, _vp]),
+    'hnrf_lpips_head_fwd': (_int, [_vp, _vp, _int, _i64, _int, _vp, _vp, _int, _vp, _vp]),
+    'hnrf_lpips_head_bwd': (_int, [_vp, _vp, _vp, _int, _i64, _int, _vp, _int, _vp]),
+    'hnrf_lpips_workspace_bytes': (_sz, [_int, _int, _int, _int]),
+    'hnrf_lpips_fwd': (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _vp, _sz, _vp, _vp, _vp]),
+    'hnrf_lpips_bwd': (_int, [_vp, _vp, _int, _int, _int, _vp, _sz, _vp, _vp]),
 }
 
 _lib = None

@@ -1039,3 +1039,137 @@ def raster_mesh(verts, faces, colors, cam, H, W, z_near, flags):
                                     _ptr(out['depth']), out['tri_id'].data_ptr(), _ptr(ws), ws.numel() * 4, _stream()),
                'hnrf_raster_mesh')
     return out
+
+
+# ------------------------------------------------------------------------------------------------------------ LPIPS
+LPIPS_CONVS = [(3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256), (256, 512), (512, 512),
+               (512, 512), (512, 512), (512, 512), (512, 512)]       # (Cin, Cout) of trunk layers 0..12 (hnrf.h)
+LPIPS_TAPS = [(1, 64), (3, 128), (6, 256), (9, 512), (12, 512)]      # (layer, channels) of the five taps
+
+
+def _aligned(nbytes, device):
+    """Uninitialised fp32 buffer of at least ``nbytes`` whose data pointer is 256-byte aligned."""
+    t = torch.empty(nbytes // 4 + 64, device=device)
+    off = (-t.data_ptr() % 256) // 4
+    return t[off:off + (nbytes + 3) // 4]
+
+
+def lpips_pack(weights, biases, lins):
+    """hnrf_lpips_pack: the 13 (Cout,Cin,3,3) weights, 13 biases and 5 head vectors -> the packed image."""
+    lib = _lib.load()
+    lins = [v.reshape(-1) for v in lins]
+    _chk(*weights, *biases, *lins)
+    assert len(weights) == 13 and len(biases) == 13 and len(lins) == 5
+    for w, b, (ci, co) in zip(weights, biases, LPIPS_CONVS):
+        assert tuple(w.shape) == (co, ci, 3, 3) and b.numel() == co, (tuple(w.shape), (co, ci, 3, 3))
+    for v, (_, c) in zip(lins, LPIPS_TAPS):
+        assert v.numel() == c
+    out = _aligned(lib.hnrf_lpips_packed_bytes(), weights[0].device)
+    _lib.check(lib.hnrf_lpips_pack(_ptr_array(weights), _ptr_array(biases), _ptr_array(lins), _ptr(out), _stream()),
+               'hnrf_lpips_pack')
+    return out
+
+
+def conv3x3_fwd(x, packed, layer, scale_input=False, out=None):
+    """hnrf_conv3x3_fwd: x (N,H,W,Cin) -> relu(conv + bias) (N,H,W,Cout) of trunk layer ``layer``."""
+    lib = _lib.load()
+    _chk(x, packed, out)
+    N, H, W, C = x.shape
+    assert C == LPIPS_CONVS[layer][0]
+    y = out if out is not None else torch.empty(N, H, W, LPIPS_CONVS[layer][1], device=x.device)
+    _lib.check(lib.hnrf_conv3x3_fwd(_ptr(x), _ptr(packed), int(layer), N, H, W, int(bool(scale_input)), _ptr(y),
+                                    _stream()), 'hnrf_conv3x3_fwd')
+    return y
+
+
+def conv3x3_bwd_data(dy, y_saved, packed, layer, unscale_output=False, out=None):
+    """hnrf_conv3x3_bwd_data: dy (N,H,W,Cout) [masked by y_saved > 0] -> dx (N,H,W,Cin)."""
+    lib = _lib.load()
+    _chk(dy, y_saved, packed, out)
+    N, H, W, C = dy.shape
+    assert C == LPIPS_CONVS[layer][1] and (y_saved is None or y_saved.shape == dy.shape)
+    dx = out if out is not None else torch.empty(N, H, W, LPIPS_CONVS[layer][0], device=dy.device)
+    _lib.check(lib.hnrf_conv3x3_bwd_data(_ptr(dy), _ptr(y_saved), _ptr(packed), int(layer), N, H, W,
+                                         int(bool(unscale_output)), _ptr(dx), _stream()), 'hnrf_conv3x3_bwd_data')
+    return dx
+
+
+def maxpool2_fwd(x, out=None):
+    """hnrf_maxpool2_fwd: (N,H,W,C) -> (N,H//2,W//2,C)."""
+    lib = _lib.load()
+    _chk(x, out)
+    N, H, W, C = x.shape
+    y = out if out is not None else torch.empty(N, H // 2, W // 2, C, device=x.device)
+    _lib.check(lib.hnrf_maxpool2_fwd(_ptr(x), N, H, W, C, _ptr(y), _stream()), 'hnrf_maxpool2_fwd')
+    return y
+
+
+def maxpool2_bwd(x, dy, out=None):
+    """hnrf_maxpool2_bwd: the gradient of maxpool2_fwd(x) with respect to x."""
+    lib = _lib.load()
+    _chk(x, dy, out)
+    N, H, W, C = x.shape
+    assert dy.shape == (N, H // 2, W // 2, C)
+    dx = out if out is not None else torch.empty_like(x)
+    _lib.check(lib.hnrf_maxpool2_bwd(_ptr(x), _ptr(dy), N, H, W, C, _ptr(dx), _stream()), 'hnrf_maxpool2_bwd')
+    return dx
+
+
+def lpips_head_fwd(f, w, out=None, accumulate=False, pix=None):
+    """hnrf_lpips_head_fwd: f (2N,P,C) (first the N maps of image 0, then those of image 1), w (C) -> (out (N), v (N))."""
+    lib = _lib.load()
+    _chk(f, w, out, pix)
+    B, P, C = f.shape
+    N = B // 2
+    assert B == 2 * N and w.numel() == C
+    pix = pix if pix is not None else torch.empty(max(N * P, 1), device=f.device)
+    out = out if out is not None else torch.empty(N, device=f.device)
+    val = torch.empty(N, device=f.device)
+    _lib.check(lib.hnrf_lpips_head_fwd(_ptr(f), _ptr(w), N, P, C, _ptr(pix), _ptr(out), int(bool(accumulate)),
+                                       _ptr(val), _stream()), 'hnrf_lpips_head_fwd')
+    return out, val
+
+
+def lpips_head_bwd(f, w, grad_out, out=None, accumulate=False):
+    """hnrf_lpips_head_bwd: d/d f[:N] of sum_n grad_out[n] v[n] -> (N,P,C), added to ``out`` when ``accumulate``."""
+    lib = _lib.load()
+    _chk(f, w, grad_out, out)
+    B, P, C = f.shape
+    N = B // 2
+    assert B == 2 * N and w.numel() == C and grad_out.numel() == N
+    dx = out if out is not None else torch.empty(N, P, C, device=f.device)
+    _lib.check(lib.hnrf_lpips_head_bwd(_ptr(f), _ptr(w), _ptr(grad_out), N, P, C, _ptr(dx), int(bool(accumulate)),
+                                       _stream()), 'hnrf_lpips_head_bwd')
+    return dx
+
+
+def lpips_workspace(N, H, W, want_grad, device):
+    need = _lib.load().hnrf_lpips_workspace_bytes(int(N), int(H), int(W), int(bool(want_grad)))
+    if need == 0:
+        raise _lib.HnrfError(f'lpips: N={N} images of {H}x{W} refused (H, W >= 16, 2*N*H*W*64 < 2^31)')
+    return _aligned(need, device)
+
+
+def lpips_fwd(img0, img1, packed, want_grad=False, workspace=None, want_layers=False):
+    """hnrf_lpips_fwd: img0, img1 (N,H,W,3) in [-1, 1] -> (value (N), per-tap values (5,N) or None, workspace)."""
+    lib = _lib.load()
+    _chk(img0, img1, packed, workspace)
+    N, H, W, C = img0.shape
+    assert C == 3 and img1.shape == img0.shape
+    ws = workspace if workspace is not None else lpips_workspace(N, H, W, want_grad, img0.device)
+    out = torch.empty(N, device=img0.device)
+    per = torch.empty(5, N, device=img0.device) if want_layers else None
+    _lib.check(lib.hnrf_lpips_fwd(_ptr(img0), _ptr(img1), _ptr(packed), N, H, W, int(bool(want_grad)), _ptr(ws),
+                                  ws.numel() * 4, _ptr(out), _ptr(per), _stream()), 'hnrf_lpips_fwd')
+    return out, per, ws
+
+
+def lpips_bwd(grad_out, packed, workspace, N, H, W):
+    """hnrf_lpips_bwd on the workspace of lpips_fwd(..., want_grad=True): -> d img0 (N,H,W,3)."""
+    lib = _lib.load()
+    _chk(grad_out, packed, workspace)
+    assert grad_out.numel() == N
+    d = torch.empty(N, H, W, 3, device=grad_out.device)
+    _lib.check(lib.hnrf_lpips_bwd(_ptr(grad_out), _ptr(packed), N, H, W, _ptr(workspace), workspace.numel() * 4,
+                                  _ptr(d), _stream()), 'hnrf_lpips_bwd')
+    return d

@@ -636,6 +636,63 @@ int hnrf_raster_mesh(const float* verts, int64_t V, const int* faces, int64_t F,
                      float* rgb, float* alpha, float* depth, int* tri_id, void* workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---- LPIPS ---- the perceptual loss and metric LPIPS(net='vgg', version='0.1', lpips=True, layers=[0..4]) in eval mode
+ * (third_parties/lpips/lpips.py:84-129, pretrained_networks.py:96-134, __init__.py:40-42; humannerf_amd/lpips.py).
+ * The arithmetic, stated once:
+ *  1. img0, img1: [N,H,W,3] fp32 in [-1, 1], NHWC; H, W >= 16 (HNRF_E_UNSUPPORTED below, before any launch).
+ *  2. Scaling layer: s = (x - shift) / scale, shift = (-.030, -.088, -.188), scale = (.458, .448, .450), applied to
+ *     in-range pixels as the first convolution loads them.  That convolution's zero padding is a zero of the SCALED
+ *     image, so the shift is not folded into its bias (that would be wrong on every border pixel).
+ *  3. Trunk: the 13 conv3x3 (pad 1, stride 1) + bias + ReLU layers of VGG16 features[0..29], layers 0..12 with
+ *     (Cin, Cout) = (3,64) (64,64) | (64,128) (128,128) | (128,256) (256,256) (256,256) | (256,512) (512,512) (512,512) |
+ *     (512,512) x 3; a 2x2 / stride-2 max-pool in floor mode (odd sizes drop the last row and column) at every `|`;
+ *     taps after layers 1, 3, 6, 9, 12 with 64, 128, 256, 512, 512 channels.  Every convolution is an fp32 fma chain
+ *     over k = tap * Cin + ci (v_mfma_f32_32x32x2_f32), in an order fixed by the layer and by H * W alone.
+ *  4. Head: per tap f = x / (sqrt(sum_c x^2 + 1e-10) + 1e-10) for both images, d = (f0 - f1)^2,
+ *     v_l = mean_{h,w} sum_c w_c d_c with the 1x1 head weights; the value is sum_l v_l, one per image pair.
+ *  5. Backward: with respect to img0 only, the trunk is frozen.  conv backward-data = the same convolution on the
+ *     second packed image (taps rotated 180 degrees, channel roles swapped), the incoming gradient masked by the saved
+ *     output y > 0 on load; pool backward routes to the first maximum in row-major scan order (torch's CPU kernel); the
+ *     chain through the scaling layer is / scale.
+ *  6. Determinism: no floating-point atomics, every reduction in a fixed order; results are bit-identical from run to
+ *     run, and pair n's value and gradient do not depend on the rest of the batch.
+ * Activations are NHWC fp32, pointers 16-byte aligned; `packed` and `workspace` 256-byte aligned.
+ *
+ * hnrf_lpips_pack: w[13] / b[13] / lin[5] are HOST arrays of device pointers to the (Cout,Cin,3,3) weights, (Cout)
+ *  biases and (C) head weights; `packed`: hnrf_lpips_packed_bytes() bytes.  Holds the forward image [Cout][9 Cin]
+ *  (layer 0: K = 27 padded to 32), the backward-data image [Cin][9 Cout] (layer 0: 3 rows padded to 32), biases, heads.
+ * hnrf_conv3x3_fwd: y [N,H,W,Cout] = relu(conv(x [N,H,W,Cin]) + bias) of trunk layer `layer`; scale_input (layer 0
+ *  only) applies the scaling layer on load.  Any H, W >= 1.
+ * hnrf_conv3x3_bwd_data: dx [N,H,W,Cin] from dy [N,H,W,Cout]; y_saved (nullable, dy's shape): dy counts only where
+ *  y_saved > 0; unscale_output (layer 0 only): dx / scale.
+ * hnrf_maxpool2_fwd / _bwd: x [N,H,W,C] -> y [N,H/2,W/2,C]; dx [N,H,W,C] from x and dy (every element written).  C % 4 == 0.
+ * hnrf_lpips_head_fwd: f [2N,P,C] (maps of the N first images, then of the N second ones), w [C], C in {64,128,256,512};
+ *  pix_ws [N P] scratch; out[n] = (accumulate ? out[n] : 0) + v[n]; layer_val (nullable) [N] = v.
+ * hnrf_lpips_head_bwd: dx [N,P,C] (+)= grad_out[n] dv[n] / dx0.
+ * hnrf_lpips_fwd: out [N]; per_layer (nullable) [5][N] the true per-tap values (the reference's retPerLayer list is
+ *  aliased: `val = res[0]; val += res[l]` makes res[0] the total).  Both image sets run as one batch of 2N through every
+ *  launch.  want_grad != 0 keeps the 13 activations in `workspace` for hnrf_lpips_bwd, which must get the same N, H, W
+ *  and the untouched workspace; want_grad == 0 needs two buffers only.  hnrf_lpips_workspace_bytes: 0 for sizes refused.
+ * hnrf_lpips_bwd: d_img0 [N,H,W,3] = sum_n grad_out[n] d value[n] / d img0.
+ * No allocation, no synchronisation; null pointers HNRF_E_ARG, sizes / layers not built HNRF_E_UNSUPPORTED. */
+size_t hnrf_lpips_packed_bytes(void);
+int hnrf_lpips_pack(const float* const* w, const float* const* b, const float* const* lin, void* packed, void* stream);
+int hnrf_conv3x3_fwd(const float* x, const void* packed, int layer, int N, int H, int W, int scale_input, float* y,
+                     void* stream);
+int hnrf_conv3x3_bwd_data(const float* dy, const float* y_saved, const void* packed, int layer, int N, int H, int W,
+                          int unscale_output, float* dx, void* stream);
+int hnrf_maxpool2_fwd(const float* x, int N, int H, int W, int C, float* y, void* stream);
+int hnrf_maxpool2_bwd(const float* x, const float* dy, int N, int H, int W, int C, float* dx, void* stream);
+int hnrf_lpips_head_fwd(const float* f, const float* w, int N, int64_t P, int C, float* pix_ws, float* out,
+                        int accumulate, float* layer_val, void* stream);
+int hnrf_lpips_head_bwd(const float* f, const float* w, const float* grad_out, int N, int64_t P, int C, float* dx,
+                        int accumulate, void* stream);
+size_t hnrf_lpips_workspace_bytes(int N, int H, int W, int want_grad);
+int hnrf_lpips_fwd(const float* img0, const float* img1, const void* packed, int N, int H, int W, int want_grad,
+                   void* workspace, size_t workspace_bytes, float* out, float* per_layer, void* stream);
+int hnrf_lpips_bwd(const float* grad_out, const void* packed, int N, int H, int W, void* workspace,
+                   size_t workspace_bytes, float* d_img0, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
