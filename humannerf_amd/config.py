@@ -178,6 +178,11 @@ _DEFAULTS = {
         # 512x512x128 frame: 91.5 ms with and without it -- the MLP kernels are power-limited, so whatever K1 draws
         # beside them they lose; off by default
         'overlap_warp': False,
+        # dense inference in 'f16x3' with cull_eps == 0: samples whose x_skel is so small that the split-f16 operands of
+        # the non-rigid MLP are those of x_skel = 0, and whose x_skel + offset rounds to the offset, share ONE evaluation
+        # of both MLPs per frame (the predicate: include/hnrf.h, hnrf_share_compact; DESIGN.md "Shared underflowing
+        # inputs").  Bit-identical outputs; False = the launches without it
+        'share_underflow': True,
         # multi-GPU training: 'volume' = average the 3.3 MB weight-volume gradient in front of the decoder backward (the
         # decoder's 254 MB of gradients never travel; needs the same priors on every rank, verified at run time),
         # 'full' = plain all-reduce of every gradient
@@ -226,8 +231,11 @@ cfg = _resolve_cfg()
 def check_amd_options(node=None):
     """Validate the options of the two baked approximations that go together (``node``: an ``amd`` mapping, default
     cfg.amd) and return (canonical, nonrigid, nonrigid_bake_resolution).  ValueError: a value that is not 'mlp' or
-    'baked', a resolution that is no integer in [8, 512], or nonrigid = 'baked' without canonical = 'baked'."""
+    'baked', a resolution that is no integer in [8, 512], nonrigid = 'baked' without canonical = 'baked', or a
+    share_underflow that is no bool."""
     get = amd_option if node is None else (lambda k: node.get(k, _DEFAULTS['amd'][k]))
+    if not isinstance(get('share_underflow'), bool):
+        raise ValueError('cfg.amd.share_underflow must be True or False, got %r' % (get('share_underflow'),))
     canonical, nonrigid, M = get('canonical'), get('nonrigid'), get('nonrigid_bake_resolution')
     if canonical not in ('mlp', 'baked'):
         raise ValueError("cfg.amd.canonical must be 'mlp' or 'baked', got %r" % (canonical,))

@@ -56,6 +56,13 @@ struct CnlSource {
 // no offset grid: xyz comes from K2 (nr_packed) or is x_skel
 constexpr BakedGrid kNoOffGrid{nullptr, 0, nullptr, nullptr};
 
+// Shared underflowing inputs (hnrf.h, hnrf_render_frame_shared_fwd): the frame's representative slot -- 16 floats,
+// x = +0 at [0..2], c_off at [4..6], c_xyz at [8..10], c_raw at [12..15] -- and the chunk's live count.  rep null = off.
+struct Share {
+    const float* rep;
+    int* count;
+};
+
 // K2 -> K3 -> K4 of one ray chunk whose K1 results are in `c`: the whole of hnrf_render_rays_fwd after K1, and the body
 // of every chunk of hnrf_render_frame_fwd.  cull_eps > 0: the MLPs run only on the compacted samples.  ev_start /
 // ev_stop (hipEvent_t, nullable) are recorded right before / after the canonical-MLP (or grid sampler) launch.
@@ -64,7 +71,7 @@ constexpr BakedGrid kNoOffGrid{nullptr, 0, nullptr, nullptr};
 int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w, const void* nr_packed,
                  const BakedGrid& off, const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t R,
                  int S, float* rgb, float* alpha, float* depth, const DiagRows& d, void* ev_start, void* ev_stop,
-                 hipStream_t st) {
+                 hipStream_t st, const Share& sh = Share{nullptr, nullptr}) {
     const size_t P = (size_t)R * (size_t)S;
     const bool cull = cull_eps > 0.f, diag = d.weights != nullptr;
     int rc;
@@ -72,6 +79,12 @@ int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w,
     const int* ci = cull ? c.idx : nullptr;
     const int* cc = cull ? c.count : nullptr;
     float* xyz = diag ? d.xyz : c.xyz;
+    if (sh.rep) {                                                 // (with K2 and K3 from the MLPs and cull_eps == 0 only)
+        if ((rc = share_compact(c.x_skel, sh.rep + 4, sh.rep + 8, sh.rep + 12, (int64_t)P, c.idx, sh.count, d.offsets,
+                                diag ? d.xyz : nullptr, c.raw, st))) return rc;
+        ci = c.idx;
+        cc = sh.count;
+    }
     const float* cnl_in = c.x_skel;
     if (off.grid) {
         if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
@@ -196,6 +209,10 @@ extern "C" int hnrf_render_rays_baked_nr_fwd(const float* rays_o, const float* r
 // L2-gather kernel without LDS) of chunk i+1 runs while the matrix-bound MLP kernels of chunk i own the CUs: K1 leaves
 // the critical path (3 % of a 512x512x128 frame).  Two workspaces alternate; the caller provides the events.
 extern "C" size_t hnrf_render_frame_workspace_bytes(int64_t chunk, int S) { return 2 * hnrf_render_workspace_bytes(chunk, S); }
+// + the representative slot behind the two chunk workspaces
+extern "C" size_t hnrf_render_frame_shared_workspace_bytes(int64_t chunk, int S) {
+    return hnrf_render_frame_workspace_bytes(chunk, S) + 256;
+}
 
 namespace {
 int render_frame(const char* who, const float* rays_o, const float* rays_d, const float* near, const float* far,
@@ -205,7 +222,7 @@ int render_frame(const char* who, const float* rays_o, const float* rays_d, cons
                  int S, int B, int G, int64_t chunk, void* workspace, size_t workspace_bytes, float* rgb, float* alpha, float* depth,
                  float* weights_on_rays, float* rgb_on_rays, float* cnl_xyz, float* cnl_rgb, float* cnl_weight,
                  float* xyz_on_rays, float* bmw, float* offsets, void* side_stream, void* const* events,
-                 void* const* mlp_events, void* stream) {
+                 void* const* mlp_events, void* stream, int* live_counts = nullptr) {
     HNRF_REQUIRE(workspace && rgb && alpha && depth, HNRF_E_ARG, "%s: null pointer", who);
     int src = check_source(who, cnl);
     if (src) return src;
@@ -217,6 +234,14 @@ int render_frame(const char* who, const float* rays_o, const float* rays_d, cons
     HNRF_REQUIRE(workspace_bytes >= 2 * ws_one, HNRF_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who,
                  workspace_bytes, 2 * ws_one);
     HNRF_REQUIRE(nr_packed == nullptr || hann_w != nullptr, HNRF_E_ARG, "%s: hann_w missing", who);
+    const bool share = live_counts != nullptr;
+    if (share) {
+        HNRF_REQUIRE((mode & HNRF_MLP_ARITH_MASK) == HNRF_MLP_F16X3 && nr_packed && cnl.packed && !cnl.grid && !off.grid &&
+                         cull_eps == 0.f, HNRF_E_UNSUPPORTED,
+                     "%s: shared inputs exist for HNRF_MLP_F16X3 with both MLPs and cull_eps == 0 only", who);
+        HNRF_REQUIRE(workspace_bytes >= 2 * ws_one + 256, HNRF_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who,
+                     workspace_bytes, 2 * ws_one + 256);
+    }
     const bool diag = weights_on_rays != nullptr;
     HNRF_REQUIRE(!diag || (rgb_on_rays && cnl_xyz && cnl_rgb && cnl_weight && xyz_on_rays && bmw && offsets), HNRF_E_ARG,
                  "%s: the eight diagnostic outputs go together", who);
@@ -245,6 +270,16 @@ int render_frame(const char* who, const float* rays_o, const float* rays_d, cons
     int rc = warp(0);
     if (rc) return rc;
     if (two) HNRF_HIP(hipEventRecord(ev_k1[0], sd));
+    float* rep = share ? (float*)((char*)workspace + 2 * ws_one) : nullptr;
+    if (share) {
+        // the representative x = (+0, +0, +0) through the chunks' kernel instances (guarded unless no chunk is: the
+        // guard sees the shared class through it), once per frame; no mlp_events around it
+        const int rmode = mode & (HNRF_MLP_ARITH_MASK | HNRF_MLP_NO_RANGE_GUARD);
+        HNRF_HIP(hipMemsetAsync(rep, 0, 64, st));
+        HNRF_HIP(hipMemsetAsync(live_counts, 0, (size_t)nchunk * sizeof(int), st));
+        if ((rc = hnrf_nonrigid_fwd_sparse(rep, hann_w, nr_packed, rmode, 1, nullptr, nullptr, rep + 8, rep + 4, st))) return rc;
+        if ((rc = hnrf_canonical_fwd_sparse(rep + 8, cnl.packed, rmode, 1, nullptr, nullptr, rep + 12, st))) return rc;
+    }
     for (int64_t i = 0; i < nchunk; ++i) {
         const int64_t r0 = i * chunk, R = (N - r0 < chunk) ? N - r0 : chunk;
         if (i + 1 < nchunk) {                                     // next chunk's K1: its workspace was last read by chunk i-1
@@ -263,7 +298,8 @@ int render_frame(const char* who, const float* rays_o, const float* rays_d, cons
                                 : DiagRows{};
         if ((rc = render_chunk(carve(i, R), rays_d + 3 * r0, hann_w, nr_packed, off, cnl, bgcolor, cmode, cull_eps, R, S,
                                rgb + 3 * r0, alpha + r0, depth + r0, d, mlp_events ? mlp_events[2 * i] : nullptr,
-                               mlp_events ? mlp_events[2 * i + 1] : nullptr, st))) return rc;
+                               mlp_events ? mlp_events[2 * i + 1] : nullptr, st,
+                               Share{rep, share ? live_counts + i : nullptr}))) return rc;
         if (two) HNRF_HIP(hipEventRecord(ev_done[i & 1], st));
         if (!two && i + 1 < nchunk && (rc = warp(i + 1))) return rc;   // single stream: plain sequence
     }
@@ -286,6 +322,24 @@ extern "C" int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, c
                         mode, cull_eps, N, S, B, G, chunk, workspace, workspace_bytes, rgb, alpha, depth, weights_on_rays,
                         rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays, bmw, offsets, side_stream, events,
                         mlp_events, stream);
+}
+
+extern "C" int hnrf_render_frame_shared_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                            const float* t_rand, const float* motion_Rs, const float* motion_Ts,
+                                            const float* vol, const float* bbox_min, const float* bbox_scale,
+                                            const float* hann_w, const void* nr_packed, const void* cnl_packed,
+                                            const float* bgcolor, int mode, float cull_eps, int64_t N, int S, int B, int G,
+                                            int64_t chunk, void* workspace, size_t workspace_bytes, float* rgb, float* alpha,
+                                            float* depth, float* weights_on_rays, float* rgb_on_rays, float* cnl_xyz,
+                                            float* cnl_rgb, float* cnl_weight, float* xyz_on_rays, float* bmw, float* offsets,
+                                            int* live_counts, void* side_stream, void* const* events,
+                                            void* const* mlp_events, void* stream) {
+    HNRF_REQUIRE(live_counts, HNRF_E_ARG, "hnrf_render_frame_shared_fwd: null live_counts");
+    return render_frame("hnrf_render_frame_shared_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol,
+                        bbox_min, bbox_scale, hann_w, nr_packed, kNoOffGrid, CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr},
+                        bgcolor, mode, cull_eps, N, S, B, G, chunk, workspace, workspace_bytes, rgb, alpha, depth,
+                        weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays, bmw, offsets, side_stream,
+                        events, mlp_events, stream, live_counts);
 }
 
 extern "C" int hnrf_render_frame_baked_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,

@@ -59,6 +59,11 @@ static inline RenderCarve render_carve(void* base, int64_t R, int S) {
     return c;
 }
 
+// hnrf_share_compact (hnrf_sample_warp.hip) without the argument checks and without zeroing *count: the frame entry
+// zeroes its per-chunk counts once.
+int share_compact(const float* x_skel, const float* c_off, const float* c_xyz, const float* c_raw, int64_t P, int* idx,
+                  int* count, float* offsets, float* xyz, float* raw, hipStream_t st);
+
 // Opt a kernel into > 64 KiB of dynamic LDS, once per device of this process (`done`: one bit per device id;
 // the attribute is per device, and a process may drive more than one).
 static inline int reserve_lds(const void* fn, int bytes, unsigned long long& done, const char* what) {

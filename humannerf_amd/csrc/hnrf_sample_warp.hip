@@ -190,7 +190,75 @@ __global__ __launch_bounds__(256) void compact_kernel(const float* __restrict__ 
     if (keep) idx[off] = (int)p;
 }
 
+// Samples whose K2 / K3 inputs underflow to those of x_skel = (+0, +0, +0) (the predicate: hnrf.h, hnrf_share_compact):
+// such a sample's offsets / xyz / raw are the representative's c_off / c_xyz / c_raw bit for bit, so they are written
+// here and the MLPs run on the rest, idx[0..count) in compact_kernel's order.  *count must be 0 at launch.
+// offsets / xyz nullable (the lean form reads neither).
+__global__ __launch_bounds__(256) void share_compact_kernel(const float* __restrict__ x_skel, const float* __restrict__ c_off,
+                                                            const float* __restrict__ c_xyz, const float* __restrict__ c_raw,
+                                                            int64_t P, int* __restrict__ idx, int* __restrict__ count,
+                                                            float* __restrict__ offsets, float* __restrict__ xyz,
+                                                            float4* __restrict__ raw) {
+#pragma clang fp contract(off)
+    __shared__ int wave_tot[4];
+    __shared__ int block_base;
+    const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    bool shared = p < P;
+    if (shared) {
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const float x = x_skel[p * 3 + a];
+            // (a NaN fails the first comparison: always live); the sum is K2's own `x + offset`, one rounded fp32 add
+            shared &= fabsf(x) <= HNRF_SHARE_T && __float_as_uint(x + c_off[a]) == __float_as_uint(c_xyz[a]);
+        }
+    }
+    const bool keep = p < P && !shared;
+    const unsigned long long bal = __ballot(keep);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int before = __popcll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_tot[wave] = __popcll(bal);
+    __syncthreads();
+    if (threadIdx.x == 0) block_base = atomicAdd(count, wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3]);
+    __syncthreads();
+    int off = block_base + before;
+    for (int w = 0; w < wave; ++w) off += wave_tot[w];
+    if (keep) idx[off] = (int)p;
+    if (shared) {
+        raw[p] = make_float4(c_raw[0], c_raw[1], c_raw[2], c_raw[3]);
+        if (offsets) {
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                offsets[p * 3 + a] = c_off[a];
+                xyz[p * 3 + a] = c_xyz[a];
+            }
+        }
+    }
+}
+
+int share_compact(const float* x_skel, const float* c_off, const float* c_xyz, const float* c_raw, int64_t P, int* idx,
+                  int* count, float* offsets, float* xyz, float* raw, hipStream_t st) {
+    if (P == 0) return HNRF_OK;
+    hipLaunchKernelGGL(share_compact_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, x_skel, c_off, c_xyz, c_raw,
+                       P, idx, count, offsets, xyz, (float4*)raw);
+    return check_launch("hnrf_share_compact");
+}
+
 }  // namespace hnrf
+
+extern "C" int hnrf_share_compact(const float* x_skel, const float* c_off, const float* c_xyz, const float* c_raw,
+                                  int64_t P, int* idx, int* count, float* offsets, float* xyz, float* raw, void* stream) {
+    using namespace hnrf;
+    HNRF_REQUIRE(x_skel && c_off && c_xyz && c_raw && idx && count && raw, HNRF_E_ARG, "hnrf_share_compact: null pointer");
+    HNRF_REQUIRE((offsets == nullptr) == (xyz == nullptr), HNRF_E_ARG, "hnrf_share_compact: offsets and xyz go together");
+    HNRF_REQUIRE(P >= 0 && P < 2147483647LL, HNRF_E_ARG, "hnrf_share_compact: bad P");
+    HNRF_REQUIRE(((uintptr_t)raw & 15) == 0, HNRF_E_ARG, "hnrf_share_compact: raw must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (hipMemsetAsync(count, 0, sizeof(int), st) != hipSuccess) {
+        set_error("hnrf_share_compact: memset failed");
+        return HNRF_E_LAUNCH;
+    }
+    return share_compact(x_skel, c_off, c_xyz, c_raw, P, idx, count, offsets, xyz, raw, st);
+}
 
 extern "C" int hnrf_compact_samples(const float* fg_mask, float eps, int64_t P, int* idx, int* count, void* stream) {
     using namespace hnrf;

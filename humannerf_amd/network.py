@@ -525,6 +525,8 @@ class Network(nn.Module):
         self._nr_bake_ws = None
         self.nonrigid_bake_count = 0
         self._workspace = None
+        # cfg.amd.share_underflow: (live counts per chunk on the device, samples) of the last frame, None = path off
+        self._share_last = None
         # set by train.Trainer when world_size > 1: dist.GradientSync whose volume_hook averages the weight-volume
         # gradient over the ranks in front of the decoder backward
         self.grad_sync = None
@@ -762,12 +764,19 @@ class Network(nn.Module):
             # optionally K1 of the next chunk on a side stream under the MLP kernels of the current one
             # (cfg.amd.overlap_warp).  With diagnostics on, term_eps is ignored: early termination has no 11-output form
             gmode, guarded = self._guard_plan(mode, -(-N // int(cfg.chunk)))
+            cull_eps = 0.0 if diag else float(amd_option('cull_eps', 0.0))
+            # one evaluation for the samples whose inputs underflow to those of x_skel = 0 (hnrf.h, hnrf_share_compact;
+            # its threshold assumes Hann weights <= 1: checked on the host copy, nothing waits for the device)
+            share = (bool(amd_option('share_underflow', True)) and mode == 'f16x3' and nr_packed is not None
+                     and baked is None and cull_eps == 0.0 and float(hann_host.max()) <= 1.0)
+            share_log = [] if share else None
             out, self._workspace = ops.render_frame(
                 rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w, nr_packed,
                 cnl_packed, bg, S, int(cfg.chunk), gmode, diagnostics=diag,
-                cull_eps=0.0 if diag else float(amd_option('cull_eps', 0.0)), workspace=self._workspace,
+                cull_eps=cull_eps, workspace=self._workspace,
                 overlap=bool(amd_option('overlap_warp', False)), mlp_event_log=self.mlp_event_log, baked=baked,
-                baked_nr=baked_nr)
+                baked_nr=baked_nr, share_log=share_log)
+            self._share_last = share_log[0] if share else None
             if mode == 'f16x3' and guarded != set():
                 self._watch_f16_range(cnl_packed, nr_packed if baked_nr is None else nr_baked_on, mode)
         else:
@@ -776,6 +785,7 @@ class Network(nn.Module):
             chunk = int(cfg.chunk)
             chunks = []
             guarded = None
+            self._share_last = None
             if not train_path:
                 _, guarded = self._guard_plan(mode, -(-N // chunk))
                 need = ops.render_term_workspace_bytes(min(chunk, N), S) // 4 + 64
@@ -799,6 +809,16 @@ class Network(nn.Module):
                 self._watch_f16_range(cnl_packed, nr_packed, mode)
         lead = list(rays_shape[:-1])
         return {k: v.reshape(lead + list(v.shape[1:])) for k, v in out.items()}
+
+    def shared_sample_share(self):
+        """Share of the last frame's samples that took the shared evaluation of cfg.amd.share_underflow instead of a pass
+        through the MLPs (0.0 when the path was off for that frame).  Waits for the device: for profiling tools and
+        tests, not for render loops."""
+        if self._share_last is None:
+            return 0.0
+        live, total = self._share_last
+        torch.cuda.synchronize(live.device)
+        return 1.0 - float(live.sum().item()) / float(max(total, 1))
 
     def _nonrigid_of_zero(self):
         """NonRigidMotionMLP.forward (mlp_offset.py:74-114) on an all-zero input row: (3,), differentiable."""

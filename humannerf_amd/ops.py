@@ -270,7 +270,7 @@ def _frame_streams(device):
 
 def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w, nr_packed,
                  cnl_packed, bgcolor, n_samples, chunk, mode='f16x3', diagnostics=True, cull_eps=0.0, workspace=None,
-                 overlap=True, mlp_event_log=None, baked=None, baked_nr=None):
+                 overlap=True, mlp_event_log=None, baked=None, baked_nr=None, share_log=None):
     """The whole frame in one call (hnrf_render_frame_fwd): all ray chunks through K1..K4, results in whole-frame tensors;
     K1 of the next chunk on a side stream while the MLP kernels of the current one run.  Returns (dict of outputs,
     workspace).  ``mlp_event_log``: list that receives one (start, stop) torch.cuda.Event pair per chunk.  ``baked``:
@@ -278,15 +278,21 @@ def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, b
     the event pairs around its launches) and ``cnl_packed`` is not used (may be None).  ``baked_nr``: (off_grid, bbox_min,
     bbox_max) of bake_nonrigid, with ``baked`` only -- xyz and raw then come from the fused sampler of the two grids
     (hnrf_render_frame_baked_nr_fwd; xyz_on_rays / offsets are the interpolated values) and ``hann_w`` / ``nr_packed``
-    are not used (may be None)."""
+    are not used (may be None).  ``share_log``: a list selects hnrf_render_frame_shared_fwd (f16x3, both MLPs, cull_eps == 0;
+    the caller has checked that every Hann weight is <= 1) and receives (live_counts, samples): the device int32 tensor
+    of the samples per chunk that went through the MLPs, and the frame's sample count."""
     lib = _lib.load()
     _chk_baked_nr(baked, baked_nr)
     N, S, B, G = rays_o.shape[0], int(n_samples), motion_Rs.shape[0], vol.shape[-1]
     dev = rays_o.device
     chunk = int(chunk)
+    share = share_log is not None
+    if share and (baked is not None or baked_nr is not None):
+        raise _lib.HnrfError('render_frame: shared inputs exist with both MLPs only, not with a baked grid')
+    ws_bytes = lib.hnrf_render_frame_shared_workspace_bytes if share else lib.hnrf_render_frame_workspace_bytes
     args, workspace = _render_args((rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
                                     hann_w, nr_packed, cnl_packed, bgcolor), workspace,
-                                   lib.hnrf_render_frame_workspace_bytes(min(chunk, max(N, 1)), S))
+                                   ws_bytes(min(chunk, max(N, 1)), S))
     shp = {'rgb': (3,), 'alpha': (), 'depth': ()}
     if diagnostics:
         shp.update(weights_on_rays=(S,), rgb_on_rays=(S, 3), cnl_xyz=(3,), cnl_rgb=(3,), cnl_weight=(), xyz_on_rays=(S, 3),
@@ -312,12 +318,18 @@ def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, b
     if baked_nr is not None:
         fn, name = lib.hnrf_render_frame_baked_nr_fwd, 'hnrf_render_frame_baked_nr_fwd'
         ptrs[10:12] = _baked_args(baked_nr, dev)
+    live = ()
+    if share:
+        fn, name = lib.hnrf_render_frame_shared_fwd, 'hnrf_render_frame_shared_fwd'
+        live = (torch.empty(max(1, -(-N // chunk)), dtype=torch.int32, device=dev),)
     _lib.check(fn(
         *ptrs, _mode_arg(mode), float(cull_eps), N, S, B, G, chunk, _ptr(workspace),
         workspace.numel() * workspace.element_size(), g('rgb'), g('alpha'), g('depth'),
         g('weights_on_rays'), g('rgb_on_rays'), g('cnl_xyz'), g('cnl_rgb'), g('cnl_weight'), g('xyz_on_rays'),
-        g('backward_motion_weights'), g('offsets'), side.cuda_stream if side is not None else None, ev_arr, mlp_arr,
-        _stream()), name)
+        g('backward_motion_weights'), g('offsets'), *map(_ptr, live), side.cuda_stream if side is not None else None,
+        ev_arr, mlp_arr, _stream()), name)
+    if share:
+        share_log.append((live[0], N * S))
     if side is not None:
         # the side stream read the inputs and wrote backward_motion_weights / the workspace: keep the allocator from
         # handing those blocks out again before it is done (everything it did is also ordered on the main stream)

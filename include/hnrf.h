@@ -237,6 +237,42 @@ int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, const float*
                           float* cnl_weight, float* xyz_on_rays, float* bmw, float* offsets, void* side_stream,
                           void* const* events, void* const* mlp_events, void* stream);
 
+/* ---- samples whose MLP inputs underflow to those of x_skel = 0 (HNRF_MLP_F16X3 only) --------
+ * Far from every bone K1 leaves x_skel ~ 1e-16: tiny, rarely zero.  K2's split-f16 B operand cannot tell such a value
+ * from zero -- its positional encoding is hann_k sin(2^k x), at most 32 |x| while every hann_k <= 1, whose f16 high and
+ * low parts are both +-0 below 2^-25, and its cosines are exactly 1 -- so the offset is the per-frame constant
+ * c_off = K2(+0, +0, +0); where x_skel + c_off also rounds to c_xyz = +0 + c_off, K3 sees the representative's bits too
+ * and raw is the constant c_raw.  THE PREDICATE: a sample is SHARED when for a = 0..2
+ *   (a) |x_skel[a]| <= HNRF_SHARE_T, and
+ *   (b) the bits of x_skel[a] + c_off[a] (one rounded fp32 add, K2's own) equal the bits of c_xyz[a];
+ * a NaN or infinite coordinate fails (a).  HNRF_SHARE_T = 2^-31 leaves a factor 2 under the f16 tie at 2^-25 for the
+ * top octave and holds only while every Hann weight is <= 1 -- the CALLER checks that before it uses these entries.
+ *
+ * hnrf_share_compact: idx[0 .. *count) = the samples p < P that are NOT shared (order as hnrf_compact_samples; count is
+ *  zeroed and written on the device, idx[*count .. P) keeps what it held), and for every shared p: raw[p] = c_raw [4],
+ *  offsets[p] = c_off [3], xyz[p] = c_xyz [3] (offsets and xyz both NULL = not written); the rows of live samples are
+ *  not touched.  c_off / c_xyz / c_raw: device pointers, what K2 and K3 wrote for x_skel = (+0, +0, +0).
+ *  raw 16-byte aligned, P < 2^31 - 1; P == 0 sets *count = 0 without a launch. */
+#define HNRF_SHARE_T 4.656612873077392578125e-10f
+int hnrf_share_compact(const float* x_skel, const float* c_off, const float* c_xyz, const float* c_raw, int64_t P,
+                       int* idx, int* count, float* offsets, float* xyz, float* raw, void* stream);
+/* hnrf_render_frame_fwd with every chunk as K1 -> hnrf_share_compact -> K2 and K3 on the live list -> K4, the
+ * representative evaluated once per frame in front of chunk 0 by the same kernel instances (guarded unless
+ * HNRF_MLP_NO_RANGE_GUARD; no mlp_events around it, the pairs stay one per chunk, around K3 on the live list).  Every
+ * output equals hnrf_render_frame_fwd's bit for bit.  live_counts [ceil(N / chunk)] (device, required): receives the
+ * number of samples of each chunk that went through the MLPs.  HNRF_E_UNSUPPORTED unless mode is HNRF_MLP_F16X3,
+ * nr_packed is given and cull_eps == 0.  workspace: hnrf_render_frame_shared_workspace_bytes(chunk, S). */
+size_t hnrf_render_frame_shared_workspace_bytes(int64_t chunk, int S);
+int hnrf_render_frame_shared_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                 const float* t_rand, const float* motion_Rs, const float* motion_Ts, const float* vol,
+                                 const float* bbox_min, const float* bbox_scale, const float* hann_w, const void* nr_packed,
+                                 const void* cnl_packed, const float* bgcolor, int mode, float cull_eps, int64_t N, int S,
+                                 int B, int G, int64_t chunk, void* workspace, size_t workspace_bytes, float* rgb,
+                                 float* alpha, float* depth, float* weights_on_rays, float* rgb_on_rays, float* cnl_xyz,
+                                 float* cnl_rgb, float* cnl_weight, float* xyz_on_rays, float* bmw, float* offsets,
+                                 int* live_counts, void* side_stream, void* const* events, void* const* mlp_events,
+                                 void* stream);
+
 /* =============================== training (backward) ===============================
  * The reference trains through torch.autograd over the ops above (trainer.py:206-220).
  * Here: the forward runs the *_fwd_train variants (either arithmetic mode) which also save the
