@@ -99,6 +99,8 @@ SIGNATURES = {
     'hnrf_lpips_workspace_bytes': (_sz, [_int, _int, _int, _int]),
     'hnrf_lpips_fwd': (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _vp, _sz, _vp, _vp, _vp]),
     'hnrf_lpips_bwd': (_int, [_vp, _vp, _int, _int, _int, _vp, _sz, _vp, _vp]),
+    'hnrf_image_metrics_workspace_bytes': (_sz, [_int, _int, _int]),
+    'hnrf_image_metrics': (_int, [_vp, _vp, _vp, _int, _int, _int, ctypes.c_double, _vp, _sz, _vp, _vp]),
 }
 
 _lib = None

@@ -190,6 +190,11 @@ _DEFAULTS = {
         # run the collectives of the training step even when world_size == 1 (identities over a one-rank group):
         # exercises the RCCL code path on a single-GPU box (tests/test_gpu_dist.py)
         'ddp_single_rank_collectives': False,
+        # run.run_movement: where the per-image PSNR / SSIM / LPIPS are computed.  'host' = MetricsWriter.append on the
+        # images that arrived on the host (the reference's route: scipy / torch on the thread that drives the GPU),
+        # 'device' = in the frame's own launches on the 8-bit device images (render_frames(metrics=...): exact integer
+        # moments, hnrf_image_metrics), the values travelling behind the images; needs a GPU
+        'metrics': 'host',
         # gc.freeze() at the start of the training / render loops (config.quiet_gc)
         'freeze_gc': True,
     },
@@ -232,10 +237,12 @@ def check_amd_options(node=None):
     """Validate the options of the two baked approximations that go together (``node``: an ``amd`` mapping, default
     cfg.amd) and return (canonical, nonrigid, nonrigid_bake_resolution).  ValueError: a value that is not 'mlp' or
     'baked', a resolution that is no integer in [8, 512], nonrigid = 'baked' without canonical = 'baked', or a
-    share_underflow that is no bool."""
+    share_underflow that is no bool, or a metrics route that is not 'host' or 'device'."""
     get = amd_option if node is None else (lambda k: node.get(k, _DEFAULTS['amd'][k]))
     if not isinstance(get('share_underflow'), bool):
         raise ValueError('cfg.amd.share_underflow must be True or False, got %r' % (get('share_underflow'),))
+    if get('metrics') not in ('host', 'device'):
+        raise ValueError("cfg.amd.metrics must be 'host' or 'device', got %r" % (get('metrics'),))
     canonical, nonrigid, M = get('canonical'), get('nonrigid'), get('nonrigid_bake_resolution')
     if canonical not in ('mlp', 'baked'):
         raise ValueError("cfg.amd.canonical must be 'mlp' or 'baked', got %r" % (canonical,))

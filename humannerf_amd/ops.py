@@ -1185,3 +1185,54 @@ def lpips_bwd(grad_out, packed, workspace, N, H, W):
     _lib.check(lib.hnrf_lpips_bwd(_ptr(grad_out), _ptr(packed), N, H, W, _ptr(workspace), workspace.numel() * 4,
                                   _ptr(d), _stream()), 'hnrf_lpips_bwd')
     return d
+
+
+# ---------------------------------------------------------------------------------------------------- image metrics
+_metrics_ws = {}                      # (n, H, W, device) -> workspace of the last call of that shape
+
+
+def image_metrics_workspace(n, H, W, device):
+    """Workspace of hnrf_image_metrics, kept per shape (a frame loop compares one image size); calls that share it
+    must be ordered on one stream."""
+    key = (int(n), int(H), int(W), torch.device(device))
+    ws = _metrics_ws.get(key)
+    if ws is None:
+        need = _lib.load().hnrf_image_metrics_workspace_bytes(int(n), int(H), int(W))
+        if need == 0:
+            raise _lib.HnrfError(f'image_metrics: {n} images of {H}x{W} out of range')
+        if len(_metrics_ws) >= 8:
+            _metrics_ws.clear()
+        ws = _metrics_ws[key] = _aligned(need, device)
+    return ws
+
+
+def image_metrics(pred8, target8, mask=None, data_range=1.0):
+    """hnrf_image_metrics: PSNR and SSIM (render.psnr / render.ssim; render.metrics_u8 is the numpy twin) of uint8
+    images on the device, (H, W, 3) or (N, H, W, 3); ``mask`` (H, W), (H, W, 1) or (N, H, W[, 1]) uint8 / bool, non-zero
+    = inside.  Returns a float64 device tensor (n, 2): psnr, ssim per image.  No synchronisation; anything that is not
+    uint8 on the GPU raises."""
+    lib = _lib.load()
+    for t, what in ((pred8, 'pred8'), (target8, 'target8')):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8):
+            raise _lib.HnrfError('image_metrics: %s must be a uint8 tensor on the GPU (float images go through '
+                                 'MetricsWriter.append)' % what)
+    if pred8.dim() == 3:
+        pred8, target8 = pred8[None], target8[None]
+        mask = None if mask is None else mask[None]
+    if pred8.dim() != 4 or pred8.shape[3] != 3 or target8.shape != pred8.shape:
+        raise _lib.HnrfError('image_metrics: images must be (H, W, 3) or (N, H, W, 3) of one shape, got %s and %s'
+                             % (tuple(pred8.shape), tuple(target8.shape)))
+    n, H, W, _ = pred8.shape
+    pred8, target8 = pred8.contiguous(), target8.contiguous()
+    if mask is not None:
+        if not (torch.is_tensor(mask) and mask.is_cuda and mask.dtype in (torch.uint8, torch.bool)):
+            raise _lib.HnrfError('image_metrics: mask must be a uint8 or bool tensor on the GPU')
+        if mask.numel() != n * H * W:
+            raise _lib.HnrfError('image_metrics: mask %s does not fit %d images of %dx%d' % (tuple(mask.shape), n, H, W))
+        mask = mask.reshape(n, H, W).contiguous().view(torch.uint8)
+    with torch.cuda.device(pred8.device):
+        ws = image_metrics_workspace(n, H, W, pred8.device)
+        out = torch.empty(n, 2, dtype=torch.float64, device=pred8.device)
+        _lib.check(lib.hnrf_image_metrics(pred8.data_ptr(), target8.data_ptr(), _ptr(mask), n, H, W, float(data_range),
+                                          ws.data_ptr(), ws.numel() * 4, out.data_ptr(), _stream()), 'hnrf_image_metrics')
+    return out

@@ -12,6 +12,9 @@ an image to be written.
   psnr, MetricsWriter                                         metrics_util.py:9-88                (same fixture)
   ssim                                                        metrics_util.py:90-106 calls skimage -- not importable
                                                               here: the published algorithm, parity unpinned
+  metrics_u8                                                  psnr / ssim of 8-bit images from exact integer moments: the
+                                                              numpy twin of ops.image_metrics (csrc/hnrf_metrics.hip), which
+                                                              render_frames(metrics=...) runs on the device
   ImageWriter                                                 image_util.py:55-128 (PNG via PIL; the MP4 of finalize()
                                                               needs imageio, which is absent: frames + .npy instead)
 """
@@ -132,6 +135,59 @@ def ssim(pred, target, mask=None, data_range=1.0):
     return float(np.mean(vals))
 
 
+def metrics_u8(pred, target, mask=None, data_range=1.0):
+    """PSNR and SSIM of uint8 images, (H, W, 3) or (N, H, W, 3), as ``psnr`` / ``ssim`` above define them for the pixels
+    k / 255 -- the numpy twin of the device kernel (ops.image_metrics, csrc/hnrf_metrics.hip) and the CPU statement
+    its tests compare against.  ``mask``: (H, W[, 1]) or (N, H, W[, 1]), non-zero = inside.  Returns float64 (n, 2):
+    psnr, ssim per image.
+
+    The inputs are 8-bit, so everything up to the closed form is exact integer arithmetic: SSE is an integer sum,
+    psnr = -10 log10(SSE / (255^2 count)), count = 3 H W or 3 nnz(mask); the window moments are integer 7x7 sums Sx, Sy,
+    Sxx, Syy, Sxy, with ux = Sx / (49 * 255), uxx = Sxx / (49 * 255^2) (one rounding each) entering ``ssim``'s fp64
+    expression in its operand order.  A window's value has the same bits here and in the kernel; only the order of the
+    sum over the windows differs (numpy adds pairwise).  Equal images give psnr +inf; an empty mask gives (NaN, NaN)
+    and a crop narrower than the window gives ssim NaN (``ssim`` returns NaN for the narrow crop and raises for the
+    empty mask)."""
+    a, b = np.asarray(pred), np.asarray(target)
+    if a.dtype != np.uint8 or b.dtype != np.uint8 or a.shape != b.shape or a.ndim not in (3, 4) or a.shape[-1] != 3:
+        raise ValueError('metrics_u8 takes two uint8 images (H, W, 3) or (N, H, W, 3) of one shape')
+    if a.ndim == 3:
+        a, b = a[None], b[None]
+    n, H, W, _ = a.shape
+    m = None if mask is None else (np.asarray(mask).reshape(n, H, W) != 0)
+    win = 7
+    c1, c2 = (0.01 * data_range) * (0.01 * data_range), (0.03 * data_range) * (0.03 * data_range)
+    cov_norm = win * win / (win * win - 1.0)
+
+    def window_sums(v):                                                  # (h, w) int64 -> (h - 6, w - 6) exact 7x7 sums
+        c = np.zeros((v.shape[0] + 1, v.shape[1] + 1), dtype=np.int64)
+        c[1:, 1:] = v.cumsum(0).cumsum(1)
+        return c[win:, win:] - c[:-win, win:] - c[win:, :-win] + c[:-win, :-win]
+
+    out = np.empty((n, 2), dtype=np.float64)
+    for i in range(n):
+        x, y = a[i].astype(np.int64), b[i].astype(np.int64)
+        inside = np.ones((H, W), dtype=bool) if m is None else m[i]
+        sse, count = int((((x - y) ** 2).sum(-1))[inside].sum()), 3 * int(inside.sum())
+        with np.errstate(divide='ignore', invalid='ignore'):
+            out[i, 0] = -10.0 * np.log10(np.float64(sse) / (65025.0 * np.float64(count)))
+        ys, xs = np.where(inside)
+        if ys.size == 0 or ys.max() - ys.min() + 1 < win or xs.max() - xs.min() + 1 < win:
+            out[i, 1] = np.nan
+            continue
+        x, y = x[ys.min():ys.max() + 1, xs.min():xs.max() + 1], y[ys.min():ys.max() + 1, xs.min():xs.max() + 1]
+        vals = []
+        for ch in range(3):
+            p, q = x[..., ch], y[..., ch]
+            ux, uy = window_sums(p) / 12495.0, window_sums(q) / 12495.0
+            uxx, uyy, uxy = window_sums(p * p) / 3186225.0, window_sums(q * q) / 3186225.0, window_sums(p * q) / 3186225.0
+            vx, vy, vxy = cov_norm * (uxx - ux * ux), cov_norm * (uyy - uy * uy), cov_norm * (uxy - ux * uy)
+            s = ((2 * ux * uy + c1) * (2 * vxy + c2)) / ((ux * ux + uy * uy + c1) * (vx + vy + c2))
+            vals.append(s.mean())
+        out[i, 1] = ((vals[0] + vals[1]) + vals[2]) / 3.0
+    return out
+
+
 class MetricsWriter:
     """Per-image and average metric text files in the reference's format (metrics_util.py:9-60): ``<exp>-metrics.
     perimg.txt`` gets ``name: psnr-26.2530 ssim-0.9123 `` per image, ``<exp>-metrics.average.txt`` gets
@@ -168,6 +224,20 @@ class MetricsWriter:
         self.name2metrics[name] = {}
         for k in self.metrics:
             v = self.funcs[k](pred, target, mask)
+            self.name2metrics[name][k] = v
+            self.sums[k] += v
+            self.per_img_f.writelines('{}-{:.4f} '.format(k, v))
+        self.per_img_f.writelines('\n')
+
+    def append_values(self, name, values):
+        """The bookkeeping and the line of ``append`` for metric values computed elsewhere (``values``: {metric: float}
+        holding every entry of ``self.metrics``; render_frames(on_metrics=...) with cfg.amd.metrics = 'device')."""
+        self.N += 1
+        assert name not in self.name2metrics, name
+        self.per_img_f.writelines('%s: ' % name)
+        self.name2metrics[name] = {}
+        for k in self.metrics:
+            v = float(values[k])
             self.name2metrics[name][k] = v
             self.sums[k] += v
             self.per_img_f.writelines('{}-{:.4f} '.format(k, v))
@@ -273,18 +343,19 @@ class ImageWriter:
 
 # --------------------------------------------------------------------------------------------- frame loop
 class _PinnedPool:
-    """A few page-locked uint8 staging buffers per image shape: device -> host copies into pageable memory are
-    staged and synchronous inside the runtime; into pinned memory they are real asynchronous DMA."""
+    """A few page-locked staging buffers per shape and dtype (uint8 images; the float64 metric vector of a frame):
+    device -> host copies into pageable memory are staged and synchronous inside the runtime; into pinned memory they
+    are real asynchronous DMA."""
 
     def __init__(self):
         self.free = defaultdict(list)
 
-    def take(self, shape):
-        lst = self.free[tuple(shape)]
-        return lst.pop() if lst else torch.empty(tuple(shape), dtype=torch.uint8, pin_memory=True)
+    def take(self, shape, dtype=torch.uint8):
+        lst = self.free[(tuple(shape), dtype)]
+        return lst.pop() if lst else torch.empty(tuple(shape), dtype=dtype, pin_memory=True)
 
     def give(self, t):
-        self.free[tuple(t.shape)].append(t)
+        self.free[(tuple(t.shape), t.dtype)].append(t)
 
 
 _FRAME_KEYS = ('dst_Rs', 'dst_Ts', 'cnl_gtfms', 'dst_posevec', 'cnl_bbox_min_xyz', 'cnl_bbox_scale_xyz', 'bgcolor')
@@ -446,7 +517,11 @@ class FramePrefetcher:
                 self._slots.release()
 
 
-def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, show_truth=False, prefetch=None):
+METRIC_NAMES = ('psnr', 'ssim', 'lpips')
+
+
+def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, show_truth=False, prefetch=None,
+                  metrics=None, lpips_fn=None, on_metrics=None):
     """Render ``frames`` (sequence of per-frame input dicts, numpy or tensors) frame-sharded.
 
     Returns {frame_idx: uint8 rgb image on the host} for this rank's frames.  ``on_image(idx, rgb8, alpha8[,
@@ -463,8 +538,29 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
     stream); finished images leave through pinned buffers on a copy stream and are handed to ``on_image`` one frame
     late at the earliest -- after the next frame's forward has looked at this frame's f16-range verdict
     (Network.check_f16_range), so that with ``cfg.amd.on_f16_range = 'f32'`` a frame rendered out of range is
-    rendered again with the exact kernels before anybody sees it."""
+    rendered again with the exact kernels before anybody sees it.
+
+    ``metrics`` (a list out of 'psnr', 'ssim', 'lpips'; GPU only, needs ``show_truth``): every frame that has its truth
+    gets the metrics of its 8-bit render against its 8-bit truth ON THE DEVICE, as part of the frame's launches --
+    ops.image_metrics (exact integer moments, render.metrics_u8 is its numpy statement) and, for 'lpips',
+    1000 * ``lpips_fn(rgb8 / 255, truth8 / 255)`` on the device tensors (LpipsVGG.metric; the host's float32 pixels).  The values travel as one
+    float64 vector through a pinned buffer behind the frame's images, under the same event, and arrive as
+    ``on_metrics(idx, {name: float})`` right after that frame's ``on_image``.  Nothing of it synchronises, and a frame
+    rendered again after an f16-range hit gets its metrics again.  The pixels are always divided by 255
+    (MetricsWriter.normalize leaves an image whose maximum is <= 2 as it is)."""
     device = device or next(network.parameters()).device
+    metrics = list(metrics) if metrics else None
+    if metrics is not None:
+        bad = [k for k in metrics if k not in METRIC_NAMES]
+        if bad:
+            raise ValueError('render_frames: unknown metrics %r (out of %r)' % (bad, METRIC_NAMES))
+        if device.type != 'cuda':
+            raise ValueError('render_frames: device metrics need a GPU (got device %s); on the host use MetricsWriter.append'
+                             % device)
+        if 'lpips' in metrics and lpips_fn is None:
+            raise ValueError('metric lpips needs an lpips_fn (LPIPS-VGG weights are not obtainable offline)')
+        from . import ops
+        unit = (torch.arange(256, dtype=torch.float32) / 255).to(device) if 'lpips' in metrics else None
     network.eval()
     quiet_gc()
     old = cfg.perturb
@@ -473,7 +569,7 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
     on_gpu = device.type == 'cuda'
     copy_stream = torch.cuda.Stream(device=device) if on_gpu else None
     pool = _PinnedPool()
-    pending = []                                    # [idx, hosts, event, item, watch id]: oldest first
+    pending = []                                    # [idx, hosts, event, item, watch id, metric host]: oldest first
     guard = hasattr(network, 'check_f16_range')
 
     t_submit, t_wait, t_user = [], [], []           # per frame: launches queued / waiting for the image / on_image
@@ -491,6 +587,11 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
         t1 = time.perf_counter()
         if on_image is not None:
             on_image(i, *arrs)
+        if entry[5] is not None:
+            vals = entry[5].tolist()
+            pool.give(entry[5])
+            if on_metrics is not None:
+                on_metrics(i, dict(zip(metrics, vals)))
         t_wait.append(t1 - t0)
         t_user.append(time.perf_counter() - t1)
 
@@ -505,12 +606,22 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
             res = network(**item['data'], iter_val=float(cfg.eval_iter))
         rgb8, a8, t8 = unpack_to_image(item['W'], item['H'], None, item['data']['bgcolor'] / 255., res['rgb'], res['alpha'],
                                        item['truth'], ray_index=item['ray_index'])
+        mvec = None
+        if metrics is not None and item['truth'] is not None:
+            vals = {}
+            if 'psnr' in metrics or 'ssim' in metrics:
+                pm = ops.image_metrics(rgb8, t8)
+                vals['psnr'], vals['ssim'] = pm[0, 0], pm[0, 1]
+            if 'lpips' in metrics:
+                # (a table of the host's float32 k / 255: the device divides by a scalar as a product with 1 / 255)
+                vals['lpips'] = 1000 * lpips_fn(unit[rgb8.long()], unit[t8.long()]).reshape(()).to(torch.float64)
+            mvec = torch.stack([vals[k] for k in metrics])
         if timing:
             gpu_ev[-1][1].record()
         imgs = [rgb8, a8] + ([t8] if item['truth'] is not None else [])
         wid = network.f16_range_watched if guard else 0
         if not on_gpu:
-            return [item['idx'], [im.cpu() for im in imgs], None, item, wid]
+            return [item['idx'], [im.cpu() for im in imgs], None, item, wid, None]
         copy_stream.wait_stream(torch.cuda.current_stream(device))      # overlap D2H with the next frame
         hosts = []
         with torch.cuda.stream(copy_stream):
@@ -519,9 +630,14 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
                 h.copy_(im, non_blocking=True)
                 im.record_stream(copy_stream)
                 hosts.append(h)
+            mhost = None
+            if mvec is not None:
+                mhost = pool.take(mvec.shape, torch.float64)
+                mhost.copy_(mvec, non_blocking=True)
+                mvec.record_stream(copy_stream)
             ev = torch.cuda.Event()
             ev.record(copy_stream)
-        return [item['idx'], hosts, ev, item, wid]
+        return [item['idx'], hosts, ev, item, wid, mhost]
 
     def mlp_mode():
         return network._mlp_mode() if hasattr(network, '_mlp_mode') else None
@@ -537,6 +653,8 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
             if on_gpu:
                 for h in entry[1]:
                     pool.give(h)
+                if entry[5] is not None:
+                    pool.give(entry[5])
             pending[k] = render(entry[3])
 
     def verdicts(wait, upto=None):

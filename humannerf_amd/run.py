@@ -75,21 +75,28 @@ def _baked_folder(network, subject, folder):
     return folder
 
 
-def _render_loop(network, frames, names, folder, logdir, rank, world, device, metrics=None):
+def _render_loop(network, frames, names, folder, logdir, rank, world, device, metrics=None, on_device=False,
+                 lpips_fn=None):
+    """``metrics``: a MetricsWriter.  ``on_device``: its values come from render_frames' device pass (cfg.amd.metrics =
+    'device') instead of MetricsWriter.append on the delivered images."""
     out_dir = _output_dir(logdir)
     writer = render.ImageWriter(out_dir, folder)
     own = list(range(rank, len(frames), world))
 
     def on_image(i, rgb8, alpha8, truth8=None):
         writer.append(_panels(rgb8, alpha8, truth8), img_name=names[i])
-        if metrics is not None and truth8 is not None:
+        if metrics is not None and truth8 is not None and not on_device:
             metrics.append(name=names[i], pred=rgb8, target=truth8, mask=None)
 
+    extra = {}
+    if metrics is not None and on_device:
+        extra = dict(metrics=metrics.metrics, lpips_fn=lpips_fn,
+                     on_metrics=lambda i, values: metrics.append_values(names[i], values))
     old = cfg.perturb
     cfg.perturb = 0.                                                   # run.py:71, 214
     try:
         images = render.render_frames(network, frames, rank=rank, world=world, device=device, on_image=on_image,
-                                      show_truth=True)
+                                      show_truth=True, **extra)
     finally:
         cfg.perturb = old
     stack = writer.finalize()
@@ -100,9 +107,16 @@ def _render_loop(network, frames, names, folder, logdir, rank, world, device, me
 def run_movement(network, subject, render_folder_name='movement', logdir=None, rank=0, world=1, device=None,
                  test_num=-1, metrics=None, lpips_fn=None):
     """run.py:212-445.  Frames are loaded with their images (truth panel and metrics), rays come from the device ray
-    generator.  Returns the per-rank result dict of the loop; ``['metrics']`` holds this rank's averages."""
-    cfg.show_truth = True
+    generator.  Returns the per-rank result dict of the loop; ``['metrics']`` holds this rank's averages.
+    cfg.amd.metrics = 'device' computes them in the frame's launches on the GPU (render.render_frames(metrics=...)) and
+    writes the same files; on a CPU device it raises."""
+    from .config import amd_option, check_amd_options
+    check_amd_options()
     device = device or next(network.parameters()).device
+    on_device = amd_option('metrics', 'host') == 'device'
+    if on_device and device.type != 'cuda':
+        raise ValueError("cfg.amd.metrics = 'device' needs a GPU, got device %s" % device)
+    cfg.show_truth = True
     n = len(subject) if test_num < 0 else min(test_num, len(subject))
     # camera-only frames: rays come from the device generator, the truth pixels are picked on the device
     # (the prefetcher thread of render_frames builds them: PNG decoding on the host, undistortion / composite / resize on
@@ -113,7 +127,8 @@ def run_movement(network, subject, render_folder_name='movement', logdir=None, r
     suffix = '' if world == 1 else '.rank%d' % rank
     mw = render.MetricsWriter(_output_dir(logdir), render_folder_name + suffix, dataset=subject.dataset_path,
                               metrics=metrics, lpips_fn=lpips_fn)
-    return _render_loop(network, frames, names, render_folder_name, logdir, rank, world, device, metrics=mw)
+    return _render_loop(network, frames, names, render_folder_name, logdir, rank, world, device, metrics=mw,
+                        on_device=on_device, lpips_fn=lpips_fn)
 
 
 def run_freeview(network, subject, frame_idx=None, total_frames=None, render_folder_name=None, logdir=None, rank=0,

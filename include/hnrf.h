@@ -729,6 +729,27 @@ int hnrf_lpips_fwd(const float* img0, const float* img1, const void* packed, int
 int hnrf_lpips_bwd(const float* grad_out, const void* packed, int N, int H, int W, void* workspace,
                    size_t workspace_bytes, float* d_img0, void* stream);
 
+/* ---- Image metrics ---- PSNR and SSIM of 8-bit image pairs that are on the device already: replaces, for uint8 images,
+ * compute_psnr / compute_ssim as MetricsWriter.append calls them per frame on the host (metrics_util.py:78-106;
+ * humannerf_amd/render.py psnr, ssim; the numpy statement of exactly this arithmetic is render.metrics_u8).
+ *  pred, target [n_img,H,W,3] uint8; mask (nullable) [n_img,H,W] uint8, non-zero = inside; out [n_img][2] = psnr, ssim (fp64).
+ *  - psnr = -10 log10(SSE / (255^2 count)), count = 3 H W or 3 nnz(mask), SSE an exact integer sum over the pixels
+ *    inside; equal images give +inf, an empty mask NaN;
+ *  - ssim: with a mask both images are cropped to the bounding box of its non-zero pixels (cv2.boundingRect); per
+ *    channel a 7x7 uniform window at every position where it fits entirely, from exact int32 window sums of x, y, x^2,
+ *    y^2, xy: ux = Sx / (49 255), uxx = Sxx / (49 255^2), vx = 49/48 (uxx - ux ux), C1 = (0.01 data_range)^2,
+ *    C2 = (0.03 data_range)^2, s = ((2 ux uy + C1)(2 vxy + C2)) / ((ux^2 + uy^2 + C1)(vx + vy + C2)) in fp64 without
+ *    contraction; the mean over the positions, then over the three channels.  A crop narrower than 7 in either
+ *    direction (an empty mask included) gives NaN;
+ *  - no atomics, every sum in a fixed order: bit-identical from run to run, and image n's values do not depend on
+ *    the rest of the batch.
+ * 1 <= n_img <= 65535, 1 <= H, W <= 8192, data_range > 0 (HNRF_E_UNSUPPORTED otherwise; null pointers HNRF_E_ARG;
+ * hnrf_image_metrics_workspace_bytes: 0 for sizes refused).  `workspace` 256-byte aligned; the bounding boxes stay in it
+ * between the four launches.  No allocation, no synchronisation, ordered on `stream`. */
+size_t hnrf_image_metrics_workspace_bytes(int n_img, int H, int W);
+int hnrf_image_metrics(const uint8_t* pred, const uint8_t* target, const uint8_t* mask, int n_img, int H, int W,
+                       double data_range, void* workspace, size_t workspace_bytes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
