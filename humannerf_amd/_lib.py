@@ -62,6 +62,7 @@ SIGNATURES = {
     'hnrf_render_frame_workspace_bytes': (_sz, [_i64, _int]),
     'hnrf_render_frame_fwd': (_int, [_vp] * 14 + [_int, ctypes.c_float, _i64, _int, _int, _int, _i64, _vp, _sz] + [_vp] * 11 + [_vp, _vp, _vp, _vp]),
     'hnrf_share_compact': (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'hnrf_sample_warp_share_fwd': (_int, [_vp] * 10 + [_i64, _int, _int, _int] + [_vp] * 4 + [_vp] * 8 + [_vp]),
     'hnrf_render_frame_shared_workspace_bytes': (_sz, [_i64, _int]),
     'hnrf_render_frame_shared_fwd': (_int, [_vp] * 14 + [_int, ctypes.c_float, _i64, _int, _int, _int, _i64, _vp, _sz] + [_vp] * 11 + [_vp, _vp, _vp, _vp, _vp]),
     'hnrf_render_term_workspace_bytes': (_sz, [_i64, _int]),

@@ -58,9 +58,12 @@ constexpr BakedGrid kNoOffGrid{nullptr, 0, nullptr, nullptr};
 
 // Shared underflowing inputs (hnrf.h, hnrf_render_frame_shared_fwd): the frame's representative slot -- 16 floats,
 // x = +0 at [0..2], c_off at [4..6], c_xyz at [8..10], c_raw at [12..15] -- and the chunk's live count.  rep null = off.
+// fused: K1 has already classified (hnrf_sample_warp_share_fwd): idx, the count and the fills are written; otherwise
+// hnrf_share_compact runs here.
 struct Share {
     const float* rep;
     int* count;
+    bool fused;
 };
 
 // K2 -> K3 -> K4 of one ray chunk whose K1 results are in `c`: the whole of hnrf_render_rays_fwd after K1, and the body
@@ -71,7 +74,7 @@ struct Share {
 int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w, const void* nr_packed,
                  const BakedGrid& off, const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t R,
                  int S, float* rgb, float* alpha, float* depth, const DiagRows& d, void* ev_start, void* ev_stop,
-                 hipStream_t st, const Share& sh = Share{nullptr, nullptr}) {
+                 hipStream_t st, const Share& sh = Share{nullptr, nullptr, false}) {
     const size_t P = (size_t)R * (size_t)S;
     const bool cull = cull_eps > 0.f, diag = d.weights != nullptr;
     int rc;
@@ -80,8 +83,8 @@ int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w,
     const int* cc = cull ? c.count : nullptr;
     float* xyz = diag ? d.xyz : c.xyz;
     if (sh.rep) {                                                 // (with K2 and K3 from the MLPs and cull_eps == 0 only)
-        if ((rc = share_compact(c.x_skel, sh.rep + 4, sh.rep + 8, sh.rep + 12, (int64_t)P, c.idx, sh.count, d.offsets,
-                                diag ? d.xyz : nullptr, c.raw, st))) return rc;
+        if (!sh.fused && (rc = share_compact(c.x_skel, sh.rep + 4, sh.rep + 8, sh.rep + 12, (int64_t)P, c.idx, sh.count,
+                                             d.offsets, diag ? d.xyz : nullptr, c.raw, st))) return rc;
         ci = c.idx;
         cc = sh.count;
     }
@@ -252,14 +255,35 @@ int render_frame(const char* who, const float* rays_o, const float* rays_d, cons
     const bool two = side_stream != nullptr && side_stream != stream;
     const int64_t nchunk = (N + chunk - 1) / chunk;
     auto carve = [&](int64_t i, int64_t R) { return render_carve((char*)workspace + (size_t)(i & 1) * ws_one, R, S); };
+    float* rep = share ? (float*)((char*)workspace + 2 * ws_one) : nullptr;
+    const bool fused = share && B == 24;                          // K1 classifies; any other bone count: hnrf_share_compact
     auto warp = [&](int64_t i) {                                  // K1 of chunk i on the side stream
         const int64_t r0 = i * chunk, R = (N - r0 < chunk) ? N - r0 : chunk;
         const RenderCarve c = carve(i, R);
+        if (fused)
+            return sample_warp_share(rays_o + 3 * r0, rays_d + 3 * r0, near + r0, far + r0, t_rand ? t_rand + r0 * S : nullptr,
+                                     motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, R, S, G, c.z_vals, c.x_skel, c.mask,
+                                     bmw ? bmw + r0 * S * B : nullptr, rep + 4, rep + 8, rep + 12, c.idx, live_counts + i,
+                                     diag ? offsets + r0 * S * 3 : nullptr, diag ? xyz_on_rays + r0 * S * 3 : nullptr, c.raw,
+                                     sd);
         return hnrf_sample_warp_fwd(rays_o + 3 * r0, rays_d + 3 * r0, near + r0, far + r0, t_rand ? t_rand + r0 * S : nullptr,
                                     motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, R, S, B, G, c.z_vals, c.x_skel, c.mask,
                                     bmw ? bmw + r0 * S * B : nullptr, sd);
     };
     hipEvent_t ev_in = nullptr, ev_k1[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
+    int rc;
+    if (share) {
+        // the representative x = (+0, +0, +0) through the chunks' kernel instances (guarded unless no chunk is: the
+        // guard sees the shared class through it), once per frame; no mlp_events around it.  In front of K1 of chunk 0
+        // and of ev_in: the fused K1 reads c_off / c_xyz / c_raw and counts into live_counts, on either stream.  (K1 of
+        // chunk i+1 writes idx and the raw fills of the workspace chunk i-1 used: it waits for ev_done of chunk i-1,
+        // recorded behind that chunk's K4, the last reader of both.)
+        const int rmode = mode & (HNRF_MLP_ARITH_MASK | HNRF_MLP_NO_RANGE_GUARD);
+        HNRF_HIP(hipMemsetAsync(rep, 0, 64, st));
+        HNRF_HIP(hipMemsetAsync(live_counts, 0, (size_t)nchunk * sizeof(int), st));
+        if ((rc = hnrf_nonrigid_fwd_sparse(rep, hann_w, nr_packed, rmode, 1, nullptr, nullptr, rep + 8, rep + 4, st))) return rc;
+        if ((rc = hnrf_canonical_fwd_sparse(rep + 8, cnl.packed, rmode, 1, nullptr, nullptr, rep + 12, st))) return rc;
+    }
     if (two) {
         ev_in = (hipEvent_t)events[0];
         ev_k1[0] = (hipEvent_t)events[1]; ev_k1[1] = (hipEvent_t)events[2];
@@ -267,19 +291,8 @@ int render_frame(const char* who, const float* rays_o, const float* rays_d, cons
         HNRF_HIP(hipEventRecord(ev_in, st));                      // the side stream starts behind everything queued so far
         HNRF_HIP(hipStreamWaitEvent(sd, ev_in, 0));
     }
-    int rc = warp(0);
-    if (rc) return rc;
+    if ((rc = warp(0))) return rc;
     if (two) HNRF_HIP(hipEventRecord(ev_k1[0], sd));
-    float* rep = share ? (float*)((char*)workspace + 2 * ws_one) : nullptr;
-    if (share) {
-        // the representative x = (+0, +0, +0) through the chunks' kernel instances (guarded unless no chunk is: the
-        // guard sees the shared class through it), once per frame; no mlp_events around it
-        const int rmode = mode & (HNRF_MLP_ARITH_MASK | HNRF_MLP_NO_RANGE_GUARD);
-        HNRF_HIP(hipMemsetAsync(rep, 0, 64, st));
-        HNRF_HIP(hipMemsetAsync(live_counts, 0, (size_t)nchunk * sizeof(int), st));
-        if ((rc = hnrf_nonrigid_fwd_sparse(rep, hann_w, nr_packed, rmode, 1, nullptr, nullptr, rep + 8, rep + 4, st))) return rc;
-        if ((rc = hnrf_canonical_fwd_sparse(rep + 8, cnl.packed, rmode, 1, nullptr, nullptr, rep + 12, st))) return rc;
-    }
     for (int64_t i = 0; i < nchunk; ++i) {
         const int64_t r0 = i * chunk, R = (N - r0 < chunk) ? N - r0 : chunk;
         if (i + 1 < nchunk) {                                     // next chunk's K1: its workspace was last read by chunk i-1
@@ -299,7 +312,7 @@ int render_frame(const char* who, const float* rays_o, const float* rays_d, cons
         if ((rc = render_chunk(carve(i, R), rays_d + 3 * r0, hann_w, nr_packed, off, cnl, bgcolor, cmode, cull_eps, R, S,
                                rgb + 3 * r0, alpha + r0, depth + r0, d, mlp_events ? mlp_events[2 * i] : nullptr,
                                mlp_events ? mlp_events[2 * i + 1] : nullptr, st,
-                               Share{rep, share ? live_counts + i : nullptr}))) return rc;
+                               Share{rep, share ? live_counts + i : nullptr, fused}))) return rc;
         if (two) HNRF_HIP(hipEventRecord(ev_done[i & 1], st));
         if (!two && i + 1 < nchunk && (rc = warp(i + 1))) return rc;   // single stream: plain sequence
     }

@@ -64,6 +64,14 @@ static inline RenderCarve render_carve(void* base, int64_t R, int S) {
 int share_compact(const float* x_skel, const float* c_off, const float* c_xyz, const float* c_raw, int64_t P, int* idx,
                   int* count, float* offsets, float* xyz, float* raw, hipStream_t st);
 
+// hnrf_sample_warp_share_fwd (hnrf_sample_warp.hip: K1 with the classification fused in, 24 bones) without the
+// argument checks of the share part and without zeroing *count.
+int sample_warp_share(const float* rays_o, const float* rays_d, const float* near, const float* far, const float* t_rand,
+                      const float* motion_Rs, const float* motion_Ts, const float* vol, const float* bbox_min,
+                      const float* bbox_scale, int64_t R, int S, int G, float* z_vals, float* x_skel, float* fg_mask,
+                      float* bmw, const float* c_off, const float* c_xyz, const float* c_raw, int* idx, int* count,
+                      float* offsets, float* xyz, float* raw, hipStream_t st);
+
 // Opt a kernel into > 64 KiB of dynamic LDS, once per device of this process (`done`: one bit per device id;
 // the attribute is per device, and a process may drive more than one).
 static inline int reserve_lds(const void* fn, int bytes, unsigned long long& done, const char* what) {

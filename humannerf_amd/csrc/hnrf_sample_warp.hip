@@ -27,9 +27,20 @@ __device__ __forceinline__ float z_at(float nr, float fr, int s, int S) {
     return nr * (1.0f - t) + fr * t;
 }
 
+// SHARE: what the block does with its x_skel while it still has it in registers (hnrf_sample_warp_share_fwd, hnrf.h):
+// the predicate of hnrf_share_compact decides shared / live, the live samples go onto the chunk's list and the shared
+// rows get the representative's results.  offsets / xyz nullable (the lean form).  *count must be 0 before the first
+// block runs.
+struct ShareOut {
+    const float *c_off, *c_xyz, *c_raw;
+    int *idx, *count;
+    float4* raw;
+    float *offsets, *xyz;
+};
+
 // BT: the bone count as a compile-time constant (24 = the SMPL skeleton of every config of the reference; 0 = read B at
 // run time).  With BT the four-bone trips lose their per-bone `b < B` branches.
-template <bool WRITE_BMW, int BT>
+template <bool WRITE_BMW, int BT, bool SHARE = false>
 __global__ __launch_bounds__(256) void sample_warp_kernel(
     const float* __restrict__ rays_o, const float* __restrict__ rays_d,
     const float* __restrict__ near, const float* __restrict__ far,
@@ -39,7 +50,7 @@ __global__ __launch_bounds__(256) void sample_warp_kernel(
     const float* __restrict__ bbox_scale,
     int64_t P, int S, int B, int G,
     float* __restrict__ z_vals, float* __restrict__ x_skel,
-    float* __restrict__ fg_mask, float* __restrict__ bmw) {
+    float* __restrict__ fg_mask, float* __restrict__ bmw, ShareOut sh) {
     // the diagnostic per-bone weights of a block's 256 samples are one contiguous run of 256 B floats: staged in LDS as
     // [quad of bones][sample] and written back as whole 1-KiB wavefront stores (as they leave the bone loop -- 16 bytes
     // per lane at a 96-byte stride -- every store instruction touched 64 different 128-byte lines: 1.28 GB of write
@@ -147,13 +158,49 @@ __global__ __launch_bounds__(256) void sample_warp_kernel(
     }
     if (bmw4) stage[(b0 >> 2) * 256 + threadIdx.x] = make_float4(w4[0], w4[1], w4[2], w4[3]);
     }
+    const float den = fmaxf(wsum, 0.0001f);
+    const float xs[3] = {ax / den, ay / den, az / den};
     if (in_range) {
-        const float den = fmaxf(wsum, 0.0001f);
         z_vals[p] = z;
-        x_skel[p * 3 + 0] = ax / den;
-        x_skel[p * 3 + 1] = ay / den;
-        x_skel[p * 3 + 2] = az / den;
+        x_skel[p * 3 + 0] = xs[0];
+        x_skel[p * 3 + 1] = xs[1];
+        x_skel[p * 3 + 2] = xs[2];
         fg_mask[p] = wsum;
+    }
+    if constexpr (SHARE) {
+        // share_compact_kernel's classification and list, on the values just stored: one atomic per block, issued while
+        // the CU's other resident blocks are in their bone loops, instead of a second pass whose blocks do little else
+        // than wait for theirs
+        __shared__ int wave_tot[4];
+        __shared__ int block_base;
+        bool shared = in_range;
+#pragma unroll
+        for (int a = 0; a < 3; ++a)        // (a NaN fails the first comparison: always live); the sum is K2's own `x + offset`
+            shared &= fabsf(xs[a]) <= HNRF_SHARE_T && __float_as_uint(xs[a] + sh.c_off[a]) == __float_as_uint(sh.c_xyz[a]);
+        const bool keep = in_range && !shared;
+        const unsigned long long bal = __ballot(keep);
+        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int before = __popcll(bal & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_tot[wave] = __popcll(bal);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int tot = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+            block_base = tot ? atomicAdd(sh.count, tot) : 0;
+        }
+        __syncthreads();
+        int off = block_base + before;
+        for (int w = 0; w < wave; ++w) off += wave_tot[w];
+        if (keep) sh.idx[off] = (int)p;
+        if (shared) {
+            sh.raw[p] = make_float4(sh.c_raw[0], sh.c_raw[1], sh.c_raw[2], sh.c_raw[3]);
+            if (sh.offsets) {
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    sh.offsets[p * 3 + a] = sh.c_off[a];
+                    sh.xyz[p * 3 + a] = sh.c_xyz[a];
+                }
+            }
+        }
     }
     if (bmw4) {                                        // (block-uniform: no thread has left the kernel)
         __syncthreads();
@@ -274,6 +321,48 @@ extern "C" int hnrf_compact_samples(const float* fg_mask, float eps, int64_t P, 
     return check_launch("hnrf_compact_samples");
 }
 
+namespace hnrf {
+// hnrf_sample_warp_fwd; sh != null: the fused classification (24 bones only, the caller's to check; *sh->count zeroed
+// by the caller)
+int sample_warp(const float* rays_o, const float* rays_d, const float* near, const float* far, const float* t_rand,
+                const float* motion_Rs, const float* motion_Ts, const float* vol, const float* bbox_min,
+                const float* bbox_scale, int64_t R, int S, int B, int G, float* z_vals, float* x_skel, float* fg_mask,
+                float* bmw, const ShareOut* sh, hipStream_t st) {
+    const char* who = sh ? "hnrf_sample_warp_share_fwd" : "hnrf_sample_warp_fwd";
+    HNRF_REQUIRE(rays_o && rays_d && near && far && motion_Rs && motion_Ts && vol && bbox_min && bbox_scale,
+                 HNRF_E_ARG, "%s: null input pointer", who);
+    HNRF_REQUIRE(z_vals && x_skel && fg_mask, HNRF_E_ARG, "%s: null output pointer", who);
+    HNRF_REQUIRE(R >= 0 && S >= 2 && B >= 1 && G >= 2 && G <= 1024, HNRF_E_ARG,
+                 "%s: bad dims R=%lld S=%d B=%d G=%d", who, (long long)R, S, B, G);
+    HNRF_REQUIRE(!bmw || B != 24 || ((uintptr_t)bmw & 15) == 0, HNRF_E_ARG,
+                 "%s: with 24 bones the per-bone weight output must be 16-byte aligned (written in 16-byte pieces)", who);
+    if (R == 0) return HNRF_OK;
+    const int64_t P = R * (int64_t)S;
+    const int64_t blocks = (P + 255) / 256;
+    HNRF_REQUIRE(blocks < (int64_t)2147483647, HNRF_E_ARG, "%s: too many samples", who);
+    const ShareOut so = sh ? *sh : ShareOut{};
+#define HNRF_K1(W, BT_, SH_)                                                                                          \
+    hipLaunchKernelGGL((sample_warp_kernel<W, BT_, SH_>), dim3((unsigned)blocks), dim3(256), 0, st, rays_o, rays_d, near, \
+                       far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, P, S, B, G, z_vals, x_skel, fg_mask, \
+                       bmw, so)
+    if (sh) { if (bmw) HNRF_K1(true, 24, true); else HNRF_K1(false, 24, true); }
+    else if (bmw) { if (B == 24) HNRF_K1(true, 24, false); else HNRF_K1(true, 0, false); }
+    else { if (B == 24) HNRF_K1(false, 24, false); else HNRF_K1(false, 0, false); }
+#undef HNRF_K1
+    return check_launch(who);
+}
+
+int sample_warp_share(const float* rays_o, const float* rays_d, const float* near, const float* far, const float* t_rand,
+                      const float* motion_Rs, const float* motion_Ts, const float* vol, const float* bbox_min,
+                      const float* bbox_scale, int64_t R, int S, int G, float* z_vals, float* x_skel, float* fg_mask,
+                      float* bmw, const float* c_off, const float* c_xyz, const float* c_raw, int* idx, int* count,
+                      float* offsets, float* xyz, float* raw, hipStream_t st) {
+    const ShareOut sh{c_off, c_xyz, c_raw, idx, count, (float4*)raw, offsets, xyz};
+    return sample_warp(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, R, S, 24, G,
+                       z_vals, x_skel, fg_mask, bmw, &sh, st);
+}
+}  // namespace hnrf
+
 extern "C" int hnrf_sample_warp_fwd(const float* rays_o, const float* rays_d,
                                     const float* near, const float* far, const float* t_rand,
                                     const float* motion_Rs, const float* motion_Ts,
@@ -281,24 +370,28 @@ extern "C" int hnrf_sample_warp_fwd(const float* rays_o, const float* rays_d,
                                     int64_t R, int S, int B, int G,
                                     float* z_vals, float* x_skel, float* fg_mask, float* bmw,
                                     void* stream) {
+    return hnrf::sample_warp(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, R, S, B, G,
+                             z_vals, x_skel, fg_mask, bmw, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int hnrf_sample_warp_share_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                          const float* t_rand, const float* motion_Rs, const float* motion_Ts,
+                                          const float* vol, const float* bbox_min, const float* bbox_scale, int64_t R,
+                                          int S, int B, int G, float* z_vals, float* x_skel, float* fg_mask, float* bmw,
+                                          const float* c_off, const float* c_xyz, const float* c_raw, int* idx, int* count,
+                                          float* offsets, float* xyz, float* raw, void* stream) {
     using namespace hnrf;
-    HNRF_REQUIRE(rays_o && rays_d && near && far && motion_Rs && motion_Ts && vol && bbox_min && bbox_scale,
-                 HNRF_E_ARG, "hnrf_sample_warp_fwd: null input pointer");
-    HNRF_REQUIRE(z_vals && x_skel && fg_mask, HNRF_E_ARG, "hnrf_sample_warp_fwd: null output pointer");
-    HNRF_REQUIRE(R >= 0 && S >= 2 && B >= 1 && G >= 2 && G <= 1024, HNRF_E_ARG,
-                 "hnrf_sample_warp_fwd: bad dims R=%lld S=%d B=%d G=%d", (long long)R, S, B, G);
-    HNRF_REQUIRE(!bmw || B != 24 || ((uintptr_t)bmw & 15) == 0, HNRF_E_ARG,
-                 "hnrf_sample_warp_fwd: with 24 bones the per-bone weight output must be 16-byte aligned (written in 16-byte pieces)");
-    if (R == 0) return HNRF_OK;
-    const int64_t P = R * (int64_t)S;
-    const int64_t blocks = (P + 255) / 256;
-    HNRF_REQUIRE(blocks < (int64_t)2147483647, HNRF_E_ARG, "hnrf_sample_warp_fwd: too many samples");
+    const char* who = "hnrf_sample_warp_share_fwd";
+    HNRF_REQUIRE(B == 24, HNRF_E_UNSUPPORTED, "%s: the fused classification exists for 24 bones only (B=%d)", who, B);
+    HNRF_REQUIRE(c_off && c_xyz && c_raw && idx && count && raw, HNRF_E_ARG, "%s: null pointer", who);
+    HNRF_REQUIRE((offsets == nullptr) == (xyz == nullptr), HNRF_E_ARG, "%s: offsets and xyz go together", who);
+    HNRF_REQUIRE(R >= 0 && S >= 2 && R * (int64_t)S < 2147483647LL, HNRF_E_ARG, "%s: bad R=%lld S=%d", who, (long long)R, S);
+    HNRF_REQUIRE(((uintptr_t)raw & 15) == 0, HNRF_E_ARG, "%s: raw must be 16-byte aligned", who);
     hipStream_t st = (hipStream_t)stream;
-#define HNRF_K1(W, BT_)                                                                                               \
-    hipLaunchKernelGGL((sample_warp_kernel<W, BT_>), dim3((unsigned)blocks), dim3(256), 0, st, rays_o, rays_d, near, far, \
-                       t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, P, S, B, G, z_vals, x_skel, fg_mask, bmw)
-    if (bmw) { if (B == 24) HNRF_K1(true, 24); else HNRF_K1(true, 0); }
-    else { if (B == 24) HNRF_K1(false, 24); else HNRF_K1(false, 0); }
-#undef HNRF_K1
-    return check_launch("hnrf_sample_warp_fwd");
+    if (hipMemsetAsync(count, 0, sizeof(int), st) != hipSuccess) {
+        set_error("%s: memset failed", who);
+        return HNRF_E_LAUNCH;
+    }
+    return sample_warp_share(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, R, S, G,
+                             z_vals, x_skel, fg_mask, bmw, c_off, c_xyz, c_raw, idx, count, offsets, xyz, raw, st);
 }

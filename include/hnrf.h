@@ -256,7 +256,18 @@ int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, const float*
 #define HNRF_SHARE_T 4.656612873077392578125e-10f
 int hnrf_share_compact(const float* x_skel, const float* c_off, const float* c_xyz, const float* c_raw, int64_t P,
                        int* idx, int* count, float* offsets, float* xyz, float* raw, void* stream);
-/* hnrf_render_frame_fwd with every chunk as K1 -> hnrf_share_compact -> K2 and K3 on the live list -> K4, the
+/* The same classification inside K1 (24 bones only: HNRF_E_UNSUPPORTED otherwise), on the x_skel values the block
+ * still holds in registers: no second pass over x_skel, and the one atomic per block of 256 samples waits under the
+ * arithmetic of the CU's other resident blocks.  Arguments through bmw as hnrf_sample_warp_fwd, and z_vals / x_skel /
+ * fg_mask / bmw are written exactly as there; c_off .. raw as hnrf_share_compact, with P = R S < 2^31 - 1. */
+int hnrf_sample_warp_share_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                               const float* t_rand, const float* motion_Rs, const float* motion_Ts, const float* vol,
+                               const float* bbox_min, const float* bbox_scale, int64_t R, int S, int B, int G,
+                               float* z_vals, float* x_skel, float* fg_mask, float* bmw, const float* c_off,
+                               const float* c_xyz, const float* c_raw, int* idx, int* count, float* offsets, float* xyz,
+                               float* raw, void* stream);
+/* hnrf_render_frame_fwd with every chunk as K1 with the classification fused in (hnrf_sample_warp_share_fwd; any bone
+ * count but 24: K1 -> hnrf_share_compact) -> K2 and K3 on the live list -> K4, the
  * representative evaluated once per frame in front of chunk 0 by the same kernel instances (guarded unless
  * HNRF_MLP_NO_RANGE_GUARD; no mlp_events around it, the pairs stay one per chunk, around K3 on the live list).  Every
  * output equals hnrf_render_frame_fwd's bit for bit.  live_counts [ceil(N / chunk)] (device, required): receives the
