@@ -6,109 +6,61 @@ missing or a symbol cannot be resolved, importing/using the ops raises.
 """
 import ctypes
 import os
+import re
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HNRF_LIB_PATH', os.path.join(_HERE, 'libhnrf.so'))   # override: diagnostic builds only
 
-_vp, _i64, _int, _sz = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_size_t
+HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf.h'))
 
-# name -> (restype, argtypes); mirrors include/hnrf.h one to one
-SIGNATURES = {
-    'hnrf_abi_version': (_int, []),
-    'hnrf_last_error': (ctypes.c_char_p, []),
-    'hnrf_sample_warp_fwd': (_int, [_vp] * 10 + [_i64, _int, _int, _int] + [_vp] * 4 + [_vp]),
-    'hnrf_nonrigid_packed_bytes': (_sz, [_int]),
-    'hnrf_canonical_status_offset': (_sz, [_int]),
-    'hnrf_nonrigid_status_offset': (_sz, [_int]),
-    'hnrf_nonrigid_pack': (_int, [_vp, _vp, _vp, _int, _vp, _vp]),
-    'hnrf_nonrigid_fwd': (_int, [_vp, _vp, _vp, _int, _i64, _vp, _vp, _vp]),
-    'hnrf_canonical_packed_bytes': (_sz, [_int]),
-    'hnrf_canonical_pack': (_int, [_vp, _vp, _int, _vp, _vp]),
-    'hnrf_canonical_fwd': (_int, [_vp, _vp, _int, _i64, _vp, _vp]),
-    'hnrf_composite_fwd': (_int, [_vp] * 6 + [_i64, _int, ctypes.c_float] + [_vp] * 8 + [_vp]),
-    'hnrf_compact_samples': (_int, [_vp, ctypes.c_float, _i64, _vp, _vp, _vp]),
-    'hnrf_canonical_fwd_sparse': (_int, [_vp, _vp, _int, _i64, _vp, _vp, _vp, _vp]),
-    'hnrf_nonrigid_fwd_sparse': (_int, [_vp, _vp, _vp, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
-    'hnrf_canonical_fwd_train': (_int, [_vp, _vp, _int, _i64, _vp, _vp, _vp, _vp, _vp]),
-    'hnrf_nonrigid_fwd_train': (_int, [_vp, _vp, _vp, _int, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'hnrf_composite_bwd': (_int, [_vp] * 8 + [_i64, _int, _vp, _vp, _vp]),
-    'hnrf_pe_bwd': (_int, [_vp, _vp, _vp, _i64, _int, _int, _int, _vp, _vp]),
-    'hnrf_sample_warp_bwd': (_int, [_vp] * 12 + [_i64, _int, _int, _int, _vp, _vp, _vp, _vp]),
-    'hnrf_mlp_dw_workspace_bytes': (_sz, [_i64, _int, _int]),
-    'hnrf_mlp_dw': (_int, [_vp, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _int, _vp, _i64, _vp, _vp, _sz, _vp]),
-    'hnrf_motion_basis_saved_bytes': (_sz, []),
-    'hnrf_motion_basis_fwd': (_int, [_vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
-    'hnrf_motion_basis_bwd': (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
-    'hnrf_refined_motion_basis_fwd': (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp]),
-    'hnrf_refined_motion_basis_bwd': (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
-    'hnrf_pose_mlp_saved_bytes': (_sz, [_int]),
-    'hnrf_pose_mlp_fwd': (_int, [_vp, _vp, _vp, _vp, _int, _vp, _vp, _vp]),
-    'hnrf_pose_mlp_bwd': (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp]),
-    'hnrf_mlp_dw_h_workspace_bytes': (_sz, [_i64, _int, _int]),
-    'hnrf_mlp_dw_h': (_int, [_vp, _i64, _vp, _i64, _i64, _int, _int, _int, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
-    'hnrf_canonical_bwd_packed_bytes': (_sz, [_int]),
-    'hnrf_nonrigid_bwd_packed_bytes': (_sz, [_int]),
-    'hnrf_canonical_bwd_pack': (_int, [_vp, _int, _vp, _vp]),
-    'hnrf_nonrigid_bwd_pack': (_int, [_vp, _int, _vp, _vp]),
-    'hnrf_canonical_bwd': (_int, [_vp, _vp, _vp, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp]),
-    'hnrf_nonrigid_bwd': (_int, [_vp, _vp, _vp, _vp, _vp, _int, _vp, _i64, _vp, _vp, _vp, _vp]),
-    'hnrf_gen_rays_workspace_bytes': (_sz, [_int, _int]),
-    'hnrf_gen_rays': (_int, [_vp] * 5 + [_int, _int] + [_vp] * 7 + [_sz, _vp]),
-    'hnrf_undistort_image': (_int, [_vp, _int, _int, _int, _vp, _vp, _int, _int, _vp, _vp]),
-    'hnrf_composite_windows': (_int, [_vp, _vp, _int, _int, _vp, _int, _vp, _vp, _vp, _vp, _int, _int, _vp, _int, _int, _int, _vp, _vp]),
-    'hnrf_resize_mask': (_int, [_vp, _int, _int, _int, _int, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp]),
-    'hnrf_deconv_fold': (_int, [_vp, _vp, _int, _int, _int, _int, _vp, _vp]),
-    'hnrf_render_workspace_bytes': (_sz, [_i64, _int]),
-    'hnrf_render_frame_workspace_bytes': (_sz, [_i64, _int]),
-    'hnrf_render_frame_fwd': (_int, [_vp] * 14 + [_int, ctypes.c_float, _i64, _int, _int, _int, _i64, _vp, _sz] + [_vp] * 11 + [_vp, _vp, _vp, _vp]),
-    'hnrf_share_compact': (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'hnrf_sample_warp_share_fwd': (_int, [_vp] * 10 + [_i64, _int, _int, _int] + [_vp] * 4 + [_vp] * 8 + [_vp]),
-    'hnrf_render_frame_shared_workspace_bytes': (_sz, [_i64, _int]),
-    'hnrf_render_frame_shared_fwd': (_int, [_vp] * 14 + [_int, ctypes.c_float, _i64, _int, _int, _int, _i64, _vp, _sz] + [_vp] * 11 + [_vp, _vp, _vp, _vp, _vp]),
-    'hnrf_render_term_workspace_bytes': (_sz, [_i64, _int]),
-    'hnrf_render_rays_term_fwd': (_int, [_vp] * 14 + [_int, ctypes.c_float, ctypes.c_float, _i64, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp, _vp]),
-    'hnrf_render_rays_fwd': (_int, [_vp] * 14 + [_int, ctypes.c_float, _i64, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'hnrf_density_grid_workspace_bytes': (_sz, [_int]),
-    'hnrf_density_grid': (_int, [_vp, _int, _vp, _int, _int, _vp, _vp, _vp, _int, _vp, _sz, _vp, _vp, _vp, _vp]),
-    'hnrf_mesh_workspace_bytes': (_sz, [_int]),
-    'hnrf_mesh_count': (_int, [_vp, _int, ctypes.c_float, _vp, _sz, _vp, _vp]),
-    'hnrf_mesh_emit': (_int, [_vp, _int, ctypes.c_float, _vp, _vp, _vp, _sz, _i64, _i64, _vp, _vp, _vp]),
-    'hnrf_forward_skin': (_int, [_vp, _i64, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp]),
-    'hnrf_baked_grid_bytes': (_sz, [_int]),
-    'hnrf_bake_canonical_workspace_bytes': (_sz, [_int]),
-    'hnrf_bake_canonical': (_int, [_vp, _int, _vp, _vp, _int, _vp, _sz, _vp, _vp, _vp]),
-    'hnrf_baked_sample': (_int, [_vp, _vp, _int, _vp, _vp, _i64, _vp, _vp]),
-    'hnrf_baked_sample_sparse': (_int, [_vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
-    'hnrf_render_rays_baked_fwd': (_int, [_vp] * 13 + [_int, _vp, _vp, _vp, _int, ctypes.c_float, _i64, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'hnrf_render_frame_baked_fwd': (_int, [_vp] * 13 + [_int, _vp, _vp, _vp, _int, ctypes.c_float, _i64, _int, _int, _int, _i64, _vp, _sz] + [_vp] * 11 + [_vp, _vp, _vp, _vp]),
-    'hnrf_bake_nonrigid_workspace_bytes': (_sz, [_int]),
-    'hnrf_bake_nonrigid': (_int, [_vp, _vp, _int, _vp, _vp, _int, _vp, _sz, _vp, _vp, _vp]),
-    'hnrf_baked_warp_sample': (_int, [_vp, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp]),
-    'hnrf_baked_warp_sample_sparse': (_int, [_vp, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'hnrf_render_rays_baked_nr_fwd': (_int, [_vp] * 11 + [_int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int, ctypes.c_float, _i64, _int, _int, _int, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp]),
-    'hnrf_render_frame_baked_nr_fwd': (_int, [_vp] * 11 + [_int, _vp, _vp, _vp, _int, _vp, _vp, _vp, _int, ctypes.c_float, _i64, _int, _int, _int, _i64, _vp, _sz] + [_vp] * 11 + [_vp, _vp, _vp, _vp]),
-    'hnrf_raster_workspace_bytes': (_sz, [_i64, _i64, _int, _int]),
-    'hnrf_raster_mesh': (_int, [_vp, _i64, _vp, _i64] + [_vp] * 5 + [_int, _int, ctypes.c_float, _int] + [_vp] * 4 + [_vp, _sz, _vp]),
-    'hnrf_lpips_packed_bytes': (_sz, []),
-    'hnrf_lpips_pack': (_int, [_vp, _vp, _vp, _vp, _vp]),
-    'hnrf_conv3x3_fwd': (_int, [_vp, _vp, _int, _int, _int, _int, _int, _vp, _vp]),
-    'hnrf_conv3x3_bwd_data': (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _int, _vp, _vp]),
-    'hnrf_maxpool2_fwd': (_int, [_vp, _int, _int, _int, _int, _vp, _vp]),
-    'hnrf_maxpool2_bwd': (_int, [_vp, _vp, _int, _int, _int, _int, _vp, _vp]),
-    'hnrf_lpips_head_fwd': (_int, [_vp, _vp, _int, _i64, _int, _vp, _vp, _int, _vp, _vp]),
-    'hnrf_lpips_head_bwd': (_int, [_vp, _vp, _vp, _int, _i64, _int, _vp, _int, _vp]),
-    'hnrf_lpips_workspace_bytes': (_sz, [_int, _int, _int, _int]),
-    'hnrf_lpips_fwd': (_int, [_vp, _vp, _vp, _int, _int, _int, _int, _vp, _sz, _vp, _vp, _vp]),
-    'hnrf_lpips_bwd': (_int, [_vp, _vp, _int, _int, _int, _vp, _sz, _vp, _vp]),
-    'hnrf_image_metrics_workspace_bytes': (_sz, [_int, _int, _int]),
-    'hnrf_image_metrics': (_int, [_vp, _vp, _vp, _int, _int, _int, ctypes.c_double, _vp, _sz, _vp, _vp]),
-}
-
-_lib = None
+_SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float,
+            'double': ctypes.c_double}
+_DECL = re.compile(r'([\w\s]+?[\s*]+)(hnrf_\w+)\s*\(([^()]*)\)\s*;')
 
 
 class HnrfError(RuntimeError):
     pass
+
+
+def _ctype(text, decl, ret=False):
+    """ctypes type of one C type as the header writes it; anything it does not know raises (it never guesses)."""
+    words = text.replace('*', ' * ').split()
+    if '*' in words:
+        return ctypes.c_char_p if ret and words == ['const', 'char', '*'] else ctypes.c_void_p
+    if len(words) == 1 and words[0] in _SCALARS:
+        return _SCALARS[words[0]]
+    raise HnrfError(f'include/hnrf.h: unknown type {text.strip()!r} in `{decl}`')
+
+
+def parse_header(text):
+    """name -> (restype, argtypes) of every function declared in `text` (the C of include/hnrf.h)."""
+    text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+    text = re.sub(r'//[^\n]*|^\s*#[^\n]*', ' ', text, flags=re.M)
+    sigs = {}
+    for m in _DECL.finditer(text):
+        decl = ' '.join(m.group(0).split())
+        params = [] if m.group(3).strip() in ('', 'void') else m.group(3).split(',')
+        # a parameter is its type followed by its name; the name is the last identifier
+        args = [_ctype(re.sub(r'\w+\s*$', '', q), decl) for q in params]
+        sigs[m.group(2)] = (_ctype(m.group(1), decl, ret=True), args)
+    missed = set(re.findall(r'\b(hnrf_\w+)\s*\(', text)) - set(sigs)      # (a parameter list with parentheses, say)
+    if missed:
+        raise HnrfError(f'include/hnrf.h: cannot parse the declaration of {sorted(missed)}')
+    return sigs
+
+
+def _signatures():
+    try:
+        with open(HEADER_PATH) as f:
+            return parse_header(f.read())
+    except OSError as e:
+        raise HnrfError(f'{HEADER_PATH}: cannot read the C ABI declarations ({e})') from None
+
+
+# name -> (restype, argtypes), derived from the declarations of include/hnrf.h
+SIGNATURES = _signatures()
+
+_lib = None
 
 
 def load():

@@ -7,7 +7,7 @@
 #include <stdarg.h>
 #include <string.h>
 
-#include "hnrf_common.h"
+#include "hnrf_block_scan.h"
 
 namespace hnrf {
 static thread_local char g_err[512] = "";
@@ -39,12 +39,6 @@ extern "C" size_t hnrf_render_workspace_bytes(int64_t R, int S) {
     } while (0)
 
 namespace {
-// The chunk's rows of hnrf_render_frame_fwd's eight diagnostic outputs; all null = the lean form (rgb / alpha / depth).
-// (backward_motion_weights is K1's and written before render_chunk.)
-struct DiagRows {
-    float *weights, *rgb_on_rays, *cnl_xyz, *cnl_rgb, *cnl_weight, *xyz, *offsets;
-};
-
 // Where a chunk's raw comes from: the canonical MLP on `packed`, or -- grid != null -- the baked grid's sampler.
 struct CnlSource {
     const void* packed;
@@ -56,13 +50,12 @@ struct CnlSource {
 // no offset grid: xyz comes from K2 (nr_packed) or is x_skel
 constexpr BakedGrid kNoOffGrid{nullptr, 0, nullptr, nullptr};
 
-// Shared underflowing inputs (hnrf.h, hnrf_render_frame_shared_fwd): the frame's representative slot -- 16 floats,
-// x = +0 at [0..2], c_off at [4..6], c_xyz at [8..10], c_raw at [12..15] -- and the chunk's live count.  rep null = off.
-// fused: K1 has already classified (hnrf_sample_warp_share_fwd): idx, the count and the fills are written; otherwise
-// hnrf_share_compact runs here.
+// Shared underflowing inputs (hnrf.h, hnrf_render_frame_shared_fwd): the chunk's ShareOut -- c_off / c_xyz / c_raw in the
+// frame's representative slot (16 floats: x = +0 at [0..2], c_off at [4..6], c_xyz at [8..10], c_raw at [12..15]), the
+// chunk's live count.  out null = off.  fused: K1 has already classified (hnrf_sample_warp_share_fwd): idx, the count
+// and the fills are written; otherwise hnrf_share_compact runs here.
 struct Share {
-    const float* rep;
-    int* count;
+    const ShareOut* out;
     bool fused;
 };
 
@@ -73,8 +66,8 @@ struct Share {
 // K2 and K3; the lean form then writes no xyz at all.
 int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w, const void* nr_packed,
                  const BakedGrid& off, const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t R,
-                 int S, float* rgb, float* alpha, float* depth, const DiagRows& d, void* ev_start, void* ev_stop,
-                 hipStream_t st, const Share& sh = Share{nullptr, nullptr, false}) {
+                 int S, const FrameOut& d, void* ev_start, void* ev_stop, hipStream_t st,
+                 const Share& sh = Share{nullptr, false}) {
     const size_t P = (size_t)R * (size_t)S;
     const bool cull = cull_eps > 0.f, diag = d.weights != nullptr;
     int rc;
@@ -82,39 +75,39 @@ int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w,
     const int* ci = cull ? c.idx : nullptr;
     const int* cc = cull ? c.count : nullptr;
     float* xyz = diag ? d.xyz : c.xyz;
-    if (sh.rep) {                                                 // (with K2 and K3 from the MLPs and cull_eps == 0 only)
-        if (!sh.fused && (rc = share_compact(c.x_skel, sh.rep + 4, sh.rep + 8, sh.rep + 12, (int64_t)P, c.idx, sh.count,
-                                             d.offsets, diag ? d.xyz : nullptr, c.raw, st))) return rc;
+    if (sh.out) {                                                 // (with K2 and K3 from the MLPs and cull_eps == 0 only)
+        if (!sh.fused && (rc = share_compact(c.x_skel, (int64_t)P, *sh.out, st))) return rc;
         ci = c.idx;
-        cc = sh.count;
+        cc = sh.out->count;
     }
     const float* cnl_in = c.x_skel;
+    // (d's eight diagnostic pointers are all null in the lean form -- FrameOut::rows, hnrf_render_rays_* -- so d.xyz and
+    // d.offsets need no `diag ?` of their own)
     if (off.grid) {
         if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
         rc = baked_warp_sample(c.x_skel, off, BakedGrid{cnl.grid, cnl.N, cnl.bmin, cnl.bmax}, (int64_t)P, ci, cc, c.raw,
-                               diag ? d.xyz : nullptr, d.offsets, st);
+                               d.xyz, d.offsets, st);
         if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
         if (rc) return rc;
-        return hnrf_composite_fwd(c.raw, c.mask, c.z_vals, rays_d, diag ? d.xyz : nullptr, bgcolor, R, S,
-                                  cull ? cull_eps : 0.f, rgb, alpha, depth, d.weights, d.rgb_on_rays, d.cnl_xyz,
-                                  d.cnl_rgb, d.cnl_weight, st);
+        cnl_in = d.xyz;
+    } else {
+        if (nr_packed) {
+            if ((rc = hnrf_nonrigid_fwd_sparse(c.x_skel, hann_w, nr_packed, mode, (int64_t)P, ci, cc, xyz, d.offsets, st)))
+                return rc;
+            cnl_in = xyz;
+        } else if (diag) {                                        // network.py:276-277: xyz = x_skel, offsets = 0
+            HNRF_HIP(hipMemcpyAsync(xyz, c.x_skel, P * 12, hipMemcpyDeviceToDevice, st));
+            HNRF_HIP(hipMemsetAsync(d.offsets, 0, P * 12, st));
+        }
+        if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
+        rc = cnl.grid ? baked_sample(cnl_in, cnl.grid, cnl.N, cnl.bmin, cnl.bmax, (int64_t)P, ci, cc, c.raw, st)
+                      : hnrf_canonical_fwd_sparse(cnl_in, cnl.packed, mode, (int64_t)P, ci, cc, c.raw, st);
+        if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
+        if (rc) return rc;
     }
-    if (nr_packed) {
-        if ((rc = hnrf_nonrigid_fwd_sparse(c.x_skel, hann_w, nr_packed, mode, (int64_t)P, ci, cc, xyz, d.offsets, st)))
-            return rc;
-        cnl_in = xyz;
-    } else if (diag) {                                            // network.py:276-277: xyz = x_skel, offsets = 0
-        HNRF_HIP(hipMemcpyAsync(xyz, c.x_skel, P * 12, hipMemcpyDeviceToDevice, st));
-        HNRF_HIP(hipMemsetAsync(d.offsets, 0, P * 12, st));
-    }
-    if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-    rc = cnl.grid ? baked_sample(cnl_in, cnl.grid, cnl.N, cnl.bmin, cnl.bmax, (int64_t)P, ci, cc, c.raw, st)
-                  : hnrf_canonical_fwd_sparse(cnl_in, cnl.packed, mode, (int64_t)P, ci, cc, c.raw, st);
-    if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
-    if (rc) return rc;
     return hnrf_composite_fwd(c.raw, c.mask, c.z_vals, rays_d, diag ? cnl_in : nullptr, bgcolor, R, S,
-                              cull ? cull_eps : 0.f, rgb, alpha, depth, d.weights, d.rgb_on_rays, d.cnl_xyz, d.cnl_rgb,
-                              d.cnl_weight, st);
+                              cull ? cull_eps : 0.f, d.rgb, d.alpha, d.depth, d.weights, d.rgb_on_rays, d.cnl_xyz,
+                              d.cnl_rgb, d.cnl_weight, st);
 }
 // the baked entries' grid arguments (the sampler launches from inside render_chunk without further checks)
 int check_source(const char* who, const CnlSource& cnl) {
@@ -138,12 +131,10 @@ int check_off_source(const char* who, const BakedGrid& off, const CnlSource& cnl
     return HNRF_OK;
 }
 
-int render_rays(const char* who, const float* rays_o, const float* rays_d, const float* near, const float* far,
-                const float* t_rand, const float* motion_Rs, const float* motion_Ts, const float* vol,
-                const float* bbox_min, const float* bbox_scale, const float* hann_w, const void* nr_packed,
+int render_rays(const char* who, const Rays& rays, const WarpField& field, const float* hann_w, const void* nr_packed,
                 const BakedGrid& off, const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t R,
-                int S, int B, int G, void* workspace, size_t workspace_bytes, float* rgb, float* alpha, float* depth,
-                void* ev_mlp_start, void* ev_mlp_stop, void* stream) {
+                int S, void* workspace, size_t workspace_bytes, const FrameOut& out, void* ev_mlp_start,
+                void* ev_mlp_stop, void* stream) {
     HNRF_REQUIRE(workspace, HNRF_E_ARG, "%s: null workspace / canonical weights", who);
     int src = check_source(who, cnl);
     if (src) return src;
@@ -153,11 +144,10 @@ int render_rays(const char* who, const float* rays_o, const float* rays_d, const
                  "%s: workspace %zu < %zu bytes", who, workspace_bytes, hnrf_render_workspace_bytes(R, S));
     HNRF_REQUIRE(nr_packed == nullptr || hann_w != nullptr, HNRF_E_ARG, "%s: hann_w missing", who);
     const RenderCarve c = render_carve(workspace, R, S);
-    int rc = hnrf_sample_warp_fwd(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
-                                  R, S, B, G, c.z_vals, c.x_skel, c.mask, nullptr, stream);
-    if (rc) return rc;
-    return render_chunk(c, rays_d, hann_w, nr_packed, off, cnl, bgcolor, mode, cull_eps, R, S, rgb, alpha, depth,
-                        DiagRows{}, ev_mlp_start, ev_mlp_stop, (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = sample_warp(rays, field, R, S, c.z_vals, c.x_skel, c.mask, nullptr, nullptr, st)) return rc;
+    return render_chunk(c, rays.d, hann_w, nr_packed, off, cnl, bgcolor, mode, cull_eps, R, S, out, ev_mlp_start,
+                        ev_mlp_stop, st);
 }
 }  // namespace
 
@@ -168,10 +158,10 @@ extern "C" int hnrf_render_rays_fwd(const float* rays_o, const float* rays_d, co
                                     const float* bgcolor, int mode, float cull_eps, int64_t R, int S, int B, int G,
                                     void* workspace, size_t workspace_bytes, float* rgb, float* alpha, float* depth,
                                     void* ev_mlp_start, void* ev_mlp_stop, void* stream) {
-    return render_rays("hnrf_render_rays_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min,
-                       bbox_scale, hann_w, nr_packed, kNoOffGrid, CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor,
-                       mode, cull_eps, R, S, B, G, workspace, workspace_bytes, rgb, alpha, depth, ev_mlp_start, ev_mlp_stop,
-                       stream);
+    return render_rays("hnrf_render_rays_fwd", Rays{rays_o, rays_d, near, far, t_rand},
+                       WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, hann_w, nr_packed, kNoOffGrid,
+                       CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor, mode, cull_eps, R, S, workspace,
+                       workspace_bytes, FrameOut{rgb, alpha, depth}, ev_mlp_start, ev_mlp_stop, stream);
 }
 
 extern "C" int hnrf_render_rays_baked_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
@@ -183,10 +173,10 @@ extern "C" int hnrf_render_rays_baked_fwd(const float* rays_o, const float* rays
                                           size_t workspace_bytes, float* rgb, float* alpha, float* depth,
                                           void* ev_mlp_start, void* ev_mlp_stop, void* stream) {
     HNRF_REQUIRE(grid, HNRF_E_ARG, "hnrf_render_rays_baked_fwd: null grid");
-    return render_rays("hnrf_render_rays_baked_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol,
-                       bbox_min, bbox_scale, hann_w, nr_packed, kNoOffGrid,
-                       CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max}, bgcolor, mode, cull_eps, R, S, B, G,
-                       workspace, workspace_bytes, rgb, alpha, depth, ev_mlp_start, ev_mlp_stop, stream);
+    return render_rays("hnrf_render_rays_baked_fwd", Rays{rays_o, rays_d, near, far, t_rand},
+                       WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, hann_w, nr_packed, kNoOffGrid,
+                       CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max}, bgcolor, mode, cull_eps, R, S,
+                       workspace, workspace_bytes, FrameOut{rgb, alpha, depth}, ev_mlp_start, ev_mlp_stop, stream);
 }
 
 extern "C" int hnrf_render_rays_baked_nr_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
@@ -200,10 +190,11 @@ extern "C" int hnrf_render_rays_baked_nr_fwd(const float* rays_o, const float* r
                                              void* ev_mlp_start, void* ev_mlp_stop, void* stream) {
     HNRF_REQUIRE(off_grid, HNRF_E_ARG, "hnrf_render_rays_baked_nr_fwd: null offset grid");
     HNRF_REQUIRE(grid, HNRF_E_ARG, "hnrf_render_rays_baked_nr_fwd: null grid");
-    return render_rays("hnrf_render_rays_baked_nr_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol,
-                       bbox_min, bbox_scale, nullptr, nullptr, BakedGrid{off_grid, off_M, off_bbox_min, off_bbox_max},
-                       CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max}, bgcolor, mode, cull_eps, R, S, B, G,
-                       workspace, workspace_bytes, rgb, alpha, depth, ev_mlp_start, ev_mlp_stop, stream);
+    return render_rays("hnrf_render_rays_baked_nr_fwd", Rays{rays_o, rays_d, near, far, t_rand},
+                       WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, nullptr, nullptr,
+                       BakedGrid{off_grid, off_M, off_bbox_min, off_bbox_max},
+                       CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max}, bgcolor, mode, cull_eps, R, S,
+                       workspace, workspace_bytes, FrameOut{rgb, alpha, depth}, ev_mlp_start, ev_mlp_stop, stream);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -218,15 +209,11 @@ extern "C" size_t hnrf_render_frame_shared_workspace_bytes(int64_t chunk, int S)
 }
 
 namespace {
-int render_frame(const char* who, const float* rays_o, const float* rays_d, const float* near, const float* far,
-                 const float* t_rand, const float* motion_Rs, const float* motion_Ts, const float* vol,
-                 const float* bbox_min, const float* bbox_scale, const float* hann_w, const void* nr_packed,
+int render_frame(const char* who, const Rays& rays, const WarpField& field, const float* hann_w, const void* nr_packed,
                  const BakedGrid& off, const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t N,
-                 int S, int B, int G, int64_t chunk, void* workspace, size_t workspace_bytes, float* rgb, float* alpha, float* depth,
-                 float* weights_on_rays, float* rgb_on_rays, float* cnl_xyz, float* cnl_rgb, float* cnl_weight,
-                 float* xyz_on_rays, float* bmw, float* offsets, void* side_stream, void* const* events,
-                 void* const* mlp_events, void* stream, int* live_counts = nullptr) {
-    HNRF_REQUIRE(workspace && rgb && alpha && depth, HNRF_E_ARG, "%s: null pointer", who);
+                 int S, int64_t chunk, void* workspace, size_t workspace_bytes, const FrameOut& out, void* side_stream,
+                 void* const* events, void* const* mlp_events, void* stream, int* live_counts = nullptr) {
+    HNRF_REQUIRE(workspace && out.rgb && out.alpha && out.depth, HNRF_E_ARG, "%s: null pointer", who);
     int src = check_source(who, cnl);
     if (src) return src;
     if ((src = check_off_source(who, off, cnl))) return src;
@@ -245,30 +232,36 @@ int render_frame(const char* who, const float* rays_o, const float* rays_d, cons
         HNRF_REQUIRE(workspace_bytes >= 2 * ws_one + 256, HNRF_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who,
                      workspace_bytes, 2 * ws_one + 256);
     }
-    const bool diag = weights_on_rays != nullptr;
-    HNRF_REQUIRE(!diag || (rgb_on_rays && cnl_xyz && cnl_rgb && cnl_weight && xyz_on_rays && bmw && offsets), HNRF_E_ARG,
-                 "%s: the eight diagnostic outputs go together", who);
+    const bool diag = out.weights != nullptr;
+    HNRF_REQUIRE(!diag || (out.rgb_on_rays && out.cnl_xyz && out.cnl_rgb && out.cnl_weight && out.xyz && out.bmw &&
+                           out.offsets), HNRF_E_ARG, "%s: the eight diagnostic outputs go together", who);
     HNRF_REQUIRE(!diag || cull_eps == 0.f, HNRF_E_UNSUPPORTED, "%s: sample culling exists in the lean form only", who);
     HNRF_REQUIRE(side_stream == nullptr || events != nullptr, HNRF_E_ARG, "%s: a side stream needs 5 events", who);
     if (N == 0) return HNRF_OK;
     hipStream_t st = (hipStream_t)stream, sd = side_stream ? (hipStream_t)side_stream : st;
     const bool two = side_stream != nullptr && side_stream != stream;
     const int64_t nchunk = (N + chunk - 1) / chunk;
-    auto carve = [&](int64_t i, int64_t R) { return render_carve((char*)workspace + (size_t)(i & 1) * ws_one, R, S); };
     float* rep = share ? (float*)((char*)workspace + 2 * ws_one) : nullptr;
-    const bool fused = share && B == 24;                          // K1 classifies; any other bone count: hnrf_share_compact
-    auto warp = [&](int64_t i) {                                  // K1 of chunk i on the side stream
+    const bool fused = share && field.B == 24;                    // K1 classifies; any other bone count: hnrf_share_compact
+    // chunk i: its rays, its workspace slot, its rows of the outputs and -- with shared inputs -- its ShareOut
+    struct Chunk {
+        int64_t R;
+        Rays rays;
+        RenderCarve c;
+        FrameOut o;
+        ShareOut sh;
+    };
+    auto chunk_at = [&](int64_t i) {
         const int64_t r0 = i * chunk, R = (N - r0 < chunk) ? N - r0 : chunk;
-        const RenderCarve c = carve(i, R);
-        if (fused)
-            return sample_warp_share(rays_o + 3 * r0, rays_d + 3 * r0, near + r0, far + r0, t_rand ? t_rand + r0 * S : nullptr,
-                                     motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, R, S, G, c.z_vals, c.x_skel, c.mask,
-                                     bmw ? bmw + r0 * S * B : nullptr, rep + 4, rep + 8, rep + 12, c.idx, live_counts + i,
-                                     diag ? offsets + r0 * S * 3 : nullptr, diag ? xyz_on_rays + r0 * S * 3 : nullptr, c.raw,
-                                     sd);
-        return hnrf_sample_warp_fwd(rays_o + 3 * r0, rays_d + 3 * r0, near + r0, far + r0, t_rand ? t_rand + r0 * S : nullptr,
-                                    motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, R, S, B, G, c.z_vals, c.x_skel, c.mask,
-                                    bmw ? bmw + r0 * S * B : nullptr, sd);
+        Chunk k{R, rays.rows(r0, S), render_carve((char*)workspace + (size_t)(i & 1) * ws_one, R, S),
+                out.rows(r0, S, field.B), ShareOut{}};
+        if (share)
+            k.sh = ShareOut{rep + 4, rep + 8, rep + 12, k.c.idx, live_counts + i, (float4*)k.c.raw, k.o.offsets, k.o.xyz};
+        return k;
+    };
+    auto warp = [&](int64_t i) {                                  // K1 of chunk i on the side stream
+        const Chunk k = chunk_at(i);
+        return sample_warp(k.rays, field, k.R, S, k.c.z_vals, k.c.x_skel, k.c.mask, k.o.bmw, fused ? &k.sh : nullptr, sd);
     };
     hipEvent_t ev_in = nullptr, ev_k1[2] = {nullptr, nullptr}, ev_done[2] = {nullptr, nullptr};
     int rc;
@@ -294,7 +287,6 @@ int render_frame(const char* who, const float* rays_o, const float* rays_d, cons
     if ((rc = warp(0))) return rc;
     if (two) HNRF_HIP(hipEventRecord(ev_k1[0], sd));
     for (int64_t i = 0; i < nchunk; ++i) {
-        const int64_t r0 = i * chunk, R = (N - r0 < chunk) ? N - r0 : chunk;
         if (i + 1 < nchunk) {                                     // next chunk's K1: its workspace was last read by chunk i-1
             if (two && i >= 1) HNRF_HIP(hipStreamWaitEvent(sd, ev_done[(i + 1) & 1], 0));
             if (two) {
@@ -306,13 +298,10 @@ int render_frame(const char* who, const float* rays_o, const float* rays_d, cons
         // f16-range guard (hnrf.h): every chunk, none, or the one chunk the caller's rotating index names
         int cmode = mode & (HNRF_MLP_ARITH_MASK | HNRF_MLP_NO_RANGE_GUARD);
         if ((mode & HNRF_MLP_GUARD_ONE_CHUNK) && (int64_t)((unsigned)mode >> 16) % nchunk != i) cmode |= HNRF_MLP_NO_RANGE_GUARD;
-        const DiagRows d = diag ? DiagRows{weights_on_rays + r0 * S, rgb_on_rays + r0 * S * 3, cnl_xyz + 3 * r0,
-                                           cnl_rgb + 3 * r0, cnl_weight + r0, xyz_on_rays + r0 * S * 3, offsets + r0 * S * 3}
-                                : DiagRows{};
-        if ((rc = render_chunk(carve(i, R), rays_d + 3 * r0, hann_w, nr_packed, off, cnl, bgcolor, cmode, cull_eps, R, S,
-                               rgb + 3 * r0, alpha + r0, depth + r0, d, mlp_events ? mlp_events[2 * i] : nullptr,
-                               mlp_events ? mlp_events[2 * i + 1] : nullptr, st,
-                               Share{rep, share ? live_counts + i : nullptr, fused}))) return rc;
+        const Chunk k = chunk_at(i);
+        if ((rc = render_chunk(k.c, k.rays.d, hann_w, nr_packed, off, cnl, bgcolor, cmode, cull_eps, k.R, S, k.o,
+                               mlp_events ? mlp_events[2 * i] : nullptr, mlp_events ? mlp_events[2 * i + 1] : nullptr, st,
+                               Share{share ? &k.sh : nullptr, fused}))) return rc;
         if (two) HNRF_HIP(hipEventRecord(ev_done[i & 1], st));
         if (!two && i + 1 < nchunk && (rc = warp(i + 1))) return rc;   // single stream: plain sequence
     }
@@ -330,11 +319,13 @@ extern "C" int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, c
                                      float* depth, float* weights_on_rays, float* rgb_on_rays, float* cnl_xyz,
                                      float* cnl_rgb, float* cnl_weight, float* xyz_on_rays, float* bmw, float* offsets,
                                      void* side_stream, void* const* events, void* const* mlp_events, void* stream) {
-    return render_frame("hnrf_render_frame_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min,
-                        bbox_scale, hann_w, nr_packed, kNoOffGrid, CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor,
-                        mode, cull_eps, N, S, B, G, chunk, workspace, workspace_bytes, rgb, alpha, depth, weights_on_rays,
-                        rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays, bmw, offsets, side_stream, events,
-                        mlp_events, stream);
+    return render_frame("hnrf_render_frame_fwd", Rays{rays_o, rays_d, near, far, t_rand},
+                        WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, hann_w, nr_packed, kNoOffGrid,
+                        CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor, mode, cull_eps, N, S, chunk,
+                        workspace, workspace_bytes,
+                        FrameOut{rgb, alpha, depth, weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays,
+                                 bmw, offsets},
+                        side_stream, events, mlp_events, stream);
 }
 
 extern "C" int hnrf_render_frame_shared_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
@@ -348,11 +339,13 @@ extern "C" int hnrf_render_frame_shared_fwd(const float* rays_o, const float* ra
                                             int* live_counts, void* side_stream, void* const* events,
                                             void* const* mlp_events, void* stream) {
     HNRF_REQUIRE(live_counts, HNRF_E_ARG, "hnrf_render_frame_shared_fwd: null live_counts");
-    return render_frame("hnrf_render_frame_shared_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol,
-                        bbox_min, bbox_scale, hann_w, nr_packed, kNoOffGrid, CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr},
-                        bgcolor, mode, cull_eps, N, S, B, G, chunk, workspace, workspace_bytes, rgb, alpha, depth,
-                        weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays, bmw, offsets, side_stream,
-                        events, mlp_events, stream, live_counts);
+    return render_frame("hnrf_render_frame_shared_fwd", Rays{rays_o, rays_d, near, far, t_rand},
+                        WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, hann_w, nr_packed, kNoOffGrid,
+                        CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor, mode, cull_eps, N, S, chunk,
+                        workspace, workspace_bytes,
+                        FrameOut{rgb, alpha, depth, weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays,
+                                 bmw, offsets},
+                        side_stream, events, mlp_events, stream, live_counts);
 }
 
 extern "C" int hnrf_render_frame_baked_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
@@ -367,10 +360,12 @@ extern "C" int hnrf_render_frame_baked_fwd(const float* rays_o, const float* ray
                                            float* offsets, void* side_stream, void* const* events,
                                            void* const* mlp_events, void* stream) {
     HNRF_REQUIRE(grid, HNRF_E_ARG, "hnrf_render_frame_baked_fwd: null grid");
-    return render_frame("hnrf_render_frame_baked_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol,
-                        bbox_min, bbox_scale, hann_w, nr_packed, kNoOffGrid,
-                        CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max}, bgcolor, mode, cull_eps, N, S, B, G, chunk, workspace, workspace_bytes, rgb, alpha, depth,
-                        weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays, bmw, offsets,
+    return render_frame("hnrf_render_frame_baked_fwd", Rays{rays_o, rays_d, near, far, t_rand},
+                        WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, hann_w, nr_packed, kNoOffGrid,
+                        CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max}, bgcolor, mode, cull_eps, N, S,
+                        chunk, workspace, workspace_bytes,
+                        FrameOut{rgb, alpha, depth, weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays,
+                                 bmw, offsets},
                         side_stream, events, mlp_events, stream);
 }
 
@@ -388,9 +383,12 @@ extern "C" int hnrf_render_frame_baked_nr_fwd(const float* rays_o, const float* 
                                               void* const* mlp_events, void* stream) {
     HNRF_REQUIRE(off_grid, HNRF_E_ARG, "hnrf_render_frame_baked_nr_fwd: null offset grid");
     HNRF_REQUIRE(grid, HNRF_E_ARG, "hnrf_render_frame_baked_nr_fwd: null grid");
-    return render_frame("hnrf_render_frame_baked_nr_fwd", rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol,
-                        bbox_min, bbox_scale, nullptr, nullptr, BakedGrid{off_grid, off_M, off_bbox_min, off_bbox_max},
-                        CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max}, bgcolor, mode, cull_eps, N, S, B, G,
-                        chunk, workspace, workspace_bytes, rgb, alpha, depth, weights_on_rays, rgb_on_rays, cnl_xyz,
-                        cnl_rgb, cnl_weight, xyz_on_rays, bmw, offsets, side_stream, events, mlp_events, stream);
+    return render_frame("hnrf_render_frame_baked_nr_fwd", Rays{rays_o, rays_d, near, far, t_rand},
+                        WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, nullptr, nullptr,
+                        BakedGrid{off_grid, off_M, off_bbox_min, off_bbox_max},
+                        CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max}, bgcolor, mode, cull_eps, N, S,
+                        chunk, workspace, workspace_bytes,
+                        FrameOut{rgb, alpha, depth, weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays,
+                                 bmw, offsets},
+                        side_stream, events, mlp_events, stream);
 }

@@ -59,18 +59,42 @@ static inline RenderCarve render_carve(void* base, int64_t R, int S) {
     return c;
 }
 
-// hnrf_share_compact (hnrf_sample_warp.hip) without the argument checks and without zeroing *count: the frame entry
-// zeroes its per-chunk counts once.
-int share_compact(const float* x_skel, const float* c_off, const float* c_xyz, const float* c_raw, int64_t P, int* idx,
-                  int* count, float* offsets, float* xyz, float* raw, hipStream_t st);
+// The argument bundles of the render entries: what the C ABI passes as runs of loose pointers, named once.
+// A chunk of a frame is rows [r0, r0 + R) of the frame's rays and outputs.
+struct Rays {                 // o [N,3], d [N,3], near [N], far [N], t_rand [N,S] or null
+    const float *o, *d, *near, *far, *t_rand;
+    Rays rows(int64_t r0, int S) const {
+        return Rays{o + 3 * r0, d + 3 * r0, near + r0, far + r0, t_rand ? t_rand + r0 * S : nullptr};
+    }
+};
+struct WarpField {            // K1's motion field: B bones, their G^3 weight volume and its bbox
+    const float *Rs, *Ts, *vol, *bbox_min, *bbox_scale;
+    int B, G;
+};
+// rgb / alpha / depth and hnrf_render_frame_fwd's eight diagnostic outputs.  weights == null = the lean form: the six
+// that follow, xyz and offsets then count as null; bmw is K1's and goes by itself.
+struct FrameOut {
+    float *rgb, *alpha, *depth;
+    float *weights, *rgb_on_rays, *cnl_xyz, *cnl_rgb, *cnl_weight, *xyz, *bmw, *offsets;
+    FrameOut rows(int64_t r0, int S, int B) const {
+        const bool diag = weights != nullptr;
+        auto at = [](float* p, bool on, int64_t off) { return on ? p + off : nullptr; };
+        return FrameOut{rgb + 3 * r0, alpha + r0, depth + r0, at(weights, diag, r0 * S), at(rgb_on_rays, diag, r0 * S * 3),
+                        at(cnl_xyz, diag, 3 * r0), at(cnl_rgb, diag, 3 * r0), at(cnl_weight, diag, r0),
+                        at(xyz, diag, r0 * S * 3), at(bmw, bmw != nullptr, r0 * S * B), at(offsets, diag, r0 * S * 3)};
+    }
+};
 
-// hnrf_sample_warp_share_fwd (hnrf_sample_warp.hip: K1 with the classification fused in, 24 bones) without the
-// argument checks of the share part and without zeroing *count.
-int sample_warp_share(const float* rays_o, const float* rays_d, const float* near, const float* far, const float* t_rand,
-                      const float* motion_Rs, const float* motion_Ts, const float* vol, const float* bbox_min,
-                      const float* bbox_scale, int64_t R, int S, int G, float* z_vals, float* x_skel, float* fg_mask,
-                      float* bmw, const float* c_off, const float* c_xyz, const float* c_raw, int* idx, int* count,
-                      float* offsets, float* xyz, float* raw, hipStream_t st);
+// hnrf_sample_warp_fwd (hnrf_sample_warp.hip) on the bundles, R rays of S samples.  sh != null: the fused
+// classification, hnrf_sample_warp_share_fwd without the argument checks of the share part and without zeroing
+// *sh->count (f.B must be 24: the caller's to check).
+struct ShareOut;              // hnrf_block_scan.h
+int sample_warp(const Rays& rays, const WarpField& f, int64_t R, int S, float* z_vals, float* x_skel, float* fg_mask,
+                float* bmw, const ShareOut* sh, hipStream_t st);
+
+// hnrf_share_compact (hnrf_sample_warp.hip) without the argument checks and without zeroing *sh.count: the frame entry
+// zeroes its per-chunk counts once.
+int share_compact(const float* x_skel, int64_t P, const ShareOut& sh, hipStream_t st);
 
 // Opt a kernel into > 64 KiB of dynamic LDS, once per device of this process (`done`: one bit per device id;
 // the attribute is per device, and a process may drive more than one).

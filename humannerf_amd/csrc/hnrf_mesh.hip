@@ -20,7 +20,7 @@
 // counterpart of K1's inverse warp on the same volume.
 #include <math.h>
 
-#include "hnrf_common.h"
+#include "hnrf_block_scan.h"
 
 namespace hnrf {
 namespace {
@@ -124,30 +124,6 @@ __global__ __launch_bounds__(kThreads) void density_epilogue_kernel(
 }
 
 // ---- marching tetrahedra -------------------------------------------------------------------------------------------
-// Exclusive prefix of v over the block's threads (in thread order); *total = the block's sum.  Integer sums: the
-// result does not depend on the order of the additions.
-__device__ __forceinline__ int block_exclusive_scan(int v, int* total) {
-    __shared__ int wave_sum[kThreads / kWave];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    int incl = v;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const int u = __shfl_up(incl, d, kWave);
-        if (lane >= d) incl += u;
-    }
-    if (lane == kWave - 1) wave_sum[wave] = incl;
-    __syncthreads();
-    int before = 0, sum = 0;
-#pragma unroll
-    for (int w = 0; w < kThreads / kWave; ++w) {
-        before += (w < wave) ? wave_sum[w] : 0;
-        sum += wave_sum[w];
-    }
-    __syncthreads();                          // (wave_sum is reused by the next call)
-    *total = sum;
-    return before + incl - v;
-}
-
 struct Cell {
     unsigned inside;    // bit c: corner c of the cell at p is inside (corners outside the lattice: 0)
     unsigned valid;     // bit c: corner c exists

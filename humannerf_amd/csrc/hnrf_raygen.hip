@@ -12,9 +12,9 @@
 // produced in HBM in pixel order (the order Network.forward and the image unpack rely on).
 //
 // Three launches: (1) hit flag per pixel + per-block counts, (2) exclusive scan of the block counts
-// (one block), (3) recompute + write at block offset + rank (ballot / popcount).  HBM-bound: 1 B (mask)
+// (one block), (3) recompute + write at block offset + rank (block_rank).  HBM-bound: 1 B (mask)
 // + 32 B per kept ray written, nothing read but 30 scalars.
-#include "hnrf_common.h"
+#include "hnrf_block_scan.h"
 
 namespace hnrf {
 
@@ -86,7 +86,6 @@ __device__ __forceinline__ Cam load_cam(const float* kinv, const float* R, const
 __global__ __launch_bounds__(256) void raygen_mask_kernel(const float* kinv, const float* R, const float* T,
                                                           const float* bmin, const float* bmax, int H, int W,
                                                           uint8_t* __restrict__ ray_mask, int* __restrict__ blk_cnt) {
-    __shared__ int wave_tot[4];
     const Cam c = load_cam(kinv, R, T, bmin, bmax);
     const int p = blockIdx.x * 256 + threadIdx.x;
     bool hit = false;
@@ -94,10 +93,9 @@ __global__ __launch_bounds__(256) void raygen_mask_kernel(const float* kinv, con
         hit = make_ray(c, p % W, p / W).hit;
         ray_mask[p] = hit ? 1 : 0;
     }
-    const unsigned long long bal = __ballot(hit);
-    if ((threadIdx.x & 63) == 0) wave_tot[threadIdx.x >> 6] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    int total;
+    (void)block_rank(hit, &total);
+    if (threadIdx.x == 0) blk_cnt[blockIdx.x] = total;
 }
 
 // exclusive scan of n block counts in place; total -> *count.  One block of 1024 threads.
@@ -129,19 +127,15 @@ __global__ __launch_bounds__(256) void raygen_emit_kernel(const float* kinv, con
                                                           const int* __restrict__ blk_off, float* __restrict__ rays_o,
                                                           float* __restrict__ rays_d, float* __restrict__ near,
                                                           float* __restrict__ far) {
-    __shared__ int wave_tot[4];
     const Cam c = load_cam(kinv, R, T, bmin, bmax);
     const int p = blockIdx.x * 256 + threadIdx.x;
     Ray r;
     r.hit = false;
     if (p < H * W) r = make_ray(c, p % W, p / W);
-    const unsigned long long bal = __ballot(r.hit);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) wave_tot[wave] = __popcll(bal);
-    __syncthreads();
+    int total;
+    const int rank = block_rank(r.hit, &total);
     if (!r.hit) return;
-    int idx = blk_off[blockIdx.x] + __popcll(bal & ((1ull << lane) - 1ull));
-    for (int w = 0; w < wave; ++w) idx += wave_tot[w];
+    const int idx = blk_off[blockIdx.x] + rank;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         rays_o[(int64_t)idx * 3 + k] = r.o[k];

@@ -10,7 +10,7 @@
 // Memory: the weight volume (24 x 32^3 fp32 = 3.1 MB) is L2-resident; the 8
 // corner gathers per bone are the dominant traffic (768 B of cache traffic per
 // sample).  HBM traffic per sample is 4 B (z) + 12 B (x_skel) + 4 B (mask) out.
-#include "hnrf_common.h"
+#include "hnrf_block_scan.h"
 
 namespace hnrf {
 
@@ -27,17 +27,9 @@ __device__ __forceinline__ float z_at(float nr, float fr, int s, int S) {
     return nr * (1.0f - t) + fr * t;
 }
 
-// SHARE: what the block does with its x_skel while it still has it in registers (hnrf_sample_warp_share_fwd, hnrf.h):
-// the predicate of hnrf_share_compact decides shared / live, the live samples go onto the chunk's list and the shared
-// rows get the representative's results.  offsets / xyz nullable (the lean form).  *count must be 0 before the first
-// block runs.
-struct ShareOut {
-    const float *c_off, *c_xyz, *c_raw;
-    int *idx, *count;
-    float4* raw;
-    float *offsets, *xyz;
-};
-
+// SHARE: the block classifies its samples while it still has their x_skel in registers (share_classify;
+// hnrf_sample_warp_share_fwd, hnrf.h): one atomic per block, issued while the CU's other resident blocks are in their
+// bone loops, instead of a second pass whose blocks do little else than wait for theirs.
 // BT: the bone count as a compile-time constant (24 = the SMPL skeleton of every config of the reference; 0 = read B at
 // run time).  With BT the four-bone trips lose their per-bone `b < B` branches.
 template <bool WRITE_BMW, int BT, bool SHARE = false>
@@ -167,41 +159,7 @@ __global__ __launch_bounds__(256) void sample_warp_kernel(
         x_skel[p * 3 + 2] = xs[2];
         fg_mask[p] = wsum;
     }
-    if constexpr (SHARE) {
-        // share_compact_kernel's classification and list, on the values just stored: one atomic per block, issued while
-        // the CU's other resident blocks are in their bone loops, instead of a second pass whose blocks do little else
-        // than wait for theirs
-        __shared__ int wave_tot[4];
-        __shared__ int block_base;
-        bool shared = in_range;
-#pragma unroll
-        for (int a = 0; a < 3; ++a)        // (a NaN fails the first comparison: always live); the sum is K2's own `x + offset`
-            shared &= fabsf(xs[a]) <= HNRF_SHARE_T && __float_as_uint(xs[a] + sh.c_off[a]) == __float_as_uint(sh.c_xyz[a]);
-        const bool keep = in_range && !shared;
-        const unsigned long long bal = __ballot(keep);
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        const int before = __popcll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_tot[wave] = __popcll(bal);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            const int tot = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-            block_base = tot ? atomicAdd(sh.count, tot) : 0;
-        }
-        __syncthreads();
-        int off = block_base + before;
-        for (int w = 0; w < wave; ++w) off += wave_tot[w];
-        if (keep) sh.idx[off] = (int)p;
-        if (shared) {
-            sh.raw[p] = make_float4(sh.c_raw[0], sh.c_raw[1], sh.c_raw[2], sh.c_raw[3]);
-            if (sh.offsets) {
-#pragma unroll
-                for (int a = 0; a < 3; ++a) {
-                    sh.offsets[p * 3 + a] = sh.c_off[a];
-                    sh.xyz[p * 3 + a] = sh.c_xyz[a];
-                }
-            }
-        }
-    }
+    if constexpr (SHARE) share_classify(in_range, p, xs, sh);
     if (bmw4) {                                        // (block-uniform: no thread has left the kernel)
         __syncthreads();
         const int64_t base = (int64_t)blockIdx.x * 256;
@@ -221,72 +179,29 @@ __global__ __launch_bounds__(256) void sample_warp_kernel(
 // eps = 0 keeps everything.  Order: block-contiguous runs, blocks in arrival order (irrelevant to the MLPs).
 __global__ __launch_bounds__(256) void compact_kernel(const float* __restrict__ fg_mask, float eps, int64_t P,
                                                       int* __restrict__ idx, int* __restrict__ count) {
-    __shared__ int wave_tot[4];
-    __shared__ int block_base;
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool keep = p < P && fg_mask[p] >= eps;
-    const unsigned long long bal = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) block_base = atomicAdd(count, wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3]);
-    __syncthreads();
-    int off = block_base + before;
-    for (int w = 0; w < wave; ++w) off += wave_tot[w];
-    if (keep) idx[off] = (int)p;
+    const int slot = block_append(keep, count);
+    if (keep) idx[slot] = (int)p;
 }
 
 // Samples whose K2 / K3 inputs underflow to those of x_skel = (+0, +0, +0) (the predicate: hnrf.h, hnrf_share_compact):
 // such a sample's offsets / xyz / raw are the representative's c_off / c_xyz / c_raw bit for bit, so they are written
-// here and the MLPs run on the rest, idx[0..count) in compact_kernel's order.  *count must be 0 at launch.
-// offsets / xyz nullable (the lean form reads neither).
-__global__ __launch_bounds__(256) void share_compact_kernel(const float* __restrict__ x_skel, const float* __restrict__ c_off,
-                                                            const float* __restrict__ c_xyz, const float* __restrict__ c_raw,
-                                                            int64_t P, int* __restrict__ idx, int* __restrict__ count,
-                                                            float* __restrict__ offsets, float* __restrict__ xyz,
-                                                            float4* __restrict__ raw) {
-#pragma clang fp contract(off)
-    __shared__ int wave_tot[4];
-    __shared__ int block_base;
+// here and the MLPs run on the rest, idx[0..count) in compact_kernel's order.
+__global__ __launch_bounds__(256) void share_compact_kernel(const float* __restrict__ x_skel, int64_t P, ShareOut sh) {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    bool shared = p < P;
-    if (shared) {
+    const bool in_range = p < P;
+    float x[3] = {0.f, 0.f, 0.f};
+    if (in_range) {
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const float x = x_skel[p * 3 + a];
-            // (a NaN fails the first comparison: always live); the sum is K2's own `x + offset`, one rounded fp32 add
-            shared &= fabsf(x) <= HNRF_SHARE_T && __float_as_uint(x + c_off[a]) == __float_as_uint(c_xyz[a]);
-        }
+        for (int a = 0; a < 3; ++a) x[a] = x_skel[p * 3 + a];
     }
-    const bool keep = p < P && !shared;
-    const unsigned long long bal = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) block_base = atomicAdd(count, wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3]);
-    __syncthreads();
-    int off = block_base + before;
-    for (int w = 0; w < wave; ++w) off += wave_tot[w];
-    if (keep) idx[off] = (int)p;
-    if (shared) {
-        raw[p] = make_float4(c_raw[0], c_raw[1], c_raw[2], c_raw[3]);
-        if (offsets) {
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                offsets[p * 3 + a] = c_off[a];
-                xyz[p * 3 + a] = c_xyz[a];
-            }
-        }
-    }
+    share_classify(in_range, p, x, sh);
 }
 
-int share_compact(const float* x_skel, const float* c_off, const float* c_xyz, const float* c_raw, int64_t P, int* idx,
-                  int* count, float* offsets, float* xyz, float* raw, hipStream_t st) {
+int share_compact(const float* x_skel, int64_t P, const ShareOut& sh, hipStream_t st) {
     if (P == 0) return HNRF_OK;
-    hipLaunchKernelGGL(share_compact_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, x_skel, c_off, c_xyz, c_raw,
-                       P, idx, count, offsets, xyz, (float4*)raw);
+    hipLaunchKernelGGL(share_compact_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, x_skel, P, sh);
     return check_launch("hnrf_share_compact");
 }
 
@@ -304,7 +219,7 @@ extern "C" int hnrf_share_compact(const float* x_skel, const float* c_off, const
         set_error("hnrf_share_compact: memset failed");
         return HNRF_E_LAUNCH;
     }
-    return share_compact(x_skel, c_off, c_xyz, c_raw, P, idx, count, offsets, xyz, raw, st);
+    return share_compact(x_skel, P, ShareOut{c_off, c_xyz, c_raw, idx, count, (float4*)raw, offsets, xyz}, st);
 }
 
 extern "C" int hnrf_compact_samples(const float* fg_mask, float eps, int64_t P, int* idx, int* count, void* stream) {
@@ -322,14 +237,11 @@ extern "C" int hnrf_compact_samples(const float* fg_mask, float eps, int64_t P, 
 }
 
 namespace hnrf {
-// hnrf_sample_warp_fwd; sh != null: the fused classification (24 bones only, the caller's to check; *sh->count zeroed
-// by the caller)
-int sample_warp(const float* rays_o, const float* rays_d, const float* near, const float* far, const float* t_rand,
-                const float* motion_Rs, const float* motion_Ts, const float* vol, const float* bbox_min,
-                const float* bbox_scale, int64_t R, int S, int B, int G, float* z_vals, float* x_skel, float* fg_mask,
+int sample_warp(const Rays& rays, const WarpField& f, int64_t R, int S, float* z_vals, float* x_skel, float* fg_mask,
                 float* bmw, const ShareOut* sh, hipStream_t st) {
     const char* who = sh ? "hnrf_sample_warp_share_fwd" : "hnrf_sample_warp_fwd";
-    HNRF_REQUIRE(rays_o && rays_d && near && far && motion_Rs && motion_Ts && vol && bbox_min && bbox_scale,
+    const int B = f.B, G = f.G;
+    HNRF_REQUIRE(rays.o && rays.d && rays.near && rays.far && f.Rs && f.Ts && f.vol && f.bbox_min && f.bbox_scale,
                  HNRF_E_ARG, "%s: null input pointer", who);
     HNRF_REQUIRE(z_vals && x_skel && fg_mask, HNRF_E_ARG, "%s: null output pointer", who);
     HNRF_REQUIRE(R >= 0 && S >= 2 && B >= 1 && G >= 2 && G <= 1024, HNRF_E_ARG,
@@ -342,24 +254,14 @@ int sample_warp(const float* rays_o, const float* rays_d, const float* near, con
     HNRF_REQUIRE(blocks < (int64_t)2147483647, HNRF_E_ARG, "%s: too many samples", who);
     const ShareOut so = sh ? *sh : ShareOut{};
 #define HNRF_K1(W, BT_, SH_)                                                                                          \
-    hipLaunchKernelGGL((sample_warp_kernel<W, BT_, SH_>), dim3((unsigned)blocks), dim3(256), 0, st, rays_o, rays_d, near, \
-                       far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, P, S, B, G, z_vals, x_skel, fg_mask, \
-                       bmw, so)
+    hipLaunchKernelGGL((sample_warp_kernel<W, BT_, SH_>), dim3((unsigned)blocks), dim3(256), 0, st, rays.o, rays.d,  \
+                       rays.near, rays.far, rays.t_rand, f.Rs, f.Ts, f.vol, f.bbox_min, f.bbox_scale, P, S, B, G,     \
+                       z_vals, x_skel, fg_mask, bmw, so)
     if (sh) { if (bmw) HNRF_K1(true, 24, true); else HNRF_K1(false, 24, true); }
     else if (bmw) { if (B == 24) HNRF_K1(true, 24, false); else HNRF_K1(true, 0, false); }
     else { if (B == 24) HNRF_K1(false, 24, false); else HNRF_K1(false, 0, false); }
 #undef HNRF_K1
     return check_launch(who);
-}
-
-int sample_warp_share(const float* rays_o, const float* rays_d, const float* near, const float* far, const float* t_rand,
-                      const float* motion_Rs, const float* motion_Ts, const float* vol, const float* bbox_min,
-                      const float* bbox_scale, int64_t R, int S, int G, float* z_vals, float* x_skel, float* fg_mask,
-                      float* bmw, const float* c_off, const float* c_xyz, const float* c_raw, int* idx, int* count,
-                      float* offsets, float* xyz, float* raw, hipStream_t st) {
-    const ShareOut sh{c_off, c_xyz, c_raw, idx, count, (float4*)raw, offsets, xyz};
-    return sample_warp(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, R, S, 24, G,
-                       z_vals, x_skel, fg_mask, bmw, &sh, st);
 }
 }  // namespace hnrf
 
@@ -370,8 +272,9 @@ extern "C" int hnrf_sample_warp_fwd(const float* rays_o, const float* rays_d,
                                     int64_t R, int S, int B, int G,
                                     float* z_vals, float* x_skel, float* fg_mask, float* bmw,
                                     void* stream) {
-    return hnrf::sample_warp(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, R, S, B, G,
-                             z_vals, x_skel, fg_mask, bmw, nullptr, (hipStream_t)stream);
+    using namespace hnrf;
+    return sample_warp(Rays{rays_o, rays_d, near, far, t_rand}, WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G},
+                       R, S, z_vals, x_skel, fg_mask, bmw, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int hnrf_sample_warp_share_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
@@ -392,6 +295,7 @@ extern "C" int hnrf_sample_warp_share_fwd(const float* rays_o, const float* rays
         set_error("%s: memset failed", who);
         return HNRF_E_LAUNCH;
     }
-    return sample_warp_share(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, R, S, G,
-                             z_vals, x_skel, fg_mask, bmw, c_off, c_xyz, c_raw, idx, count, offsets, xyz, raw, st);
+    const ShareOut sh{c_off, c_xyz, c_raw, idx, count, (float4*)raw, offsets, xyz};
+    return sample_warp(Rays{rays_o, rays_d, near, far, t_rand}, WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G},
+                       R, S, z_vals, x_skel, fg_mask, bmw, &sh, st);
 }

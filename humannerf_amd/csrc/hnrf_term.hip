@@ -7,10 +7,10 @@
 // arithmetic (term_eps = 0 never takes this path; the default path evaluates everything).
 //
 // The samples are walked in depth slabs of `SS` samples: per slab (1) the samples of still-alive rays that also
-// pass the foreground-likelihood cut are compacted (ballot / popcount, count stays on the device), (2) K2 and K3
+// pass the foreground-likelihood cut are compacted (block_append, count stays on the device), (2) K2 and K3
 // run in their sparse forms on that list, (3) the slab is composited into per-ray running sums and the running
 // transmittance.  2 rays per wavefront (32 samples each), segmented product scan.
-#include "hnrf_common.h"
+#include "hnrf_block_scan.h"
 
 namespace hnrf {
 
@@ -28,8 +28,6 @@ __global__ __launch_bounds__(256) void compact_slab_kernel(const float* __restri
                                                            const float* __restrict__ st, float cull_eps,
                                                            float term_eps, int64_t R, int S, int s0, int ss,
                                                            int* __restrict__ idx, int* __restrict__ count) {
-    __shared__ int wave_tot[4];
-    __shared__ int block_base;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     bool keep = false;
     int64_t p = 0;
@@ -38,16 +36,8 @@ __global__ __launch_bounds__(256) void compact_slab_kernel(const float* __restri
         p = r * S + s0 + (int)(i - r * ss);
         keep = st[r * 6] >= term_eps && fg_mask[p] >= cull_eps;
     }
-    const unsigned long long bal = __ballot(keep);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int before = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(bal);
-    __syncthreads();
-    if (threadIdx.x == 0) block_base = atomicAdd(count, wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3]);
-    __syncthreads();
-    int off = block_base + before;
-    for (int w = 0; w < wave; ++w) off += wave_tot[w];
-    if (keep) idx[off] = (int)p;
+    const int slot = block_append(keep, count);
+    if (keep) idx[slot] = (int)p;
 }
 
 // One slab of <= 32 samples of one ray per half-wave: alpha from raw where the sample was evaluated (same
@@ -144,6 +134,8 @@ extern "C" int hnrf_render_rays_term_fwd(const float* rays_o, const float* rays_
                                          const float* bgcolor, int mode, float cull_eps, float term_eps, int64_t R,
                                          int S, int B, int G, void* workspace, size_t workspace_bytes, float* rgb,
                                          float* alpha, float* depth, int* evaluated, void* stream) {
+    const Rays rays{rays_o, rays_d, near, far, t_rand};
+    const WarpField field{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G};
     HNRF_REQUIRE(workspace && cnl_packed && rgb && alpha && depth, HNRF_E_ARG, "hnrf_render_rays_term_fwd: null pointer");
     HNRF_REQUIRE(((uintptr_t)workspace & 255) == 0, HNRF_E_ARG, "hnrf_render_rays_term_fwd: workspace must be 256-byte aligned");
     HNRF_REQUIRE(workspace_bytes >= hnrf_render_term_workspace_bytes(R, S), HNRF_E_WORKSPACE,
@@ -157,8 +149,7 @@ extern "C" int hnrf_render_rays_term_fwd(const float* rays_o, const float* rays_
     const RenderCarve c = render_carve(workspace, R, S);
     float* st = (float*)((char*)workspace + c.bytes);
     hipStream_t stq = (hipStream_t)stream;
-    int rc = hnrf_sample_warp_fwd(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
-                                  R, S, B, G, c.z_vals, c.x_skel, c.mask, nullptr, stream);
+    int rc = sample_warp(rays, field, R, S, c.z_vals, c.x_skel, c.mask, nullptr, nullptr, stq);
     if (rc) return rc;
     hipLaunchKernelGGL(term_init_kernel, dim3((unsigned)((R * 6 + 255) / 256)), dim3(256), 0, stq, st, R);
     if (evaluated && hipMemsetAsync(evaluated, 0, sizeof(int), stq) != hipSuccess) {

@@ -213,6 +213,23 @@ def _render_args(operands, workspace, need, grow=True):
     return args, workspace
 
 
+def _lean_out(R, dev):
+    return {'rgb': torch.empty(R, 3, device=dev), 'alpha': torch.empty(R, device=dev), 'depth': torch.empty(R, device=dev)}
+
+
+def _render_entry(lib, kind, args, baked, baked_nr, share=False):
+    """The hnrf_render_<kind>*_fwd entry that goes with the grids, its name, and the pointers of ``args`` (rays_o ..
+    bgcolor) with the grids' arguments in the place of cnl_packed (``baked``) and of hann_w, nr_packed (``baked_nr``).
+    ``share`` names hnrf_render_frame_shared_fwd whatever the grids are: render_frame refuses the two together."""
+    stem, ptrs, dev = '', list(map(_ptr, args)), args[0].device
+    if baked is not None:
+        stem, ptrs[12:13] = '_baked', _baked_args(baked, dev)
+    if baked_nr is not None:
+        stem, ptrs[10:12] = '_baked_nr', _baked_args(baked_nr, dev)
+    name = f'hnrf_render_{kind}{"_shared" if share else stem}_fwd'
+    return getattr(lib, name), name, ptrs
+
+
 def render_rays(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
                 hann_w, nr_packed, cnl_packed, bgcolor, n_samples, mode='f32', workspace=None, out=None,
                 mlp_events=None, cull_eps=0.0, baked=None, baked_nr=None):
@@ -230,23 +247,15 @@ def render_rays(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bb
     args, workspace = _render_args((rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
                                     hann_w, nr_packed, cnl_packed, bgcolor), workspace,
                                    lib.hnrf_render_workspace_bytes(R, S), grow=False)
-    dev = rays_o.device
     if out is None:
-        out = {'rgb': torch.empty(R, 3, device=dev), 'alpha': torch.empty(R, device=dev),
-               'depth': torch.empty(R, device=dev)}
+        out = _lean_out(R, rays_o.device)
     ev = (0, 0)
     if mlp_events is not None:
         for e in mlp_events:
             if not e.cuda_event:
                 e.record()            # forces creation of the hipEvent_t
         ev = (mlp_events[0].cuda_event, mlp_events[1].cuda_event)
-    fn, name, ptrs = lib.hnrf_render_rays_fwd, 'hnrf_render_rays_fwd', list(map(_ptr, args))
-    if baked is not None:
-        fn, name = lib.hnrf_render_rays_baked_fwd, 'hnrf_render_rays_baked_fwd'
-        ptrs[12:13] = _baked_args(baked, dev)
-    if baked_nr is not None:
-        fn, name = lib.hnrf_render_rays_baked_nr_fwd, 'hnrf_render_rays_baked_nr_fwd'
-        ptrs[10:12] = _baked_args(baked_nr, dev)
+    fn, name, ptrs = _render_entry(lib, 'rays', args, baked, baked_nr)
     _lib.check(fn(*ptrs, _mode_arg(mode), float(cull_eps), R, S, motion_Rs.shape[0],
                   vol.shape[-1], _ptr(workspace), workspace.numel() * workspace.element_size(),
                   _ptr(out['rgb']), _ptr(out['alpha']), _ptr(out['depth']), ev[0], ev[1], _stream()), name)
@@ -311,17 +320,8 @@ def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, b
             a.record()
             b.record()
         mlp_arr = (ctypes.c_void_p * (2 * nchunk))(*[e.cuda_event for p in pairs for e in p])
-    fn, name, ptrs = lib.hnrf_render_frame_fwd, 'hnrf_render_frame_fwd', list(map(_ptr, args))
-    if baked is not None:
-        fn, name = lib.hnrf_render_frame_baked_fwd, 'hnrf_render_frame_baked_fwd'
-        ptrs[12:13] = _baked_args(baked, dev)
-    if baked_nr is not None:
-        fn, name = lib.hnrf_render_frame_baked_nr_fwd, 'hnrf_render_frame_baked_nr_fwd'
-        ptrs[10:12] = _baked_args(baked_nr, dev)
-    live = ()
-    if share:
-        fn, name = lib.hnrf_render_frame_shared_fwd, 'hnrf_render_frame_shared_fwd'
-        live = (torch.empty(max(1, -(-N // chunk)), dtype=torch.int32, device=dev),)
+    fn, name, ptrs = _render_entry(lib, 'frame', args, baked, baked_nr, share)
+    live = (torch.empty(max(1, -(-N // chunk)), dtype=torch.int32, device=dev),) if share else ()
     _lib.check(fn(
         *ptrs, _mode_arg(mode), float(cull_eps), N, S, B, G, chunk, _ptr(workspace),
         workspace.numel() * workspace.element_size(), g('rgb'), g('alpha'), g('depth'),
@@ -351,9 +351,8 @@ def render_rays_term(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vo
     args, workspace = _render_args((rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
                                     hann_w, nr_packed, cnl_packed, bgcolor), workspace,
                                    lib.hnrf_render_term_workspace_bytes(R, S))
-    dev = rays_o.device
-    out = {'rgb': torch.empty(R, 3, device=dev), 'alpha': torch.empty(R, device=dev), 'depth': torch.empty(R, device=dev)}
-    ev = torch.empty(1, dtype=torch.int32, device=dev) if want_count else None
+    out = _lean_out(R, rays_o.device)
+    ev = torch.empty(1, dtype=torch.int32, device=rays_o.device) if want_count else None
     _lib.check(lib.hnrf_render_rays_term_fwd(*map(_ptr, args), _mode_arg(mode), float(cull_eps), float(term_eps), R, S,
                                              motion_Rs.shape[0], vol.shape[-1], _ptr(workspace),
                                              workspace.numel() * workspace.element_size(), _ptr(out['rgb']),

@@ -224,12 +224,29 @@ def _compact(mask_np, eps):
     return idx[1:1 + P].cpu().numpy(), int(count.item())
 
 
-@pytest.mark.parametrize('P', [0, 1, 63, 64, 65, 255, 256, 257, 100003])
-def test_compaction_sets_counts_and_bounds(P):
-    """Exact index set and count; nothing written at or past idx[count]; a NaN entry is never kept."""
-    rs = np.random.RandomState(P)
-    m = rs.uniform(0, 1, P).astype(np.float32)
-    m[::7] = 0
+def _empty_block_mask():
+    """769 samples of which eps = 0.5 keeps all of block 0, none of block 1 (it issues no atomic), three scattered ones of
+    block 2 and the one sample of block 3."""
+    m = np.zeros(769, np.float32)
+    m[:256] = 1
+    m[[512 + 5, 512 + 64, 512 + 255, 768]] = 1
+    return m
+
+
+COMPACT_SIZES = [0, 1, 63, 64, 65, 255, 256, 257, 100003]
+
+
+@pytest.mark.parametrize('P,mask', [(P, None) for P in COMPACT_SIZES] + [(769, _empty_block_mask())],
+                         ids=[str(P) for P in COMPACT_SIZES] + ['empty-block'])
+def test_compaction_sets_counts_and_bounds(P, mask):
+    """Exact index set and count; nothing written at or past idx[count]; a NaN entry is never kept.  mask None: random
+    values with every seventh zero."""
+    if mask is not None:
+        m = mask.copy()
+    else:
+        rs = np.random.RandomState(P)
+        m = rs.uniform(0, 1, P).astype(np.float32)
+        m[::7] = 0
     if P:
         m[P // 2] = np.nan
     nan = np.isnan(m)

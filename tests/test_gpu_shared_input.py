@@ -134,6 +134,35 @@ def test_predicate_kernel_against_twin(lean):
             assert bool((got[lv] == 7.0).all()), k                 # live rows are the MLPs' to write
 
 
+@pytest.mark.parametrize('lean', [False, True])
+def test_predicate_kernel_with_an_all_shared_block(lean):
+    """P = 769: block 1 is entirely shared -- an empty block of the list, which issues no atomic -- between block 0
+    (both classes), block 2 (three live samples) and block 3 (its one sample, live).  Against the numpy twin."""
+    vals = np.array([0.0, -0.0, 1e-45, -1e-45, 2.0 ** -40, -2.0 ** -40], dtype=F)
+    x = vals[np.random.RandomState(769).randint(0, vals.size, size=(769, 3))]   # every row shared: c absorbs these ...
+    x[:256:3] = F(2.0 ** -20)                                      # ... but these: live
+    x[[512 + 5, 512 + 64, 512 + 255, 768]] = F(1e-3)
+    c = np.array([-0.0686608, -0.00916304, 0.06966332], F)         # an offset of the seeded network's size
+    cx = (np.zeros(3, F) + c).astype(F)
+    c_raw = G(np.array([0.25, -1.5, 3.0, -0.0], dtype=F))
+    m = si.shared_mask(x, c, cx)
+    assert m[256:512].all() and 0 < m[:256].sum() < 256 and (~m[512:768]).sum() == 3 and not m[768]
+    idx, count, out = _share_compact(G(x), G(c), G(cx), c_raw, lean)
+    live = si.live_indices(x, c, cx)
+    assert count == live.size == 86 + 3 + 1
+    assert np.array_equal(np.sort(idx[:count]), live)
+    assert (idx[count:] == -1).all()
+    sh, lv = G(m), G(~m)
+    assert torch.equal(bits(out['raw'][sh]), bits(c_raw)[None].expand(int(m.sum()), -1))
+    assert bool((out['raw'][lv] == 7.0).all())
+    for k, want in (('offsets', G(c)), ('xyz', G(cx))):
+        if lean:
+            assert bool((out[k] == 7.0).all()), k
+        else:
+            assert torch.equal(bits(out[k][sh]), bits(want)[None].expand(int(m.sum()), -1)), k
+            assert bool((out[k][lv] == 7.0).all()), k
+
+
 # ------------------------------------------------------------------------------------- 3. end to end, on against off
 KEYS11 = ('rgb', 'alpha', 'depth', 'weights_on_rays', 'rgb_on_rays', 'cnl_xyz', 'cnl_rgb', 'cnl_weight', 'xyz_on_rays',
           'backward_motion_weights', 'offsets')

@@ -51,12 +51,54 @@ def test_abi_exports_every_declared_symbol():
         text = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
     declared = set(re.findall(r'\b(hnrf_[a-z0-9_]+)\s*\(', text))
     assert declared == set(_lib.SIGNATURES), declared ^ set(_lib.SIGNATURES)
+    assert len(_lib.SIGNATURES) == 88
+    # the types, written out for entries of every shape: _lib derives them from the header's declarations
+    import ctypes
+    vp, i64, i, sz, f, d = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_size_t, ctypes.c_float,
+                            ctypes.c_double)
+    want = {
+        'hnrf_last_error': (ctypes.c_char_p, []),
+        'hnrf_render_workspace_bytes': (sz, [i64, i]),
+        'hnrf_compact_samples': (i, [vp, f, i64, vp, vp, vp]),
+        'hnrf_mlp_dw': (i, [vp, i64, vp, i64, i64, i, i, i, vp, i, vp, i64, vp, vp, sz, vp]),
+        'hnrf_image_metrics': (i, [vp, vp, vp, i, i, i, d, vp, sz, vp, vp]),
+        'hnrf_raster_mesh': (i, [vp, i64, vp, i64, vp, vp, vp, vp, vp, i, i, f, i, vp, vp, vp, vp, vp, sz, vp]),
+        'hnrf_render_rays_baked_nr_fwd': (i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, vp, vp, vp, i, vp, vp, vp, i,
+                                              f, i64, i, i, i, vp, sz, vp, vp, vp, vp, vp, vp]),
+        'hnrf_render_frame_shared_fwd': (i, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i, f, i64, i, i, i,
+                                             i64, vp, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    }
+    for name, sig in want.items():
+        assert _lib.SIGNATURES[name] == sig, name
     lib = _lib.load()
     for name in declared:
         assert hasattr(lib, name)
     assert lib.hnrf_abi_version() == 13
     assert lib.hnrf_canonical_packed_bytes(0) > 1 << 20
     assert lib.hnrf_render_workspace_bytes(4, 128) >= 4 * 128 * 44
+
+
+def test_header_parser_never_guesses():
+    """_lib.parse_header: a type it does not know raises and names the declaration; a declaration over several lines
+    and a pointer to const pointers parse."""
+    import ctypes
+    from humannerf_amd import _lib
+    with pytest.raises(_lib.HnrfError, match=r'unsigned.*hnrf_bad\(const float\* x, unsigned n\)'):
+        _lib.parse_header('int hnrf_bad(const float* x, unsigned n);')
+    with pytest.raises(_lib.HnrfError, match='hnrf_bad_ret'):
+        _lib.parse_header('void hnrf_bad_ret(int n);')
+    got = _lib.parse_header("""
+        /* int hnrf_commented(int a); */
+        #define HNRF_X 1   // int hnrf_also_commented(int a);
+        size_t hnrf_split(const float* const* w,   /* [n] */
+                          void* const* events, int64_t P,
+                          double r,
+                          void* stream);
+        const char* hnrf_text(void);
+    """)
+    vp = ctypes.c_void_p
+    assert got == {'hnrf_split': (ctypes.c_size_t, [vp, vp, ctypes.c_int64, ctypes.c_double, vp]),
+                   'hnrf_text': (ctypes.c_char_p, [])}
 
 
 def test_abi_argument_errors_do_not_need_a_gpu():

@@ -79,3 +79,7 @@ def test_case_has_the_classes_it_claims(seeded_params, e2e_frame, representative
         assert any(mixed)
     if case == 'frame':
         assert abs(float(m.mean()) - 0.42) < 0.02
+        # whole blocks of shared samples between blocks that list some: a block that appends nothing (and issues no
+        # atomic) must leave the runs of its neighbours alone, and this window shows it
+        live = [int((~m[b:b + 256]).sum()) for b in range(0, m.size, 256)]
+        assert any(n == 0 and any(live[:i]) and any(live[i + 1:]) for i, n in enumerate(live))
