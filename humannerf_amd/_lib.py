@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HNRF_LIB_PATH', os.path.join(_HERE, 'libhnrf.so'))   # override: diagnostic builds only
 
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf.h'))
+CLOUD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_cloud.h'))   # included by hnrf.h
 
 _SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float,
             'double': ctypes.c_double}
@@ -49,16 +50,19 @@ def parse_header(text):
     return sigs
 
 
-def _signatures():
+def _signatures(path=HEADER_PATH):
     try:
-        with open(HEADER_PATH) as f:
+        with open(path) as f:
             return parse_header(f.read())
     except OSError as e:
-        raise HnrfError(f'{HEADER_PATH}: cannot read the C ABI declarations ({e})') from None
+        raise HnrfError(f'{path}: cannot read the C ABI declarations ({e})') from None
 
 
 # name -> (restype, argtypes), derived from the declarations of include/hnrf.h
 SIGNATURES = _signatures()
+# the surface-point / frame-distance entries of include/hnrf_cloud.h: additive to ABI version 13, so a library of that
+# version built before them (HNRF_LIB_PATH) still loads; load_cloud() binds them and raises when they are missing
+CLOUD_SIGNATURES = _signatures(CLOUD_HEADER_PATH)
 
 _lib = None
 
@@ -86,6 +90,26 @@ def load():
         fn.restype = res
         fn.argtypes = args
     _lib = lib
+    return lib
+
+
+_cloud_bound = False
+
+
+def load_cloud():
+    """load() plus the entries of include/hnrf_cloud.h, typed.  A library without them raises HnrfError."""
+    global _cloud_bound
+    lib = load()
+    if not _cloud_bound:
+        for name, (res, args) in CLOUD_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise HnrfError(f'{LIB_PATH} does not export {name}: it was built before the surface-point and '
+                                f'frame-distance kernels (include/hnrf_cloud.h); rebuild it') from None
+            fn.restype = res
+            fn.argtypes = args
+        _cloud_bound = True
     return lib
 
 

@@ -1235,3 +1235,76 @@ def image_metrics(pred8, target8, mask=None, data_range=1.0):
         _lib.check(lib.hnrf_image_metrics(pred8.data_ptr(), target8.data_ptr(), _ptr(mask), n, H, W, float(data_range),
                                           ws.data_ptr(), ws.numel() * 4, out.data_ptr(), _stream()), 'hnrf_image_metrics')
     return out
+
+
+# ------------------------------------------------------------------------------- surface points and frame distance
+def _chk_dev(t, dtype, what):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous()):
+        raise _lib.HnrfError('%s must be a contiguous %s tensor on the GPU, got %s' % (
+            what, dtype, (t.dtype, t.device, tuple(t.shape)) if torch.is_tensor(t) else type(t)))
+
+
+def surface_points(weights, xyz, bmw):
+    """hnrf_surface_points: weights (R, S), xyz (R, S, 3), bmw (R, S, B) -> wxyz (R, 3), wmax (R,), lbs (R,) int32."""
+    lib = _lib.load_cloud()
+    _chk(weights, xyz, bmw)
+    if weights.dim() != 2 or xyz.shape != weights.shape + (3,) or bmw.dim() != 3 or bmw.shape[:2] != weights.shape:
+        raise _lib.HnrfError('surface_points: weights (R, S), xyz (R, S, 3), bmw (R, S, B) expected, got %s %s %s'
+                             % (tuple(weights.shape), tuple(xyz.shape), tuple(bmw.shape)))
+    R, S = weights.shape
+    dev = weights.device
+    wxyz, wmax = torch.empty(R, 3, device=dev), torch.empty(R, device=dev)
+    lbs = torch.empty(R, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        _lib.check(lib.hnrf_surface_points(_ptr(weights), _ptr(xyz), _ptr(bmw), R, S, int(bmw.shape[2]), _ptr(wxyz),
+                                           _ptr(wmax), _ptr(lbs), _stream()), 'hnrf_surface_points')
+    return wxyz, wmax, lbs
+
+
+def cloud_nn(a, b, idx=None, d2=None):
+    """hnrf_cloud_nn: a (Na, 3), b (Nb, 3) -> idx (Na,) int32, d2 (Na,): the nearest neighbour of every a in b (brute
+    force; ties to the lowest index).  ``idx`` / ``d2``: outputs of at least Na elements to write into."""
+    lib = _lib.load_cloud()
+    _chk(a, b, d2)
+    if a.dim() != 2 or a.shape[1] != 3 or b.dim() != 2 or b.shape[1] != 3:
+        raise _lib.HnrfError('cloud_nn: clouds must be (N, 3), got %s and %s' % (tuple(a.shape), tuple(b.shape)))
+    Na, Nb = a.shape[0], b.shape[0]
+    idx = torch.empty(Na, dtype=torch.int32, device=a.device) if idx is None else idx
+    d2 = torch.empty(Na, device=a.device) if d2 is None else d2
+    _chk_dev(idx, torch.int32, 'cloud_nn: idx')
+    if idx.numel() < Na or d2.numel() < Na:
+        raise _lib.HnrfError('cloud_nn: outputs of %d / %d elements for %d points' % (idx.numel(), d2.numel(), Na))
+    with torch.cuda.device(a.device):
+        _lib.check(lib.hnrf_cloud_nn(_ptr(a), Na, _ptr(b), Nb, _ptr(idx), _ptr(d2), _stream()), 'hnrf_cloud_nn')
+    return idx, d2
+
+
+def cloud_distance_pairs(xyz, rgb, orig, offsets, pairs, tau, axis, max_n, want_match=False):
+    """hnrf_cloud_distance_pairs on packed, per-frame sorted clouds (include/hnrf_cloud.h): xyz, rgb (total, 3), orig
+    (total,) int32, offsets (F + 1,) int64, pairs (P, 2) int32, all on the GPU; ``max_n`` >= every frame's count.
+    Returns D (P,) float64 and, with ``want_match``, match (P, max_n) int32 (else None)."""
+    lib = _lib.load_cloud()
+    _chk(xyz, rgb)
+    _chk_dev(orig, torch.int32, 'cloud_distance_pairs: orig')
+    _chk_dev(offsets, torch.int64, 'cloud_distance_pairs: offsets')
+    _chk_dev(pairs, torch.int32, 'cloud_distance_pairs: pairs')
+    total = xyz.shape[0]
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or rgb.shape != xyz.shape or orig.shape != (total,):
+        raise _lib.HnrfError('cloud_distance_pairs: xyz, rgb (total, 3) and orig (total,) expected, got %s %s %s'
+                             % (tuple(xyz.shape), tuple(rgb.shape), tuple(orig.shape)))
+    if offsets.dim() != 1 or offsets.numel() < 1 or pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise _lib.HnrfError('cloud_distance_pairs: offsets (F + 1,) and pairs (P, 2) expected, got %s %s'
+                             % (tuple(offsets.shape), tuple(pairs.shape)))
+    F, P, max_n = offsets.numel() - 1, pairs.shape[0], int(max_n)
+    dev = xyz.device
+    D = torch.empty(P, dtype=torch.float64, device=dev)
+    match = torch.empty(P, max_n, dtype=torch.int32, device=dev) if want_match else None
+    with torch.cuda.device(dev):
+        need = lib.hnrf_cloud_distance_pairs_workspace_bytes(P, max_n)
+        if need == 0:
+            raise _lib.HnrfError('cloud_distance_pairs: %d pairs of at most %d points out of range' % (P, max_n))
+        ws = _aligned(need, dev)
+        _lib.check(lib.hnrf_cloud_distance_pairs(_ptr(xyz), _ptr(rgb), _ptr(orig), _ptr(offsets), F, total, _ptr(pairs), P,
+                                                 max_n, int(axis), float(tau), ws.data_ptr(), ws.numel() * 4, _ptr(D),
+                                                 _ptr(match), _stream()), 'hnrf_cloud_distance_pairs')
+    return D, match

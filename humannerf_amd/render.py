@@ -271,6 +271,7 @@ class ImageWriter:
         self.frame_idx = -1
         self.keep = keep_frames
         self.images_np, self.image_names = [], []
+        self.name_3d_together = {}
         self._q = queue.Queue(maxsize=4 * workers)
         self._err = []
         self._threads = [threading.Thread(target=self._work, daemon=True) for _ in range(workers)]
@@ -317,6 +318,10 @@ class ImageWriter:
         with open(os.path.join(self.obj_dir, obj_name + '.obj'), 'w') as f:
             f.writelines('v %.7f %.7f %.7f %.7f %.7f %.7f \n' % (*xyz, *rgb) for xyz, rgb in zip(cnl_xyz, cnl_rgb))
 
+    def append_3d_together(self, name, data):
+        """One frame's [N, 10] record tensor (moved to the host here), kept until finalize."""
+        self.name_3d_together[name] = torch.as_tensor(data).detach().cpu()
+
     def finalize(self, video_name=None):
         for _ in self._threads:
             self._q.put(None)
@@ -324,6 +329,9 @@ class ImageWriter:
             t.join()
         if self._err:
             raise self._err[0]
+        if self.name_3d_together:
+            self.path_3d_together = os.path.join(self.output_dir, 'name-2-3d.bin')
+            torch.save(self.name_3d_together, self.path_3d_together)
         if self.keep and self.images_np:
             order = sorted(range(len(self.images_np)), key=lambda i: self.image_names[i])
             stack = np.stack([self.images_np[i] for i in order], axis=0)

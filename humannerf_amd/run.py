@@ -11,6 +11,9 @@ render.ImageWriter / MetricsWriter on worker threads.
   run_tpose      run.py:178-183   the canonical pose on a turntable, non-rigid motion off
   run_mesh       (no counterpart) the canonical body as a coloured triangle mesh, and that mesh skinned into frames
   run_mesh_render (no counterpart) the movement / freeview / tpose sequences as rasterised pictures of that mesh: a preview
+  run_surface_points  run.py:388-404   cfg.test.save_3d_together: one canonical surface point per ray of every movement
+                                  frame, collected as ``name-2-3d.bin``
+  run_distance_matrix tools/compute_distance*.py   the frame x frame appearance distance of those records
 
 Output layout as in the reference: ``<logdir>/<load_net><eval_output_tag>/<folder>/NAME.png`` plus
 ``<folder>-metrics.perimg.txt / .average.txt`` (movement) and the stacked frames (MP4 when imageio is importable).
@@ -263,3 +266,74 @@ def run_mesh_render(network, subject, kind='movement', resolution=256, level=Non
         deliver(pending.pop(0))
     stack = writer.finalize()
     return {'frames': list(range(n)), 'images': images, 'image_dir': writer.image_dir, 'stack': stack}
+
+
+def run_surface_points(network, subject, weight_threshold=None, render_folder_name='movement', logdir=None, rank=0,
+                       world=1, device=None, test_num=-1):
+    """run.py:388-404 (cfg.test.save_3d_together) over the movement frames: one forward per frame with the eleven
+    outputs (cfg.amd.diagnostics is switched on for the loop), cloud.surface_records on them, and the records of this
+    rank's frames (rank, rank + world, ...) written by ImageWriter.finalize as ``<out>/name-2-3d.bin`` -- with
+    world > 1 ``name-2-3d.rank<r>.bin``, to be merged by the caller.  The dict is keyed by the frame name as the
+    subject's frame list has it, like the reference's.  ``weight_threshold``: None = cfg.test.weight_threshold, and
+    0.3 (the reference's configs/default.yaml:285) where the configuration has no such key.
+    Returns {'frames', 'records': {name: CPU tensor [N, 10]}, 'path'}."""
+    import torch
+    from . import cloud
+    device = device or next(network.parameters()).device
+    if weight_threshold is None:
+        weight_threshold = (cfg.get('test', None) or {}).get('weight_threshold', 0.3)
+    n = len(subject) if test_num < 0 else min(test_num, len(subject))
+    frames = _Frames(n, lambda i: subject.movement_frame(i, load_image=True, device=device))
+    own = list(range(rank, n, world))
+    writer = render.ImageWriter(_output_dir(logdir), render_folder_name, workers=1, keep_frames=False)
+    amd = cfg.get('amd', None)
+    old_perturb, had_diag, old_diag = cfg.perturb, amd is not None and 'diagnostics' in amd, (amd or {}).get('diagnostics')
+    cfg.perturb = 0.                                                   # run.py:214
+    if amd is not None:
+        amd['diagnostics'] = True
+    network.eval()
+    pre = render.FramePrefetcher(frames, own, device, show_truth=True)
+    try:
+        for item in pre:
+            with torch.no_grad():
+                out = network(**item['data'], iter_val=float(cfg.eval_iter))
+            rec = cloud.surface_records(out, item['truth'], item['ray_index'], item['W'], weight_threshold)
+            writer.append_3d_together(str(subject.framelist[item['idx']]), rec)
+    finally:
+        pre.close()
+        cfg.perturb = old_perturb
+        if had_diag:
+            amd['diagnostics'] = old_diag
+        elif amd is not None:
+            amd.pop('diagnostics', None)
+    records = dict(writer.name_3d_together)
+    writer.finalize()
+    path = getattr(writer, 'path_3d_together', None)
+    if path is not None and world > 1:
+        ranked = path[:-len('.bin')] + '.rank%d.bin' % rank
+        os.replace(path, ranked)
+        path = ranked
+    return {'frames': own, 'records': records, 'path': path}
+
+
+def run_distance_matrix(records_or_path, valid_weight_threshold=0.3, dist_thresh=0.002, chunk=(0, 1), method='window',
+                        axis=None, logdir=None, out_dir=None, backend='hip', device=None):
+    """The main loop of tools/compute_distance*.py on ``name-2-3d.bin`` (a path, or the dict it holds):
+    cloud.distance_matrix, saved as ``<out_dir>/distance_mat/distance_mat_{vwt:.2f}-{tau:.2f}[.{chunk_id}-{chunk_n}].npy``
+    -- the reference's names, so that its cluster.py reads the file.  ``out_dir``: None = the directory of the records
+    file, or the run's output directory for a dict.  Returns {'matrix', 'path', 'names'}."""
+    from . import cloud
+    records = records_or_path
+    if isinstance(records_or_path, (str, os.PathLike)):
+        import torch
+        records = torch.load(records_or_path, map_location='cpu')
+        if out_dir is None:
+            out_dir = os.path.dirname(os.path.abspath(records_or_path))
+    if out_dir is None:
+        out_dir = _output_dir(logdir)
+    D = cloud.distance_matrix(records, valid_weight_threshold=valid_weight_threshold, dist_thresh=dist_thresh, chunk=chunk,
+                              method=method, axis=axis, backend=backend, device=device)
+    path = os.path.join(out_dir, 'distance_mat', cloud.matrix_file_name(valid_weight_threshold, dist_thresh, chunk))
+    os.makedirs(os.path.dirname(path), exist_ok=True)
+    np.save(path, D)
+    return {'matrix': D, 'path': path, 'names': sorted(records.keys())}

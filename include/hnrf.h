@@ -761,6 +761,11 @@ size_t hnrf_image_metrics_workspace_bytes(int n_img, int H, int W);
 int hnrf_image_metrics(const uint8_t* pred, const uint8_t* target, const uint8_t* mask, int n_img, int H, int W,
                        double data_range, void* workspace, size_t workspace_bytes, double* out, void* stream);
 
+/* ---- Surface points and frame distance ---- one canonical surface point per ray (run.py:388-404, save_3d_together),
+ * the brute-force nearest neighbour of two point clouds, and the batched, windowed frame x frame appearance distance of
+ * tools/compute_distance*.py.  Additive to ABI version 13; contracts and declarations in hnrf_cloud.h. */
+#include "hnrf_cloud.h"
+
 #ifdef __cplusplus
 }
 #endif
