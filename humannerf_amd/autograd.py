@@ -150,8 +150,7 @@ class RenderRays(torch.autograd.Function):
     With ``diag`` the other keys of the reference's return dict (network.py:776-789) come out too, as
     non-differentiable tensors, in OUTPUT_KEYS order."""
 
-    OUTPUT_KEYS = ('rgb', 'alpha', 'depth', 'weights_on_rays', 'rgb_on_rays', 'cnl_xyz', 'cnl_rgb', 'cnl_weight',
-                   'xyz_on_rays', 'backward_motion_weights', 'offsets')
+    OUTPUT_KEYS = tuple(ops.output_shapes(0, 0))
 
     @staticmethod
     def forward(ctx, rays_o, rays_d, near, far, t_rand, bbox_min, bbox_scale, hann_w, cond, bg, n_samples,

@@ -29,6 +29,7 @@ import torch.nn.functional as F
 from . import ops
 from .autograd import RenderRays
 from .config import cfg, amd_option, check_amd_options
+from .range_guard import ActivationRangeError, InferenceRangeGuard     # noqa: F401  (the error's importers look here)
 
 SMPL_PARENT = [-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16,
                17, 18, 19, 20, 21]          # core/utils/network_util.py:91-94
@@ -434,6 +435,23 @@ def _versions(params):
     return tuple((p.data_ptr(), p._version) for p in params)
 
 
+def _resident(tensors):
+    """What _still_resident recognises ``tensors`` by later: a weak reference and the ``_version`` of each."""
+    return tuple((weakref.ref(t), t._version) for t in tensors)
+
+
+def _still_resident(refs, tensors):
+    """True when ``tensors`` are the very objects ``refs`` = _resident(...) was built from, unwritten since: a driver
+    that keeps its per-subject tensors on the device hits without a look at their values, i.e. without a host
+    synchronisation.  Equal values in other objects do not count: the caller compares those once, or not at all."""
+    return refs is not None and len(refs) == len(tensors) \
+        and all(r() is t and v == t._version for (r, v), t in zip(refs, tensors))
+
+
+def _vec3(a, dev):
+    return torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(3).contiguous()
+
+
 # --------------------------------------------------------------------------- network
 def _node(root, path, default=None):
     cur = root
@@ -480,12 +498,6 @@ def check_config_is_built(config):
                                   '(SURVEY.md section 2.1): ' + '; '.join(bad))
 
 
-class ActivationRangeError(RuntimeError):
-    """A hidden activation of one of the two MLPs left the range in which the split-f16 arithmetic is fp32-accurate
-    (|x| >= 128, hnrf.h; the kernels clamp at 65504): the frames rendered with these weights in mlp_mode 'f16x3' are not
-    the network's output."""
-
-
 class Network(nn.Module):
     def __init__(self):
         super().__init__()
@@ -508,13 +520,8 @@ class Network(nn.Module):
                 mlp_depth=cfg.pose_decoder.mlp_depth, total_bones=cfg.total_bones)
         self._cnl_pack = None     # (key, packed image)
         self._nr_pack_buf = None
-        # f16-range guard of inference (the training side has autograd.OperandRangeGuard): pinned copy of the two
-        # images' status words, the event behind it, and the mode forced after a hit with cfg.amd.on_f16_range = 'f32'
-        self._range_watch = None
-        self._guard_state = None    # [canonical pack key, frames rendered with it]: the audit schedule of _guard_plan
-        self._forced_mode = None
-        self.f16_range_hits = self.f16_range_watched = self.f16_range_checked = 0
-        self._vol_cache = None    # (key, priors, volume)
+        self.f16_guard = InferenceRangeGuard()
+        self._vol_cache = None    # (key, priors, volume, _resident((priors,)))
         # baked canonical grid (cfg.amd.canonical = 'baked'): dict(grid, bmin, bmax, key, injected, refs) or None;
         # bake_count counts the bakes this network ran
         self._baked = None
@@ -541,92 +548,34 @@ class Network(nn.Module):
 
     # packed-weight caches ----------------------------------------------------
     def _mlp_mode(self):
-        return self._forced_mode or amd_option('mlp_mode', 'f16x3')
+        return self.f16_guard.mode()
 
-    # f16-range guard ---------------------------------------------------------
-    def _guard_plan(self, mode, n_chunks):
-        """Which ray chunks of this frame run the GUARDED kernel instances (cfg.amd.f16_range_guard; the guard costs
-        3 % of the frame).  'full': all.  'off': none.  'audit' (default): all chunks of the first frame after the
-        weights changed -- a checkpoint that does not fit the f16 range shows on its first frame -- then one chunk per
-        frame, rotating, so that every region of the image and every pose is sampled as a sequence goes on.
-        Returns (mode string for hnrf_render_frame_fwd, set of guarded chunk numbers or None = all)."""
-        if mode != 'f16x3':
-            return mode, None
-        policy = amd_option('f16_range_guard', 'audit')
-        if policy == 'full':
-            return mode, None
-        if policy == 'off':
-            return mode + '+noguard', set()
-        key = self._cnl_pack[0] if self._cnl_pack is not None else None
-        if self._guard_state is None or self._guard_state[0] != key:
-            self._guard_state = [key, 0]
-        frame_no = self._guard_state[1]
-        self._guard_state[1] += 1
-        if frame_no == 0:
-            return mode, None
-        k = (frame_no - 1) % max(1, n_chunks)
-        return mode + '+guard1:%d' % k, {k}
-
-    def _watch_f16_range(self, cnl_packed, nr_packed, mode):
-        """Called after a frame's inference kernels are queued: copies the two images' status words into a pinned slot
-        -- behind the kernels in stream order, in front of the next frame's pack, which zeroes the non-rigid image's
-        word -- and notes the event behind the copy.  Nothing waits: check_f16_range looks at the slots whose copy has
-        landed (Network.forward does at its start, i.e. one frame late when the host keeps up with the GPU)."""
-        words = [ops.status_word(cnl_packed, 'canonical', mode),
-                 None if nr_packed is None else ops.status_word(nr_packed, 'nonrigid', mode)]
-        if words[0] is None and words[1] is None:
-            return
-        if self._range_watch is None:
-            import collections
-            self._range_watch = {'pending': collections.deque(), 'free': []}
-        w = self._range_watch
-        host = w['free'].pop() if w['free'] else torch.zeros(2, dtype=torch.int32).pin_memory()
-        host.zero_()
-        for i, word in enumerate(words):
-            if word is not None:
-                host[i:i + 1].copy_(word, non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        w['pending'].append((host, ev))
-        self.f16_range_watched += 1
+    # f16-range guard (range_guard.InferenceRangeGuard) ------------------------
+    f16_range_hits = property(lambda self: self.f16_guard.hits)
+    f16_range_watched = property(lambda self: self.f16_guard.watched)
+    f16_range_checked = property(lambda self: self.f16_guard.checked)
 
     def check_f16_range(self, wait=True, upto=None):
-        """Act on the status words of the watched frames whose copies have landed (``wait``: of all watched frames,
-        blocking -- render loops call this once after their last frame; ``upto``: block only until the first ``upto``
-        watched frames have their verdict).  ``f16_range_checked`` counts the frames whose verdict is known.  Returns
-        True when one of them left the range."""
-        w = self._range_watch
-        if w is None:
-            return False
-        cnl_hit = nr_hit = 0
-        while w['pending']:
-            host, ev = w['pending'][0]
-            if not ev.query():
-                if not wait or (upto is not None and self.f16_range_checked >= upto):
-                    break
-                ev.synchronize()
-            w['pending'].popleft()
-            self.f16_range_checked += 1
-            cnl_hit |= int(host[0])
-            nr_hit |= int(host[1])
-            w['free'].append(host)
-        if not (cnl_hit or nr_hit):
-            return False
-        self.f16_range_hits += 1
-        self._cnl_pack = None                                   # (a fresh pack clears the canonical image's word)
-        policy = amd_option('on_f16_range', 'raise')
-        msg = ("a hidden activation of the %s MLP left the range of the split-f16 arithmetic (|x| >= 128) in mlp_mode "
-               "'f16x3': the frames rendered with these weights are not the network's output to fp32 accuracy; render "
-               "with cfg.amd.mlp_mode = 'f32'"
-               % (' and the '.join(n for n, h in (('canonical', cnl_hit), ('non-rigid', nr_hit)) if h)))
-        if policy == 'ignore':
-            return True
-        if policy == 'f32':
-            import warnings
-            warnings.warn(msg + " -- switching this network to 'f32' (cfg.amd.on_f16_range = 'f32')")
-            self._forced_mode = 'f32'
-            return True
-        raise ActivationRangeError(msg)
+        """Act on the verdicts of the watched frames (InferenceRangeGuard.check, then its policy step ``act``; render
+        loops call this once after their last frame).  Returns True when one of them left the range."""
+        hit = self.f16_guard.check(wait, upto)
+        if any(hit):
+            self._cnl_pack = None                               # (a fresh pack clears the canonical image's word)
+        return self.f16_guard.act(*hit)
+
+    def _canonical_pass(self, op):
+        """``op(packed canonical image, mode)`` of a canonical-MLP pass outside forward, with its status word acted on
+        exactly as forward does (cfg.amd.on_f16_range: raise, warn and switch to 'f32', or ignore): after a hit that
+        forced another mode the pass runs again in that mode, so the result returned is one of _mlp_mode().  Waits
+        for the device."""
+        while True:
+            mode, packed = self._mlp_mode(), self._canonical_packed()
+            res = op(packed, mode)
+            if mode != 'f16x3':
+                return res
+            self.f16_guard.watch(packed, None, mode)
+            if not (self.check_f16_range(wait=True) and self._mlp_mode() != mode):
+                return res
 
     def _canonical_packed(self):
         lin = self.cnl_mlp.module.linears()
@@ -653,20 +602,42 @@ class Network(nn.Module):
                 and self._vol_cache[1].shape == priors.shape:
             # same tensor object as last frame (a driver that keeps the priors resident): no comparison, no host
             # synchronisation; a fresh tensor is compared by value (one device round trip per frame)
-            ref, ver = self._vol_cache[3]
-            if ref() is priors and ver == priors._version:
+            if _still_resident(self._vol_cache[3], (priors,)):
                 return self._vol_cache[2]
             if torch.equal(self._vol_cache[1], priors):
                 # equal by value: remember THIS tensor, so that the frames that follow hit by identity (a render loop
                 # uploads the subject's priors once per loop; comparing every frame blocked the host for a whole frame)
-                self._vol_cache = self._vol_cache[:3] + ((weakref.ref(priors), priors._version),)
+                self._vol_cache = self._vol_cache[:3] + (_resident((priors,)),)
                 return self._vol_cache[2]
         vol = self.mweight_vol_decoder(motion_weights_priors=priors[None])[0].contiguous()
         if use_cache:
-            self._vol_cache = (key, priors.clone(), vol, (weakref.ref(priors), priors._version))
+            self._vol_cache = (key, priors.clone(), vol, _resident((priors,)))
         return vol
 
     # forward -------------------------------------------------------------------
+    def _refines_pose(self, iter_val):
+        return iter_val >= cfg.pose_decoder.get('kick_in_iter', 0) and not cfg.get('pose_decoder_off', False)
+
+    def _conditioning(self, dst_posevec, iter_val, dev, want_device_hann, want_rvec=True, want_hann=True):
+        """What a frame's pose vector (fp32 on ``dev``) and ``iter_val`` make of the two motion models: (rvec, cond,
+        hann_host, hann_w, nr_inputs_are_zero) -- the pose refiner's axis-angle corrections (23, 3) from its kick-in on
+        (network.py:667-688; None before it or without ``want_rvec``), the non-rigid MLP's condition code (zeroed below
+        non_rigid_motion_mlp.kick_in_iter, network.py:735-737), the Hann window on the host and, with
+        ``want_device_hann``, on the device (both None without ``want_hann``), and whether the MLP is fed zeros at every
+        sample.  Nothing is read back from the device."""
+        rvec = self.pose_decoder.rvec(dst_posevec[None]) if want_rvec and self._refines_pose(iter_val) else None
+        nr_cfg = cfg.non_rigid_motion_mlp
+        below = iter_val < nr_cfg.kick_in_iter
+        cond = torch.zeros_like(dst_posevec) * dst_posevec if below else dst_posevec
+        hann_host = hann_w = None
+        if want_hann:
+            hann_host = hann_window_weights(iter_val, nr_cfg.multires, nr_cfg.kick_in_iter, nr_cfg.full_band_iter)
+            if want_device_hann:
+                # through pinned memory: a pageable host-to-device copy waits for everything queued on the stream, i.e.
+                # it would synchronise host and GPU once per training step / frame
+                hann_w = hann_host.pin_memory().to(dev, non_blocking=True) if dev.type == 'cuda' else hann_host.to(dev)
+        return rvec, cond, hann_host, hann_w, want_hann and below and float(hann_host.abs().max()) == 0.0
+
     def forward(self, rays, dst_Rs, dst_Ts, cnl_gtfms, motion_weights_priors, dst_posevec=None,
                 near=None, far=None, iter_val=1e7, cnl_bbox_min_xyz=None, cnl_bbox_scale_xyz=None,
                 bgcolor=None, t_rand=None, **kwargs):
@@ -674,7 +645,7 @@ class Network(nn.Module):
         stratified-sampling uniforms (parity tests); unknown kwargs are ignored
         like the reference's **kwargs."""
         train_path = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
-        if self._range_watch is not None and self._range_watch['pending']:
+        if self.f16_guard.pending:
             self.check_f16_range(wait=False)       # the previous frames' f16-range verdicts (may switch the mode, or raise)
         iter_val = float(iter_val)
         dev = dst_Rs.device
@@ -683,132 +654,119 @@ class Network(nn.Module):
         dst_Rs, dst_Ts, dst_posevec = f32(dst_Rs), f32(dst_Ts), f32(dst_posevec)
         cnl_gtfms, priors = f32(cnl_gtfms), f32(motion_weights_priors)
 
-        # pose refinement (network.py:667-688)
-        rvec = None
-        if iter_val >= cfg.pose_decoder.get('kick_in_iter', 0) and not cfg.get('pose_decoder_off', False):
-            rvec = self.pose_decoder.rvec(dst_posevec[None])              # (23,3); Rodrigues + correction: motion_basis
-
         ignore_nr = bool(cfg.ignore_non_rigid_motions)
-        nr_cfg = cfg.non_rigid_motion_mlp
-        cond = dst_posevec
-        if iter_val < nr_cfg.kick_in_iter:
-            cond = torch.zeros_like(cond) * cond                            # network.py:735-737
-        motion_Rs, motion_Ts = motion_basis(dst_Rs, dst_Ts, cnl_gtfms, rvec)
-        vol = self._weight_volume(priors)
-        self.motion_weights_vol = vol
-        if train_path and self.grad_sync is not None:
-            vol = self.grad_sync.volume_hook(vol, priors)
-
         mode = self._mlp_mode()
         canonical, nonrigid, _ = check_amd_options()      # (ValueError: unknown values, 'baked' offsets without a grid)
         # the offsets come from the frame's offset grid: no per-frame pack and no window upload unless it is (re)baked
         nr_from_grid = nonrigid == 'baked' and not train_path and not ignore_nr
-        nr_packed, cnl_packed, hann_w, hann_host = None, None, None, None
-        self._nr_inputs_are_zero = False
-        if not ignore_nr:
-            hann_host = hann_window_weights(iter_val, nr_cfg.multires, nr_cfg.kick_in_iter, nr_cfg.full_band_iter)
-            self._nr_inputs_are_zero = iter_val < nr_cfg.kick_in_iter and float(hann_host.abs().max()) == 0.0
-            if not nr_from_grid:
-                # through pinned memory: a pageable host-to-device copy waits for everything queued on the stream, i.e.
-                # it would synchronise host and GPU once per training step / frame
-                hann_w = hann_host.pin_memory().to(dev, non_blocking=True) if dev.type == 'cuda' else hann_host.to(dev)
+        rvec, cond, hann_host, hann_w, nr_inputs_are_zero = self._conditioning(
+            dst_posevec, iter_val, dev, not nr_from_grid, want_hann=not ignore_nr)
+        motion_Rs, motion_Ts = motion_basis(dst_Rs, dst_Ts, cnl_gtfms, rvec)   # (Rodrigues + correction: in there)
+        vol = self._weight_volume(priors)
+        self.motion_weights_vol = vol
+        if train_path and self.grad_sync is not None:
+            vol = self.grad_sync.volume_hook(vol, priors)
+        nr_packed, cnl_packed = None, None
         if not train_path:
             cnl_packed = self._canonical_packed()
             if not ignore_nr and not nr_from_grid:
                 nr_packed = self._nonrigid_packed(cond)
 
-        rays_o, rays_d = rays[0], rays[1]
-        rays_shape = rays_d.shape
-        rays_o = f32(rays_o).reshape(-1, 3).contiguous()
-        rays_d = f32(rays_d).reshape(-1, 3).contiguous()
-        N = rays_o.shape[0]
-        near = f32(near).reshape(-1).contiguous()
-        far = f32(far).reshape(-1).contiguous()
-        bbox_min = f32(cnl_bbox_min_xyz).contiguous()
-        bbox_scale = f32(cnl_bbox_scale_xyz).contiguous()
-        bg = f32(bgcolor).contiguous()
-        S = int(cfg.N_samples)
+        rays_shape = rays[1].shape
+        rays_o = f32(rays[0]).reshape(-1, 3).contiguous()
+        rays_d = f32(rays[1]).reshape(-1, 3).contiguous()
+        N, S = rays_o.shape[0], int(cfg.N_samples)
         if cfg.perturb > 0.:
             if t_rand is None:
                 t_rand = torch.rand(N, S, device=dev)                       # network.py:468
             t_rand = f32(t_rand).reshape(N, S).contiguous()
         else:
             t_rand = None
+        per_ray = (rays_o, rays_d, f32(near).reshape(-1).contiguous(), f32(far).reshape(-1).contiguous(), t_rand)
+        per_frame = (motion_Rs, motion_Ts, vol, f32(cnl_bbox_min_xyz).contiguous(), f32(cnl_bbox_scale_xyz).contiguous(),
+                     hann_w)
+        bg = f32(bgcolor).contiguous()
         diag = bool(amd_option('diagnostics', True))
+        term_eps = float(amd_option('term_eps', 0.0))
         if N == 0:
             # a camera that does not see the subject's bbox (the reference's chunk loop, network.py:330-352, has nothing
             # to concatenate then and raises; a render loop should get its background image): the 11 keys, empty
-            shp = {'rgb': (3,), 'alpha': (), 'depth': ()}
-            if diag or train_path:
-                shp.update(weights_on_rays=(S,), rgb_on_rays=(S, 3), cnl_xyz=(3,), cnl_rgb=(3,), cnl_weight=(),
-                           xyz_on_rays=(S, 3), backward_motion_weights=(S, self.total_bones), offsets=(S, 3))
             zero = sum(p.sum() for p in self.parameters() if p.requires_grad) * 0.0 if train_path else None
             out = {k: torch.zeros((0,) + v, device=dev) + (zero if zero is not None and k in ('rgb', 'alpha', 'depth') else 0.0)
-                   for k, v in shp.items()}
-            return {k: v.reshape(list(rays_shape[:-1]) + list(v.shape[1:])) for k, v in out.items()}
-
-        term_eps = float(amd_option('term_eps', 0.0))
-        baked, baked_nr = None, None
-        if canonical == 'baked' and not train_path:          # (training ignores the option: _render_rays_train)
-            if not diag and term_eps > 0.0:
-                raise NotImplementedError("cfg.amd.term_eps > 0 with cfg.amd.canonical = 'baked': early ray termination "
-                                          "has no baked form (hnrf_render_rays_term_fwd runs the canonical MLP)")
-            baked = self._baked_for_frame(cnl_bbox_min_xyz, kwargs.get('cnl_bbox_max_xyz'), cnl_bbox_scale_xyz)
-            if nr_from_grid:
-                # over the canonical grid's box; nr_baked_on: the image this frame's bake ran on (its status word is
-                # watched below), None when the grid of the last frame still holds
-                baked_nr, nr_baked_on = self._baked_nr_for_frame(posevec_arg, iter_val, hann_host, baked[1], baked[2])
-        if not train_path and (diag or term_eps == 0.0):
-            # inference: the whole frame in one library call -- chunk loop of network.py:330-352, results straight into
-            # whole-frame tensors (the reference concatenates per-chunk results: one more pass over 17 KB per ray);
-            # optionally K1 of the next chunk on a side stream under the MLP kernels of the current one
-            # (cfg.amd.overlap_warp).  With diagnostics on, term_eps is ignored: early termination has no 11-output form
-            gmode, guarded = self._guard_plan(mode, -(-N // int(cfg.chunk)))
-            cull_eps = 0.0 if diag else float(amd_option('cull_eps', 0.0))
-            # one evaluation for the samples whose inputs underflow to those of x_skel = 0 (hnrf.h, hnrf_share_compact;
-            # its threshold assumes Hann weights <= 1: checked on the host copy, nothing waits for the device)
-            share = (bool(amd_option('share_underflow', True)) and mode == 'f16x3' and nr_packed is not None
-                     and baked is None and cull_eps == 0.0 and float(hann_host.max()) <= 1.0)
-            share_log = [] if share else None
-            out, self._workspace = ops.render_frame(
-                rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w, nr_packed,
-                cnl_packed, bg, S, int(cfg.chunk), gmode, diagnostics=diag,
-                cull_eps=cull_eps, workspace=self._workspace,
-                overlap=bool(amd_option('overlap_warp', False)), mlp_event_log=self.mlp_event_log, baked=baked,
-                baked_nr=baked_nr, share_log=share_log)
-            self._share_last = share_log[0] if share else None
-            if mode == 'f16x3' and guarded != set():
-                self._watch_f16_range(cnl_packed, nr_packed if baked_nr is None else nr_baked_on, mode)
+                   for k, v in ops.output_shapes(S, self.total_bones, diag or train_path).items()}
+        elif train_path:
+            out = self._forward_chunks(per_ray, per_frame, bg, S, mode, diag,
+                                       train=(cond, not ignore_nr, nr_inputs_are_zero))
         else:
-            # per ray chunk (network.py:333): training (autograd.RenderRays), or the lean inference path with early ray
-            # termination (hnrf_render_rays_term_fwd, one workspace for every chunk)
-            chunk = int(cfg.chunk)
-            chunks = []
-            guarded = None
-            self._share_last = None
-            if not train_path:
-                _, guarded = self._guard_plan(mode, -(-N // chunk))
-                need = ops.render_term_workspace_bytes(min(chunk, N), S) // 4 + 64
-                if self._workspace is None or self._workspace.numel() < need or self._workspace.device != rays_o.device:
-                    self._workspace = torch.empty(need, device=rays_o.device)
-            for ci, i in enumerate(range(0, N, chunk)):
-                sl = slice(i, min(i + chunk, N))
-                tr = None if t_rand is None else t_rand[sl]
-                if train_path:
-                    chunks.append(self._render_rays_train(rays_o[sl], rays_d[sl], near[sl], far[sl], tr, motion_Rs,
-                                                          motion_Ts, vol, bbox_min, bbox_scale, hann_w, cond, bg, S,
-                                                          not ignore_nr, diag))
-                    continue
-                chunks.append(ops.render_rays_term(rays_o[sl], rays_d[sl], near[sl], far[sl], tr, motion_Rs, motion_Ts,
-                                                   vol, bbox_min, bbox_scale, hann_w, nr_packed, cnl_packed, bg, S,
-                                                   mode if guarded is None or ci in guarded else mode + '+noguard',
-                                                   term_eps=term_eps, cull_eps=float(amd_option('cull_eps', 0.0)),
-                                                   workspace=self._workspace))
-            out = {k: (torch.cat([c[k] for c in chunks], 0) if len(chunks) > 1 else chunks[0][k]) for k in chunks[0]}
-            if not train_path and mode == 'f16x3' and guarded != set():
-                self._watch_f16_range(cnl_packed, nr_packed, mode)
+            baked, baked_nr, nr_baked_on = None, None, None
+            if canonical == 'baked':                             # (training ignores the option: _render_rays_train)
+                if not diag and term_eps > 0.0:
+                    raise NotImplementedError("cfg.amd.term_eps > 0 with cfg.amd.canonical = 'baked': early ray termination "
+                                              "has no baked form (hnrf_render_rays_term_fwd runs the canonical MLP)")
+                baked = self._baked_for_frame(cnl_bbox_min_xyz, kwargs.get('cnl_bbox_max_xyz'), cnl_bbox_scale_xyz)
+                if nr_from_grid:
+                    # over the canonical grid's box; nr_baked_on: the image this frame's bake ran on (its status word is
+                    # watched by _forward_frame), None when the grid of the last frame still holds
+                    baked_nr, nr_baked_on = self._baked_nr_for_frame(posevec_arg, iter_val, hann_host, baked[1], baked[2])
+            if diag or term_eps == 0.0:    # (with diagnostics on, term_eps is ignored: early termination has no 11-output form)
+                out = self._forward_frame(per_ray, per_frame, nr_packed, cnl_packed, bg, S, mode, diag, hann_host,
+                                          baked, baked_nr, nr_baked_on)
+            else:
+                out = self._forward_chunks(per_ray, per_frame, bg, S, mode, diag, packs=(nr_packed, cnl_packed),
+                                           term_eps=term_eps)
         lead = list(rays_shape[:-1])
         return {k: v.reshape(lead + list(v.shape[1:])) for k, v in out.items()}
+
+    def _guard_plan(self, mode, n_rays):
+        return self.f16_guard.plan(mode, -(-n_rays // int(cfg.chunk)), None if self._cnl_pack is None else self._cnl_pack[0])
+
+    def _forward_frame(self, per_ray, per_frame, nr_packed, cnl_packed, bg, S, mode, diag, hann_host, baked, baked_nr,
+                       nr_baked_on):
+        """Inference, the whole frame in one library call -- chunk loop of network.py:330-352, results straight into
+        whole-frame tensors (the reference concatenates per-chunk results: one more pass over 17 KB per ray);
+        optionally K1 of the next chunk on a side stream under the MLP kernels of the current one
+        (cfg.amd.overlap_warp)."""
+        gmode, guarded = self._guard_plan(mode, per_ray[0].shape[0])
+        cull_eps = 0.0 if diag else float(amd_option('cull_eps', 0.0))
+        # one evaluation for the samples whose inputs underflow to those of x_skel = 0 (hnrf.h, hnrf_share_compact;
+        # its threshold assumes Hann weights <= 1: checked on the host copy, nothing waits for the device)
+        share = (bool(amd_option('share_underflow', True)) and mode == 'f16x3' and nr_packed is not None
+                 and baked is None and cull_eps == 0.0 and float(hann_host.max()) <= 1.0)
+        share_log = [] if share else None
+        out, self._workspace = ops.render_frame(
+            *per_ray, *per_frame, nr_packed, cnl_packed, bg, S, int(cfg.chunk), gmode, diagnostics=diag,
+            cull_eps=cull_eps, workspace=self._workspace,
+            overlap=bool(amd_option('overlap_warp', False)), mlp_event_log=self.mlp_event_log, baked=baked,
+            baked_nr=baked_nr, share_log=share_log)
+        self._share_last = share_log[0] if share else None
+        if mode == 'f16x3' and guarded != set():
+            self.f16_guard.watch(cnl_packed, nr_packed if baked_nr is None else nr_baked_on, mode)
+        return out
+
+    def _forward_chunks(self, per_ray, per_frame, bg, S, mode, diag, train=None, packs=None, term_eps=0.0):
+        """Per ray chunk (network.py:333): training (``train`` = (cond, use_nonrigid, nr_inputs_are_zero):
+        autograd.RenderRays), or the lean inference path with early ray termination (``packs`` = (nr_packed,
+        cnl_packed): hnrf_render_rays_term_fwd, one workspace for every chunk)."""
+        N, chunk = per_ray[0].shape[0], int(cfg.chunk)
+        self._share_last = None
+        if train is None:
+            _, guarded = self._guard_plan(mode, N)
+            cull_eps = float(amd_option('cull_eps', 0.0))
+            need = ops.render_term_workspace_bytes(min(chunk, N), S) // 4 + 64
+            if self._workspace is None or self._workspace.numel() < need or self._workspace.device != per_ray[0].device:
+                self._workspace = torch.empty(need, device=per_ray[0].device)
+        chunks = []
+        for ci, i in enumerate(range(0, N, chunk)):
+            part = [None if t is None else t[i:i + chunk] for t in per_ray]
+            if train is not None:
+                chunks.append(self._render_rays_train(*part, *per_frame, train[0], bg, S, train[1], diag, train[2]))
+                continue
+            chunks.append(ops.render_rays_term(*part, *per_frame, *packs, bg, S,
+                                               mode if guarded is None or ci in guarded else mode + '+noguard',
+                                               term_eps=term_eps, cull_eps=cull_eps, workspace=self._workspace))
+        if train is None and mode == 'f16x3' and guarded != set():
+            self.f16_guard.watch(packs[1], packs[0], mode)
+        return {k: (torch.cat([c[k] for c in chunks], 0) if len(chunks) > 1 else chunks[0][k]) for k in chunks[0]}
 
     def shared_sample_share(self):
         """Share of the last frame's samples that took the shared evaluation of cfg.amd.share_underflow instead of a pass
@@ -835,7 +793,7 @@ class Network(nn.Module):
         return F.linear(torch.relu(h), lin[-1].weight, lin[-1].bias)
 
     def _render_rays_train(self, rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
-                           hann_w, cond, bg, S, use_nonrigid, diag):
+                           hann_w, cond, bg, S, use_nonrigid, diag, nr_inputs_are_zero):
         """Differentiable chunk: autograd.RenderRays (activation-saving MLP kernels).  rgb / alpha / depth carry
         gradient (the trainer's loss reads rgb, trainer.py:121); with ``cfg.amd.diagnostics`` the other eight keys of
         the reference's return dict (network.py:776-789) are returned too, detached.  cfg.amd.canonical = 'baked' is
@@ -846,7 +804,7 @@ class Network(nn.Module):
             hann_w = torch.ones(6, device=rays_o.device)
         params = [l.weight for l in nr] + [l.bias for l in nr] + [l.weight for l in cn] + [l.bias for l in cn]
         const_offset = None
-        if use_nonrigid and getattr(self, '_nr_inputs_are_zero', False):
+        if use_nonrigid and nr_inputs_are_zero:
             # before non_rigid_motion_mlp.kick_in_iter the MLP is fed zeros at every sample (condition code x 0,
             # network.py:735-737; Hann weights all 0, hannw_fourier.py:28-40): its offset is the per-frame constant MLP(0)
             # (SURVEY section 7).  Evaluated once, in fp32 with torch's autograd, instead of 786 432 times: the first
@@ -879,22 +837,18 @@ class Network(nn.Module):
         with torch.no_grad():
             N = baked_mod.check_resolution(amd_option('bake_resolution', 256) if resolution is None else resolution)
             dev = self._mesh_device()
-            f32 = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(3).contiguous()
-            bmin = f32(cnl_bbox_min_xyz)
-            bmax = f32(cnl_bbox_max_xyz) if cnl_bbox_max_xyz is not None else (bmin + 2.0 / f32(cnl_bbox_scale_xyz)).contiguous()
-            while True:
-                mode = self._mlp_mode()
-                packed = self._canonical_packed()
-                grid, sat = ops.bake_canonical(packed, bmin, bmax, N, mode, want_saturated=True)
-                if not self._f16_rerun(packed, mode):
-                    break
+            bmin = _vec3(cnl_bbox_min_xyz, dev)
+            bmax = _vec3(cnl_bbox_max_xyz, dev) if cnl_bbox_max_xyz is not None \
+                else (bmin + 2.0 / _vec3(cnl_bbox_scale_xyz, dev)).contiguous()
+            grid, sat = self._canonical_pass(
+                lambda packed, mode: ops.bake_canonical(packed, bmin, bmax, N, mode, want_saturated=True))
             n_sat = int(sat)
             if n_sat:
                 import warnings
                 warnings.warn('bake_canonical: %d canonical-MLP outputs beyond +-65504 were saturated in the f16 grid: '
                               'the baked render differs from the exact one there' % n_sat)
             self.bake_count += 1
-            self._baked = {'grid': grid, 'bmin': bmin, 'bmax': bmax, 'key': (_versions(self._cnl_tensors()), mode, N),
+            self._baked = {'grid': grid, 'bmin': bmin, 'bmax': bmax, 'key': (_versions(self._cnl_tensors()), self._mlp_mode(), N),
                            'injected': False, 'refs': None}
             return grid
 
@@ -915,8 +869,7 @@ class Network(nn.Module):
         N = baked_mod.check_resolution(g.shape[0])
         if tuple(g.shape) != (N, N, N, 4) or g.dtype != torch.float16:
             raise ValueError('set_baked_grid: grid must be float16 (N, N, N, 4), got %s %s' % (g.dtype, tuple(g.shape)))
-        f32 = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(3).contiguous()
-        self._baked = {'grid': g.to(dev).contiguous(), 'bmin': f32(bbox_min), 'bmax': f32(bbox_max), 'key': None,
+        self._baked = {'grid': g.to(dev).contiguous(), 'bmin': _vec3(bbox_min, dev), 'bmax': _vec3(bbox_max, dev), 'key': None,
                        'injected': True, 'refs': None}
 
     # baked non-rigid offset field (no counterpart in the reference; humannerf_amd/baked.py) -------------------------
@@ -936,15 +889,9 @@ class Network(nn.Module):
         with torch.no_grad():
             M = baked_mod.check_resolution(amd_option('nonrigid_bake_resolution', 128) if resolution is None else resolution)
             dev = self._mesh_device()
-            f32 = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(3).contiguous()
-            bmin, bmax = f32(box[0]), f32(box[1])
-            nr_cfg = cfg.non_rigid_motion_mlp
-            iter_val = float(iter_val)
-            cond = torch.as_tensor(dst_posevec).to(device=dev, dtype=torch.float32).reshape(-1)
-            if iter_val < nr_cfg.kick_in_iter:
-                cond = torch.zeros_like(cond)                               # network.py:735-737
-            hann = hann_window_weights(iter_val, nr_cfg.multires, nr_cfg.kick_in_iter, nr_cfg.full_band_iter)
-            hann = hann.pin_memory().to(dev, non_blocking=True) if dev.type == 'cuda' else hann.to(dev)
+            bmin, bmax = _vec3(box[0], dev), _vec3(box[1], dev)
+            posevec = torch.as_tensor(dst_posevec).to(device=dev, dtype=torch.float32).reshape(-1)
+            _, cond, _, hann, _ = self._conditioning(posevec, float(iter_val), dev, True, want_rvec=False)
             mode = self._mlp_mode()
             packed = self._nonrigid_packed(cond)
             if self._nr_bake_ws is None or self._nr_bake_ws[0] != (M, dev):
@@ -966,12 +913,11 @@ class Network(nn.Module):
                iter_val < cfg.non_rigid_motion_mlp.kick_in_iter)
         watched = (dst_posevec, bmin, bmax)
         b = self._baked_nr
-        if b is not None and b['key'] == key and b['refs'] is not None \
-                and all(r() is t and v == t._version for (r, v), t in zip(b['refs'], watched)):
+        if b is not None and b['key'] == key and _still_resident(b['refs'], watched):
             return (b['grid'], b['bmin'], b['bmax']), None
         self.bake_nonrigid(dst_posevec, iter_val, (bmin, bmax), M)
         b = self._baked_nr
-        b['key'], b['refs'] = key, tuple((weakref.ref(t), t._version) for t in watched)
+        b['key'], b['refs'] = key, _resident(watched)
         return (b['grid'], b['bmin'], b['bmax']), b['packed']
 
     def _baked_for_frame(self, bbox_min, bbox_max, bbox_scale):
@@ -982,23 +928,20 @@ class Network(nn.Module):
         b = self._baked
         if b is not None and b['injected']:
             return b['grid'], b['bmin'], b['bmax']
-        other = bbox_max if bbox_max is not None else bbox_scale
-        refs = lambda: tuple((weakref.ref(t), t._version) for t in (bbox_min, other))
+        box = (bbox_min, bbox_max if bbox_max is not None else bbox_scale)
         key = (_versions(self._cnl_tensors()), self._mlp_mode(), int(amd_option('bake_resolution', 256)))
         if b is not None and b['key'] == key:
-            if b['refs'] is not None and all(r() is t and v == t._version
-                                             for (r, v), t in zip(b['refs'], (bbox_min, other))):
+            if _still_resident(b['refs'], box):
                 return b['grid'], b['bmin'], b['bmax']
             dev = b['bmin'].device
-            f32 = lambda t: t.to(device=dev, dtype=torch.float32).reshape(3)
-            bmin = f32(bbox_min)
-            bmax = f32(bbox_max) if bbox_max is not None else bmin + 2.0 / f32(bbox_scale)
+            bmin = _vec3(bbox_min, dev)
+            bmax = _vec3(bbox_max, dev) if bbox_max is not None else bmin + 2.0 / _vec3(bbox_scale, dev)
             if torch.equal(bmin, b['bmin']) and torch.equal(bmax, b['bmax']):
-                b['refs'] = refs()
+                b['refs'] = _resident(box)
                 return b['grid'], b['bmin'], b['bmax']
         self.bake_canonical(bbox_min, bbox_max, key[2], bbox_scale)
         b = self._baked
-        b['refs'] = refs()
+        b['refs'] = _resident(box)
         return b['grid'], b['bmin'], b['bmax']
 
     # mesh extraction (no counterpart in the reference) ------------------------------------------------------------
@@ -1012,20 +955,10 @@ class Network(nn.Module):
 
     def _mesh_bbox(self, cnl_bbox_min_xyz, cnl_bbox_max_xyz, cnl_bbox_scale_xyz=None):
         dev = self._mesh_device()
-        f32 = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(3).contiguous()
-        bmin, bmax = f32(cnl_bbox_min_xyz), f32(cnl_bbox_max_xyz)
+        bmin, bmax = _vec3(cnl_bbox_min_xyz, dev), _vec3(cnl_bbox_max_xyz, dev)
         # the datasets' cnl_bbox_scale_xyz = 2 / (max - min) in float32 (dataset.Subject._skeleton_entries)
-        scale = f32(cnl_bbox_scale_xyz) if cnl_bbox_scale_xyz is not None else (2.0 / (bmax - bmin)).contiguous()
+        scale = _vec3(cnl_bbox_scale_xyz, dev) if cnl_bbox_scale_xyz is not None else (2.0 / (bmax - bmin)).contiguous()
         return bmin, bmax, scale
-
-    def _f16_rerun(self, packed, mode):
-        """After a canonical-MLP pass outside forward: act on its status word exactly as forward does
-        (cfg.amd.on_f16_range: raise, warn and switch to 'f32', or ignore).  True when the pass must run again in the
-        mode just forced."""
-        if mode != 'f16x3':
-            return False
-        self._watch_f16_range(packed, None, mode)
-        return self.check_f16_range(wait=True) and self._mlp_mode() != mode
 
     def canonical_density_grid(self, cnl_bbox_min_xyz, cnl_bbox_max_xyz, motion_weights_priors, resolution=256,
                                cnl_bbox_scale_xyz=None, return_parts=False):
@@ -1037,12 +970,8 @@ class Network(nn.Module):
             dev = self._mesh_device()
             bmin, bmax, scale = self._mesh_bbox(cnl_bbox_min_xyz, cnl_bbox_max_xyz, cnl_bbox_scale_xyz)
             vol = self._weight_volume(torch.as_tensor(motion_weights_priors).to(device=dev, dtype=torch.float32))
-            while True:
-                mode = self._mlp_mode()
-                packed = self._canonical_packed()
-                out = ops.density_grid(packed, vol, bmin, bmax, scale, int(resolution), mode, want_parts=return_parts)
-                if not self._f16_rerun(packed, mode):
-                    return out
+            return self._canonical_pass(lambda packed, mode: ops.density_grid(
+                packed, vol, bmin, bmax, scale, int(resolution), mode, want_parts=return_parts))
 
     def vertex_colors(self, verts):
         """sigmoid(raw[:3]) of the canonical MLP at the vertices (V, 3) -- the activation of _raw2outputs."""
@@ -1050,12 +979,8 @@ class Network(nn.Module):
             verts = verts.to(device=self._mesh_device(), dtype=torch.float32).contiguous()
             if verts.shape[0] == 0:
                 return verts.new_zeros(0, 3)
-            while True:
-                mode = self._mlp_mode()
-                packed = self._canonical_packed()
-                raw = ops.canonical(verts, packed, mode)
-                if not self._f16_rerun(packed, mode):
-                    return torch.sigmoid(raw[:, :3])
+            raw = self._canonical_pass(lambda packed, mode: ops.canonical(verts, packed, mode))
+            return torch.sigmoid(raw[:, :3])
 
     def extract_canonical_mesh(self, cnl_bbox_min_xyz, cnl_bbox_max_xyz, motion_weights_priors, resolution=256,
                                level=MESH_LEVEL, cnl_bbox_scale_xyz=None):
@@ -1076,9 +1001,7 @@ class Network(nn.Module):
         t = lambda k: torch.as_tensor(frame[k]).to(device=dev, dtype=torch.float32)
         with torch.no_grad():
             dst_Rs, dst_Ts, cnl_gtfms = t('dst_Rs'), t('dst_Ts'), t('cnl_gtfms')
-            rvec = None
-            if float(iter_val) >= cfg.pose_decoder.get('kick_in_iter', 0) and not cfg.get('pose_decoder_off', False):
-                rvec = self.pose_decoder.rvec(t('dst_posevec')[None])
+            rvec = self.pose_decoder.rvec(t('dst_posevec')[None]) if self._refines_pose(float(iter_val)) else None
             motion_Rs, motion_Ts = motion_basis(dst_Rs, dst_Ts, cnl_gtfms, rvec)
             vol = self._weight_volume(t('motion_weights_priors'))
         return motion_Rs.contiguous(), motion_Ts.contiguous(), vol
@@ -1091,8 +1014,7 @@ class Network(nn.Module):
         dataset.Subject.movement_frame dict (or any dict with forward's per-frame inputs)."""
         motion_Rs, motion_Ts, vol = self.frame_motion(frame, iter_val)
         dev = self._mesh_device()
-        f32 = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(3).contiguous()
-        bmin, scale = f32(frame['cnl_bbox_min_xyz']), f32(frame['cnl_bbox_scale_xyz'])
+        bmin, scale = _vec3(frame['cnl_bbox_min_xyz'], dev), _vec3(frame['cnl_bbox_scale_xyz'], dev)
         with torch.no_grad():
             verts = verts.to(device=self._mesh_device(), dtype=torch.float32).contiguous()
             return ops.forward_skin(verts, motion_Rs, motion_Ts, vol, bmin, scale)

@@ -163,6 +163,17 @@ def canonical(xyz, packed, mode='f32'):
     return raw
 
 
+def output_shapes(S, B, diagnostics=True):
+    """The keys of a render's output dict (network.py:776-789) with their per-ray trailing shapes for S samples and B
+    bones, in the order of autograd.RenderRays.OUTPUT_KEYS: rgb / alpha / depth, and with ``diagnostics`` the other
+    eight."""
+    shp = {'rgb': (3,), 'alpha': (), 'depth': ()}
+    if diagnostics:
+        shp.update(weights_on_rays=(S,), rgb_on_rays=(S, 3), cnl_xyz=(3,), cnl_rgb=(3,), cnl_weight=(), xyz_on_rays=(S, 3),
+                   backward_motion_weights=(S, B), offsets=(S, 3))
+    return shp
+
+
 def composite(raw, fg_mask, z_vals, rays_d, xyz, bgcolor, diagnostics=True, cull_eps=0.0, out=None):
     """K4 (network.py:355-388).  Returns dict with rgb/alpha/depth and, when
     ``diagnostics``, weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight.  ``out``: dict of contiguous
@@ -171,9 +182,7 @@ def composite(raw, fg_mask, z_vals, rays_d, xyz, bgcolor, diagnostics=True, cull
     _chk(raw, fg_mask, z_vals, rays_d, xyz, bgcolor)
     R, S = z_vals.shape
     dev = raw.device
-    shapes = {'rgb': (R, 3), 'alpha': (R,), 'depth': (R,)}
-    if diagnostics:
-        shapes.update(weights_on_rays=(R, S), rgb_on_rays=(R, S, 3), cnl_xyz=(R, 3), cnl_rgb=(R, 3), cnl_weight=(R,))
+    shapes = {k: (R,) + v for k, v in list(output_shapes(S, 0, diagnostics).items())[:8]}    # (K4 writes the first eight)
     if out is None:
         out = {k: torch.empty(*sh, device=dev) for k, sh in shapes.items()}
     else:
@@ -302,11 +311,7 @@ def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, b
     args, workspace = _render_args((rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
                                     hann_w, nr_packed, cnl_packed, bgcolor), workspace,
                                    ws_bytes(min(chunk, max(N, 1)), S))
-    shp = {'rgb': (3,), 'alpha': (), 'depth': ()}
-    if diagnostics:
-        shp.update(weights_on_rays=(S,), rgb_on_rays=(S, 3), cnl_xyz=(3,), cnl_rgb=(3,), cnl_weight=(), xyz_on_rays=(S, 3),
-                   backward_motion_weights=(S, B), offsets=(S, 3))
-    out = {k: torch.empty((N,) + v, device=dev) for k, v in shp.items()}
+    out = {k: torch.empty((N,) + v, device=dev) for k, v in output_shapes(S, B, diagnostics).items()}
     g = lambda k: _ptr(out.get(k))
     side, evs, ev_arr = None, None, None
     if overlap and N > chunk:

@@ -22,7 +22,7 @@ import os
 import queue
 import threading
 import time
-from collections import defaultdict
+from collections import defaultdict, namedtuple
 
 import numpy as np
 import torch
@@ -527,6 +527,11 @@ class FramePrefetcher:
 
 METRIC_NAMES = ('psnr', 'ssim', 'lpips')
 
+# a frame of render_frames between its launches and its hand-over: frame index, pinned image buffers, the event behind
+# their copies, the prefetcher's item (to render it again), the number of frames the network's f16-range guard had
+# watched once this one was queued, the pinned metric vector or None
+_InFlight = namedtuple('_InFlight', 'idx hosts event item watch_id metric_host')
+
 
 def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, show_truth=False, prefetch=None,
                   metrics=None, lpips_fn=None, on_metrics=None):
@@ -577,16 +582,16 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
     on_gpu = device.type == 'cuda'
     copy_stream = torch.cuda.Stream(device=device) if on_gpu else None
     pool = _PinnedPool()
-    pending = []                                    # [idx, hosts, event, item, watch id, metric host]: oldest first
+    pending = []                                    # _InFlight records, oldest first
     guard = hasattr(network, 'check_f16_range')
 
     t_submit, t_wait, t_user = [], [], []           # per frame: launches queued / waiting for the image / on_image
 
     def deliver(entry):
-        i, hosts, e = entry[:3]
+        i, hosts = entry.idx, entry.hosts
         t0 = time.perf_counter()
-        if e is not None:
-            e.synchronize()
+        if entry.event is not None:
+            entry.event.synchronize()
         arrs = [h.numpy().copy() if on_gpu else h.numpy() for h in hosts]
         if on_gpu:
             for h in hosts:
@@ -595,9 +600,9 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
         t1 = time.perf_counter()
         if on_image is not None:
             on_image(i, *arrs)
-        if entry[5] is not None:
-            vals = entry[5].tolist()
-            pool.give(entry[5])
+        if entry.metric_host is not None:
+            vals = entry.metric_host.tolist()
+            pool.give(entry.metric_host)
             if on_metrics is not None:
                 on_metrics(i, dict(zip(metrics, vals)))
         t_wait.append(t1 - t0)
@@ -629,7 +634,7 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
         imgs = [rgb8, a8] + ([t8] if item['truth'] is not None else [])
         wid = network.f16_range_watched if guard else 0
         if not on_gpu:
-            return [item['idx'], [im.cpu() for im in imgs], None, item, wid, None]
+            return _InFlight(item['idx'], [im.cpu() for im in imgs], None, item, wid, None)
         copy_stream.wait_stream(torch.cuda.current_stream(device))      # overlap D2H with the next frame
         hosts = []
         with torch.cuda.stream(copy_stream):
@@ -645,35 +650,38 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
                 mvec.record_stream(copy_stream)
             ev = torch.cuda.Event()
             ev.record(copy_stream)
-        return [item['idx'], hosts, ev, item, wid, mhost]
+        return _InFlight(item['idx'], hosts, ev, item, wid, mhost)
 
-    def mlp_mode():
-        return network._mlp_mode() if hasattr(network, '_mlp_mode') else None
+    def guard_state():
+        return (network.f16_range_hits, network._mlp_mode() if hasattr(network, '_mlp_mode') else None) if guard else None
 
-    def rerender_pending():
-        """A range hit with cfg.amd.on_f16_range = 'f32' has switched the network to the exact kernels: every frame not
-        yet handed over was rendered with the clamped ones (or has no verdict yet) and is rendered again; frames
-        handed over earlier had their verdict and were fine.  A hit that left the mode as it was ('ignore') renders
-        nothing again: the frames are delivered as they are."""
+    def rerender_if_switched(before):
+        """``before``: guard_state() in front of a call that looked at verdicts.  A range hit with cfg.amd.on_f16_range =
+        'f32' has switched the network to the exact kernels: every frame not yet handed over was rendered with the
+        clamped ones (or has no verdict yet) and is rendered again; frames handed over earlier had their verdict and
+        were fine.  A hit that left the mode as it was ('ignore') renders nothing again: the frames are delivered as
+        they are."""
+        now = guard_state()
+        if not guard or now[0] == before[0] or now[1] == before[1]:
+            return
         for k, entry in enumerate(pending):
-            if entry[2] is not None:
-                entry[2].synchronize()
+            if entry.event is not None:
+                entry.event.synchronize()
             if on_gpu:
-                for h in entry[1]:
+                for h in entry.hosts:
                     pool.give(h)
-                if entry[5] is not None:
-                    pool.give(entry[5])
-            pending[k] = render(entry[3])
+                if entry.metric_host is not None:
+                    pool.give(entry.metric_host)
+            pending[k] = render(entry.item)
 
     def verdicts(wait, upto=None):
         if guard:
-            hits, mode = network.f16_range_hits, mlp_mode()
+            before = guard_state()
             network.check_f16_range(wait=wait, upto=upto)
-            if network.f16_range_hits != hits and mlp_mode() != mode:
-                rerender_pending()
+            rerender_if_switched(before)
 
     def known(entry):
-        return not guard or network.f16_range_checked >= entry[4]
+        return not guard or network.f16_range_checked >= entry.watch_id
 
     # frames in the making at once: a frame's build takes ~260 ms of LATENCY behind the render kernels, the render 85 ms;
     # three builders to start with, FramePrefetcher adds more while the renderer has to wait (14 MB of device memory per frame)
@@ -683,16 +691,15 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
                           workers=workers)
     try:
         for item in pre:
-            hits, mode = (network.f16_range_hits, mlp_mode()) if guard else (0, None)
+            before = guard_state()
             t0 = time.perf_counter()
             pending.append(render(item))                                 # (forward looks at the verdicts that have arrived)
             t_submit.append(time.perf_counter() - t0)
-            if guard and network.f16_range_hits != hits and mlp_mode() != mode:
-                rerender_pending()
+            rerender_if_switched(before)
             # a frame is handed over once its verdict is known and its copy has landed; at most three in flight
-            while pending and (len(pending) > 3 or (known(pending[0]) and (pending[0][2] is None or pending[0][2].query()))):
+            while pending and (len(pending) > 3 or (known(pending[0]) and (pending[0].event is None or pending[0].event.query()))):
                 if not known(pending[0]):
-                    verdicts(wait=True, upto=pending[0][4])              # (of the oldest frame only: the queue stays full)
+                    verdicts(wait=True, upto=pending[0].watch_id)              # (of the oldest frame only: the queue stays full)
                 deliver(pending.pop(0))
         verdicts(wait=True)
         verdicts(wait=True)                                              # (of the frames a hit had rendered again)

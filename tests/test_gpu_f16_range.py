@@ -477,21 +477,21 @@ def test_density_grid_guard(hot_net, golden_frame):
     assert int(ops.status_word(packed, 'canonical', 'f16x3').item()) == 1
     try:
         cfg.amd.mlp_mode = 'f16x3'
-        net._forced_mode, net._range_watch = None, None
+        net.f16_guard.reset()
         with pytest.raises(ActivationRangeError, match='canonical'):
             net.canonical_density_grid(bmin, bmax, fr['motion_weights_priors'], resolution=32)
         cfg.amd.on_f16_range = 'f32'
-        net._forced_mode, net._range_watch = None, None
+        net.f16_guard.reset()
         with pytest.warns(UserWarning, match="switching this network to 'f32'"):
             grid = net.canonical_density_grid(bmin, bmax, fr['motion_weights_priors'], resolution=32)
         assert net._mlp_mode() == 'f32'
         cfg.amd.mlp_mode, cfg.amd.on_f16_range = 'f32', 'raise'
-        net._forced_mode, net._range_watch = None, None
+        net.f16_guard.reset()
         want = net.canonical_density_grid(bmin, bmax, fr['motion_weights_priors'], resolution=32)
         assert torch.equal(grid, want)
     finally:
         cfg.amd.mlp_mode, cfg.amd.on_f16_range = 'f16x3', 'raise'
-        net._forced_mode, net._range_watch = None, None
+        net.f16_guard.reset()
 
 
 # ------------------------------------------------------------------ 5. the frame loop under each policy
@@ -520,7 +520,8 @@ def test_render_frames_under_each_policy(policy, hot_net, monkeypatch):
         cfg.amd.mlp_mode = 'f32'
         want = render.render_frames(net, frames)
         cfg.amd.mlp_mode, cfg.amd.on_f16_range = 'f16x3', policy
-        net._forced_mode, net._range_watch, net._cnl_pack = None, None, None
+        net.f16_guard.reset()
+        net._cnl_pack = None
         monkeypatch.setattr(net, 'forward', counting)
         if policy == 'raise':
             with pytest.raises(ActivationRangeError):
@@ -541,4 +542,5 @@ def test_render_frames_under_each_policy(policy, hot_net, monkeypatch):
                 assert np.array_equal(got[i], want[i]), i
     finally:
         cfg.amd.diagnostics, cfg.amd.mlp_mode, cfg.amd.on_f16_range = True, 'f16x3', 'raise'
-        net._forced_mode, net._range_watch, net._cnl_pack = None, None, None
+        net.f16_guard.reset()
+        net._cnl_pack = None

@@ -178,7 +178,7 @@ def test_f16_range_guard_of_inference(which, diag, gpu_net, golden_frame, seeded
                 gpu_net(**data, iter_val=1e7)
             # fall-back policy: warn, switch to the exact kernels, which then agree with the CPU oracle on these weights
             cfg.amd.on_f16_range = 'f32'
-            gpu_net._range_watch = None
+            gpu_net.f16_guard.reset()
             gpu_net(**data, iter_val=1e7)
             with pytest.warns(UserWarning, match="switching this network to 'f32'"):
                 assert gpu_net.check_f16_range(wait=True) is True
@@ -193,7 +193,8 @@ def test_f16_range_guard_of_inference(which, diag, gpu_net, golden_frame, seeded
         with torch.no_grad():
             sd[which].copy_(torch.from_numpy(seeded_params[which]))
         cfg.amd.on_f16_range, cfg.amd.diagnostics, cfg.perturb = 'raise', True, 1.0
-        gpu_net._forced_mode, gpu_net._range_watch, gpu_net._cnl_pack = None, None, None
+        gpu_net.f16_guard.reset()
+        gpu_net._cnl_pack = None
 
 
 def test_lean_path_equals_diagnostic_path(gpu_net, golden_frame, monkeypatch):

@@ -205,7 +205,7 @@ def frame():
 def _render(net, frame, cfg, share, frames=1):
     """``frames`` frames from a fresh guard schedule; returns (outputs of every frame, share of the last)."""
     cfg.amd.share_underflow = share
-    net._guard_state = None
+    net.f16_guard.restart_schedule()
     outs = []
     with torch.no_grad():
         for _ in range(frames):

@@ -350,19 +350,19 @@ def test_f16_range_guard_schedule():
     old = cfg.amd.get('f16_range_guard', 'audit')
     try:
         cfg.amd.f16_range_guard = 'audit'
-        net._cnl_pack = (('f16x3', 1), None)
-        assert net._guard_plan('f16x3', 8) == ('f16x3', None)
-        got = [net._guard_plan('f16x3', 8) for _ in range(9)]
+        plan, key = net.f16_guard.plan, ('f16x3', 1)
+        assert plan('f16x3', 8, key) == ('f16x3', None)
+        got = [plan('f16x3', 8, key) for _ in range(9)]
         assert [g[0] for g in got] == ['f16x3+guard1:%d' % (k % 8) for k in range(9)]
         assert [g[1] for g in got] == [{k % 8} for k in range(9)]
-        net._cnl_pack = (('f16x3', 2), None)                                  # an optimizer step / a new checkpoint
-        assert net._guard_plan('f16x3', 8) == ('f16x3', None)
-        assert net._guard_plan('f16x3', 1) == ('f16x3+guard1:0', {0})         # one-chunk frames stay fully guarded
-        assert net._guard_plan('f32', 8) == ('f32', None)
+        key = ('f16x3', 2)                                                    # an optimizer step / a new checkpoint
+        assert plan('f16x3', 8, key) == ('f16x3', None)
+        assert plan('f16x3', 1, key) == ('f16x3+guard1:0', {0})               # one-chunk frames stay fully guarded
+        assert plan('f32', 8, key) == ('f32', None)
         cfg.amd.f16_range_guard = 'off'
-        assert net._guard_plan('f16x3', 8) == ('f16x3+noguard', set())
+        assert plan('f16x3', 8, key) == ('f16x3+noguard', set())
         cfg.amd.f16_range_guard = 'full'
-        assert net._guard_plan('f16x3', 8) == ('f16x3', None)
+        assert plan('f16x3', 8, key) == ('f16x3', None)
     finally:
         cfg.amd.f16_range_guard = old
     assert ops._mode_arg('f16x3') == 1 and ops._mode_arg('f32') == 0
