@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get('HNRF_LIB_PATH', os.path.join(_HERE, 'libhnrf.so'))   
 
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf.h'))
 CLOUD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_cloud.h'))   # included by hnrf.h
+VIDEO_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_video.h'))   # included by hnrf.h
 
 _SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float,
             'double': ctypes.c_double}
@@ -64,6 +65,9 @@ SIGNATURES = _signatures()
 # version built before them (HNRF_LIB_PATH) still loads; load_cloud() binds them and raises when they are missing
 CLOUD_SIGNATURES = _signatures(CLOUD_HEADER_PATH)
 
+# the JPEG encoder's entries of include/hnrf_video.h: additive to ABI version 13 in the same way (load_video)
+VIDEO_SIGNATURES = _signatures(VIDEO_HEADER_PATH)
+
 _lib = None
 
 
@@ -110,6 +114,26 @@ def load_cloud():
             fn.restype = res
             fn.argtypes = args
         _cloud_bound = True
+    return lib
+
+
+_video_bound = False
+
+
+def load_video():
+    """load() plus the entries of include/hnrf_video.h, typed.  A library without them raises HnrfError."""
+    global _video_bound
+    lib = load()
+    if not _video_bound:
+        for name, (res, args) in VIDEO_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise HnrfError(f'{LIB_PATH} does not export {name}: it was built before the JPEG encoder '
+                                f'(include/hnrf_video.h); rebuild it') from None
+            fn.restype = res
+            fn.argtypes = args
+        _video_bound = True
     return lib
 
 

@@ -195,6 +195,14 @@ _DEFAULTS = {
         # 'device' = in the frame's own launches on the 8-bit device images (render_frames(metrics=...): exact integer
         # moments, hnrf_image_metrics), the values travelling behind the images; needs a GPU
         'metrics': 'host',
+        # run.run_movement / run_freeview / run_tpose / run_mesh_render: a Motion-JPEG video of the panels next to the PNGs.
+        # 'none' = nothing changes; 'mjpeg' = every frame's panels are JPEG-encoded on the device in the frame's launches
+        # (humannerf_amd/video.py, csrc/hnrf_video.hip) and written as <image_dir>.avi (.rank<r>.avi with world > 1:
+        # video.merge_parts joins them); 'mjpeg_only' = the video alone: no 8-bit image is copied to the host, no PNG is
+        # written (with metrics it needs metrics = 'device')
+        'video': 'none',
+        'video_quality': 90,              # 1 .. 100, the scale of PIL.Image.save(quality=)
+        'video_fps': 10,                  # integer >= 1; 10 as the reference's ImageWriter.finalize
         # gc.freeze() at the start of the training / render loops (config.quiet_gc)
         'freeze_gc': True,
     },
@@ -237,12 +245,24 @@ def check_amd_options(node=None):
     """Validate the options of the two baked approximations that go together (``node``: an ``amd`` mapping, default
     cfg.amd) and return (canonical, nonrigid, nonrigid_bake_resolution).  ValueError: a value that is not 'mlp' or
     'baked', a resolution that is no integer in [8, 512], nonrigid = 'baked' without canonical = 'baked', or a
-    share_underflow that is no bool, or a metrics route that is not 'host' or 'device'."""
+    share_underflow that is no bool, or a metrics route that is not 'host' or 'device', or a video option out of range
+    (video 'none' / 'mjpeg' / 'mjpeg_only', video_quality an integer in [1, 100], video_fps an integer >= 1), or
+    video = 'mjpeg_only' with metrics = 'host' (the host route needs the images that mode does not copy)."""
     get = amd_option if node is None else (lambda k: node.get(k, _DEFAULTS['amd'][k]))
     if not isinstance(get('share_underflow'), bool):
         raise ValueError('cfg.amd.share_underflow must be True or False, got %r' % (get('share_underflow'),))
     if get('metrics') not in ('host', 'device'):
         raise ValueError("cfg.amd.metrics must be 'host' or 'device', got %r" % (get('metrics'),))
+    video, vq, fps = get('video'), get('video_quality'), get('video_fps')
+    if video not in ('none', 'mjpeg', 'mjpeg_only'):
+        raise ValueError("cfg.amd.video must be 'none', 'mjpeg' or 'mjpeg_only', got %r" % (video,))
+    if isinstance(vq, bool) or not isinstance(vq, int) or not 1 <= vq <= 100:
+        raise ValueError('cfg.amd.video_quality must be an integer in [1, 100], got %r' % (vq,))
+    if isinstance(fps, bool) or not isinstance(fps, int) or fps < 1:
+        raise ValueError('cfg.amd.video_fps must be an integer >= 1, got %r' % (fps,))
+    if video == 'mjpeg_only' and get('metrics') == 'host':
+        raise ValueError("cfg.amd.video = 'mjpeg_only' copies no image to the host, so cfg.amd.metrics = 'host' cannot "
+                         "compute anything: set cfg.amd.metrics = 'device' or cfg.amd.video = 'mjpeg'")
     canonical, nonrigid, M = get('canonical'), get('nonrigid'), get('nonrigid_bake_resolution')
     if canonical not in ('mlp', 'baked'):
         raise ValueError("cfg.amd.canonical must be 'mlp' or 'baked', got %r" % (canonical,))

@@ -16,7 +16,8 @@ an image to be written.
                                                               numpy twin of ops.image_metrics (csrc/hnrf_metrics.hip), which
                                                               render_frames(metrics=...) runs on the device
   ImageWriter                                                 image_util.py:55-128 (PNG via PIL; the MP4 of finalize()
-                                                              needs imageio, which is absent: frames + .npy instead)
+                                                              needs imageio, which is absent: frames + .npy instead;
+                                                              a Motion-JPEG .avi: render_frames(video=...), video.py)
 """
 import os
 import queue
@@ -258,7 +259,9 @@ class ImageWriter:
     ``append`` returns at once and can be used as ``render_frames(on_image=...)``; ``finalize`` drains the queue.  The
     reference's finalize() also writes an MP4 through imageio (fps 10, quality 8): done when imageio is importable;
     it is not in this image, so the frames are then stacked into ``<exp_name>.npy`` (sorted by name like the
-    reference) and the encoder is left to the user.  ``append_3d`` / ``append_cnl_3d`` write the point clouds of
+    reference).  A video without imageio comes from cfg.amd.video = 'mjpeg' / 'mjpeg_only': the run_* loops then
+    JPEG-encode every frame's panels on the device and write ``<exp_name>.avi`` (Motion-JPEG, humannerf_amd/video.py)
+    next to, or instead of, what this class writes; this class is unchanged by it.  ``append_3d`` / ``append_cnl_3d`` write the point clouds of
     run.py's 3-D dumps as Wavefront .obj text exactly like image_util.py:85-109."""
 
     def __init__(self, output_dir, exp_name, workers=4, keep_frames=True):
@@ -529,12 +532,32 @@ METRIC_NAMES = ('psnr', 'ssim', 'lpips')
 
 # a frame of render_frames between its launches and its hand-over: frame index, pinned image buffers, the event behind
 # their copies, the prefetcher's item (to render it again), the number of frames the network's f16-range guard had
-# watched once this one was queued, the pinned metric vector or None
-_InFlight = namedtuple('_InFlight', 'idx hosts event item watch_id metric_host')
+# watched once this one was queued, the pinned metric vector or None, the frame's JPEG stream or None: (the pinned first
+# video_copy_cap bytes, the pinned length word, the device buffer a longer stream's remainder is fetched from)
+_InFlight = namedtuple('_InFlight', 'idx hosts event item watch_id metric_host video', defaults=(None,))
+
+
+def select_panels(rgb8, alpha8, truth8=None):
+    """run.py:143-149 / 359-364: [render | truth if cfg.show_truth | alpha if cfg.show_alpha], as a list (arrays or
+    tensors): what run._panels concatenates on the host and render_frames(video=...) on the device."""
+    imgs = [rgb8]
+    if cfg.get('show_truth', False) and truth8 is not None:
+        imgs.append(truth8)
+    if cfg.get('show_alpha', False):
+        imgs.append(alpha8)
+    return imgs
+
+
+def video_copy_cap(height, width):
+    """Bytes of a frame's JPEG stream that render_frames copies to the host before it knows the stream's length:
+    3 bits per pixel of the panels, at least 64 KiB.  (A 512 x 512 render panel at quality 90 takes 15-40 KB; 3 bits per
+    pixel is what dense texture takes at that quality.)  A longer stream costs one synchronous copy of the remainder when
+    the frame is handed over, counted in render_frames.last_video['fallbacks']."""
+    return max(64 << 10, (3 * height * width) // 8)
 
 
 def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, show_truth=False, prefetch=None,
-                  metrics=None, lpips_fn=None, on_metrics=None):
+                  metrics=None, lpips_fn=None, on_metrics=None, video=None, on_video=None, images='host'):
     """Render ``frames`` (sequence of per-frame input dicts, numpy or tensors) frame-sharded.
 
     Returns {frame_idx: uint8 rgb image on the host} for this rank's frames.  ``on_image(idx, rgb8, alpha8[,
@@ -560,8 +583,25 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
     float64 vector through a pinned buffer behind the frame's images, under the same event, and arrive as
     ``on_metrics(idx, {name: float})`` right after that frame's ``on_image``.  Nothing of it synchronises, and a frame
     rendered again after an f16-range hit gets its metrics again.  The pixels are always divided by 255
-    (MetricsWriter.normalize leaves an image whose maximum is <= 2 as it is)."""
+    (MetricsWriter.normalize leaves an image whose maximum is <= 2 as it is).
+
+    ``video`` (a video.JpegEncoder on ``device``): the frame's panels (select_panels: the choice run._panels makes on
+    the host) are concatenated on the device and JPEG-encoded as part of the frame's launches.  The stream's length is
+    not known when its copy is queued, so the first video_copy_cap(H, W) bytes and the length word travel through
+    pinned buffers behind the images, under the same event; they arrive as ``on_video(idx, bytes)`` after that frame's
+    ``on_image`` (and ``on_metrics``).  Only a stream longer than the cap fetches its remainder, synchronously, at
+    hand-over (render_frames.last_video = {'frames', 'fallbacks', 'bytes', 'cap'}): no synchronisation enters the loop.
+    A frame rendered again after an f16-range hit is encoded again.  ``images='none'`` (only with ``video``): no 8-bit
+    image is copied to the host, ``on_image`` is never called and the returned dict is empty."""
     device = device or next(network.parameters()).device
+    if images not in ('host', 'none'):
+        raise ValueError("render_frames: images must be 'host' or 'none', got %r" % (images,))
+    if images == 'none' and video is None:
+        raise ValueError("render_frames: images = 'none' delivers nothing without a video encoder (video=...)")
+    if video is not None and video.device != device:
+        raise ValueError('render_frames: the video encoder is on %s, the frames on %s' % (video.device, device))
+    vstat = {'frames': 0, 'fallbacks': 0, 'bytes': 0, 'cap': 0}
+    render_frames.last_video = vstat
     metrics = list(metrics) if metrics else None
     if metrics is not None:
         bad = [k for k in metrics if k not in METRIC_NAMES]
@@ -596,15 +636,30 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
         if on_gpu:
             for h in hosts:
                 pool.give(h)
-        out[i] = arrs[0]
+        if arrs:
+            out[i] = arrs[0]
         t1 = time.perf_counter()
-        if on_image is not None:
+        if on_image is not None and arrs:
             on_image(i, *arrs)
         if entry.metric_host is not None:
             vals = entry.metric_host.tolist()
             pool.give(entry.metric_host)
             if on_metrics is not None:
                 on_metrics(i, dict(zip(metrics, vals)))
+        if entry.video is not None:
+            vhost, vlen, vdev = entry.video
+            n = int(vlen[0])
+            data = vhost[:min(n, vhost.shape[0])].numpy().tobytes()
+            if n > vhost.shape[0]:                   # longer than the cap: the remainder, synchronously, once
+                data += vdev[vhost.shape[0]:n].cpu().numpy().tobytes()
+                vstat['fallbacks'] += 1
+            if on_gpu:
+                pool.give(vhost)
+                pool.give(vlen)
+            vstat['frames'] += 1
+            vstat['bytes'] += n
+            if on_video is not None:
+                on_video(i, data)
         t_wait.append(t1 - t0)
         t_user.append(time.perf_counter() - t1)
 
@@ -629,12 +684,19 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
                 # (a table of the host's float32 k / 255: the device divides by a scalar as a product with 1 / 255)
                 vals['lpips'] = 1000 * lpips_fn(unit[rgb8.long()], unit[t8.long()]).reshape(()).to(torch.float64)
             mvec = torch.stack([vals[k] for k in metrics])
+        vbuf = vlen = None
+        if video is not None:
+            panels = select_panels(rgb8, a8, t8 if item['truth'] is not None else None)
+            vbuf, vlen = video.encode(panels[0] if len(panels) == 1 else torch.cat(panels, dim=1))
         if timing:
             gpu_ev[-1][1].record()
         imgs = [rgb8, a8] + ([t8] if item['truth'] is not None else [])
+        if images == 'none':
+            imgs = []
         wid = network.f16_range_watched if guard else 0
         if not on_gpu:
-            return _InFlight(item['idx'], [im.cpu() for im in imgs], None, item, wid, None)
+            return _InFlight(item['idx'], [im.cpu() for im in imgs], None, item, wid, None,
+                             None if vbuf is None else (vbuf, vlen, vbuf))
         copy_stream.wait_stream(torch.cuda.current_stream(device))      # overlap D2H with the next frame
         hosts = []
         with torch.cuda.stream(copy_stream):
@@ -648,9 +710,19 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
                 mhost = pool.take(mvec.shape, torch.float64)
                 mhost.copy_(mvec, non_blocking=True)
                 mvec.record_stream(copy_stream)
+            vid = None
+            if vbuf is not None:
+                cap = min(int(vbuf.shape[0]), video_copy_cap(item['H'], item['W'] * len(panels)))
+                vstat['cap'] = cap
+                vhost, lhost = pool.take((cap,)), pool.take((1,), torch.int64)
+                vhost.copy_(vbuf[:cap], non_blocking=True)
+                lhost.copy_(vlen, non_blocking=True)
+                vbuf.record_stream(copy_stream)
+                vlen.record_stream(copy_stream)
+                vid = (vhost, lhost, vbuf)
             ev = torch.cuda.Event()
             ev.record(copy_stream)
-        return _InFlight(item['idx'], hosts, ev, item, wid, mhost)
+        return _InFlight(item['idx'], hosts, ev, item, wid, mhost, vid)
 
     def guard_state():
         return (network.f16_range_hits, network._mlp_mode() if hasattr(network, '_mlp_mode') else None) if guard else None
@@ -672,6 +744,9 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
                     pool.give(h)
                 if entry.metric_host is not None:
                     pool.give(entry.metric_host)
+                if entry.video is not None:
+                    pool.give(entry.video[0])
+                    pool.give(entry.video[1])
             pending[k] = render(entry.item)
 
     def verdicts(wait, upto=None):

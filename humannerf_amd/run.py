@@ -17,6 +17,9 @@ render.ImageWriter / MetricsWriter on worker threads.
 
 Output layout as in the reference: ``<logdir>/<load_net><eval_output_tag>/<folder>/NAME.png`` plus
 ``<folder>-metrics.perimg.txt / .average.txt`` (movement) and the stacked frames (MP4 when imageio is importable).
+cfg.amd.video = 'mjpeg' adds ``<folder>.avi`` (Motion-JPEG of the same panels, encoded on the device; the result dict's
+``'video'``), 'mjpeg_only' writes that file and no PNG; with world > 1 ``<folder>.rank<r>.avi`` per rank, joined by
+video.merge_parts.
 With world > 1 every rank writes its own frames into the same folder; metrics are reduced by the caller
 (``MetricsWriter`` files are per rank: ``<folder>.rank<r>``).
 """
@@ -48,12 +51,38 @@ class _Frames:
 
 def _panels(rgb8, alpha8, truth8=None):
     """run.py:143-149 / 359-364: [render | truth if cfg.show_truth | alpha if cfg.show_alpha]."""
-    imgs = [rgb8]
-    if cfg.get('show_truth', False) and truth8 is not None:
-        imgs.append(truth8)
-    if cfg.get('show_alpha', False):
-        imgs.append(alpha8)
-    return np.concatenate(imgs, axis=1)
+    return np.concatenate(render.select_panels(rgb8, alpha8, truth8), axis=1)
+
+
+class _VideoOut:
+    """cfg.amd.video of a render loop: the device encoder to hand to the loop (``encoder``, None for 'none'), the
+    collector of its streams (``add(i, bytes)``) and the file at the end (``finalize() -> path or None``):
+    ``<image_dir>.avi``, ``<image_dir>.rank<r>.avi`` with world > 1 (video.merge_parts joins the ranks' files).  A frame
+    without a name is called by its index, %06d, like ImageWriter calls it."""
+
+    def __init__(self, image_dir, names, rank, world, device):
+        from . import video
+        from .config import amd_option, check_amd_options
+        check_amd_options()
+        self.mode = amd_option('video', 'none')
+        self.only = self.mode == 'mjpeg_only'
+        self.encoder = self.writer = None
+        self.names = names
+        if self.mode == 'none':
+            return
+        self._video = video
+        self.fps = int(amd_option('video_fps', 10))
+        self.encoder = video.JpegEncoder(device, int(amd_option('video_quality', 90)))
+        self.path = image_dir.rstrip('/') + ('.avi' if world == 1 else '.rank%d.avi' % rank)
+
+    def add(self, i, data):
+        if self.writer is None:
+            height, width = self._video.jpeg_size(data)
+            self.writer = self._video.MjpegWriter(self.path, width, height, self.fps)
+        self.writer.add(self.names[i] if self.names[i] is not None else '%06d' % i, data)
+
+    def finalize(self):
+        return self.writer.finalize() if self.writer is not None else None
 
 
 def _baked_folder(network, subject, folder):
@@ -83,7 +112,9 @@ def _render_loop(network, frames, names, folder, logdir, rank, world, device, me
     """``metrics``: a MetricsWriter.  ``on_device``: its values come from render_frames' device pass (cfg.amd.metrics =
     'device') instead of MetricsWriter.append on the delivered images."""
     out_dir = _output_dir(logdir)
-    writer = render.ImageWriter(out_dir, folder)
+    device = device or next(network.parameters()).device
+    vout = _VideoOut(os.path.join(out_dir, folder), names, rank, world, device)
+    writer = None if vout.only else render.ImageWriter(out_dir, folder)          # 'mjpeg_only': no PNG, no directory
     own = list(range(rank, len(frames), world))
 
     def on_image(i, rgb8, alpha8, truth8=None):
@@ -92,8 +123,10 @@ def _render_loop(network, frames, names, folder, logdir, rank, world, device, me
             metrics.append(name=names[i], pred=rgb8, target=truth8, mask=None)
 
     extra = {}
+    if vout.encoder is not None:
+        extra = dict(video=vout.encoder, on_video=vout.add, images='none' if vout.only else 'host')
     if metrics is not None and on_device:
-        extra = dict(metrics=metrics.metrics, lpips_fn=lpips_fn,
+        extra.update(metrics=metrics.metrics, lpips_fn=lpips_fn,
                      on_metrics=lambda i, values: metrics.append_values(names[i], values))
     old = cfg.perturb
     cfg.perturb = 0.                                                   # run.py:71, 214
@@ -102,9 +135,13 @@ def _render_loop(network, frames, names, folder, logdir, rank, world, device, me
                                       show_truth=True, **extra)
     finally:
         cfg.perturb = old
-    stack = writer.finalize()
+    stack = writer.finalize() if writer is not None else None
     averages = metrics.finalize() if metrics is not None else None
-    return {'frames': own, 'images': images, 'image_dir': writer.image_dir, 'stack': stack, 'metrics': averages}
+    result = {'frames': own, 'images': images, 'image_dir': os.path.join(out_dir, folder), 'stack': stack,
+              'metrics': averages}
+    if vout.encoder is not None:
+        result['video'] = vout.finalize()
+    return result
 
 
 def run_movement(network, subject, render_folder_name='movement', logdir=None, rank=0, world=1, device=None,
@@ -226,20 +263,31 @@ def run_mesh_render(network, subject, kind='movement', resolution=256, level=Non
         frames = _Frames(n, lambda i: subject.tpose_frame(i, n, image_size=size, bgcolor=cfg.bgcolor))
         names = [None] * n
         folder = render_folder_name or 'mesh_tpose'
-    writer = render.ImageWriter(_output_dir(logdir), folder)
     device = verts.device
+    vout = _VideoOut(os.path.join(_output_dir(logdir), folder), names, 0, 1, device)
+    writer = None if vout.only else render.ImageWriter(_output_dir(logdir), folder)
     copy_stream = torch.cuda.Stream(device=device)
     pool = render._PinnedPool()
-    images, pending = {}, []                        # pending: [idx, pinned rgb, pinned alpha, event], oldest first
+    images, pending = {}, []                # pending: [idx, pinned images (rgb, alpha), video or None, event], oldest first
 
     def deliver(entry):
-        i, h_rgb, h_alpha, ev = entry
+        i, hosts, vid, ev = entry
         ev.synchronize()                            # the one wait per frame: its copy has landed
-        rgb8, alpha8 = h_rgb.numpy().copy(), h_alpha.numpy().copy()
-        pool.give(h_rgb)
-        pool.give(h_alpha)
-        images[i] = rgb8
-        writer.append(_panels(rgb8, alpha8), img_name=names[i])
+        if hosts:
+            rgb8, alpha8 = hosts[0].numpy().copy(), hosts[1].numpy().copy()
+            pool.give(hosts[0])
+            pool.give(hosts[1])
+            images[i] = rgb8
+            writer.append(_panels(rgb8, alpha8), img_name=names[i])
+        if vid is not None:                         # (as render.render_frames hands a stream over)
+            vhost, lhost, vbuf = vid
+            n = int(lhost[0])
+            data = vhost[:min(n, vhost.shape[0])].numpy().tobytes()
+            if n > vhost.shape[0]:
+                data += vbuf[vhost.shape[0]:n].cpu().numpy().tobytes()
+            pool.give(vhost)
+            pool.give(lhost)
+            vout.add(i, data)
 
     network.eval()
     # the subject's priors, uploaded once: Network keeps the weight volume of a resident tensor without comparing it
@@ -249,23 +297,39 @@ def run_mesh_render(network, subject, kind='movement', resolution=256, level=Non
         out = network.render_mesh(verts, faces, colors, frame, iter_val=float(cfg.get('eval_iter', 1e7)),
                                   shade=shade, cull=cull)
         imgs = [render.to_8b_image(out['rgb']), render.to_8b3ch_image(out['alpha']).contiguous()]
+        vbuf = vlen = None
+        if vout.encoder is not None:
+            panels = render.select_panels(imgs[0], imgs[1])
+            vbuf, vlen = vout.encoder.encode(panels[0] if len(panels) == 1 else torch.cat(panels, dim=1))
         copy_stream.wait_stream(torch.cuda.current_stream(device))
-        hosts = []
+        hosts, vid = [], None
         with torch.cuda.stream(copy_stream):
-            for im in imgs:
+            for im in ([] if vout.only else imgs):
                 h = pool.take(im.shape)
                 h.copy_(im, non_blocking=True)
                 im.record_stream(copy_stream)
                 hosts.append(h)
+            if vbuf is not None:
+                cap = min(int(vbuf.shape[0]), render.video_copy_cap(imgs[0].shape[0], imgs[0].shape[1] * len(panels)))
+                vhost, lhost = pool.take((cap,)), pool.take((1,), torch.int64)
+                vhost.copy_(vbuf[:cap], non_blocking=True)
+                lhost.copy_(vlen, non_blocking=True)
+                vbuf.record_stream(copy_stream)
+                vlen.record_stream(copy_stream)
+                vid = (vhost, lhost, vbuf)
             ev = torch.cuda.Event()
             ev.record(copy_stream)
-        pending.append([i] + hosts + [ev])
+        pending.append([i, hosts, vid, ev])
         while len(pending) > 2:                     # two frames in flight: the copy of one overlaps the next raster
             deliver(pending.pop(0))
     while pending:
         deliver(pending.pop(0))
-    stack = writer.finalize()
-    return {'frames': list(range(n)), 'images': images, 'image_dir': writer.image_dir, 'stack': stack}
+    stack = writer.finalize() if writer is not None else None
+    result = {'frames': list(range(n)), 'images': images, 'image_dir': os.path.join(_output_dir(logdir), folder),
+              'stack': stack}
+    if vout.encoder is not None:
+        result['video'] = vout.finalize()
+    return result
 
 
 def run_surface_points(network, subject, weight_threshold=None, render_folder_name='movement', logdir=None, rank=0,

@@ -766,6 +766,10 @@ int hnrf_image_metrics(const uint8_t* pred, const uint8_t* target, const uint8_t
  * tools/compute_distance*.py.  Additive to ABI version 13; contracts and declarations in hnrf_cloud.h. */
 #include "hnrf_cloud.h"
 
+/* ---- baseline JPEG encoding of 8-bit images on the device (the frames of a Motion-JPEG video).  Additive to ABI
+ * version 13; contracts and declarations in hnrf_video.h. */
+#include "hnrf_video.h"
+
 #ifdef __cplusplus
 }
 #endif
