@@ -373,7 +373,11 @@ extern "C" int hnrf_sample_warp_bwd(const float* rays_o, const float* rays_d, co
     const int64_t P = R * (int64_t)S;
     int64_t blocks = (P + 255) / 256;
     const size_t lds = (size_t)G * G * G * sizeof(float);
-    if (lds + 1024 <= 160 * 1024 && P >= 65536) {       // (+ the block reduction's 16 x 12 floats of static LDS)
+    // The gradient grid must fit the dynamic LDS reserved for the <true, 1024> instance (150 KiB, + the block reduction's
+    // 16 x 12 floats of static LDS, of the CU's 160 KiB): G <= 33.  A larger lattice takes the global-atomics form below,
+    // which handles any G.
+    constexpr int kGridLdsMax = 150 * 1024;
+    if (lds <= (size_t)kGridLdsMax && P >= 65536) {
         // one 128-KiB LDS grid per block -> 1 block per CU; ~2 waves of blocks over the chip
         int64_t bx = 512 / B;                        // blocks per bone
         if (bx < 1) bx = 1;
@@ -381,7 +385,7 @@ extern "C" int hnrf_sample_warp_bwd(const float* rays_o, const float* rays_d, co
         // 16 waves per block (four per SIMD): with ONE wave per SIMD every one of the ~350 instructions per (sample, bone)
         // pair costs ~5 cycles of issue (profiles/r03_mfma_issue.txt); 0.529 ms (256 threads) -> 0.357 (512) -> 0.295 (1024).
         // (Before the atomics were folded, more waves lost to LDS-atomic contention: 0.90 -> 1.00 ms, round 2.)
-        return launch_lds<sample_warp_bwd_kernel<true, 1024>, 150 * 1024>(
+        return launch_lds<sample_warp_bwd_kernel<true, 1024>, kGridLdsMax>(
             "hnrf_sample_warp_bwd", dim3((unsigned)bx, (unsigned)B), dim3(1024), lds, st, rays_o, rays_d, z_vals, motion_Rs,
             motion_Ts, vol, bbox_min, bbox_scale, x_skel, fg_mask, g_x_skel, g_mask, P, S, G, d_vol, d_Rs, d_Ts);
     }
