@@ -3,9 +3,10 @@
 What run.py does per frame (run.py:68-157, 214-445): ``model(**data, iter_val=cfg.eval_iter)`` under no_grad, scatter
 the rendered rays back into the H x W image by ``ray_mask`` with background fill (run.py:48-65), quantise to 8 bit,
 write PNGs / a video, append metrics.  Here the scatter / quantisation runs on the GPU, frames are dealt round-robin
-over the ranks (one process per GPU, no data-path collective), the finished uint8 images travel to the host
-asynchronously through pinned buffers and PNG encoding happens on worker threads, so that the GPU never waits for
-an image to be written.
+over the ranks (one process per GPU, no data-path collective), what a finished frame sends to the host (uint8 images,
+metric vector, JPEG stream) travels asynchronously through pinned buffers and PNG encoding happens on worker threads,
+so that the GPU never waits for an image to be written.  That copy-out is stated once, FrameOutbox, for every loop that
+renders frames: render_frames here, run.run_mesh_render.
 
   unpack_to_image, to_8b_image, to_8b3ch_image, tile_images   run.py:37-65, image_util.py:21-53   (byte-exact:
                                                               tests/golden/image_unpack.npz, made by the reference)
@@ -369,7 +370,110 @@ class _PinnedPool:
         self.free[(tuple(t.shape), t.dtype)].append(t)
 
 
+def video_copy_cap(height, width):
+    """Bytes of a frame's JPEG stream that FrameOutbox.post copies to the host before it knows the stream's length:
+    3 bits per pixel of the panels, at least 64 KiB.  (A 512 x 512 render panel at quality 90 takes 15-40 KB; 3 bits per
+    pixel is what dense texture takes at that quality.)  A longer stream costs one synchronous copy of the remainder when
+    the frame is handed over, counted in render_frames.last_video['fallbacks']."""
+    return max(64 << 10, (3 * height * width) // 8)
+
+
+class _Parcel:
+    """One frame's host-bound products between FrameOutbox.post and the hand-over: the staged 8-bit images, the staged
+    metric vector or None, the staged first ``cap`` bytes of the JPEG stream with its length word (and the device buffer
+    a longer stream's remainder is fetched from) or None, all behind one ``event`` (None on a CPU device, where the
+    tensors themselves stand in for the pinned copies and ``pool`` is None).  ``collect`` or ``discard`` ends it: once."""
+
+    def __init__(self, pool, event, hosts, metric_host, vhost, lhost, vdev, cap):
+        self.pool, self.event, self.hosts, self.metric_host = pool, event, hosts, metric_host
+        self.vhost, self.lhost, self.vdev, self.cap = vhost, lhost, vdev, cap
+
+    def landed(self):
+        """True once every copy has arrived; never waits."""
+        return self.event is None or self.event.query()
+
+    def buffers(self):
+        return self.hosts + [h for h in (self.metric_host, self.vhost, self.lhost) if h is not None]
+
+    def _give_back(self):
+        for h in self.buffers() if self.pool is not None else ():
+            self.pool.give(h)
+
+    def discard(self):
+        """Wait for the copies and give the buffers back unread (a frame that is rendered again)."""
+        if self.event is not None:
+            self.event.synchronize()
+        self._give_back()
+
+    def collect(self):
+        """Wait for the copies (the one wait per frame) and return (numpy images, metric values or None, JPEG bytes or
+        None, whether the stream was longer than the cap: its remainder was then fetched here, synchronously, once);
+        the buffers go back to the pool."""
+        if self.event is not None:
+            self.event.synchronize()
+        arrs = [h.numpy().copy() if self.pool is not None else h.numpy() for h in self.hosts]
+        values = None if self.metric_host is None else self.metric_host.tolist()
+        data, fell_back = None, False
+        if self.vhost is not None:
+            n, cap = int(self.lhost[0]), self.vhost.shape[0]
+            data = self.vhost[:min(n, cap)].numpy().tobytes()
+            fell_back = n > cap
+            if fell_back:
+                data += self.vdev[cap:n].cpu().numpy().tobytes()
+        self._give_back()
+        return arrs, values, data, fell_back
+
+
+class FrameOutbox:
+    """The way a finished frame leaves the GPU, for every loop that renders frames: ``post`` queues the copies of its
+    device tensors into pooled pinned buffers on a copy stream of its own, behind ONE event, and returns a _Parcel;
+    the parcel's ``collect()`` waits for that event, reads the buffers and gives them back.  On a CPU device nothing is
+    copied and nothing waits."""
+
+    def __init__(self, device):
+        self.device = device
+        self.stream = torch.cuda.Stream(device=device) if device.type == 'cuda' else None
+        self.pool = _PinnedPool()
+
+    def _stage(self, src):
+        h = self.pool.take(src.shape, src.dtype)
+        h.copy_(src, non_blocking=True)
+        src.record_stream(self.stream)
+        return h
+
+    def post(self, images, metric_vec=None, video=None):
+        """``images``: uint8 tensors; ``metric_vec``: float64 vector; ``video``: (buffer, length, height, width) -- what
+        JpegEncoder.encode returned for panels of height x width.  The stream's length is not known here, so its first
+        min(len(buffer), video_copy_cap(height, width)) bytes and the length word travel."""
+        vbuf, vlen, height, width = video if video is not None else (None, None, 0, 0)
+        if self.stream is None:
+            return _Parcel(None, None, [im.cpu() for im in images], metric_vec, vbuf, vlen, vbuf, 0)
+        self.stream.wait_stream(torch.cuda.current_stream(self.device))  # overlap D2H with the next frame
+        with torch.cuda.stream(self.stream):
+            hosts = [self._stage(im) for im in images]
+            mhost = None if metric_vec is None else self._stage(metric_vec)
+            vhost, lhost, cap = None, None, 0
+            if vbuf is not None:
+                cap = min(int(vbuf.shape[0]), video_copy_cap(height, width))
+                vhost, lhost = self._stage(vbuf[:cap]), self._stage(vlen)
+            event = torch.cuda.Event()
+            event.record(self.stream)
+        return _Parcel(self.pool, event, hosts, mhost, vhost, lhost, vbuf, cap)
+
+
 _FRAME_KEYS = ('dst_Rs', 'dst_Ts', 'cnl_gtfms', 'dst_posevec', 'cnl_bbox_min_xyz', 'cnl_bbox_scale_xyz', 'bgcolor')
+
+
+def with_rays(frame, device):
+    """``frame`` itself when it carries ``rays``; for a camera-only frame a copy with rays, near / far and ray_mask
+    from the device generator.  The rays are clipped against the POSED skeleton's bbox (freeview.py:226;
+    dataset.Subject puts it in ray_bbox_*); the synthetic frames of scene.py pose nothing and use the canonical one."""
+    if 'rays' in frame:
+        return frame
+    from . import ops
+    return dict(frame, **ops.gen_rays(frame['K'], frame['E'], frame.get('ray_bbox_min_xyz', frame['cnl_bbox_min_xyz']),
+                                      frame.get('ray_bbox_max_xyz', frame['cnl_bbox_max_xyz']),
+                                      int(frame['img_height']), int(frame['img_width']), device=device))
 
 
 class FramePrefetcher:
@@ -440,15 +544,7 @@ class FramePrefetcher:
         return t
 
     def build(self, idx):
-        fr = self.frames[idx]
-        if 'rays' not in fr:
-            from . import ops
-            fr = dict(fr)
-            # rays are clipped against the POSED skeleton's bbox (freeview.py:226; dataset.Subject puts it in
-            # ray_bbox_*); the synthetic frames of scene.py pose nothing and use the canonical one
-            fr.update(ops.gen_rays(fr['K'], fr['E'], fr.get('ray_bbox_min_xyz', fr['cnl_bbox_min_xyz']),
-                                   fr.get('ray_bbox_max_xyz', fr['cnl_bbox_max_xyz']),
-                                   int(fr['img_height']), int(fr['img_width']), device=self.device))
+        fr = with_rays(self.frames[idx], self.device)
         data = {k: self._up(fr[k]) for k in ('rays', 'near', 'far') + _FRAME_KEYS}
         data['motion_weights_priors'] = self._priors(fr['motion_weights_priors'])
         if cfg.get('amd', {}).get('canonical', 'mlp') == 'baked':
@@ -530,11 +626,10 @@ class FramePrefetcher:
 
 METRIC_NAMES = ('psnr', 'ssim', 'lpips')
 
-# a frame of render_frames between its launches and its hand-over: frame index, pinned image buffers, the event behind
-# their copies, the prefetcher's item (to render it again), the number of frames the network's f16-range guard had
-# watched once this one was queued, the pinned metric vector or None, the frame's JPEG stream or None: (the pinned first
-# video_copy_cap bytes, the pinned length word, the device buffer a longer stream's remainder is fetched from)
-_InFlight = namedtuple('_InFlight', 'idx hosts event item watch_id metric_host video', defaults=(None,))
+# a frame of render_frames between its launches and its hand-over: frame index, the FrameOutbox parcel of its copies, the
+# prefetcher's item (to render it again), the number of frames the network's f16-range guard had watched once this one
+# was queued
+_InFlight = namedtuple('_InFlight', 'idx parcel item watch_id')
 
 
 def select_panels(rgb8, alpha8, truth8=None):
@@ -546,14 +641,6 @@ def select_panels(rgb8, alpha8, truth8=None):
     if cfg.get('show_alpha', False):
         imgs.append(alpha8)
     return imgs
-
-
-def video_copy_cap(height, width):
-    """Bytes of a frame's JPEG stream that render_frames copies to the host before it knows the stream's length:
-    3 bits per pixel of the panels, at least 64 KiB.  (A 512 x 512 render panel at quality 90 takes 15-40 KB; 3 bits per
-    pixel is what dense texture takes at that quality.)  A longer stream costs one synchronous copy of the remainder when
-    the frame is handed over, counted in render_frames.last_video['fallbacks']."""
-    return max(64 << 10, (3 * height * width) // 8)
 
 
 def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, show_truth=False, prefetch=None,
@@ -571,10 +658,12 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
     per-frame numpy pass and the 32 B/ray upload.
 
     Frames are assembled ``prefetch`` ahead by ``FramePrefetcher`` (host work and every device read-back on a side
-    stream); finished images leave through pinned buffers on a copy stream and are handed to ``on_image`` one frame
-    late at the earliest -- after the next frame's forward has looked at this frame's f16-range verdict
-    (Network.check_f16_range), so that with ``cfg.amd.on_f16_range = 'f32'`` a frame rendered out of range is
-    rendered again with the exact kernels before anybody sees it.
+    stream); everything a finished frame sends to the host -- images, metric vector, JPEG stream -- is posted to one
+    FrameOutbox (pinned buffers on a copy stream, one event per frame) and handed over, ``on_image`` then ``on_metrics``
+    then ``on_video``, one frame late at the earliest -- after the next frame's forward has looked at this frame's
+    f16-range verdict (Network.check_f16_range), so that with ``cfg.amd.on_f16_range = 'f32'`` a frame rendered out
+    of range is rendered again with the exact kernels before anybody sees it.  This function keeps the device work of
+    a frame, the queue of frames in flight with that handshake, the callbacks and the timing records.
 
     ``metrics`` (a list out of 'psnr', 'ssim', 'lpips'; GPU only, needs ``show_truth``): every frame that has its truth
     gets the metrics of its 8-bit render against its 8-bit truth ON THE DEVICE, as part of the frame's launches --
@@ -586,11 +675,11 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
     (MetricsWriter.normalize leaves an image whose maximum is <= 2 as it is).
 
     ``video`` (a video.JpegEncoder on ``device``): the frame's panels (select_panels: the choice run._panels makes on
-    the host) are concatenated on the device and JPEG-encoded as part of the frame's launches.  The stream's length is
-    not known when its copy is queued, so the first video_copy_cap(H, W) bytes and the length word travel through
-    pinned buffers behind the images, under the same event; they arrive as ``on_video(idx, bytes)`` after that frame's
-    ``on_image`` (and ``on_metrics``).  Only a stream longer than the cap fetches its remainder, synchronously, at
-    hand-over (render_frames.last_video = {'frames', 'fallbacks', 'bytes', 'cap'}): no synchronisation enters the loop.
+    the host) are concatenated on the device and JPEG-encoded as part of the frame's launches.  The stream travels
+    behind the images, under the same event (FrameOutbox.post: its first video_copy_cap(H, W) bytes), and arrives as
+    ``on_video(idx, bytes)`` after that frame's ``on_image`` (and ``on_metrics``).  Only a stream longer than the cap
+    fetches its remainder, synchronously, at hand-over (render_frames.last_video = {'frames', 'fallbacks', 'bytes',
+    'cap'}: streams handed over, those that fell back, their bytes, the cap): no synchronisation enters the loop.
     A frame rendered again after an f16-range hit is encoded again.  ``images='none'`` (only with ``video``): no 8-bit
     image is copied to the host, ``on_image`` is never called and the returned dict is empty."""
     device = device or next(network.parameters()).device
@@ -620,44 +709,27 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
     cfg.perturb = 0.                                                     # run.py:71,215
     out = {}
     on_gpu = device.type == 'cuda'
-    copy_stream = torch.cuda.Stream(device=device) if on_gpu else None
-    pool = _PinnedPool()
+    outbox = FrameOutbox(device)
     pending = []                                    # _InFlight records, oldest first
     guard = hasattr(network, 'check_f16_range')
 
     t_submit, t_wait, t_user = [], [], []           # per frame: launches queued / waiting for the image / on_image
 
     def deliver(entry):
-        i, hosts = entry.idx, entry.hosts
+        i = entry.idx
         t0 = time.perf_counter()
-        if entry.event is not None:
-            entry.event.synchronize()
-        arrs = [h.numpy().copy() if on_gpu else h.numpy() for h in hosts]
-        if on_gpu:
-            for h in hosts:
-                pool.give(h)
+        arrs, values, data, fell_back = entry.parcel.collect()
         if arrs:
             out[i] = arrs[0]
         t1 = time.perf_counter()
         if on_image is not None and arrs:
             on_image(i, *arrs)
-        if entry.metric_host is not None:
-            vals = entry.metric_host.tolist()
-            pool.give(entry.metric_host)
-            if on_metrics is not None:
-                on_metrics(i, dict(zip(metrics, vals)))
-        if entry.video is not None:
-            vhost, vlen, vdev = entry.video
-            n = int(vlen[0])
-            data = vhost[:min(n, vhost.shape[0])].numpy().tobytes()
-            if n > vhost.shape[0]:                   # longer than the cap: the remainder, synchronously, once
-                data += vdev[vhost.shape[0]:n].cpu().numpy().tobytes()
-                vstat['fallbacks'] += 1
-            if on_gpu:
-                pool.give(vhost)
-                pool.give(vlen)
+        if on_metrics is not None and values is not None:
+            on_metrics(i, dict(zip(metrics, values)))
+        if data is not None:
             vstat['frames'] += 1
-            vstat['bytes'] += n
+            vstat['fallbacks'] += fell_back
+            vstat['bytes'] += len(data)
             if on_video is not None:
                 on_video(i, data)
         t_wait.append(t1 - t0)
@@ -684,45 +756,17 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
                 # (a table of the host's float32 k / 255: the device divides by a scalar as a product with 1 / 255)
                 vals['lpips'] = 1000 * lpips_fn(unit[rgb8.long()], unit[t8.long()]).reshape(()).to(torch.float64)
             mvec = torch.stack([vals[k] for k in metrics])
-        vbuf = vlen = None
+        vid = None
         if video is not None:
             panels = select_panels(rgb8, a8, t8 if item['truth'] is not None else None)
-            vbuf, vlen = video.encode(panels[0] if len(panels) == 1 else torch.cat(panels, dim=1))
+            vid = video.encode(panels[0] if len(panels) == 1 else torch.cat(panels, dim=1)) + (item['H'], item['W'] * len(panels))
         if timing:
             gpu_ev[-1][1].record()
         imgs = [rgb8, a8] + ([t8] if item['truth'] is not None else [])
-        if images == 'none':
-            imgs = []
-        wid = network.f16_range_watched if guard else 0
-        if not on_gpu:
-            return _InFlight(item['idx'], [im.cpu() for im in imgs], None, item, wid, None,
-                             None if vbuf is None else (vbuf, vlen, vbuf))
-        copy_stream.wait_stream(torch.cuda.current_stream(device))      # overlap D2H with the next frame
-        hosts = []
-        with torch.cuda.stream(copy_stream):
-            for im in imgs:
-                h = pool.take(im.shape)
-                h.copy_(im, non_blocking=True)
-                im.record_stream(copy_stream)
-                hosts.append(h)
-            mhost = None
-            if mvec is not None:
-                mhost = pool.take(mvec.shape, torch.float64)
-                mhost.copy_(mvec, non_blocking=True)
-                mvec.record_stream(copy_stream)
-            vid = None
-            if vbuf is not None:
-                cap = min(int(vbuf.shape[0]), video_copy_cap(item['H'], item['W'] * len(panels)))
-                vstat['cap'] = cap
-                vhost, lhost = pool.take((cap,)), pool.take((1,), torch.int64)
-                vhost.copy_(vbuf[:cap], non_blocking=True)
-                lhost.copy_(vlen, non_blocking=True)
-                vbuf.record_stream(copy_stream)
-                vlen.record_stream(copy_stream)
-                vid = (vhost, lhost, vbuf)
-            ev = torch.cuda.Event()
-            ev.record(copy_stream)
-        return _InFlight(item['idx'], hosts, ev, item, wid, mhost, vid)
+        parcel = outbox.post([] if images == 'none' else imgs, mvec, vid)
+        if parcel.cap:
+            vstat['cap'] = parcel.cap
+        return _InFlight(item['idx'], parcel, item, network.f16_range_watched if guard else 0)
 
     def guard_state():
         return (network.f16_range_hits, network._mlp_mode() if hasattr(network, '_mlp_mode') else None) if guard else None
@@ -737,16 +781,7 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
         if not guard or now[0] == before[0] or now[1] == before[1]:
             return
         for k, entry in enumerate(pending):
-            if entry.event is not None:
-                entry.event.synchronize()
-            if on_gpu:
-                for h in entry.hosts:
-                    pool.give(h)
-                if entry.metric_host is not None:
-                    pool.give(entry.metric_host)
-                if entry.video is not None:
-                    pool.give(entry.video[0])
-                    pool.give(entry.video[1])
+            entry.parcel.discard()
             pending[k] = render(entry.item)
 
     def verdicts(wait, upto=None):
@@ -772,7 +807,7 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
             t_submit.append(time.perf_counter() - t0)
             rerender_if_switched(before)
             # a frame is handed over once its verdict is known and its copy has landed; at most three in flight
-            while pending and (len(pending) > 3 or (known(pending[0]) and (pending[0].event is None or pending[0].event.query()))):
+            while pending and (len(pending) > 3 or (known(pending[0]) and pending[0].parcel.landed())):
                 if not known(pending[0]):
                     verdicts(wait=True, upto=pending[0].watch_id)              # (of the oldest frame only: the queue stays full)
                 deliver(pending.pop(0))
@@ -802,22 +837,15 @@ def render_frame_ray_sharded(network, frame, rank, world, device=None, group=Non
     after which every rank holds the whole image.  Returns (rgb8, alpha8) uint8 arrays on the host like
     render_frames' callbacks get them."""
     import torch.distributed as dist
-    from . import ops
     device = device or next(network.parameters()).device
     network.eval()
-    fr = dict(frame)
-    if 'rays' not in fr:
-        fr.update(ops.gen_rays(fr['K'], fr['E'], fr.get('ray_bbox_min_xyz', fr['cnl_bbox_min_xyz']),
-                               fr.get('ray_bbox_max_xyz', fr['cnl_bbox_max_xyz']), int(fr['img_height']),
-                               int(fr['img_width']), device=device))
+    fr = with_rays(frame, device)
     T = lambda v: torch.as_tensor(np.ascontiguousarray(v) if isinstance(v, np.ndarray) else v).to(device)
     rays, near, far = T(fr['rays']), T(fr['near']), T(fr['far'])
     N = rays.shape[1]
     per = -(-N // world)                                                 # equal blocks (the last one padded)
     lo, hi = min(rank * per, N), min((rank + 1) * per, N)
-    keys = ('dst_Rs', 'dst_Ts', 'cnl_gtfms', 'motion_weights_priors', 'dst_posevec', 'cnl_bbox_min_xyz',
-            'cnl_bbox_scale_xyz', 'bgcolor')
-    data = {k: T(fr[k]) for k in keys}
+    data = {k: T(fr[k]) for k in _FRAME_KEYS + ('motion_weights_priors',)}
     block = torch.zeros(per, 4, device=device)
     old = cfg.perturb
     cfg.perturb = 0.

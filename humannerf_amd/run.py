@@ -266,27 +266,15 @@ def run_mesh_render(network, subject, kind='movement', resolution=256, level=Non
     device = verts.device
     vout = _VideoOut(os.path.join(_output_dir(logdir), folder), names, 0, 1, device)
     writer = None if vout.only else render.ImageWriter(_output_dir(logdir), folder)
-    copy_stream = torch.cuda.Stream(device=device)
-    pool = render._PinnedPool()
-    images, pending = {}, []                # pending: [idx, pinned images (rgb, alpha), video or None, event], oldest first
+    outbox = render.FrameOutbox(device)
+    images, pending = {}, []                # pending: (idx, the outbox's parcel), oldest first
 
-    def deliver(entry):
-        i, hosts, vid, ev = entry
-        ev.synchronize()                            # the one wait per frame: its copy has landed
-        if hosts:
-            rgb8, alpha8 = hosts[0].numpy().copy(), hosts[1].numpy().copy()
-            pool.give(hosts[0])
-            pool.give(hosts[1])
-            images[i] = rgb8
-            writer.append(_panels(rgb8, alpha8), img_name=names[i])
-        if vid is not None:                         # (as render.render_frames hands a stream over)
-            vhost, lhost, vbuf = vid
-            n = int(lhost[0])
-            data = vhost[:min(n, vhost.shape[0])].numpy().tobytes()
-            if n > vhost.shape[0]:
-                data += vbuf[vhost.shape[0]:n].cpu().numpy().tobytes()
-            pool.give(vhost)
-            pool.give(lhost)
+    def hand_over(i, parcel):
+        arrs, _, data, _ = parcel.collect()         # the one wait per frame: its copy has landed
+        if arrs:
+            images[i] = arrs[0]
+            writer.append(_panels(*arrs), img_name=names[i])
+        if data is not None:
             vout.add(i, data)
 
     network.eval()
@@ -297,33 +285,16 @@ def run_mesh_render(network, subject, kind='movement', resolution=256, level=Non
         out = network.render_mesh(verts, faces, colors, frame, iter_val=float(cfg.get('eval_iter', 1e7)),
                                   shade=shade, cull=cull)
         imgs = [render.to_8b_image(out['rgb']), render.to_8b3ch_image(out['alpha']).contiguous()]
-        vbuf = vlen = None
+        vid = None
         if vout.encoder is not None:
             panels = render.select_panels(imgs[0], imgs[1])
-            vbuf, vlen = vout.encoder.encode(panels[0] if len(panels) == 1 else torch.cat(panels, dim=1))
-        copy_stream.wait_stream(torch.cuda.current_stream(device))
-        hosts, vid = [], None
-        with torch.cuda.stream(copy_stream):
-            for im in ([] if vout.only else imgs):
-                h = pool.take(im.shape)
-                h.copy_(im, non_blocking=True)
-                im.record_stream(copy_stream)
-                hosts.append(h)
-            if vbuf is not None:
-                cap = min(int(vbuf.shape[0]), render.video_copy_cap(imgs[0].shape[0], imgs[0].shape[1] * len(panels)))
-                vhost, lhost = pool.take((cap,)), pool.take((1,), torch.int64)
-                vhost.copy_(vbuf[:cap], non_blocking=True)
-                lhost.copy_(vlen, non_blocking=True)
-                vbuf.record_stream(copy_stream)
-                vlen.record_stream(copy_stream)
-                vid = (vhost, lhost, vbuf)
-            ev = torch.cuda.Event()
-            ev.record(copy_stream)
-        pending.append([i, hosts, vid, ev])
+            vid = vout.encoder.encode(panels[0] if len(panels) == 1 else torch.cat(panels, dim=1)) \
+                + (imgs[0].shape[0], imgs[0].shape[1] * len(panels))
+        pending.append((i, outbox.post([] if vout.only else imgs, video=vid)))
         while len(pending) > 2:                     # two frames in flight: the copy of one overlaps the next raster
-            deliver(pending.pop(0))
+            hand_over(*pending.pop(0))
     while pending:
-        deliver(pending.pop(0))
+        hand_over(*pending.pop(0))
     stack = writer.finalize() if writer is not None else None
     result = {'frames': list(range(n)), 'images': images, 'image_dir': os.path.join(_output_dir(logdir), folder),
               'stack': stack}

@@ -26,5 +26,6 @@ torch.cuda.synchronize(); t0 = time.perf_counter()
 render.render_frames(net, cams, device=dev)
 torch.cuda.synchronize(); loop = (time.perf_counter() - t0) / len(cams)
 print('pure render of the %d hit rays: %.2f ms; frame loop: %.2f ms per frame (%.2f fps); overhead %.2f ms' % (n_rays, pure * 1e3, loop * 1e3, 1 / loop, (loop - pure) * 1e3))
-sub = sorted(render.render_frames.last_prefetch['submit_ms'])
-print('submit_ms over %d frames: median %.3f min %.3f max %.3f' % (len(sub), sub[len(sub) // 2], sub[0], sub[-1]))
+for key in ('submit_ms', 'image_wait_ms'):
+    ts = sorted(render.render_frames.last_prefetch[key])
+    print('%s over %d frames: median %.3f min %.3f max %.3f' % (key, len(ts), ts[len(ts) // 2], ts[0], ts[-1]))

@@ -202,3 +202,44 @@ def test_run_mesh_render_writes_the_three_sequences(net, tmp_path):
             assert np.array_equal(im, render.to_8b_image(host['rgb']))
     finally:
         cfg.show_alpha = old
+
+
+def test_run_mesh_render_with_video(net, tmp_path):
+    """cfg.amd.video in the mesh loop, panels [render | alpha]: 'mjpeg' writes an AVI of the 2 frames next to the PNGs,
+    each frame the twin's stream of its PNG's pixels, named like the PNGs; 'mjpeg_only' writes no PNG, no directory, and
+    the same AVI byte for byte."""
+    from PIL import Image
+    from humannerf_amd import dataset, run, video
+    scene.write_synthetic_subject(str(tmp_path / 'subject'), n_frames=2, size=64)
+    subject = dataset.Subject(str(tmp_path / 'subject'))
+    old = (cfg.get('show_alpha', False), {k: cfg.amd[k] for k in ('video', 'metrics') if k in cfg.amd})
+    cfg.show_alpha = True
+    cfg.amd.metrics = 'device'              # (the loop computes none; 'mjpeg_only' is refused next to the host route)
+    try:
+        res = {}
+        for mode in ('mjpeg', 'mjpeg_only'):
+            cfg.amd.video = mode
+            res[mode] = run.run_mesh_render(net, subject, kind='tpose', total_frames=2, resolution=64, level=LEVEL,
+                                            image_size=64, logdir=str(tmp_path / mode))
+        both, only = res['mjpeg'], res['mjpeg_only']
+        assert both['video'] == both['image_dir'] + '.avi' and sorted(os.listdir(both['image_dir'])) == ['000000.png', '000001.png']
+        w, h, fps, frames = video.read_avi(both['video'])
+        assert (w, h, fps, len(frames)) == (128, 64, 10, 2)
+        for i, data in enumerate(frames):
+            pixels = np.asarray(Image.open(os.path.join(both['image_dir'], '%06d.png' % i)))
+            assert pixels.shape == (64, 128, 3) and np.array_equal(pixels[:, :64], both['images'][i])
+            assert data == video.jpeg_encode_numpy(pixels, 90)
+        assert frames[0] != frames[1]
+        with open(both['video'] + '.names.txt') as f:
+            assert f.read().split() == ['000000', '000001']
+        assert only['images'] == {} and only['stack'] is None and not os.path.exists(only['image_dir'])
+        assert [f for _, _, fs in os.walk(str(tmp_path / 'mjpeg_only')) for f in fs if f.endswith('.png')] == []
+        with open(only['video'], 'rb') as a, open(both['video'], 'rb') as b:
+            assert a.read() == b.read()
+    finally:
+        cfg.show_alpha = old[0]
+        for k in ('video', 'metrics'):
+            if k in old[1]:
+                cfg.amd[k] = old[1][k]
+            else:
+                cfg.amd.pop(k, None)

@@ -113,7 +113,57 @@ def test_refusals_launch_nothing():
         video.JpegEncoder(DEV, 90).encode(torch.zeros(4, 4, 3, device=DEV))
 
 
-# ------------------------------------------------------------------------------------------------ 5: the loops
+# ------------------------------------------------------------------------------------------------ 5: the copy-out
+def _products(seed):
+    """One frame's host-bound products on the device: three 8 x 8 images, a float64 vector, a made-up 2000-byte stream
+    in a 3000-byte buffer with its length word."""
+    rs = np.random.RandomState(seed)
+    imgs = [rs.randint(0, 256, (8, 8, 3)).astype(np.uint8) for _ in range(3)]
+    vals = rs.rand(3)
+    stream = rs.randint(0, 256, 3000).astype(np.uint8)
+    dev = lambda a: torch.from_numpy(a).to(DEV)
+    return imgs, vals, stream[:2000].tobytes(), ([dev(im) for im in imgs], dev(vals),
+                                                 (dev(stream), torch.tensor([2000], dtype=torch.int64, device=DEV), 8, 24))
+
+
+def test_frame_outbox_round_trip(monkeypatch):
+    """Three parcels in flight at once come back as posted; the real cap (>= 64 KiB) covers the stream, a cap of 700
+    makes every collect() fetch the remainder and still return all 2000 bytes."""
+    from humannerf_amd import render
+    outbox = render.FrameOutbox(DEV)
+    for cap, falls_back in ((None, False), (700, True)):
+        if cap is not None:
+            monkeypatch.setattr(render, 'video_copy_cap', lambda height, width: cap)
+        want = [_products(seed) for seed in range(3)]
+        parcels = [outbox.post(*w[3]) for w in want]
+        assert [p.cap for p in parcels] == [3000 if cap is None else cap] * 3
+        for (imgs, vals, data, _), parcel in zip(want, parcels):
+            arrs, values, stream, fell_back = parcel.collect()
+            assert len(arrs) == 3 and all(np.array_equal(a, im) for a, im in zip(arrs, imgs))
+            assert values == vals.tolist() and len(stream) == 2000 and stream == data and fell_back is falls_back
+
+
+def test_frame_outbox_reuses_its_pinned_buffers():
+    """post, collect, post of the same shapes: the second parcel's pinned buffers are the first one's -- they went back
+    to the pool; the same after discard(), which the re-render after an f16-range hit relies on."""
+    from humannerf_amd import render
+    outbox = render.FrameOutbox(DEV)
+    ptrs = lambda parcel: sorted(h.data_ptr() for h in parcel.buffers())
+    first = outbox.post(*_products(0)[3])
+    mine = ptrs(first)
+    assert len(set(mine)) == 6 and all(h.is_pinned() for h in first.buffers())       # 3 images, vector, stream, length
+    first.collect()
+    second = outbox.post(*_products(1)[3])
+    assert ptrs(second) == mine
+    second.discard()
+    third = outbox.post(*_products(2)[3])
+    assert ptrs(third) == mine
+    imgs, vals, data, _ = _products(2)
+    arrs, values, stream, _ = third.collect()
+    assert all(np.array_equal(a, im) for a, im in zip(arrs, imgs)) and values == vals.tolist() and stream == data
+
+
+# ------------------------------------------------------------------------------------------------ 6: the loops
 def _seeded_net(scale=None):
     from humannerf_amd.network import Network
     from humannerf_amd.seeded import default_shapes, seeded_state, with_density

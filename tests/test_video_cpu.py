@@ -324,6 +324,45 @@ def test_render_frames_video_on_a_cpu_device():
         cfg.show_truth, cfg.show_alpha = old
 
 
+def _outbox_case():
+    """A CPU-device FrameOutbox and one frame's products: three 24 x 40 images, a 3-element float64 vector, the twin's
+    stream of the images side by side in a buffer longer than the stream (as the encoder's is), and post()'s video tuple."""
+    import torch
+    from humannerf_amd import render
+    rs = np.random.RandomState(5)
+    imgs = [rs.randint(0, 256, (24, 40, 3)).astype(np.uint8) for _ in range(3)]
+    vals = np.array([31.25, 0.875, 1e-3 / 3], np.float64)
+    data = video.jpeg_encode_numpy(np.concatenate(imgs, axis=1), 90)
+    vid = (torch.frombuffer(bytearray(data + bytes(100)), dtype=torch.uint8), torch.tensor([len(data)], dtype=torch.int64),
+           24, 3 * 40)
+    tensors = [torch.from_numpy(im.copy()) for im in imgs]
+    return render.FrameOutbox(torch.device('cpu')), imgs, tensors, vals, data, vid
+
+
+def test_frame_outbox_returns_what_was_posted():
+    import torch
+    outbox, imgs, tensors, vals, data, vid = _outbox_case()
+    parcel = outbox.post(tensors, torch.from_numpy(vals.copy()), vid)
+    assert parcel.landed()
+    arrs, values, stream, fell_back = parcel.collect()
+    assert len(arrs) == 3 and all(a.dtype == np.uint8 and np.array_equal(a, im) for a, im in zip(arrs, imgs))
+    assert values == vals.tolist() and stream == data and fell_back is False
+
+
+def test_frame_outbox_images_only():
+    outbox, imgs, tensors, _, _, _ = _outbox_case()
+    arrs, values, stream, fell_back = outbox.post(tensors).collect()
+    assert len(arrs) == 3 and all(np.array_equal(a, im) for a, im in zip(arrs, imgs))
+    assert values is None and stream is None and fell_back is False
+
+
+def test_frame_outbox_video_only():
+    """As render_frames(images='none') posts a frame: no images come back, the whole stream does."""
+    outbox, _, _, _, data, vid = _outbox_case()
+    arrs, values, stream, fell_back = outbox.post([], video=vid).collect()
+    assert arrs == [] and values is None and stream == data and fell_back is False
+
+
 def test_rank_files_of_a_sharded_loop_merge_into_one(tmp_path):
     """run._VideoOut, the loops' side of cfg.amd.video: with world > 1 rank r writes <folder>.rank<r>.avi with its own
     frames (r, r + world, ...), unnamed frames are called by their index, and merge_parts of the ranks' files is the file
