@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get('HNRF_LIB_PATH', os.path.join(_HERE, 'libhnrf.so'))   
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf.h'))
 CLOUD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_cloud.h'))   # included by hnrf.h
 VIDEO_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_video.h'))   # included by hnrf.h
+SEGMENT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_segment.h'))   # included by hnrf.h
 
 _SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float,
             'double': ctypes.c_double}
@@ -67,6 +68,9 @@ CLOUD_SIGNATURES = _signatures(CLOUD_HEADER_PATH)
 
 # the JPEG encoder's entries of include/hnrf_video.h: additive to ABI version 13 in the same way (load_video)
 VIDEO_SIGNATURES = _signatures(VIDEO_HEADER_PATH)
+
+# the body-part segmentation's entries of include/hnrf_segment.h: additive to ABI version 13 in the same way (load_segment)
+SEGMENT_SIGNATURES = _signatures(SEGMENT_HEADER_PATH)
 
 _lib = None
 
@@ -134,6 +138,26 @@ def load_video():
             fn.restype = res
             fn.argtypes = args
         _video_bound = True
+    return lib
+
+
+_segment_bound = False
+
+
+def load_segment():
+    """load() plus the entries of include/hnrf_segment.h, typed.  A library without them raises HnrfError."""
+    global _segment_bound
+    lib = load()
+    if not _segment_bound:
+        for name, (res, args) in SEGMENT_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise HnrfError(f'{LIB_PATH} does not export {name}: it was built before the body-part segmentation '
+                                f'(include/hnrf_segment.h); rebuild it') from None
+            fn.restype = res
+            fn.argtypes = args
+        _segment_bound = True
     return lib
 
 

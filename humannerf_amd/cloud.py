@@ -7,6 +7,10 @@ dump (run.py:388-404, image_util.py:99-119) and ``tools/compute_distance*.py`` o
   nearest_pairs     find_nearest_pair_gpu: the mutual nearest neighbours of two clouds
   frame_distance    compute_distance_gpu: the summed colour error of the mutual pairs closer than dist_thresh
   distance_matrix   the frame x frame matrix of the tools' main loop, all pairs of a chunk in one launch
+  segment_records   tools/segment.py: a frame's records split by body part (include/hnrf_segment.h, csrc/hnrf_segment.hip;
+                    integer arithmetic, twin_segment / twin_compact are the numpy form, bit for bit)
+  segment_distance_matrices   the per-part matrices of tools/compute_distance_seg.py, all parts from one pack
+  cluster_frames, merge_matrix_chunks   tools/cluster.py and tools/merge_d.py, numpy on the host
 
 The arithmetic is one statement (hnrf_cloud.h): d2 = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)) in fp32, nearest =
 smallest d2 with ties to the lowest original record index, distance = fl(sqrt(d2)).  The ``twin_*`` functions below are
@@ -355,3 +359,283 @@ def _pair_value(recs, vwt, tau, method, axis, backend, device):
     pairs = torch.tensor([[0, 1]], dtype=torch.int32, device=dev)
     return float(ops.cloud_distance_pairs(pk['xyz'], pk['rgb'], pk['orig'], pk['offsets'], pairs, tau, axis,
                                           pk['max_n'])[0][0])
+
+
+# ------------------------------------------------------------------------------------------------ body parts
+# tools/segment.py:5-14 as data: part -> the bones (lbs arg-max) that seed it, in the reference's order
+BODY_PARTS = {
+    'root': (0,), 'lhip': (1,), 'rhip': (2,), 'lknee': (4,), 'rknee': (5,), 'lfoot': (7, 10), 'rfoot': (8, 11),
+    'belly': (3,), 'spine': (6,), 'chest-inshoulder-neck': (9, 12, 13, 14), 'head': (15,),
+    'lshoulder-elbow': (16, 18), 'rshoulder-elbow': (17, 19), 'lwrist-hand': (20, 22), 'rwrist-hand': (21, 23)}
+MAX_PARTS, MAX_BONES, MAX_RADIUS = 32, 32, 64
+
+
+def bone_masks(parts=None):
+    """The per-bone uint32 words of hnrf_segment_members: bit p of word b set iff bone b seeds part p (parts in the
+    mapping's order).  At most 32 parts; a bone outside [0, 32) can seed nothing and is refused."""
+    parts = BODY_PARTS if parts is None else parts
+    if not 1 <= len(parts) <= MAX_PARTS:
+        raise ValueError('parts: 1 .. %d parts, got %d' % (MAX_PARTS, len(parts)))
+    masks = np.zeros(MAX_BONES, np.uint32)
+    for p, bones in enumerate(parts.values()):
+        for b in bones:
+            if int(b) != b or not 0 <= int(b) < MAX_BONES:
+                raise ValueError('parts: bone %r outside [0, %d)' % (b, MAX_BONES))
+            masks[int(b)] |= np.uint32(1 << p)
+    return masks
+
+
+def _check_radius(radius):
+    if int(radius) != radius or not 1 <= int(radius) <= MAX_RADIUS:
+        raise ValueError('radius must be an integer in [1, %d], got %r' % (MAX_RADIUS, radius))
+    return int(radius)
+
+
+def twin_segment(rec, bone_masks, H, W, radius):
+    """One frame's part membership in numpy, the bitmap statement of include/hnrf_segment.h: rec (N, 10),
+    bone_masks (B,) uint32 -> member (N,) uint32, bit p set iff a record that seeds part p lies at L1 pixel distance
+    < radius.  A row, column or bone that is not integer-valued, or a pixel outside [0, H) x [0, W): ValueError."""
+    rec = np.asarray(rec, dtype=np.float32).reshape(-1, 10)
+    masks = np.asarray(bone_masks).astype(np.uint32).reshape(-1)
+    H, W, radius = int(H), int(W), _check_radius(radius)
+    pix, bone = rec[:, 7:9], rec[:, 9]
+    whole = lambda v: np.isfinite(v) & (v == np.floor(v)) & (np.abs(v) <= 2.0 ** 24)
+    if not whole(pix).all():
+        raise ValueError('twin_segment: a row or column that is not integer-valued')
+    r, c = pix[:, 0].astype(np.int64), pix[:, 1].astype(np.int64)
+    if ((r < 0) | (r >= H) | (c < 0) | (c >= W)).any():
+        raise ValueError('twin_segment: a pixel outside the %d x %d image' % (H, W))
+    if not whole(bone).all():
+        raise ValueError('twin_segment: a bone index that is not integer-valued')
+    b = bone.astype(np.int64)
+    seeds = np.where((b >= 0) & (b < masks.size), masks[np.clip(b, 0, masks.size - 1)], np.uint32(0))
+    seed = np.zeros((H + 2 * radius, W + 2 * radius), np.uint32)         # the image with a margin that seeds nothing
+    np.bitwise_or.at(seed, (r + radius, c + radius), seeds)
+    member = np.zeros(rec.shape[0], np.uint32)
+    for dr in range(1 - radius, radius):
+        w = radius - 1 - abs(dr)
+        for dc in range(-w, w + 1):
+            member |= seed[r + radius + dr, c + radius + dc]
+    return member
+
+
+def twin_compact(members, n_parts, weights=None, weight_min=0.0):
+    """hnrf_segment_count / _scatter in numpy: ``members`` = the per-frame member words -> (seg_offsets (P F + 1,) int64,
+    src (rows,) int32): per (part, frame), part-major, the packed rows whose bit is set (and, with ``weights`` = the
+    per-frame columns 6, whose weight is > weight_min), ascending."""
+    F = len(members)
+    starts = np.concatenate([[0], np.cumsum([len(m) for m in members])]).astype(np.int64)
+    seg, src = [0], []
+    for p in range(int(n_parts)):
+        for f in range(F):
+            keep = ((np.asarray(members[f]).astype(np.uint32) >> np.uint32(p)) & np.uint32(1)).astype(bool)
+            if weights is not None:
+                keep &= np.asarray(weights[f], dtype=np.float32) > np.float32(weight_min)
+            rows = starts[f] + np.nonzero(keep)[0]
+            src.append(rows)
+            seg.append(seg[-1] + rows.size)
+    return np.asarray(seg, np.int64), (np.concatenate(src) if src else np.zeros(0)).astype(np.int32)
+
+
+def _image_size(recs, image_size):
+    """(H, W): as given, or max row + 1 and max column + 1 over all frames' records (1 x 1 without records)."""
+    if image_size is not None:
+        H, W = int(image_size[0]), int(image_size[1])
+        if H < 1 or W < 1:
+            raise ValueError('image_size must be positive, got %r' % (image_size,))
+        return H, W
+    hi = [np.asarray(_host(r), dtype=np.float32)[:, 7:9].max(axis=0) for r in recs if r is not None and len(r)]
+    if not hi:
+        return 1, 1
+    top = np.max(hi, axis=0)
+    if not np.isfinite(top).all():
+        raise ValueError('a row or column that is not finite')
+    return int(top[0]) + 1, int(top[1]) + 1
+
+
+def _segment_pack(recs, dev):
+    """Device records -> the packed batch of include/hnrf_segment.h: rec (total, 10) and offsets (F + 1,) int64."""
+    import torch
+    counts = [r.shape[0] for r in recs]
+    offsets = torch.tensor(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), device=dev)
+    rec = torch.cat(recs).contiguous() if recs else torch.zeros(0, 10, device=dev)
+    return rec, offsets
+
+
+def _to_dev(rec, dev):
+    import torch
+    rec = torch.as_tensor(rec).to(dev, torch.float32)
+    if rec.dim() != 2 or rec.shape[1] != 10:
+        raise ValueError('a record must be [N, 10], got %s' % (tuple(rec.shape),))
+    return rec
+
+
+def segment_records(records, parts=None, radius=10, image_size=None, backend='hip', device=None):
+    """tools/segment.py:23-49: ``records`` maps frame name -> [N, 10] record tensor (or None) -> {part: {frame name:
+    tensor [n, 10] or None}}, the records within L1 pixel distance < ``radius`` of a record whose bone seeds the part,
+    in record order; None where there is none (and for a None record).  ``parts``: name -> bones, default BODY_PARTS;
+    ``image_size`` (H, W): None = max row + 1, max column + 1 over all frames.  Every record of a frame takes part (the
+    weight filter belongs to the distance step).  'hip': one membership + compaction over all frames
+    (hnrf_segment_members / _count / _scatter) and one gather per part; the results are CPU tensors.  'twin':
+    twin_segment per frame."""
+    import torch
+    if backend not in ('hip', 'twin'):
+        raise ValueError("backend must be 'hip' or 'twin'")
+    parts = BODY_PARTS if parts is None else parts
+    masks, radius = bone_masks(parts), _check_radius(radius)
+    names = [n for n in records if records[n] is not None]
+    H, W = _image_size([records[n] for n in names], image_size)
+    out = {p: {n: None for n in records} for p in parts}
+    if backend == 'twin':
+        for n in names:
+            rec = torch.as_tensor(records[n]).detach().cpu().to(torch.float32)
+            member = twin_segment(rec.numpy(), masks, H, W, radius)
+            for p, part in enumerate(parts):
+                rows = np.nonzero((member >> np.uint32(p)) & np.uint32(1))[0]
+                if rows.size:
+                    out[part][n] = rec[torch.from_numpy(rows)]
+        return out
+    from . import ops
+    dev = _device(device)
+    rec, offsets = _segment_pack([_to_dev(records[n], dev) for n in names], dev)
+    member, status = ops.segment_members(rec, offsets, torch.from_numpy(masks.view(np.int32)).to(dev), H, W, radius)
+    seg, src = ops.segment_compact(member, offsets, len(parts), status=status)
+    seg, F = seg.tolist(), len(names)
+    for p, part in enumerate(parts):
+        rows = rec[src[seg[p * F]:seg[(p + 1) * F]].long()].cpu()       # the part's records of all frames: one gather
+        for f, n in enumerate(names):
+            a, b = seg[p * F + f] - seg[p * F], seg[p * F + f + 1] - seg[p * F]
+            if b > a:
+                out[part][n] = rows[a:b]
+    return out
+
+
+def segment_distance_matrices(records, parts=None, radius=10, image_size=None, valid_weight_threshold=0.3,
+                              dist_thresh=0.002, chunk=(0, 1), axis=None, backend='hip', device=None,
+                              pairs_per_launch=1 << 16):
+    """tools/compute_distance_seg.py over every part at once: {part: np.float32 [F, F]}, what distance_matrix gives on
+    segment_records(...)[part], from ONE pack.  Every frame (sorted name order) is sorted once along ``axis`` with a
+    stable sort, membership runs on the sorted rows, and the compaction keeps per (part, frame) the members with column
+    6 > ``valid_weight_threshold`` -- a stable compaction of a sorted frame is sorted, so the P F segments are the clouds
+    of hnrf_cloud_distance_pairs as they stand, with ``orig`` = the record's index in its frame (a monotone relabelling
+    of its index inside the filtered segment: ties fall the same way).  ``axis``: None = the axis of largest extent over
+    the points that pass the weight filter."""
+    if backend not in ('hip', 'twin'):
+        raise ValueError("backend must be 'hip' or 'twin'")
+    tau = float(dist_thresh)
+    if not (np.isfinite(tau) and tau > 0):
+        raise ValueError('dist_thresh must be finite and > 0, got %r' % dist_thresh)
+    parts = BODY_PARTS if parts is None else parts
+    masks, radius, P = bone_masks(parts), _check_radius(radius), len(parts)
+    names = sorted(records.keys())
+    F = len(names)
+    have = [records[n] is not None for n in names]
+    H, W = _image_size([records[n] for n in names], image_size)
+    rows = chunk_rows(F, chunk)
+    todo = [(i, j) for i in dict.fromkeys(rows.tolist()) for j in range(i + 1, F) if have[i] and have[j]]
+    out = {part: np.zeros((F, F), dtype=np.float32) for part in parts}
+    vwt = float(valid_weight_threshold)
+    if backend == 'twin':
+        recs = [np.asarray(_host(records[n]), dtype=np.float32).reshape(-1, 10) if have[k] else np.zeros((0, 10), np.float32)
+                for k, n in enumerate(names)]
+        if axis is None:
+            axis = default_axis([r[r[:, 6] > np.float32(vwt)][:, :3] for r in recs])
+        axis = int(axis)
+        order = [np.argsort(r[:, axis], kind='stable') for r in recs]
+        recs = [r[o] for r, o in zip(recs, order)]
+        members = [twin_segment(r, masks, H, W, radius) for r in recs]
+        seg, src = twin_compact(members, P, weights=[r[:, 6] for r in recs], weight_min=vwt)
+        cat, ocat = np.concatenate(recs), np.concatenate(order).astype(np.int32)
+        cloud = lambda s: (lambda k: {'xyz': _f32(cat[k, 0:3]), 'rgb': _f32(cat[k, 3:6]), 'orig': ocat[k]})(
+            src[seg[s]:seg[s + 1]])
+        for p, part in enumerate(parts):
+            frames = {k: cloud(p * F + k) for k in range(F) if have[k]}
+            for i, j in todo:
+                out[part][i, j] = out[part][j, i] = twin_pairs(frames[i], frames[j], tau, axis, 'window')[2]
+        return out
+    import torch
+    from . import ops
+    dev = _device(device)
+    recs = [_to_dev(records[n], dev) if have[k] else torch.zeros(0, 10, device=dev) for k, n in enumerate(names)]
+    if axis is None:
+        kept = [r[r[:, 6] > vwt][:, :3] for r in recs]
+        ext = [torch.stack([x.min(0)[0], x.max(0)[0]]) for x in kept if x.shape[0]]
+        axis = 0 if not ext else int(torch.argmax(torch.stack([e[1] for e in ext]).max(0)[0]
+                                                  - torch.stack([e[0] for e in ext]).min(0)[0]))
+    axis = int(axis)
+    order = [torch.sort(r[:, axis], stable=True)[1] for r in recs]
+    rec, offsets = _segment_pack([r[o] for r, o in zip(recs, order)], dev)
+    member, status = ops.segment_members(rec, offsets, torch.from_numpy(masks.view(np.int32)).to(dev), H, W, radius)
+    seg, src = ops.segment_compact(member, offsets, P, status=status, weight_rec=rec, weight_min=vwt)
+    if not todo or src.numel() == 0:
+        return out
+    rows = rec[src.long()]
+    xyz, rgb = rows[:, 0:3].contiguous(), rows[:, 3:6].contiguous()
+    orig = (torch.cat(order).to(torch.int32))[src.long()].contiguous()
+    max_n = int((seg[1:] - seg[:-1]).max())
+    seg_dev = seg.to(dev)
+    pairs_all = np.asarray([(p * F + i, p * F + j) for p in range(P) for i, j in todo], dtype=np.int32)
+    vals = np.empty(pairs_all.shape[0], dtype=np.float64)
+    for s in range(0, pairs_all.shape[0], int(pairs_per_launch)):
+        pairs = torch.from_numpy(pairs_all[s:s + int(pairs_per_launch)]).to(dev)
+        d, _ = ops.cloud_distance_pairs(xyz, rgb, orig, seg_dev, pairs, tau, axis, max_n)
+        vals[s:s + pairs.shape[0]] = d.cpu().numpy()
+    ti, tj = np.asarray(todo).T
+    for p, part in enumerate(parts):
+        v = vals[p * len(todo):(p + 1) * len(todo)]
+        out[part][ti, tj] = v
+        out[part][tj, ti] = v
+    return out
+
+
+def cluster_frames(D, n_clusters=4, names=None):
+    """tools/cluster.py:21-50 in numpy: ``n_clusters`` groups of M = N // n_clusters frames grown greedily from the
+    distance matrix D [N, N].  Per cluster: the seed is the lowest index not yet clustered; d = D[seed] with +inf at
+    the seed and at everything clustered; then M - 1 times i = the first argmin of d joins, d[i] is recorded and
+    d = max(D[i], d) with +inf at the cluster's members.  Returns the reference's list of {'names', 'dist'} (``names``:
+    None = the indices); the N % n_clusters frames left over stay unclustered.  A matrix that is not finite,
+    n_clusters < 1 or N < n_clusters: ValueError (the reference's argmin would pick a NaN, its seed search would raise).
+    On the host by design: N^2 comparisons in N dependent steps."""
+    D = np.asarray(D)
+    if D.ndim != 2 or D.shape[0] != D.shape[1]:
+        raise ValueError('D must be [N, N], got %s' % (D.shape,))
+    if not np.issubdtype(D.dtype, np.floating):
+        D = D.astype(np.float64)
+    N, n_clusters = D.shape[0], int(n_clusters)
+    if n_clusters < 1 or N < n_clusters:
+        raise ValueError('n_clusters must be in [1, N = %d], got %d' % (N, n_clusters))
+    if not np.isfinite(D).all():
+        raise ValueError('D must be finite')
+    names = list(range(N)) if names is None else list(names)
+    if len(names) != N:
+        raise ValueError('%d names for %d frames' % (len(names), N))
+    M, inf = N // n_clusters, D.dtype.type(np.inf)
+    clustered, results = np.zeros(N, bool), []
+    for _ in range(n_clusters):
+        seed = int(np.argmin(clustered))                                 # the first False
+        members, dist = [seed], []
+        d = D[seed].copy()
+        d[clustered] = inf
+        d[seed] = inf
+        for _ in range(M - 1):
+            i = int(np.argmin(d))
+            members.append(i)
+            dist.append(float(d[i]))
+            d = np.maximum(D[i], d)
+            d[members] = inf
+        clustered[members] = True
+        results.append({'names': [names[s] for s in members], 'dist': dist})
+    return results
+
+
+def merge_matrix_chunks(paths):
+    """tools/merge_d.py: the sum of the chunk matrices (every chunk fills its own rows and their mirror, zeros
+    elsewhere).  ``paths``: files or arrays; at least one.  The sum is the tool's: where the tail rows that chunk_rows
+    gives the last chunk hold a pair of their own (F mod chunk_n >= 2), another chunk owns that pair too and it is
+    counted twice, as in the reference."""
+    mats = [np.load(p) if isinstance(p, (str, bytes)) or hasattr(p, '__fspath__') else np.asarray(p) for p in paths]
+    if not mats:
+        raise ValueError('merge_matrix_chunks: no chunk')
+    if any(m.shape != mats[0].shape for m in mats):
+        raise ValueError('merge_matrix_chunks: shapes differ: %s' % ([m.shape for m in mats],))
+    return sum(mats[1:], mats[0].copy())

@@ -1313,3 +1313,98 @@ def cloud_distance_pairs(xyz, rgb, orig, offsets, pairs, tau, axis, max_n, want_
                                                  max_n, int(axis), float(tau), ws.data_ptr(), ws.numel() * 4, _ptr(D),
                                                  _ptr(match), _stream()), 'hnrf_cloud_distance_pairs')
     return D, match
+
+
+# ----------------------------------------------------------------------------------- body-part segmentation of records
+SEGMENT_STATUS = {1: 'a row or column that is not integer-valued', 2: 'a pixel outside the image',
+                  4: 'a bone index that is not integer-valued'}
+
+
+def _segment_status(word, what):
+    if word:
+        raise _lib.HnrfError('%s: the records hold %s (status %d); nothing was written' % (
+            what, ', '.join(v for k, v in SEGMENT_STATUS.items() if word & k) or 'an unknown fault', word))
+
+
+def segment_members(rec, offsets, bone_masks, H, W, radius, member=None, status=None, frames_per_batch=None,
+                    workspace_bytes=256 << 20):
+    """hnrf_segment_members (include/hnrf_segment.h): rec (total, 10), offsets (F + 1,) int64 and bone_masks (B,) int32
+    (the uint32 words) on the GPU -> member (total,) int32 (the uint32 words) and status (1,) int32, both device
+    tensors: the status is NOT read back here (segment_compact does, with the counts).  Frames go through in batches
+    whose bitmaps fit ``workspace_bytes`` (``frames_per_batch`` overrides); ``offsets`` must then be ascending."""
+    lib = _lib.load_segment()
+    _chk(rec)
+    _chk_dev(offsets, torch.int64, 'segment_members: offsets')
+    _chk_dev(bone_masks, torch.int32, 'segment_members: bone_masks')
+    if rec.dim() != 2 or rec.shape[1] != 10 or offsets.dim() != 1 or offsets.numel() < 1 or bone_masks.dim() != 1:
+        raise _lib.HnrfError('segment_members: rec (total, 10), offsets (F + 1,), bone_masks (B,) expected, got %s %s %s'
+                             % (tuple(rec.shape), tuple(offsets.shape), tuple(bone_masks.shape)))
+    total, F, dev = rec.shape[0], offsets.numel() - 1, rec.device
+    H, W, radius = int(H), int(W), int(radius)
+    member = torch.empty(total, dtype=torch.int32, device=dev) if member is None else member
+    status = torch.zeros(1, dtype=torch.int32, device=dev) if status is None else status
+    _chk_dev(member, torch.int32, 'segment_members: member')
+    _chk_dev(status, torch.int32, 'segment_members: status')
+    if member.numel() < total or status.numel() < 1:
+        raise _lib.HnrfError('segment_members: member of %d elements for %d records' % (member.numel(), total))
+    with torch.cuda.device(dev):
+        per = lib.hnrf_segment_workspace_bytes(1, H, W)
+        if frames_per_batch is None:
+            frames_per_batch = max(1, int(workspace_bytes) // per) if per else max(F, 1)
+        nb = max(1, min(int(frames_per_batch), F))
+        need = lib.hnrf_segment_workspace_bytes(nb, H, W)
+        ws = _aligned(max(need, 256), dev)
+
+        def launch(r, o, n_frames, m, st):
+            _lib.check(lib.hnrf_segment_members(_ptr(r), _ptr(o), n_frames, r.shape[0], _ptr(bone_masks),
+                                                bone_masks.numel(), H, W, radius, ws.data_ptr(), ws.numel() * 4, _ptr(m),
+                                                _ptr(st), _stream()), 'hnrf_segment_members')
+        if nb >= F:
+            launch(rec, offsets, F, member, status)
+            return member, status
+        host = offsets.cpu()                      # (the batches' row ranges: sizes the host side built itself)
+        word = torch.zeros(1, dtype=torch.int32, device=dev)
+        status.zero_()
+        for f0 in range(0, F, nb):
+            f1 = min(f0 + nb, F)
+            r0, r1 = int(host[f0]), int(host[f1])
+            launch(rec[r0:r1], (offsets[f0:f1 + 1] - r0).contiguous(), f1 - f0, member[r0:r1], word)
+            status |= word
+    return member, status
+
+
+def segment_compact(member, offsets, n_parts, status=None, weight_rec=None, weight_min=0.0):
+    """hnrf_segment_count + hnrf_segment_scatter: member (total,) int32, offsets (F + 1,) int64 -> seg_offsets
+    (P F + 1,) int64 on the HOST (part-major) and src (rows,) int32 on the device.  With ``weight_rec`` (total, 10) only
+    the records whose column 6 is > ``weight_min`` are kept.  One wait: the counts and the status word come back in one
+    copy, and a status that is not 0 raises HnrfError before src exists."""
+    lib = _lib.load_segment()
+    _chk(weight_rec)
+    _chk_dev(member, torch.int32, 'segment_compact: member')
+    _chk_dev(offsets, torch.int64, 'segment_compact: offsets')
+    total, F, P, dev = member.numel(), offsets.numel() - 1, int(n_parts), member.device
+    if status is not None:
+        _chk_dev(status, torch.int32, 'segment_compact: status')
+    if weight_rec is not None and tuple(weight_rec.shape) != (total, 10):
+        raise _lib.HnrfError('segment_compact: weight_rec %s for %d records' % (tuple(weight_rec.shape), total))
+    with torch.cuda.device(dev):
+        need = lib.hnrf_segment_compact_workspace_bytes(total, P)
+        if need == 0:
+            raise _lib.HnrfError('segment_compact: %d records in %d parts out of range (1 .. 32 parts)' % (total, P))
+        ws = _aligned(need, dev)
+        seg = torch.empty(max(P, 0) * F + 1, dtype=torch.int64, device=dev)
+        _lib.check(lib.hnrf_segment_count(_ptr(member), _ptr(weight_rec), float(weight_min), _ptr(offsets), F, total, P,
+                                          _ptr(status), ws.data_ptr(), ws.numel() * 4, _ptr(seg), _stream()),
+                   'hnrf_segment_count')
+        if status is None:
+            seg_host = seg.cpu()
+        else:                                                             # one copy, one wait
+            both = torch.cat([seg, status[:1].to(torch.int64)]).cpu()
+            _segment_status(int(both[-1]), 'segment_compact')              # (seg is unwritten then)
+            seg_host = both[:-1]
+        rows = int(seg_host[-1])
+        src = torch.empty(rows, dtype=torch.int32, device=dev)
+        _lib.check(lib.hnrf_segment_scatter(_ptr(member), _ptr(weight_rec), float(weight_min), total, P, _ptr(status),
+                                            ws.data_ptr(), ws.numel() * 4, _ptr(src), rows, _stream()),
+                   'hnrf_segment_scatter')
+    return seg_host, src

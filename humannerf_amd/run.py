@@ -372,3 +372,81 @@ def run_distance_matrix(records_or_path, valid_weight_threshold=0.3, dist_thresh
     os.makedirs(os.path.dirname(path), exist_ok=True)
     np.save(path, D)
     return {'matrix': D, 'path': path, 'names': sorted(records.keys())}
+
+
+def _load_records(records_or_path, out_dir, logdir):
+    """(records, directory to write next to them): a ``name-2-3d.bin`` path or the dict it holds."""
+    if isinstance(records_or_path, (str, os.PathLike)):
+        import torch
+        records = torch.load(records_or_path, map_location='cpu')
+        return records, out_dir or os.path.dirname(os.path.abspath(records_or_path))
+    return records_or_path, out_dir or _output_dir(logdir)
+
+
+def run_segments(records_or_path, parts=None, radius=10, image_size=None, logdir=None, out_dir=None, backend='hip',
+                 device=None):
+    """tools/segment.py on ``name-2-3d.bin`` (a path, or the dict it holds): cloud.segment_records, every part saved as
+    ``<out_dir>/name-2-3d.<part>.bin`` -- torch.save of {frame name: tensor [n, 10] or None}, the reference's files, which
+    its compute_distance_seg.py and run_distance_matrix read.  ``out_dir``: None = the directory of the records file, or
+    the run's output directory for a dict.  Returns {'segments': {part: {...}}, 'paths': {part: path}}."""
+    import torch
+    from . import cloud
+    records, out_dir = _load_records(records_or_path, out_dir, logdir)
+    segments = cloud.segment_records(records, parts=parts, radius=radius, image_size=image_size, backend=backend,
+                                     device=device)
+    os.makedirs(out_dir, exist_ok=True)
+    paths = {}
+    for part, seg in segments.items():
+        paths[part] = os.path.join(out_dir, 'name-2-3d.%s.bin' % part)
+        torch.save(seg, paths[part])
+    return {'segments': segments, 'paths': paths}
+
+
+def run_segment_distance_matrices(records_or_path, parts=None, radius=10, image_size=None, valid_weight_threshold=0.3,
+                                  dist_thresh=0.002, chunk=(0, 1), axis=None, logdir=None, out_dir=None, backend='hip',
+                                  device=None):
+    """tools/compute_distance_seg.py for every part, from the UNSEGMENTED ``name-2-3d.bin`` (a path or its dict):
+    cloud.segment_distance_matrices, saved as ``<out_dir>/distance_mat_seg/<part>/distance_mat_{vwt:.2f}-{tau:.2f}
+    [.{chunk_id}-{chunk_n}].npy``, the reference's tree.  Returns {'matrices': {part: D}, 'paths': {part: path},
+    'names'}."""
+    from . import cloud
+    records, out_dir = _load_records(records_or_path, out_dir, logdir)
+    mats = cloud.segment_distance_matrices(records, parts=parts, radius=radius, image_size=image_size,
+                                           valid_weight_threshold=valid_weight_threshold, dist_thresh=dist_thresh,
+                                           chunk=chunk, axis=axis, backend=backend, device=device)
+    paths = {}
+    for part, D in mats.items():
+        paths[part] = os.path.join(out_dir, 'distance_mat_seg', part,
+                                   cloud.matrix_file_name(valid_weight_threshold, dist_thresh, chunk))
+        os.makedirs(os.path.dirname(paths[part]), exist_ok=True)
+        np.save(paths[part], D)
+    return {'matrices': mats, 'paths': paths, 'names': sorted(records.keys())}
+
+
+def run_cluster(matrix_or_path, names=None, n_clusters=4, out_path=None):
+    """tools/cluster.py: cloud.cluster_frames on a distance matrix -- a ``.npy`` path, an array, or what
+    run_distance_matrix returned (its 'matrix', 'path' and 'names') -- pickled as the reference does, to the matrix
+    path with ``.npy`` replaced by ``.cluster.pkl`` (``out_path`` overrides; an array without either is not written).
+    ``names``: the frame names in matrix order, default the sorted record keys of run_distance_matrix's result, else the
+    indices.  Returns {'clusters', 'path'}."""
+    import pickle
+    from . import cloud
+    path = None
+    if isinstance(matrix_or_path, dict):
+        path = matrix_or_path.get('path')
+        names = matrix_or_path.get('names') if names is None else names
+        D = matrix_or_path['matrix']
+    elif isinstance(matrix_or_path, (str, os.PathLike)):
+        path = os.fspath(matrix_or_path)
+        D = np.load(path)
+    else:
+        D = matrix_or_path
+    clusters = cloud.cluster_frames(D, n_clusters=n_clusters, names=names)
+    if out_path is None and path is not None:
+        if not path.endswith('.npy'):
+            raise ValueError('run_cluster: %r is no .npy matrix file; give out_path' % path)
+        out_path = path[:-len('.npy')] + '.cluster.pkl'
+    if out_path is not None:
+        with open(out_path, 'wb') as f:
+            pickle.dump(clusters, f)
+    return {'clusters': clusters, 'path': out_path}

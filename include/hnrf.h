@@ -770,6 +770,11 @@ int hnrf_image_metrics(const uint8_t* pred, const uint8_t* target, const uint8_t
  * version 13; contracts and declarations in hnrf_video.h. */
 #include "hnrf_video.h"
 
+/* ---- surface records split by body part (tools/segment.py): per-record part membership from a per-frame bitmap of
+ * part masks, and the stable compaction per (part, frame).  Additive to ABI version 13; contracts and declarations in
+ * hnrf_segment.h. */
+#include "hnrf_segment.h"
+
 #ifdef __cplusplus
 }
 #endif
