@@ -15,6 +15,7 @@ HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf.h'))
 CLOUD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_cloud.h'))   # included by hnrf.h
 VIDEO_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_video.h'))   # included by hnrf.h
 SEGMENT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_segment.h'))   # included by hnrf.h
+GEOMETRY_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_geometry.h'))   # included by hnrf.h
 
 _SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float,
             'double': ctypes.c_double}
@@ -71,6 +72,9 @@ VIDEO_SIGNATURES = _signatures(VIDEO_HEADER_PATH)
 
 # the body-part segmentation's entries of include/hnrf_segment.h: additive to ABI version 13 in the same way (load_segment)
 SEGMENT_SIGNATURES = _signatures(SEGMENT_HEADER_PATH)
+
+# the geometry maps' entries of include/hnrf_geometry.h: additive to ABI version 13 in the same way (load_geometry)
+GEOMETRY_SIGNATURES = _signatures(GEOMETRY_HEADER_PATH)
 
 _lib = None
 
@@ -158,6 +162,26 @@ def load_segment():
             fn.restype = res
             fn.argtypes = args
         _segment_bound = True
+    return lib
+
+
+_geometry_bound = False
+
+
+def load_geometry():
+    """load() plus the entries of include/hnrf_geometry.h, typed.  A library without them raises HnrfError."""
+    global _geometry_bound
+    lib = load()
+    if not _geometry_bound:
+        for name, (res, args) in GEOMETRY_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise HnrfError(f'{LIB_PATH} does not export {name}: it was built before the geometry maps '
+                                f'(include/hnrf_geometry.h); rebuild it') from None
+            fn.restype = res
+            fn.argtypes = args
+        _geometry_bound = True
     return lib
 
 

@@ -203,6 +203,14 @@ _DEFAULTS = {
         'video': 'none',
         'video_quality': 90,              # 1 .. 100, the scale of PIL.Image.save(quality=)
         'video_fps': 10,                  # integer >= 1; 10 as the reference's ImageWriter.finalize
+        # the render loops of run.py: geometry panels next to the colour image, a list out of 'depth', 'normal', 'shaded',
+        # 'offset' (humannerf_amd/geometry.py, csrc/hnrf_geometry.hip: screen-space differences of the rendered surface
+        # distance, computed in the frame's launches; GPU only).  [] = nothing changes.  'offset' -- the colour map of the
+        # weighted non-rigid offset, compare_lbs_delta.py of the reference -- needs diagnostics = True
+        'maps': [],
+        # the surface distance the maps are made of: 'expected' = depth / alpha, 'median' = the depth of the sample where
+        # the cumulative weight reaches half of its total (needs diagnostics = True)
+        'maps_surface': 'expected',
         # gc.freeze() at the start of the training / render loops (config.quiet_gc)
         'freeze_gc': True,
     },
@@ -247,7 +255,9 @@ def check_amd_options(node=None):
     'baked', a resolution that is no integer in [8, 512], nonrigid = 'baked' without canonical = 'baked', or a
     share_underflow that is no bool, or a metrics route that is not 'host' or 'device', or a video option out of range
     (video 'none' / 'mjpeg' / 'mjpeg_only', video_quality an integer in [1, 100], video_fps an integer >= 1), or
-    video = 'mjpeg_only' with metrics = 'host' (the host route needs the images that mode does not copy)."""
+    video = 'mjpeg_only' with metrics = 'host' (the host route needs the images that mode does not copy), or maps that
+    is no list of distinct names out of 'depth' / 'normal' / 'shaded' / 'offset', a maps_surface that is not 'expected' or
+    'median', or 'offset' / 'median' asked for with diagnostics off."""
     get = amd_option if node is None else (lambda k: node.get(k, _DEFAULTS['amd'][k]))
     if not isinstance(get('share_underflow'), bool):
         raise ValueError('cfg.amd.share_underflow must be True or False, got %r' % (get('share_underflow'),))
@@ -263,6 +273,17 @@ def check_amd_options(node=None):
     if video == 'mjpeg_only' and get('metrics') == 'host':
         raise ValueError("cfg.amd.video = 'mjpeg_only' copies no image to the host, so cfg.amd.metrics = 'host' cannot "
                          "compute anything: set cfg.amd.metrics = 'device' or cfg.amd.video = 'mjpeg'")
+    maps, surface = get('maps'), get('maps_surface')
+    if not isinstance(maps, (list, tuple)) or any(m not in ('depth', 'normal', 'shaded', 'offset') for m in maps) \
+            or len(set(maps)) != len(maps):
+        raise ValueError("cfg.amd.maps must be a list of distinct names out of 'depth', 'normal', 'shaded', 'offset', got %r"
+                         % (maps,))
+    if surface not in ('expected', 'median'):
+        raise ValueError("cfg.amd.maps_surface must be 'expected' or 'median', got %r" % (surface,))
+    if not get('diagnostics') and maps and ('offset' in maps or surface == 'median'):
+        raise ValueError("cfg.amd.maps with 'offset', and cfg.amd.maps_surface = 'median', need cfg.amd.diagnostics = True "
+                         "(got cfg.amd.maps = %r, cfg.amd.maps_surface = %r): the lean form returns neither the per-sample "
+                         "weights nor the offsets" % (list(maps), surface))
     canonical, nonrigid, M = get('canonical'), get('nonrigid'), get('nonrigid_bake_resolution')
     if canonical not in ('mlp', 'baked'):
         raise ValueError("cfg.amd.canonical must be 'mlp' or 'baked', got %r" % (canonical,))

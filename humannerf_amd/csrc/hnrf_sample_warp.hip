@@ -11,21 +11,12 @@
 // corner gathers per bone are the dominant traffic (768 B of cache traffic per
 // sample).  HBM traffic per sample is 4 B (z) + 12 B (x_skel) + 4 B (mask) out.
 #include "hnrf_block_scan.h"
+#include "hnrf_zat.h"                   // z_at: a sample's depth, shared with hnrf_geometry.hip
 
 namespace hnrf {
 
 // 8-byte gather that only promises 4-byte alignment
 struct __attribute__((packed, aligned(4))) f32x2u { float x, y; };
-
-// torch.linspace(0, 1, S)[s] in fp32 (start + step*i below the midpoint,
-// end - step*(S-1-i) from it on; torch's own kernels differ from these two forms
-// by an ulp on some elements), then the reference's lerp (network.py:457-458).
-__device__ __forceinline__ float z_at(float nr, float fr, int s, int S) {
-#pragma clang fp contract(off)
-    const float step = 1.0f / (float)(S - 1);
-    const float t = (s < S / 2) ? step * (float)s : 1.0f - step * (float)(S - 1 - s);
-    return nr * (1.0f - t) + fr * t;
-}
 
 // SHARE: the block classifies its samples while it still has their x_skel in registers (share_classify;
 // hnrf_sample_warp_share_fwd, hnrf.h): one atomic per block, issued while the CU's other resident blocks are in their

@@ -1408,3 +1408,108 @@ def segment_compact(member, offsets, n_parts, status=None, weight_rec=None, weig
                                             ws.data_ptr(), ws.numel() * 4, _ptr(src), rows, _stream()),
                    'hnrf_segment_scatter')
     return seg_host, src
+
+
+# -------------------------------------------------------------------------------------------------- geometry maps
+def ray_surface(near, far, alpha, depth, weights=None, offsets=None, alpha_min=0.5, want_median=False, want_woff=False,
+                out=None):
+    """hnrf_ray_surface (include/hnrf_geometry.h): near, far, alpha, depth (R,), weights (R, S) and offsets (R, S, 3) or
+    None (lean) -> {'t_exp' (R,), 'valid' (R,) uint8, and when asked for 't_med' (R,), 'woff' (R, 3)}.  ``out``: a dict
+    of tensors to write into (a per-frame workspace)."""
+    lib = _lib.load_geometry()
+    _chk(near, far, alpha, depth, weights, offsets)
+    R = alpha.shape[0]
+    S = int(weights.shape[1]) if weights is not None else 1
+    if any(v.shape != (R,) for v in (near, far, alpha, depth)) or (weights is not None and weights.shape != (R, S)) or \
+            (offsets is not None and (weights is None or offsets.shape != (R, S, 3))):
+        raise _lib.HnrfError('ray_surface: near, far, alpha, depth (R,), weights (R, S), offsets (R, S, 3) expected')
+    dev = alpha.device
+    out = {} if out is None else out
+    res = {'t_exp': out.get('t_exp'), 'valid': out.get('valid'), 't_med': out.get('t_med') if want_median else None,
+           'woff': out.get('woff') if want_woff else None}
+    if res['t_exp'] is None:
+        res['t_exp'] = torch.empty(R, device=dev)
+    if res['valid'] is None:
+        res['valid'] = torch.empty(R, dtype=torch.uint8, device=dev)
+    if want_median and res['t_med'] is None:
+        res['t_med'] = torch.empty(R, device=dev)
+    if want_woff and res['woff'] is None:
+        res['woff'] = torch.empty(R, 3, device=dev)
+    _chk(res['t_exp'], res['t_med'], res['woff'])
+    _chk_dev(res['valid'], torch.uint8, 'ray_surface: valid')
+    if res['t_exp'].numel() < R or res['valid'].numel() < R or (want_median and res['t_med'].numel() < R) or \
+            (want_woff and res['woff'].numel() < 3 * R):
+        raise _lib.HnrfError('ray_surface: an output is smaller than %d rays' % R)
+    with torch.cuda.device(dev):
+        _lib.check(lib.hnrf_ray_surface(_ptr(near), _ptr(far), _ptr(alpha), _ptr(depth), _ptr(weights), _ptr(offsets), R, S,
+                                        float(alpha_min), _ptr(res['t_exp']), _ptr(res['t_med']), _ptr(res['woff']),
+                                        _ptr(res['valid']), _stream()), 'hnrf_ray_surface')
+    return {k: v for k, v in res.items() if v is not None}
+
+
+def pixel_rays(ray_index, H, W, pix2ray=None, status=None):
+    """hnrf_pixel_rays: ray_index (N,) int64 -> pix2ray (H * W,) int32 and status (1,) int32, both device tensors; the
+    status is not read back here."""
+    lib = _lib.load_geometry()
+    _chk_dev(ray_index, torch.int64, 'pixel_rays: ray_index')
+    H, W, dev = int(H), int(W), ray_index.device
+    pix2ray = torch.empty(max(H * W, 0), dtype=torch.int32, device=dev) if pix2ray is None else pix2ray
+    status = torch.zeros(1, dtype=torch.int32, device=dev) if status is None else status
+    _chk_dev(pix2ray, torch.int32, 'pixel_rays: pix2ray')
+    _chk_dev(status, torch.int32, 'pixel_rays: status')
+    if ray_index.dim() != 1 or pix2ray.numel() < H * W or status.numel() < 1:
+        raise _lib.HnrfError('pixel_rays: ray_index (N,) and pix2ray of H * W = %d elements expected' % (H * W))
+    with torch.cuda.device(dev):
+        _lib.check(lib.hnrf_pixel_rays(_ptr(ray_index), ray_index.numel(), H, W, _ptr(pix2ray), _ptr(status), _stream()),
+                   'hnrf_pixel_rays')
+    return pix2ray, status
+
+
+GEOMETRY_OUTPUTS = ('normal', 'nvalid', 'normal8', 'depth8', 'shaded8', 'offset8')
+
+
+def geometry_maps(rays_o, rays_d, surf, pix2ray, H, W, want, surface=0, alpha=None, edge=0.05, M=None, bgcolor=None,
+                  lohi=None, ambient=0.25, albedo=0.8, truth8=None, status=None, out=None):
+    """hnrf_geometry_maps: ``surf`` = what ray_surface returned, ``want`` = names out of GEOMETRY_OUTPUTS -> {name:
+    tensor}: normal (H, W, 3) fp32, nvalid (H, W) uint8, the 8-bit panels (H, W, 3) uint8.  ``out``: tensors to write
+    into."""
+    lib = _lib.load_geometry()
+    bad = [k for k in want if k not in GEOMETRY_OUTPUTS]
+    if bad:
+        raise _lib.HnrfError('geometry_maps: unknown outputs %r (out of %r)' % (bad, GEOMETRY_OUTPUTS))
+    _chk(rays_o, rays_d, alpha, M, bgcolor, lohi, surf.get('t_exp'), surf.get('t_med'), surf.get('woff'))
+    _chk_dev(pix2ray, torch.int32, 'geometry_maps: pix2ray')
+    _chk_dev(surf['valid'], torch.uint8, 'geometry_maps: valid')
+    H, W, N, dev = int(H), int(W), rays_o.shape[0], rays_o.device
+    if rays_o.shape != (N, 3) or rays_d.shape != (N, 3) or pix2ray.numel() < H * W or surf['valid'].numel() < N or \
+            any(v is not None and v.numel() < N * k for v, k in ((surf.get('t_exp'), 1), (surf.get('t_med'), 1),
+                                                                   (surf.get('woff'), 3), (alpha, 1))):
+        raise _lib.HnrfError('geometry_maps: rays (N, 3), per-ray inputs of N = %d rays and pix2ray of H * W expected' % N)
+    for name, v, k in (('M', M, 9), ('bgcolor', bgcolor, 3), ('lohi', lohi, 2)):
+        if v is not None and v.numel() != k:
+            raise _lib.HnrfError('geometry_maps: %s must hold %d floats' % (name, k))
+    if truth8 is not None:
+        _chk_dev(truth8, torch.uint8, 'geometry_maps: truth8')
+        if truth8.numel() != H * W * 3:
+            raise _lib.HnrfError('geometry_maps: truth8 must be (H, W, 3)')
+    if status is not None:
+        _chk_dev(status, torch.int32, 'geometry_maps: status')
+    out = {} if out is None else out
+    res = {}
+    for k in want:
+        shape, dtype = ((H, W, 3), torch.float32) if k == 'normal' else ((H, W), torch.uint8) if k == 'nvalid' else \
+            ((H, W, 3), torch.uint8)
+        t = out.get(k)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        _chk_dev(t, dtype, 'geometry_maps: ' + k)
+        if tuple(t.shape) != shape:
+            raise _lib.HnrfError('geometry_maps: %s must be %r, got %r' % (k, shape, tuple(t.shape)))
+        res[k] = t
+    with torch.cuda.device(dev):
+        _lib.check(lib.hnrf_geometry_maps(_ptr(rays_o), _ptr(rays_d), _ptr(surf.get('t_exp')), _ptr(surf.get('t_med')),
+                                          _ptr(surf['valid']), int(surface), _ptr(alpha), _ptr(surf.get('woff')),
+                                          _ptr(pix2ray), N, H, W, float(edge), _ptr(M), _ptr(bgcolor), _ptr(lohi),
+                                          float(ambient), float(albedo), _ptr(truth8), _ptr(status),
+                                          *[_ptr(res.get(k)) for k in GEOMETRY_OUTPUTS], _stream()), 'hnrf_geometry_maps')
+    return res

@@ -384,16 +384,20 @@ class _Parcel:
     a longer stream's remainder is fetched from) or None, all behind one ``event`` (None on a CPU device, where the
     tensors themselves stand in for the pinned copies and ``pool`` is None).  ``collect`` or ``discard`` ends it: once."""
 
-    def __init__(self, pool, event, hosts, metric_host, vhost, lhost, vdev, cap):
+    def __init__(self, pool, event, hosts, metric_host, vhost, lhost, vdev, cap, map_hosts=None):
         self.pool, self.event, self.hosts, self.metric_host = pool, event, hosts, metric_host
         self.vhost, self.lhost, self.vdev, self.cap = vhost, lhost, vdev, cap
+        # the staged geometry panels {name: buffer} (render_frames(maps=...)) or None; collect() leaves them, read, in
+        # ``map_arrays`` -- its own return value is what it was without them
+        self.map_hosts, self.map_arrays = map_hosts, None
 
     def landed(self):
         """True once every copy has arrived; never waits."""
         return self.event is None or self.event.query()
 
     def buffers(self):
-        return self.hosts + [h for h in (self.metric_host, self.vhost, self.lhost) if h is not None]
+        return self.hosts + [h for h in (self.metric_host, self.vhost, self.lhost) if h is not None] \
+            + list((self.map_hosts or {}).values())
 
     def _give_back(self):
         for h in self.buffers() if self.pool is not None else ():
@@ -413,6 +417,8 @@ class _Parcel:
             self.event.synchronize()
         arrs = [h.numpy().copy() if self.pool is not None else h.numpy() for h in self.hosts]
         values = None if self.metric_host is None else self.metric_host.tolist()
+        if self.map_hosts is not None:
+            self.map_arrays = {k: (h.numpy().copy() if self.pool is not None else h.numpy()) for k, h in self.map_hosts.items()}
         data, fell_back = None, False
         if self.vhost is not None:
             n, cap = int(self.lhost[0]), self.vhost.shape[0]
@@ -441,16 +447,19 @@ class FrameOutbox:
         src.record_stream(self.stream)
         return h
 
-    def post(self, images, metric_vec=None, video=None):
+    def post(self, images, metric_vec=None, video=None, maps=None):
         """``images``: uint8 tensors; ``metric_vec``: float64 vector; ``video``: (buffer, length, height, width) -- what
         JpegEncoder.encode returned for panels of height x width.  The stream's length is not known here, so its first
-        min(len(buffer), video_copy_cap(height, width)) bytes and the length word travel."""
+        min(len(buffer), video_copy_cap(height, width)) bytes and the length word travel.  ``maps``: {name: uint8
+        tensor}, the geometry panels: staged behind the images, under the same event."""
         vbuf, vlen, height, width = video if video is not None else (None, None, 0, 0)
         if self.stream is None:
-            return _Parcel(None, None, [im.cpu() for im in images], metric_vec, vbuf, vlen, vbuf, 0)
+            return _Parcel(None, None, [im.cpu() for im in images], metric_vec, vbuf, vlen, vbuf, 0,
+                           None if maps is None else {k: v.cpu() for k, v in maps.items()})
         self.stream.wait_stream(torch.cuda.current_stream(self.device))  # overlap D2H with the next frame
         with torch.cuda.stream(self.stream):
             hosts = [self._stage(im) for im in images]
+            map_hosts = None if maps is None else {k: self._stage(v) for k, v in maps.items()}
             mhost = None if metric_vec is None else self._stage(metric_vec)
             vhost, lhost, cap = None, None, 0
             if vbuf is not None:
@@ -458,7 +467,7 @@ class FrameOutbox:
                 vhost, lhost = self._stage(vbuf[:cap]), self._stage(vlen)
             event = torch.cuda.Event()
             event.record(self.stream)
-        return _Parcel(self.pool, event, hosts, mhost, vhost, lhost, vbuf, cap)
+        return _Parcel(self.pool, event, hosts, mhost, vhost, lhost, vbuf, cap, map_hosts)
 
 
 _FRAME_KEYS = ('dst_Rs', 'dst_Ts', 'cnl_gtfms', 'dst_posevec', 'cnl_bbox_min_xyz', 'cnl_bbox_scale_xyz', 'bgcolor')
@@ -488,8 +497,9 @@ class FramePrefetcher:
     and hands over device tensors plus the event that marks them ready.  The render stream only ever waits for that
     event: no host synchronisation is left in the loop, so the GPU renders frame n while the host prepares n+1.."""
 
-    def __init__(self, frames, indices, device, show_truth=False, depth=4, workers=3, max_workers=6):
+    def __init__(self, frames, indices, device, show_truth=False, depth=4, workers=3, max_workers=6, camera=False):
         self.frames, self.indices, self.device, self.show_truth = frames, list(indices), device, show_truth
+        self.camera = camera                        # hand over the frame's world-to-camera rotation too (item['M'])
         self.on_gpu = device.type == 'cuda'
         self._resident = {}
         self._lock = threading.Lock()
@@ -558,8 +568,12 @@ class FramePrefetcher:
             truth = self._up(fr['target_rgbs'])
         elif self.show_truth and fr.get('raw_rgbs', None) is not None:   # whole image (0..1): the pixels the rays hit
             truth = self._up(fr['raw_rgbs']).reshape(-1, 3).index_select(0, index)
-        return {'idx': idx, 'data': data, 'ray_index': index, 'truth': truth,
+        item = {'idx': idx, 'data': data, 'ray_index': index, 'truth': truth,
                 'W': int(fr['img_width']), 'H': int(fr['img_height'])}
+        if self.camera:                                                  # (a frame without a camera: the identity)
+            E = fr.get('E', None)
+            item['M'] = None if E is None else self._up(np.ascontiguousarray(np.asarray(E, dtype=np.float32)[:3, :3]))
+        return item
 
     def _work(self):
         stream = torch.cuda.Stream(device=self.device, priority=int(os.environ.get('HNRF_PREFETCH_PRIORITY', '0')))
@@ -611,7 +625,7 @@ class FramePrefetcher:
                 self._slots.release()                                    # one more frame in the making
                 t.start()
             main.wait_event(item['event'])
-            for t in list(item['data'].values()) + [item['ray_index'], item['truth']]:
+            for t in list(item['data'].values()) + [item['ray_index'], item['truth'], item.get('M')]:
                 if torch.is_tensor(t):
                     t.record_stream(main)                                # allocated on a side stream, consumed here
             yield item
@@ -632,19 +646,23 @@ METRIC_NAMES = ('psnr', 'ssim', 'lpips')
 _InFlight = namedtuple('_InFlight', 'idx parcel item watch_id')
 
 
-def select_panels(rgb8, alpha8, truth8=None):
+def select_panels(rgb8, alpha8, truth8=None, maps=None):
     """run.py:143-149 / 359-364: [render | truth if cfg.show_truth | alpha if cfg.show_alpha], as a list (arrays or
-    tensors): what run._panels concatenates on the host and render_frames(video=...) on the device."""
+    tensors): what run._panels concatenates on the host and render_frames(video=...) on the device.  ``maps``: the
+    geometry panels {name: image} of the frame (render_frames(maps=...)), appended in their order."""
     imgs = [rgb8]
     if cfg.get('show_truth', False) and truth8 is not None:
         imgs.append(truth8)
     if cfg.get('show_alpha', False):
         imgs.append(alpha8)
+    if maps:
+        imgs.extend(maps.values())
     return imgs
 
 
 def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, show_truth=False, prefetch=None,
-                  metrics=None, lpips_fn=None, on_metrics=None, video=None, on_video=None, images='host'):
+                  metrics=None, lpips_fn=None, on_metrics=None, video=None, on_video=None, images='host', maps=None,
+                  on_maps=None):
     """Render ``frames`` (sequence of per-frame input dicts, numpy or tensors) frame-sharded.
 
     Returns {frame_idx: uint8 rgb image on the host} for this rank's frames.  ``on_image(idx, rgb8, alpha8[,
@@ -681,7 +699,16 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
     fetches its remainder, synchronously, at hand-over (render_frames.last_video = {'frames', 'fallbacks', 'bytes',
     'cap'}: streams handed over, those that fell back, their bytes, the cap): no synchronisation enters the loop.
     A frame rendered again after an f16-range hit is encoded again.  ``images='none'`` (only with ``video``): no 8-bit
-    image is copied to the host, ``on_image`` is never called and the returned dict is empty."""
+    image is copied to the host, ``on_image`` is never called and the returned dict is empty.
+
+    ``maps`` (a list out of 'depth', 'normal', 'shaded', 'offset'; GPU only): the frame's geometry panels
+    (geometry.frame_maps: the surface distance cfg.amd.maps_surface of every ray, normals as screen-space differences of
+    it; three library calls in the frame's launches).  They travel behind the images, under the same event, and arrive
+    as ``on_maps(idx, {name: uint8 array (H, W, 3)})`` right after that frame's ``on_image``; select_panels puts them
+    behind the other panels, so ``video`` encodes them too.  The normal panel is in the camera frame of the frame's
+    ``E`` (the rasteriser's shade = 'normal'); 'offset' is painted where the truth has colour when the frame has one.
+    A frame rendered again after an f16-range hit gets its maps again; with ``images='none'`` they go into the video
+    only.  ``on_image`` gets what it gets without maps."""
     device = device or next(network.parameters()).device
     if images not in ('host', 'none'):
         raise ValueError("render_frames: images must be 'host' or 'none', got %r" % (images,))
@@ -691,6 +718,15 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
         raise ValueError('render_frames: the video encoder is on %s, the frames on %s' % (video.device, device))
     vstat = {'frames': 0, 'fallbacks': 0, 'bytes': 0, 'cap': 0}
     render_frames.last_video = vstat
+    maps = list(maps) if maps else None
+    if maps is not None:
+        from . import geometry
+        from .config import amd_option
+        maps_surface = amd_option('maps_surface', 'expected')
+        geometry.check_maps(maps, maps_surface, bool(amd_option('diagnostics', True)))
+        if device.type != 'cuda':
+            raise ValueError('render_frames: geometry maps need a GPU (got device %s); on the host use geometry.maps_host'
+                             % device)
     metrics = list(metrics) if metrics else None
     if metrics is not None:
         bad = [k for k in metrics if k not in METRIC_NAMES]
@@ -724,6 +760,8 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
         t1 = time.perf_counter()
         if on_image is not None and arrs:
             on_image(i, *arrs)
+        if on_maps is not None and entry.parcel.map_arrays is not None:
+            on_maps(i, entry.parcel.map_arrays)
         if on_metrics is not None and values is not None:
             on_metrics(i, dict(zip(metrics, values)))
         if data is not None:
@@ -756,14 +794,19 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
                 # (a table of the host's float32 k / 255: the device divides by a scalar as a product with 1 / 255)
                 vals['lpips'] = 1000 * lpips_fn(unit[rgb8.long()], unit[t8.long()]).reshape(()).to(torch.float64)
             mvec = torch.stack([vals[k] for k in metrics])
+        gmaps = None
+        if maps is not None:
+            gm = geometry.frame_maps(item['data'], res, item['H'], item['W'], item['ray_index'], maps=maps,
+                                     surface=maps_surface, M=item.get('M'), truth8=t8 if item['truth'] is not None else None)
+            gmaps = {m: gm[m] for m in maps}
         vid = None
         if video is not None:
-            panels = select_panels(rgb8, a8, t8 if item['truth'] is not None else None)
+            panels = select_panels(rgb8, a8, t8 if item['truth'] is not None else None, gmaps)
             vid = video.encode(panels[0] if len(panels) == 1 else torch.cat(panels, dim=1)) + (item['H'], item['W'] * len(panels))
         if timing:
             gpu_ev[-1][1].record()
         imgs = [rgb8, a8] + ([t8] if item['truth'] is not None else [])
-        parcel = outbox.post([] if images == 'none' else imgs, mvec, vid)
+        parcel = outbox.post([] if images == 'none' else imgs, mvec, vid, None if images == 'none' else gmaps)
         if parcel.cap:
             vstat['cap'] = parcel.cap
         return _InFlight(item['idx'], parcel, item, network.f16_range_watched if guard else 0)
@@ -798,7 +841,7 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
     workers = int(os.environ.get('HNRF_PREFETCH_WORKERS', 3))
     depth = int(prefetch) if prefetch is not None else workers + 1
     pre = FramePrefetcher(frames, hdist.frame_shard(len(frames), rank, world), device, show_truth=show_truth, depth=depth,
-                          workers=workers)
+                          workers=workers, camera=maps is not None)
     try:
         for item in pre:
             before = guard_state()

@@ -14,6 +14,12 @@ render.ImageWriter / MetricsWriter on worker threads.
   run_surface_points  run.py:388-404   cfg.test.save_3d_together: one canonical surface point per ray of every movement
                                   frame, collected as ``name-2-3d.bin``
   run_distance_matrix tools/compute_distance*.py   the frame x frame appearance distance of those records
+  run_compare_lbs_delta compare_lbs_delta.py   every movement frame with and without the non-rigid motions, next to the
+                                  colour map of the weighted non-rigid offset and the truth, both PSNRs in the file name
+
+cfg.amd.maps (a list out of 'depth', 'normal', 'shaded', 'offset') adds geometry panels to every frame of the loops:
+``[render | truth | alpha | maps...]`` in the PNG and in the video (humannerf_amd/geometry.py: screen-space differences of
+the rendered surface distance, computed on the device in the frame's launches).
 
 Output layout as in the reference: ``<logdir>/<load_net><eval_output_tag>/<folder>/NAME.png`` plus
 ``<folder>-metrics.perimg.txt / .average.txt`` (movement) and the stacked frames (MP4 when imageio is importable).
@@ -117,14 +123,26 @@ def _render_loop(network, frames, names, folder, logdir, rank, world, device, me
     writer = None if vout.only else render.ImageWriter(out_dir, folder)          # 'mjpeg_only': no PNG, no directory
     own = list(range(rank, len(frames), world))
 
+    from .config import amd_option
+    maps = list(amd_option('maps', []) or [])
+    held = {}                                       # with maps: a frame's images between on_image and its on_maps
+
     def on_image(i, rgb8, alpha8, truth8=None):
-        writer.append(_panels(rgb8, alpha8, truth8), img_name=names[i])
+        if maps:
+            held[i] = (rgb8, alpha8, truth8)
+        else:
+            writer.append(_panels(rgb8, alpha8, truth8), img_name=names[i])
         if metrics is not None and truth8 is not None and not on_device:
             metrics.append(name=names[i], pred=rgb8, target=truth8, mask=None)
 
+    def on_maps(i, panels):
+        writer.append(np.concatenate(render.select_panels(*held.pop(i), maps=panels), axis=1), img_name=names[i])
+
     extra = {}
+    if maps:
+        extra = dict(maps=maps, on_maps=on_maps)
     if vout.encoder is not None:
-        extra = dict(video=vout.encoder, on_video=vout.add, images='none' if vout.only else 'host')
+        extra.update(video=vout.encoder, on_video=vout.add, images='none' if vout.only else 'host')
     if metrics is not None and on_device:
         extra.update(metrics=metrics.metrics, lpips_fn=lpips_fn,
                      on_metrics=lambda i, values: metrics.append_values(names[i], values))
@@ -349,6 +367,79 @@ def run_surface_points(network, subject, weight_threshold=None, render_folder_na
         os.replace(path, ranked)
         path = ranked
     return {'frames': own, 'records': records, 'path': path}
+
+
+def run_compare_lbs_delta(network, subject, logdir=None, rank=0, world=1, device=None, test_num=-1):
+    """compare_lbs_delta.py of the reference as one loop: every movement frame is rendered twice, with
+    cfg.ignore_non_rigid_motions True (LBS only) and then False (the full model), and
+    ``<output_dir>/cmp_lbs_delta/movement/{name}_lbs-{s1:.1f}_full-{s2:.1f}.png`` = [lbs render | full render | offset map
+    | truth] is written, s1 and s2 the two PSNRs against the truth (compare_lbs_delta.py:21, 36-37, 47-50).  The offset
+    map is the geometry panel 'offset' of the full render (sum_s w_s offset_s through the reference's colour map, painted
+    where the truth has colour; geometry.frame_maps), so cfg.amd.diagnostics is switched on for the loop.  The PSNRs come
+    from MetricsWriter -- ``cmp_lbs_delta/movement_lbs-metrics.perimg.txt`` and ``..._full-...`` are written -- on the
+    host, or with cfg.amd.metrics = 'device' from render_frames' device pass.  GPU only.
+    Returns {'lbs': [psnr per frame of this rank], 'full': [...], 'names', 'paths', 'image_dir'}."""
+    from .config import amd_option, check_amd_options
+    check_amd_options()
+    device = device or next(network.parameters()).device
+    if device.type != 'cuda':
+        raise ValueError('run_compare_lbs_delta: the offset map needs a GPU, got device %s' % device)
+    on_device = amd_option('metrics', 'host') == 'device'
+    n = len(subject) if test_num < 0 else min(test_num, len(subject))
+    frames = _Frames(n, lambda i: subject.movement_frame(i, load_image=True, device=device))
+    names = [str(subject.framelist[i]).replace('/', '-') for i in range(n)]
+    out_dir = _output_dir(logdir)
+    suffix = '' if world == 1 else '.rank%d' % rank
+    amd = cfg.get('amd', None)
+    had_diag, old_diag = amd is not None and 'diagnostics' in amd, (amd or {}).get('diagnostics')
+    old_nr, old_truth = cfg.ignore_non_rigid_motions, cfg.get('show_truth', False)
+    if amd is not None:
+        amd['diagnostics'] = True
+    cfg.show_truth = True
+    imgs = {'lbs': {}, 'full': {}}                  # frame -> (render, truth) / -> offset panel
+    offset, scores = {}, {}
+    try:
+        for tag, flag in (('lbs', True), ('full', False)):
+            cfg.ignore_non_rigid_motions = flag
+            mw = render.MetricsWriter(os.path.join(out_dir, 'cmp_lbs_delta'), 'movement_%s%s' % (tag, suffix),
+                                      dataset=subject.dataset_path, metrics=['psnr'])
+
+            def on_image(i, rgb8, alpha8, truth8=None, tag=tag, mw=mw):
+                imgs[tag][i] = (rgb8, truth8)
+                if truth8 is not None and not on_device:
+                    mw.append(name=names[i], pred=rgb8, target=truth8, mask=None)
+
+            extra = {}
+            if on_device:
+                extra.update(metrics=['psnr'], on_metrics=lambda i, v, mw=mw: mw.append_values(names[i], v))
+            if not flag:
+                extra.update(maps=['offset'], on_maps=lambda i, panels: offset.__setitem__(i, panels['offset']))
+            render.render_frames(network, frames, rank=rank, world=world, device=device, on_image=on_image,
+                                 show_truth=True, **extra)
+            mw.finalize()
+            scores[tag] = {k: v['psnr'] for k, v in mw.name2metrics.items()}
+    finally:
+        cfg.ignore_non_rigid_motions = old_nr
+        cfg.show_truth = old_truth
+        if had_diag:
+            amd['diagnostics'] = old_diag
+        elif amd is not None:
+            amd.pop('diagnostics', None)
+    writer = render.ImageWriter(out_dir, os.path.join('cmp_lbs_delta', 'movement'), keep_frames=False)
+    own = sorted(imgs['full'])
+    paths = []
+    for i in own:
+        truth = imgs['full'][i][1]
+        if truth is None:                           # (a frame without an image has no PSNR and no fourth panel)
+            continue
+        s1, s2 = scores['lbs'][names[i]], scores['full'][names[i]]
+        name = '%s_lbs-%.1f_full-%.1f' % (names[i], s1, s2)
+        writer.append(np.concatenate([imgs['lbs'][i][0], imgs['full'][i][0], offset[i], truth], axis=1), img_name=name)
+        paths.append(os.path.join(writer.image_dir, name + '.png'))
+    writer.finalize()
+    return {'lbs': [scores['lbs'][names[i]] for i in own if names[i] in scores['lbs']],
+            'full': [scores['full'][names[i]] for i in own if names[i] in scores['full']],
+            'names': [names[i] for i in own], 'paths': paths, 'image_dir': writer.image_dir}
 
 
 def run_distance_matrix(records_or_path, valid_weight_threshold=0.3, dist_thresh=0.002, chunk=(0, 1), method='window',

@@ -775,6 +775,11 @@ int hnrf_image_metrics(const uint8_t* pred, const uint8_t* target, const uint8_t
  * hnrf_segment.h. */
 #include "hnrf_segment.h"
 
+/* ---- geometry maps of a rendered frame: the surface distance per ray, the pixel -> ray map, and the depth / normal /
+ * shaded / non-rigid-offset panels (screen-space differences of the rendered surface distance).  Additive to ABI
+ * version 13; contracts and declarations in hnrf_geometry.h. */
+#include "hnrf_geometry.h"
+
 #ifdef __cplusplus
 }
 #endif
