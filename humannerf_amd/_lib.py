@@ -16,6 +16,7 @@ CLOUD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_
 VIDEO_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_video.h'))   # included by hnrf.h
 SEGMENT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_segment.h'))   # included by hnrf.h
 GEOMETRY_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_geometry.h'))   # included by hnrf.h
+HEADS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_heads.h'))   # included by hnrf.h
 
 _SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float,
             'double': ctypes.c_double}
@@ -75,6 +76,9 @@ SEGMENT_SIGNATURES = _signatures(SEGMENT_HEADER_PATH)
 
 # the geometry maps' entries of include/hnrf_geometry.h: additive to ABI version 13 in the same way (load_geometry)
 GEOMETRY_SIGNATURES = _signatures(GEOMETRY_HEADER_PATH)
+
+# the multi-head canonical MLP's entries of include/hnrf_heads.h: additive to ABI version 13 in the same way (load_heads)
+HEADS_SIGNATURES = _signatures(HEADS_HEADER_PATH)
 
 _lib = None
 
@@ -182,6 +186,26 @@ def load_geometry():
             fn.restype = res
             fn.argtypes = args
         _geometry_bound = True
+    return lib
+
+
+_heads_bound = False
+
+
+def load_heads():
+    """load() plus the entries of include/hnrf_heads.h, typed.  A library without them raises HnrfError."""
+    global _heads_bound
+    lib = load()
+    if not _heads_bound:
+        for name, (res, args) in HEADS_SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:
+                raise HnrfError(f'{LIB_PATH} does not export {name}: it was built before the multi-head canonical MLP '
+                                f'(include/hnrf_heads.h); rebuild it') from None
+            fn.restype = res
+            fn.argtypes = args
+        _heads_bound = True
     return lib
 
 

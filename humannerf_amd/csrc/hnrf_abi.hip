@@ -59,6 +59,14 @@ struct Share {
     bool fused;
 };
 
+// All heads of a multi-head canonical image (hnrf_render_frame_heads_fwd): K3 writes the n planes raw [n][P][4] in one
+// launch, K4 runs once per plane into o[g].  Every o[g] carries the same xyz / bmw / offsets: those do not depend on the head.
+struct HeadsOut {
+    int n;
+    float* raw;
+    const FrameOut* o;
+};
+
 // K2 -> K3 -> K4 of one ray chunk whose K1 results are in `c`: the whole of hnrf_render_rays_fwd after K1, and the body
 // of every chunk of hnrf_render_frame_fwd.  cull_eps > 0: the MLPs run only on the compacted samples.  ev_start /
 // ev_stop (hipEvent_t, nullable) are recorded right before / after the canonical-MLP (or grid sampler) launch.
@@ -67,7 +75,7 @@ struct Share {
 int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w, const void* nr_packed,
                  const BakedGrid& off, const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t R,
                  int S, const FrameOut& d, void* ev_start, void* ev_stop, hipStream_t st,
-                 const Share& sh = Share{nullptr, false}) {
+                 const Share& sh = Share{nullptr, false}, const HeadsOut* hd = nullptr) {
     const size_t P = (size_t)R * (size_t)S;
     const bool cull = cull_eps > 0.f, diag = d.weights != nullptr;
     int rc;
@@ -101,9 +109,20 @@ int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w,
         }
         if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
         rc = cnl.grid ? baked_sample(cnl_in, cnl.grid, cnl.N, cnl.bmin, cnl.bmax, (int64_t)P, ci, cc, c.raw, st)
+             : hd     ? hnrf_canonical_heads_fwd_sparse(cnl_in, cnl.packed, mode, (int64_t)P, hd->n, ci, cc, hd->raw, st)
                       : hnrf_canonical_fwd_sparse(cnl_in, cnl.packed, mode, (int64_t)P, ci, cc, c.raw, st);
         if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
         if (rc) return rc;
+    }
+    if (hd) {
+        for (int g = 0; g < hd->n; ++g) {
+            const FrameOut& o = hd->o[g];
+            if ((rc = hnrf_composite_fwd(hd->raw + (size_t)g * P * 4, c.mask, c.z_vals, rays_d, diag ? cnl_in : nullptr, bgcolor,
+                                         R, S, cull ? cull_eps : 0.f, o.rgb, o.alpha, o.depth, o.weights, o.rgb_on_rays,
+                                         o.cnl_xyz, o.cnl_rgb, o.cnl_weight, st)))
+                return rc;
+        }
+        return HNRF_OK;
     }
     return hnrf_composite_fwd(c.raw, c.mask, c.z_vals, rays_d, diag ? cnl_in : nullptr, bgcolor, R, S,
                               cull ? cull_eps : 0.f, d.rgb, d.alpha, d.depth, d.weights, d.rgb_on_rays, d.cnl_xyz,
@@ -207,12 +226,19 @@ extern "C" size_t hnrf_render_frame_workspace_bytes(int64_t chunk, int S) { retu
 extern "C" size_t hnrf_render_frame_shared_workspace_bytes(int64_t chunk, int S) {
     return hnrf_render_frame_workspace_bytes(chunk, S) + 256;
 }
+// + the n_heads raw planes of one chunk behind the two chunk workspaces (K3 and the K4s of a chunk run on `stream` in
+// order, so one set serves every chunk)
+extern "C" size_t hnrf_render_frame_heads_workspace_bytes(int64_t chunk, int S, int n_heads) {
+    if (chunk < 0 || S < 0 || n_heads < 2 || n_heads > 8) return 0;
+    return hnrf_render_frame_workspace_bytes(chunk, S) + align256((size_t)n_heads * (size_t)chunk * (size_t)S * 16);
+}
 
 namespace {
 int render_frame(const char* who, const Rays& rays, const WarpField& field, const float* hann_w, const void* nr_packed,
                  const BakedGrid& off, const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t N,
                  int S, int64_t chunk, void* workspace, size_t workspace_bytes, const FrameOut& out, void* side_stream,
-                 void* const* events, void* const* mlp_events, void* stream, int* live_counts = nullptr) {
+                 void* const* events, void* const* mlp_events, void* stream, int* live_counts = nullptr, int n_heads = 0,
+                 const FrameOut* head_out = nullptr) {
     HNRF_REQUIRE(workspace && out.rgb && out.alpha && out.depth, HNRF_E_ARG, "%s: null pointer", who);
     int src = check_source(who, cnl);
     if (src) return src;
@@ -224,6 +250,10 @@ int render_frame(const char* who, const Rays& rays, const WarpField& field, cons
     HNRF_REQUIRE(workspace_bytes >= 2 * ws_one, HNRF_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who,
                  workspace_bytes, 2 * ws_one);
     HNRF_REQUIRE(nr_packed == nullptr || hann_w != nullptr, HNRF_E_ARG, "%s: hann_w missing", who);
+    const size_t heads_bytes = n_heads ? align256((size_t)n_heads * (size_t)cr * (size_t)S * 16) : 0;
+    HNRF_REQUIRE(workspace_bytes >= 2 * ws_one + heads_bytes, HNRF_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who,
+                 workspace_bytes, 2 * ws_one + heads_bytes);
+    float* heads_raw = n_heads ? (float*)((char*)workspace + 2 * ws_one) : nullptr;
     const bool share = live_counts != nullptr;
     if (share) {
         HNRF_REQUIRE((mode & HNRF_MLP_ARITH_MASK) == HNRF_MLP_F16X3 && nr_packed && cnl.packed && !cnl.grid && !off.grid &&
@@ -299,9 +329,12 @@ int render_frame(const char* who, const Rays& rays, const WarpField& field, cons
         int cmode = mode & (HNRF_MLP_ARITH_MASK | HNRF_MLP_NO_RANGE_GUARD);
         if ((mode & HNRF_MLP_GUARD_ONE_CHUNK) && (int64_t)((unsigned)mode >> 16) % nchunk != i) cmode |= HNRF_MLP_NO_RANGE_GUARD;
         const Chunk k = chunk_at(i);
+        FrameOut ho[8];
+        for (int g = 0; g < n_heads; ++g) ho[g] = head_out[g].rows(i * chunk, S, field.B);
+        const HeadsOut hd{n_heads, heads_raw, ho};
         if ((rc = render_chunk(k.c, k.rays.d, hann_w, nr_packed, off, cnl, bgcolor, cmode, cull_eps, k.R, S, k.o,
                                mlp_events ? mlp_events[2 * i] : nullptr, mlp_events ? mlp_events[2 * i + 1] : nullptr, st,
-                               Share{share ? &k.sh : nullptr, fused}))) return rc;
+                               Share{share ? &k.sh : nullptr, fused}, n_heads ? &hd : nullptr))) return rc;
         if (two) HNRF_HIP(hipEventRecord(ev_done[i & 1], st));
         if (!two && i + 1 < nchunk && (rc = warp(i + 1))) return rc;   // single stream: plain sequence
     }
@@ -326,6 +359,38 @@ extern "C" int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, c
                         FrameOut{rgb, alpha, depth, weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays,
                                  bmw, offsets},
                         side_stream, events, mlp_events, stream);
+}
+
+extern "C" int hnrf_render_frame_heads_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                           const float* t_rand, const float* motion_Rs, const float* motion_Ts,
+                                           const float* vol, const float* bbox_min, const float* bbox_scale,
+                                           const float* hann_w, const void* nr_packed, const void* cnl_packed,
+                                           const float* bgcolor, int mode, float cull_eps, int64_t N, int S, int B, int G,
+                                           int64_t chunk, int n_heads, void* workspace, size_t workspace_bytes,
+                                           float* const* rgb, float* const* alpha, float* const* depth,
+                                           float* const* weights_on_rays, float* const* rgb_on_rays, float* const* cnl_xyz,
+                                           float* const* cnl_rgb, float* const* cnl_weight, float* xyz_on_rays, float* bmw,
+                                           float* offsets, void* side_stream, void* const* events,
+                                           void* const* mlp_events, void* stream) {
+    const char* who = "hnrf_render_frame_heads_fwd";
+    HNRF_REQUIRE(n_heads >= 2 && n_heads <= 8, HNRF_E_ARG, "%s: n_heads=%d outside 2..8", who, n_heads);
+    HNRF_REQUIRE(rgb && alpha && depth, HNRF_E_ARG, "%s: null output array", who);
+    const bool diag = weights_on_rays != nullptr;
+    HNRF_REQUIRE(!diag || (rgb_on_rays && cnl_xyz && cnl_rgb && cnl_weight && xyz_on_rays && bmw && offsets), HNRF_E_ARG,
+                 "%s: the eight diagnostic outputs go together", who);
+    FrameOut ho[8];
+    for (int g = 0; g < n_heads; ++g) {
+        HNRF_REQUIRE(rgb[g] && alpha[g] && depth[g], HNRF_E_ARG, "%s: null rgb / alpha / depth plane of head %d", who, g);
+        HNRF_REQUIRE(!diag || (weights_on_rays[g] && rgb_on_rays[g] && cnl_xyz[g] && cnl_rgb[g] && cnl_weight[g]), HNRF_E_ARG,
+                     "%s: null diagnostic plane of head %d", who, g);
+        ho[g] = diag ? FrameOut{rgb[g], alpha[g], depth[g], weights_on_rays[g], rgb_on_rays[g], cnl_xyz[g], cnl_rgb[g],
+                                cnl_weight[g], xyz_on_rays, bmw, offsets}
+                     : FrameOut{rgb[g], alpha[g], depth[g], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, bmw, nullptr};
+    }
+    return render_frame(who, Rays{rays_o, rays_d, near, far, t_rand},
+                        WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, hann_w, nr_packed, kNoOffGrid,
+                        CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor, mode, cull_eps, N, S, chunk,
+                        workspace, workspace_bytes, ho[0], side_stream, events, mlp_events, stream, nullptr, n_heads, ho);
 }
 
 extern "C" int hnrf_render_frame_shared_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,

@@ -147,10 +147,12 @@ size_t canonical16_bytes();
 size_t nonrigid16_bytes();
 size_t canonical16_status_offset();
 size_t nonrigid16_status_offset();
-int canonical16_pack(const float* const* w, const float* const* b, void* packed, hipStream_t st);
+int canonical16_pack(const float* const* w, const float* const* b, void* packed, hipStream_t st, int n_heads = 1);
 int nonrigid16_pack(const float* const* w, const float* const* b, const float* cond, void* packed, hipStream_t st);
 int canonical16_fwd(const float* xyz, const void* packed, int64_t P, float* raw, const int* idx, const int* count,
                     bool guard, hipStream_t st);
+int canonical16_heads_fwd(const float* xyz, const void* packed, int64_t P, int n_heads, float* raw, const int* idx,
+                          const int* count, bool guard, hipStream_t st);
 int canonical16_fwd_train(const float* xyz, const void* packed, int64_t P, float* raw, float* pe_out, float* acts,
                           uint32_t* relu_bits, int half, hipStream_t st);
 int nonrigid16_fwd(const float* x_skel, const float* hann_w, const void* packed, int64_t P, float* xyz,

@@ -187,15 +187,20 @@ __device__ __forceinline__ void ring_fill(const float4* __restrict__ wptr, float
 // K3.  grid = ceil(P / 128) workgroups of 4 independent waves x 32 samples.
 // SAVE (training forward): also writes the positional encoding pe_out [P,63] (reference column
 // order) and the 8 post-ReLU activation matrices acts [8][P][256] that the backward GEMMs read.
-template <bool SAVE>
+// HEADS (inference, image of hnrf_canonical_heads_pack): raw is n_heads planes [n_heads][P][4]; rows 4g .. 4g+3 of the
+// ONE head tile are head g, which sits in o[4q .. 4q+3] of lane half h for g = 2 q + h (canonical_f16x3_kernel has the
+// same epilogue).  n_heads is read by the HEADS instance only.
+template <bool SAVE, bool HEADS = false>
 __global__ __launch_bounds__(256) void canonical_f32_kernel(const float* __restrict__ xyz,
                                                             const float* __restrict__ packed, int64_t P,
                                                             float4* __restrict__ raw, float* __restrict__ pe_out,
                                                             float* __restrict__ acts, uint32_t* __restrict__ relu_bits,
                                                             const int* __restrict__ idx,
-                                                            const int* __restrict__ count) {
+                                                            const int* __restrict__ count, int n_heads) {
+    static_assert(!(SAVE && HEADS), "the all-heads epilogue exists in the inference form only");
     const int lane = threadIdx.x & 63;
     const int h = lane >> 5;
+    const int64_t plane = P;                  // HEADS: samples per plane (P becomes *count in a sparse launch)
     if (idx != nullptr) {                     // sparse launch (hnrf_compact_samples): waves are independent
         P = *count;
         if (((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 32 >= P) return;
@@ -268,8 +273,17 @@ __global__ __launch_bounds__(256) void canonical_f32_kernel(const float* __restr
     }
     float o[16];
     mlp_layer<C_PH6, 1, 0, 32, true, false>(wptr, ring, bias, none, hA, o);
-    // rows 0..3 of the head tile live in registers 0..3 of the lower lane half
-    if (h == 0 && slot < P) raw[sample] = make_float4(o[0], o[1], o[2], o[3]);
+    if constexpr (HEADS) {
+        if (slot < P) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (2 * q + h < n_heads)
+                    raw[(int64_t)(2 * q + h) * plane + sample] = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+        }
+    } else {
+        // rows 0..3 of the head tile live in registers 0..3 of the lower lane half
+        if (h == 0 && slot < P) raw[sample] = make_float4(o[0], o[1], o[2], o[3]);
+    }
 }
 
 // K2.  Same structure, width 128.  SAVE: pe_out [P,36], acts [6][P][128].
@@ -377,20 +391,21 @@ extern "C" size_t hnrf_nonrigid_packed_bytes(int mode) {
 extern "C" size_t hnrf_canonical_status_offset(int mode) { return mode == HNRF_MLP_F16X3 ? canonical16_status_offset() : 0; }
 extern "C" size_t hnrf_nonrigid_status_offset(int mode) { return mode == HNRF_MLP_F16X3 ? nonrigid16_status_offset() : 0; }
 
-extern "C" int hnrf_canonical_pack(const float* const* weights, const float* const* biases, int mode, void* packed,
-                                   void* stream) {
-    HNRF_REQUIRE(weights && biases && packed, HNRF_E_ARG, "hnrf_canonical_pack: null pointer");
-    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3, HNRF_E_UNSUPPORTED,
-                 "hnrf_canonical_pack: mode %d not built", mode);
+// hnrf_canonical_pack (n_heads = 1) and hnrf_canonical_heads_pack: output_linear.0 is (4 n_heads, 256), rows
+// 0 .. 4 n_heads - 1 of the one head tile
+static int canonical_pack(const char* who, const float* const* weights, const float* const* biases, int n_heads, int mode,
+                          void* packed, void* stream) {
+    HNRF_REQUIRE(weights && biases && packed, HNRF_E_ARG, "%s: null pointer", who);
+    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3, HNRF_E_UNSUPPORTED, "%s: mode %d not built", who, mode);
     for (int i = 0; i < 9; ++i)
-        HNRF_REQUIRE(weights[i] && biases[i], HNRF_E_ARG, "hnrf_canonical_pack: null layer %d", i);
+        HNRF_REQUIRE(weights[i] && biases[i], HNRF_E_ARG, "%s: null layer %d", who, i);
     hipStream_t st = (hipStream_t)stream;
-    if (mode == HNRF_MLP_F16X3) return canonical16_pack(weights, biases, packed, st);
+    if (mode == HNRF_MLP_F16X3) return canonical16_pack(weights, biases, packed, st, n_heads);
     float* out = (float*)packed;
     int rc;
     // zero the prefetch over-run pad
     if (hipMemsetAsync(out + CNL_W_END, 0, PF * 256 * sizeof(float), st) != hipSuccess) {
-        set_error("hnrf_canonical_pack: memset failed");
+        set_error("%s: memset failed", who);
         return HNRF_E_LAUNCH;
     }
     PackLayer d{};
@@ -412,8 +427,19 @@ extern "C" int hnrf_canonical_pack(const float* const* weights, const float* con
                       CNL_W_L6 + (l - 6) * CNL_W_MID, CNL_B_OFF + l * 256};
         if ((rc = launch_pack(d, nullptr, out, st))) return rc;
     }
-    d = PackLayer{weights[8], biases[8], 4, 256, 1, 0, 32, PE_NONE, 0, 0, 1, 0, CNL_W_OUT, CNL_B_OFF + 8 * 256};
+    d = PackLayer{weights[8], biases[8], 4 * n_heads, 256, 1, 0, 32, PE_NONE, 0, 0, 1, 0, CNL_W_OUT, CNL_B_OFF + 8 * 256};
     return launch_pack(d, nullptr, out, st);
+}
+
+extern "C" int hnrf_canonical_pack(const float* const* weights, const float* const* biases, int mode, void* packed,
+                                   void* stream) {
+    return canonical_pack("hnrf_canonical_pack", weights, biases, 1, mode, packed, stream);
+}
+
+extern "C" int hnrf_canonical_heads_pack(const float* const* weights, const float* const* biases, int n_heads, int mode,
+                                         void* packed, void* stream) {
+    HNRF_REQUIRE(n_heads >= 2 && n_heads <= 8, HNRF_E_ARG, "hnrf_canonical_heads_pack: n_heads=%d outside 2..8", n_heads);
+    return canonical_pack("hnrf_canonical_heads_pack", weights, biases, n_heads, mode, packed, stream);
 }
 
 extern "C" int hnrf_nonrigid_pack(const float* const* weights, const float* const* biases, const float* cond,
@@ -466,8 +492,33 @@ extern "C" int hnrf_canonical_fwd_sparse(const float* xyz, const void* packed, i
     if (P == 0) return HNRF_OK;
     if (mode == HNRF_MLP_F16X3) return canonical16_fwd(xyz, packed, P, raw, idx, count, guard, (hipStream_t)stream);
     hipLaunchKernelGGL(canonical_f32_kernel<false>, dim3((unsigned)((P + 127) / 128)), dim3(256), 0,
-                       (hipStream_t)stream, xyz, (const float*)packed, P, (float4*)raw, nullptr, nullptr, nullptr, idx, count);
+                       (hipStream_t)stream, xyz, (const float*)packed, P, (float4*)raw, nullptr, nullptr, nullptr, idx, count, 1);
     return check_launch("hnrf_canonical_fwd");
+}
+
+extern "C" int hnrf_canonical_heads_fwd(const float* xyz, const void* packed, int mode, int64_t P, int n_heads, float* raw,
+                                        void* stream) {
+    return hnrf_canonical_heads_fwd_sparse(xyz, packed, mode, P, n_heads, nullptr, nullptr, raw, stream);
+}
+extern "C" int hnrf_canonical_heads_fwd_sparse(const float* xyz, const void* packed, int mode, int64_t P, int n_heads,
+                                               const int* idx, const int* count, float* raw, void* stream) {
+    const bool guard = !(mode & HNRF_MLP_NO_RANGE_GUARD);
+    mode &= HNRF_MLP_ARITH_MASK;
+    HNRF_REQUIRE(xyz && packed && raw, HNRF_E_ARG, "hnrf_canonical_heads_fwd: null pointer");
+    HNRF_REQUIRE(n_heads >= 2 && n_heads <= 8, HNRF_E_ARG, "hnrf_canonical_heads_fwd: n_heads=%d outside 2..8", n_heads);
+    HNRF_REQUIRE((idx == nullptr) == (count == nullptr), HNRF_E_ARG, "hnrf_canonical_heads_fwd: idx and count go together");
+    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3, HNRF_E_UNSUPPORTED,
+                 "hnrf_canonical_heads_fwd: mode %d not built", mode);
+    HNRF_REQUIRE(P >= 0 && (P + 127) / 128 < 2147483647LL, HNRF_E_ARG, "hnrf_canonical_heads_fwd: bad P=%lld", (long long)P);
+    HNRF_REQUIRE((((uintptr_t)packed | (uintptr_t)raw) & 15) == 0, HNRF_E_ARG,
+                 "hnrf_canonical_heads_fwd: packed/raw must be 16-byte aligned");
+    if (P == 0) return HNRF_OK;
+    if (mode == HNRF_MLP_F16X3)
+        return canonical16_heads_fwd(xyz, packed, P, n_heads, raw, idx, count, guard, (hipStream_t)stream);
+    hipLaunchKernelGGL((canonical_f32_kernel<false, true>), dim3((unsigned)((P + 127) / 128)), dim3(256), 0,
+                       (hipStream_t)stream, xyz, (const float*)packed, P, (float4*)raw, nullptr, nullptr, nullptr, idx, count,
+                       n_heads);
+    return check_launch("hnrf_canonical_heads_fwd");
 }
 
 extern "C" int hnrf_canonical_fwd_train(const float* xyz, const void* packed, int mode, int64_t P, float* raw,
@@ -483,7 +534,7 @@ extern "C" int hnrf_canonical_fwd_train(const float* xyz, const void* packed, in
     if (mode != HNRF_MLP_F32)
         return canonical16_fwd_train(xyz, packed, P, raw, pe_out, acts, relu_bits, mode == HNRF_MLP_F16X3_H, (hipStream_t)stream);
     hipLaunchKernelGGL(canonical_f32_kernel<true>, dim3((unsigned)((P + 127) / 128)), dim3(256), 0,
-                       (hipStream_t)stream, xyz, (const float*)packed, P, (float4*)raw, pe_out, acts, relu_bits, nullptr, nullptr);
+                       (hipStream_t)stream, xyz, (const float*)packed, P, (float4*)raw, pe_out, acts, relu_bits, nullptr, nullptr, 1);
     return check_launch("hnrf_canonical_fwd_train");
 }
 

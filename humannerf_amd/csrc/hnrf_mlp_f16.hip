@@ -88,6 +88,9 @@ struct PackLayer16 {
     int64_t off;               // byte offset of the layer's first slab
     int64_t bias_off;          // byte offset of the layer's first 128-B bias record
     int head_scale;            // 1 (head layers): weights stored x 2^k, 2^-k left in float 8 of the bias record
+                               // H >= 2 (multi-head canonical image, n_out = 4 H): head g = rows 4g .. 4g+3 has an exponent
+                               // k_g of its own, over its 4 x n_in weights, and 2^-k_g sits in float 32 + g of the record
+                               // (float 8 is the bias of row 8 there)
 };
 
 // Power-of-two exponent that brings a layer with abnormally small or large weights back to the usual magnitude
@@ -115,17 +118,26 @@ __global__ void pack_layer16_kernel(PackSet16 set, const float* __restrict__ con
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if ((int64_t)blockIdx.x * blockDim.x >= (n > d.NT * 32 ? n : (int64_t)d.NT * 32)) return;   // (grid sized for the largest layer)
     int kexp = 0;
-    if (d.head_scale) {                                            // (<= 4 x 256 weights: every block finds the maximum itself)
+    __shared__ int head_kexp[8];                                   // multi-head images: one exponent per head
+    const int n_heads = d.head_scale > 1 ? d.head_scale : 0;
+    if (d.head_scale) {                                            // (<= 4 x 256 weights per head: every block finds the maxima itself)
         __shared__ float red[256];
-        float m = 0.f;
-        for (int e = threadIdx.x; e < d.n_out * d.n_in; e += blockDim.x) m = fmaxf(m, fabsf(d.W[e]));
-        red[threadIdx.x] = m;
-        __syncthreads();
-        for (int st = 128; st >= 1; st >>= 1) {
-            if ((int)threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
+        const int n_sets = n_heads ? n_heads : 1;
+        const int set_elems = n_heads ? 4 * d.n_in : d.n_out * d.n_in;
+        for (int g = 0; g < n_sets; ++g) {
+            const float* Wg = d.W + (int64_t)g * set_elems;
+            float m = 0.f;
+            for (int e = threadIdx.x; e < set_elems; e += blockDim.x) m = fmaxf(m, fabsf(Wg[e]));
+            red[threadIdx.x] = m;
+            __syncthreads();
+            for (int st = 128; st >= 1; st >>= 1) {
+                if ((int)threadIdx.x < st) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + st]);
+                __syncthreads();
+            }
+            if (threadIdx.x == 0) head_kexp[g] = layer_exponent(red[0]);
             __syncthreads();
         }
-        kexp = layer_exponent(red[0]);
+        kexp = head_kexp[0];
     }
     if (i < (int64_t)d.NT * 32) {                                  // bias: 32 fp32 per tile
         const int row = (int)i;
@@ -134,8 +146,10 @@ __global__ void pack_layer16_kernel(PackSet16 set, const float* __restrict__ con
             v = d.b[row];
             for (int c = 0; c < d.fold_cols; ++c) v += d.W[(int64_t)row * d.n_in + c] * cond[c];
         }
-        if (d.head_scale && i == 8) v = ldexpf(1.0f, -kexp);
+        if (d.head_scale == 1 && i == 8) v = ldexpf(1.0f, -kexp);
         *reinterpret_cast<float*>(packed + d.bias_off + i * 4) = v;
+        // (floats 32 .. 39 of the head's record: behind its 32 biases, below the status word at byte 512)
+        if (n_heads && i < n_heads) *reinterpret_cast<float*>(packed + d.bias_off + (32 + i) * 4) = ldexpf(1.0f, -head_kexp[i]);
     }
     if (i >= n) return;
     const int t = (int)(i / slab_units);
@@ -158,7 +172,8 @@ __global__ void pack_layer16_kernel(PackSet16 set, const float* __restrict__ con
             col = d.b_col0 + hid_feat16(ks - d.NKA, j, h);
         }
         float w = 0.f;
-        if (row < d.n_out && col >= 0 && col < d.n_in) w = ldexpf(d.W[(int64_t)row * d.n_in + col], kexp);
+        if (row < d.n_out && col >= 0 && col < d.n_in)
+            w = ldexpf(d.W[(int64_t)row * d.n_in + col], n_heads ? head_kexp[row >> 2] : kexp);
         const _Float16 hi = (_Float16)w;
         const _Float16 lo = (_Float16)(w - (float)hi);               // un-lifted, see above
         outv[e] = part ? lo : hi;
@@ -851,14 +866,22 @@ __device__ __forceinline__ void stash_pe(const Pipe& p, int ks, const float (&v)
 // SAVE (training forward): also writes pe_out [P,63], acts [8][P][256] (fp32 post-ReLU values, as combined in the
 // epilogue) and relu_bits [8][P][8] like canonical_f32_kernel<true>; no sparse form.  SAVE == SV_ACT_H: acts and
 // pe_out are f16 matrices ([8][P][256], [P][64] with column 63 zero) for hnrf_mlp_dw_h.
-template <int SAVE, bool GUARD = false>
+// HEADS (inference, multi-head image of canonical16_pack): raw is n_heads planes [n_heads][P][4]; the head layer is the
+// same ONE 32-row tile, of which rows 0 .. 4 n_heads - 1 now hold weights.  In the 32x32 accumulator lane half h holds
+// rows 8 (r >> 2) + 4 h + (r & 3) in last[r]: head g = 2 q + h sits in last[4q .. 4q+3] of half h, and each half stores
+// its heads as one float4 per head -- no further MFMA, no LDS.  Head g equals the single-head kernel on the image packed
+// from rows 4g .. 4g+3 bit for bit (same products, same exponent: PackLayer16::head_scale).  n_heads is read by the
+// HEADS instances only.
+template <int SAVE, bool GUARD = false, bool HEADS = false>
 __global__ __launch_bounds__(256) void canonical_f16x3_kernel(const float* __restrict__ xyz,
                                                               const char* __restrict__ packed, int64_t P,
                                                               float4* __restrict__ raw, const int* __restrict__ idx,
                                                               const int* __restrict__ count,
                                                               float* __restrict__ pe_out, float* __restrict__ acts,
-                                                              uint32_t* __restrict__ relu_bits) {
+                                                              uint32_t* __restrict__ relu_bits, int n_heads) {
+    static_assert(!HEADS || SAVE == SV_NONE, "the all-heads epilogue exists in the inference form only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int64_t plane = P;                                  // HEADS: samples per plane (P becomes *count in a sparse launch)
     // sparse launch: only the `*count` samples listed in idx are evaluated (hnrf_compact_samples)
     if (idx != nullptr) {
         P = *count;
@@ -932,9 +955,24 @@ __global__ __launch_bounds__(256) void canonical_f16x3_kernel(const float* __res
     layer16<1, 1, 0, 16, false, 0, DF, false>(p, 0, 0, hA_h, hA_l, dh, dl, last, nullptr, &pend);
     // head bias and the head's power-of-two descale (pack_layer16_kernel, head_scale): scalar loads
     const float* ob = reinterpret_cast<const float*>(packed + CNL16_BIAS + CNL16_BIAS_LDS);
-    const float hs = ob[8];
-    if (h == 0 && slot < P)
-        raw[sample] = make_float4(fmaf(last[0], hs, ob[0]), fmaf(last[1], hs, ob[1]), fmaf(last[2], hs, ob[2]), fmaf(last[3], hs, ob[3]));
+    if constexpr (HEADS) {
+        if (slot < P) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int g = 2 * q + h;
+                if (g < n_heads) {
+                    const float hs = h ? ob[32 + 2 * q + 1] : ob[32 + 2 * q];     // head g's descale: floats 32 .. 39
+                    const float* bg = ob + 4 * g;
+                    raw[(int64_t)g * plane + sample] = make_float4(fmaf(last[4 * q], hs, bg[0]), fmaf(last[4 * q + 1], hs, bg[1]),
+                                                                   fmaf(last[4 * q + 2], hs, bg[2]), fmaf(last[4 * q + 3], hs, bg[3]));
+                }
+            }
+        }
+    } else {
+        const float hs = ob[8];
+        if (h == 0 && slot < P)
+            raw[sample] = make_float4(fmaf(last[0], hs, ob[0]), fmaf(last[1], hs, ob[1]), fmaf(last[2], hs, ob[2]), fmaf(last[3], hs, ob[3]));
+    }
     if constexpr (SAVE == SV_NONE && GUARD) raise_f16_range(packed, CNL16_STATUS, p.sat);
 #ifdef HNRF_STAMP
     if (threadIdx.x == 0 && blockIdx.x < 4096) {   // stamps leave through a buffer nothing else reads
@@ -1520,7 +1558,8 @@ size_t nonrigid16_bytes() { return (size_t)NR16_BYTES; }
 size_t canonical16_status_offset() { return (size_t)CNL16_STATUS; }
 size_t nonrigid16_status_offset() { return (size_t)NR16_STATUS; }
 
-int canonical16_pack(const float* const* w, const float* const* b, void* packed, hipStream_t st) {
+// n_heads >= 2: output_linear.0 is (4 n_heads, 256), the head tile's rows 0 .. 4 n_heads - 1 (PackLayer16::head_scale)
+int canonical16_pack(const float* const* w, const float* const* b, void* packed, hipStream_t st, int n_heads) {
     char* out = (char*)packed;
     if (hipMemsetAsync(out + CNL16_BIAS, 0, 9 * 1024, st) != hipSuccess) {
         set_error("hnrf_canonical_pack: memset failed");
@@ -1535,7 +1574,7 @@ int canonical16_pack(const float* const* w, const float* const* b, void* packed,
     for (int l = 6; l <= 7; ++l)
         d[l] = PackLayer16{w[l], b[l], 256, 256, 8, 0, 16, PE16_NONE, 0, 0, 0,
                            CNL16_L6 + (l - 6) * 8 * CNL16_NB_MID * KB, CNL16_BIAS + l * 1024, 0};
-    d[8] = PackLayer16{w[8], b[8], 4, 256, 1, 0, 16, PE16_NONE, 0, 0, 0, CNL16_OUT, CNL16_BIAS + 8 * 1024, 1};
+    d[8] = PackLayer16{w[8], b[8], 4 * n_heads, 256, 1, 0, 16, PE16_NONE, 0, 0, 0, CNL16_OUT, CNL16_BIAS + 8 * 1024, n_heads};
     return launch_pack16(d, 9, nullptr, out, st);
 }
 
@@ -1564,9 +1603,24 @@ int canonical16_fwd(const float* xyz, const void* packed, int64_t P, float* raw,
     const char* what = "hnrf_canonical_fwd (f16x3)";
     if (guard)
         return launch_lds<canonical_f16x3_kernel<SV_NONE, true>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
-                                                                 (float4*)raw, idx, count, nullptr, nullptr, nullptr);
+                                                                 (float4*)raw, idx, count, nullptr, nullptr, nullptr, 1);
     return launch_lds<canonical_f16x3_kernel<SV_NONE, false>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
-                                                              (float4*)raw, idx, count, nullptr, nullptr, nullptr);
+                                                              (float4*)raw, idx, count, nullptr, nullptr, nullptr, 1);
+}
+
+// all heads of a multi-head image: raw [n_heads][P][4]
+int canonical16_heads_fwd(const float* xyz, const void* packed, int64_t P, int n_heads, float* raw, const int* idx,
+                          const int* count, bool guard, hipStream_t st) {
+    constexpr int lds = CNL16_BIAS_LDS + PE_STASH + RING * CNL16_SLAB;
+    const dim3 grid((unsigned)((P + 127) / 128));
+    const char* what = "hnrf_canonical_heads_fwd (f16x3)";
+    if (guard)
+        return launch_lds<canonical_f16x3_kernel<SV_NONE, true, true>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed,
+                                                                       P, (float4*)raw, idx, count, nullptr, nullptr, nullptr,
+                                                                       n_heads);
+    return launch_lds<canonical_f16x3_kernel<SV_NONE, false, true>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
+                                                                    (float4*)raw, idx, count, nullptr, nullptr, nullptr,
+                                                                    n_heads);
 }
 
 int canonical16_fwd_train(const float* xyz, const void* packed, int64_t P, float* raw, float* pe_out, float* acts,
@@ -1576,9 +1630,9 @@ int canonical16_fwd_train(const float* xyz, const void* packed, int64_t P, float
     const char* what = "hnrf_canonical_fwd_train (f16x3)";
     if (half)
         return launch_lds<canonical_f16x3_kernel<SV_ACT_H>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
-                                                            (float4*)raw, nullptr, nullptr, pe_out, acts, relu_bits);
+                                                            (float4*)raw, nullptr, nullptr, pe_out, acts, relu_bits, 1);
     return launch_lds<canonical_f16x3_kernel<SV_ACT>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P, (float4*)raw,
-                                                      nullptr, nullptr, pe_out, acts, relu_bits);
+                                                      nullptr, nullptr, pe_out, acts, relu_bits, 1);
 }
 
 int nonrigid16_fwd(const float* x_skel, const float* hann_w, const void* packed, int64_t P, float* xyz,

@@ -115,7 +115,7 @@ class _NonRigidParams(nn.Module):
 class _CanonicalParams(nn.Module):
     """Parameters of CanonicalMLP default branch (canonical_mlps/mlp_rgb_sigma.py:64-99)."""
 
-    def __init__(self, input_ch, mlp_depth, mlp_width, skips):
+    def __init__(self, input_ch, mlp_depth, mlp_width, skips, n_heads=1):
         super().__init__()
         if not (input_ch == 63 and mlp_depth == 8 and mlp_width == 256 and list(skips) == [4]):
             raise NotImplementedError('only the default canonical MLP (8x256, skip 4, PE63) is built')
@@ -125,7 +125,8 @@ class _CanonicalParams(nn.Module):
             mods += [nn.Linear(n_in, mlp_width), nn.ReLU()]
         self.pts_linears = nn.ModuleList(mods)
         _init_sequence(self.pts_linears)
-        self.output_linear = nn.Sequential(nn.Linear(mlp_width, 4))
+        # multihead, head_depth 1 (mlp_rgb_sigma.py:114-115): head g is rows 4g .. 4g+3
+        self.output_linear = nn.Sequential(nn.Linear(mlp_width, 4 * n_heads))
         _init_sequence(self.output_linear)
 
     def linears(self):
@@ -467,7 +468,7 @@ def _node(root, path, default=None):
 # value that is built.  Module paths are compared by their last component.
 _BUILT_BRANCHES = (
     ('non_rigid_motion_model', 'mlp'),
-    ('canonical_mlp.view_dir', False), ('canonical_mlp.pose_color', 'wo'), ('canonical_mlp.multihead.enable', False),
+    ('canonical_mlp.view_dir', False), ('canonical_mlp.pose_color', 'wo'),
     ('canonical_mlp.mlp_depth_plus', 0), ('canonical_mlp.last_linear_scale', 1), ('canonical_mlp.i_embed', 0),
     ('canonical_mlp.time_input', False), ('canonical_mlp.module', 'mlp_rgb_sigma'),
     ('non_rigid_motion_mlp.mlp_depth_plus', 0), ('non_rigid_motion_mlp.last_linear_scale', 1),
@@ -480,11 +481,32 @@ _BUILT_BRANCHES = (
 )
 
 
+HEADS_MIN, HEADS_MAX = 2, 8         # the canonical MLP's head layer is one 32-row MFMA tile: up to 8 heads x 4 outputs
+
+
+def canonical_head_num(config):
+    """Number of heads of the canonical MLP ``config`` selects: 0 without ``canonical_mlp.multihead.enable``, else the
+    top-level ``multihead.head_num``.  check_config_is_built says which values are built."""
+    if not bool(_node(config, 'canonical_mlp.multihead.enable', False)):
+        return 0
+    return _node(config, 'multihead.head_num', None)
+
+
 def check_config_is_built(config):
-    """Raise unless ``config`` selects exactly the default-config branches of the reference network.  A checkpoint
-    trained with any other setting (e.g. ``mlp_depth_plus: 2``) has extra / different tensors that a
-    non-strict ``load_state_dict`` would drop silently, and the render would be wrong without an error."""
+    """Raise unless ``config`` selects exactly the default-config branches of the reference network, or those with a
+    multi-head canonical MLP of head depth 1 (``canonical_mlp.multihead.enable`` with a top-level ``multihead.head_num``
+    of 2..8, inference only).  A checkpoint trained with any other setting (e.g. ``mlp_depth_plus: 2``) has extra /
+    different tensors that a non-strict ``load_state_dict`` would drop silently, and the render would be wrong without
+    an error."""
     bad = []
+    if bool(_node(config, 'canonical_mlp.multihead.enable', False)):
+        heads = canonical_head_num(config)
+        if isinstance(heads, bool) or not isinstance(heads, int) or not HEADS_MIN <= heads <= HEADS_MAX:
+            bad.append('canonical_mlp.multihead.enable = True with multihead.head_num = %r (built: %d..%d)'
+                       % (heads, HEADS_MIN, HEADS_MAX))
+        depth = _node(config, 'canonical_mlp.multihead.head_depth', 1)
+        if depth != 1:
+            bad.append('canonical_mlp.multihead.head_depth = %r (built: 1)' % (depth,))
     for path, want in _BUILT_BRANCHES:
         have = _node(config, path, want)
         if path.endswith('.module'):
@@ -512,13 +534,22 @@ class Network(nn.Module):
         self.non_rigid_mlp = _Replicated(_NonRigidParams(
             pos_embed_size=6 * nr.multires, condition_code_size=nr.condition_code_size,
             mlp_width=nr.mlp_width, mlp_depth=nr.mlp_depth, skips=nr.skips))
+        # heads of the canonical MLP: 0 = the single-head network, else 2..8 (select_head / forward's head_id)
+        self.head_num = canonical_head_num(cfg)
         self.cnl_mlp = _Replicated(_CanonicalParams(
-            input_ch=3 + 6 * cm.multires, mlp_depth=cm.mlp_depth, mlp_width=cm.mlp_width, skips=[4]))
+            input_ch=3 + 6 * cm.multires, mlp_depth=cm.mlp_depth, mlp_width=cm.mlp_width, skips=[4],
+            n_heads=max(self.head_num, 1)))
         if not cfg.get('pose_decoder_off', False):
             self.pose_decoder = BodyPoseRefiner(
                 embedding_size=cfg.pose_decoder.embedding_size, mlp_width=cfg.pose_decoder.mlp_width,
                 mlp_depth=cfg.pose_decoder.mlp_depth, total_bones=cfg.total_bones)
         self._cnl_pack = None     # (key, packed image)
+        # multi-head: head -> (key, packed image), -1 = the all-heads image; _cnl_pack is the entry used last.  The head
+        # that _canonical_packed() packs outside forward (select_head), None = not chosen; the last device tensor read
+        # as a head_id (tensor, _version, value)
+        self._cnl_head_packs = {}
+        self._head = None
+        self._head_id_seen = None
         self._nr_pack_buf = None
         self.f16_guard = InferenceRangeGuard()
         self._vol_cache = None    # (key, priors, volume, _resident((priors,)))
@@ -561,6 +592,7 @@ class Network(nn.Module):
         hit = self.f16_guard.check(wait, upto)
         if any(hit):
             self._cnl_pack = None                               # (a fresh pack clears the canonical image's word)
+            self._cnl_head_packs.clear()
         return self.f16_guard.act(*hit)
 
     def _canonical_pass(self, op):
@@ -577,15 +609,77 @@ class Network(nn.Module):
             if not (self.check_f16_range(wait=True) and self._mlp_mode() != mode):
                 return res
 
+    def select_head(self, head):
+        """Choose the head (0 <= head < head_num) of a multi-head canonical MLP for everything that evaluates it outside
+        forward -- mesh extraction, density grid, bake, vertex colours -- and for a forward without ``head_id``; None
+        drops the choice.  The head is packed as an ordinary single-head image from rows 4 head .. 4 head + 3 of
+        output_linear.0, so every kernel and feature works on it unchanged."""
+        if head is not None:
+            if not self.head_num:
+                raise ValueError('select_head: the canonical MLP has a single head (canonical_mlp.multihead.enable is off)')
+            head = int(head)
+            if not 0 <= head < self.head_num:
+                raise ValueError('select_head: head %d outside 0..%d' % (head, self.head_num - 1))
+        self._head = head
+        return self
+
+    def _resolve_head(self, head_id):
+        """forward's ``head_id`` as an int: -1 = all heads, None = the selected head.  A tensor on the host is read there;
+        one on the device is read back once and remembered by identity and ``_version``, not once per frame."""
+        if head_id is None:
+            if self._head is None:
+                raise RuntimeError('multi-head canonical MLP (%d heads): pass head_id (0..%d, or -1 for all heads) or call '
+                                   'select_head first' % (self.head_num, self.head_num - 1))
+            return self._head
+        if torch.is_tensor(head_id):
+            if head_id.numel() != 1:
+                raise ValueError('head_id: a tensor of one element, got shape %s' % (tuple(head_id.shape),))
+            if head_id.device.type == 'cpu':
+                h = int(head_id.reshape(()).item())
+            else:
+                seen = self._head_id_seen
+                if seen is None or seen[0] is not head_id or seen[1] != head_id._version:
+                    seen = self._head_id_seen = (head_id, head_id._version, int(head_id.reshape(()).item()))
+                h = seen[2]
+        else:
+            h = int(head_id)
+        if not -1 <= h < self.head_num:
+            raise ValueError('head_id %d outside -1..%d' % (h, self.head_num - 1))
+        return h
+
     def _canonical_packed(self):
         lin = self.cnl_mlp.module.linears()
         ws, bs = [l.weight for l in lin], [l.bias for l in lin]
+        if self.head_num:
+            return self._canonical_packed_head(ws, bs)
         key = (self._mlp_mode(),) + _versions(ws + bs)
         if self._cnl_pack is None or self._cnl_pack[0] != key:
             packed = ops.canonical_pack([w.detach() for w in ws], [b.detach() for b in bs], self._mlp_mode(),
                                         out=None if self._cnl_pack is None else self._cnl_pack[1])
             self._cnl_pack = (key, packed)
         return self._cnl_pack[1]
+
+    def _canonical_packed_head(self, ws, bs):
+        """The image of the selected head (ops.canonical_pack on its four rows), or with head -1 the all-heads image
+        (ops.canonical_heads_pack); one cached image per head, the head in its key."""
+        h = self._head
+        if h is None:
+            raise RuntimeError('multi-head canonical MLP (%d heads): call select_head(h) before evaluating it outside '
+                               'forward (no head is used silently)' % self.head_num)
+        mode = self._mlp_mode()
+        key = (mode, h) + _versions(ws + bs)
+        ent = self._cnl_head_packs.get(h)
+        if ent is None or ent[0] != key:
+            W, B = [w.detach() for w in ws], [b.detach() for b in bs]
+            buf = None if ent is None else ent[1]
+            if h < 0:
+                packed = ops.canonical_heads_pack(W, B, self.head_num, mode, out=buf)
+            else:
+                W[8], B[8] = W[8][4 * h:4 * h + 4], B[8][4 * h:4 * h + 4]        # (whole rows: contiguous views)
+                packed = ops.canonical_pack(W, B, mode, out=buf)
+            ent = self._cnl_head_packs[h] = (key, packed)
+        self._cnl_pack = ent
+        return ent[1]
 
     def _nonrigid_packed(self, cond):
         lin = self.non_rigid_mlp.module.linears()
@@ -640,11 +734,30 @@ class Network(nn.Module):
 
     def forward(self, rays, dst_Rs, dst_Ts, cnl_gtfms, motion_weights_priors, dst_posevec=None,
                 near=None, far=None, iter_val=1e7, cnl_bbox_min_xyz=None, cnl_bbox_scale_xyz=None,
-                bgcolor=None, t_rand=None, **kwargs):
+                bgcolor=None, t_rand=None, head_id=None, **kwargs):
         """network.py:647-789.  Extra keyword ``t_rand`` (N,S) injects the
         stratified-sampling uniforms (parity tests); unknown kwargs are ignored
-        like the reference's **kwargs."""
+        like the reference's **kwargs.  ``head_id`` (multi-head canonical MLP only; an int or a tensor of one element):
+        the head to render, None = the one of select_head, -1 = every head of one trunk pass -- the per-head keys are then
+        lists of head_num tensors (network.py:570-601)."""
+        if self.head_num:
+            # the head holds for everything the frame evaluates (the canonical image, a bake), then the selection returns
+            prev, self._head = self._head, self._resolve_head(head_id)
+            try:
+                return self._forward(rays, dst_Rs, dst_Ts, cnl_gtfms, motion_weights_priors, dst_posevec, near, far, iter_val,
+                                     cnl_bbox_min_xyz, cnl_bbox_scale_xyz, bgcolor, t_rand, **kwargs)
+            finally:
+                self._head = prev
+        return self._forward(rays, dst_Rs, dst_Ts, cnl_gtfms, motion_weights_priors, dst_posevec, near, far, iter_val,
+                             cnl_bbox_min_xyz, cnl_bbox_scale_xyz, bgcolor, t_rand, **kwargs)
+
+    def _forward(self, rays, dst_Rs, dst_Ts, cnl_gtfms, motion_weights_priors, dst_posevec, near, far, iter_val,
+                 cnl_bbox_min_xyz, cnl_bbox_scale_xyz, bgcolor, t_rand, **kwargs):
         train_path = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        all_heads = self.head_num and self._head == -1
+        if self.head_num and train_path:
+            raise NotImplementedError('multi-head canonical MLP: inference only (the training kernels have one head; '
+                                      'checkpoints come from the reference trainer) -- call forward under torch.no_grad()')
         if self.f16_guard.pending:
             self.check_f16_range(wait=False)       # the previous frames' f16-range verdicts (may switch the mode, or raise)
         iter_val = float(iter_val)
@@ -694,6 +807,19 @@ class Network(nn.Module):
             zero = sum(p.sum() for p in self.parameters() if p.requires_grad) * 0.0 if train_path else None
             out = {k: torch.zeros((0,) + v, device=dev) + (zero if zero is not None and k in ('rgb', 'alpha', 'depth') else 0.0)
                    for k, v in ops.output_shapes(S, self.total_bones, diag or train_path).items()}
+            if all_heads:
+                out = self._heads_lists(out)
+        elif all_heads:
+            # every head of one trunk pass: the exact MLP path only
+            if canonical == 'baked':
+                raise NotImplementedError("head_id = -1 with cfg.amd.canonical = 'baked': a baked grid holds one head "
+                                          "(select_head, then bake)")
+            if term_eps > 0.0:
+                raise NotImplementedError('head_id = -1 with cfg.amd.term_eps > 0: early ray termination follows one '
+                                          "head's transmittance")
+            if nr_from_grid:
+                raise NotImplementedError("head_id = -1 with cfg.amd.nonrigid = 'baked'")
+            out = self._forward_frame_heads(per_ray, per_frame, nr_packed, cnl_packed, bg, S, mode, diag)
         elif train_path:
             out = self._forward_chunks(per_ray, per_frame, bg, S, mode, diag,
                                        train=(cond, not ignore_nr, nr_inputs_are_zero))
@@ -715,7 +841,28 @@ class Network(nn.Module):
                 out = self._forward_chunks(per_ray, per_frame, bg, S, mode, diag, packs=(nr_packed, cnl_packed),
                                            term_eps=term_eps)
         lead = list(rays_shape[:-1])
-        return {k: v.reshape(lead + list(v.shape[1:])) for k, v in out.items()}
+        shaped = lambda v: v.reshape(lead + list(v.shape[1:]))
+        return {k: [shaped(t) for t in v] if isinstance(v, list) else shaped(v) for k, v in out.items()}
+
+    def _heads_lists(self, out):
+        """A single-head output dict in the all-heads form: lists of head_num tensors for the per-head keys."""
+        H = self.head_num
+        return {k: [v.clone() for _ in range(H)] if k in ops.HEAD_KEYS else ([v] * H if k == 'xyz_on_rays' else v)
+                for k, v in out.items()}
+
+    def _forward_frame_heads(self, per_ray, per_frame, nr_packed, cnl_packed, bg, S, mode, diag):
+        """_forward_frame for every head (hnrf_render_frame_heads_fwd): the trunks of both MLPs once per chunk, one
+        compositing pass per head.  The shared evaluation of underflowing inputs (cfg.amd.share_underflow) is bypassed."""
+        gmode, guarded = self._guard_plan(mode, per_ray[0].shape[0])
+        cull_eps = 0.0 if diag else float(amd_option('cull_eps', 0.0))
+        out, self._workspace = ops.render_frame_heads(
+            *per_ray, *per_frame, nr_packed, cnl_packed, bg, S, int(cfg.chunk), self.head_num, gmode, diagnostics=diag,
+            cull_eps=cull_eps, workspace=self._workspace, overlap=bool(amd_option('overlap_warp', False)),
+            mlp_event_log=self.mlp_event_log)
+        self._share_last = None
+        if mode == 'f16x3' and guarded != set():
+            self.f16_guard.watch(cnl_packed, nr_packed, mode)
+        return out
 
     def _guard_plan(self, mode, n_rays):
         return self.f16_guard.plan(mode, -(-n_rays // int(cfg.chunk)), None if self._cnl_pack is None else self._cnl_pack[0])
@@ -848,7 +995,7 @@ class Network(nn.Module):
                 warnings.warn('bake_canonical: %d canonical-MLP outputs beyond +-65504 were saturated in the f16 grid: '
                               'the baked render differs from the exact one there' % n_sat)
             self.bake_count += 1
-            self._baked = {'grid': grid, 'bmin': bmin, 'bmax': bmax, 'key': (_versions(self._cnl_tensors()), self._mlp_mode(), N),
+            self._baked = {'grid': grid, 'bmin': bmin, 'bmax': bmax, 'key': (_versions(self._cnl_tensors()), self._mlp_mode(), N, self._head),
                            'injected': False, 'refs': None}
             return grid
 
@@ -929,7 +1076,7 @@ class Network(nn.Module):
         if b is not None and b['injected']:
             return b['grid'], b['bmin'], b['bmax']
         box = (bbox_min, bbox_max if bbox_max is not None else bbox_scale)
-        key = (_versions(self._cnl_tensors()), self._mlp_mode(), int(amd_option('bake_resolution', 256)))
+        key = (_versions(self._cnl_tensors()), self._mlp_mode(), int(amd_option('bake_resolution', 256)), self._head)
         if b is not None and b['key'] == key:
             if _still_resident(b['refs'], box):
                 return b['grid'], b['bmin'], b['bmax']

@@ -286,6 +286,24 @@ def _frame_streams(device):
     return ctx
 
 
+def _frame_sync_args(dev, N, chunk, overlap, want_mlp_events):
+    """What the frame entries order their streams and time their MLP launches with: (side stream or None, its 5 events as
+    a C array or None, the 2 x n_chunks MLP events as a C array or None, those events as (start, stop) pairs)."""
+    side, ev_arr = None, None
+    if overlap and N > chunk:
+        side, evs = _frame_streams(dev)
+        ev_arr = (ctypes.c_void_p * 5)(*[e.cuda_event for e in evs])
+    mlp_arr, pairs = None, []
+    if want_mlp_events:
+        nchunk = (N + chunk - 1) // chunk
+        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nchunk)]
+        for a, b in pairs:
+            a.record()
+            b.record()
+        mlp_arr = (ctypes.c_void_p * (2 * nchunk))(*[e.cuda_event for p in pairs for e in p])
+    return side, ev_arr, mlp_arr, pairs
+
+
 def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w, nr_packed,
                  cnl_packed, bgcolor, n_samples, chunk, mode='f16x3', diagnostics=True, cull_eps=0.0, workspace=None,
                  overlap=True, mlp_event_log=None, baked=None, baked_nr=None, share_log=None):
@@ -313,18 +331,7 @@ def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, b
                                    ws_bytes(min(chunk, max(N, 1)), S))
     out = {k: torch.empty((N,) + v, device=dev) for k, v in output_shapes(S, B, diagnostics).items()}
     g = lambda k: _ptr(out.get(k))
-    side, evs, ev_arr = None, None, None
-    if overlap and N > chunk:
-        side, evs = _frame_streams(dev)
-        ev_arr = (ctypes.c_void_p * 5)(*[e.cuda_event for e in evs])
-    mlp_arr, pairs = None, []
-    if mlp_event_log is not None:
-        nchunk = (N + chunk - 1) // chunk
-        pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nchunk)]
-        for a, b in pairs:
-            a.record()
-            b.record()
-        mlp_arr = (ctypes.c_void_p * (2 * nchunk))(*[e.cuda_event for p in pairs for e in p])
+    side, ev_arr, mlp_arr, pairs = _frame_sync_args(dev, N, chunk, overlap, mlp_event_log is not None)
     fn, name, ptrs = _render_entry(lib, 'frame', args, baked, baked_nr, share)
     live = (torch.empty(max(1, -(-N // chunk)), dtype=torch.int32, device=dev),) if share else ()
     _lib.check(fn(
@@ -652,6 +659,102 @@ def canonical_sparse(xyz, packed, idx, count, mode='f32', raw=None):
     _lib.check(lib.hnrf_canonical_fwd_sparse(_ptr(xyz), _ptr(packed), _mode_arg(mode), P, _ptr(idx), _ptr(count),
                                              _ptr(raw), _stream()), 'hnrf_canonical_fwd_sparse')
     return raw
+
+
+# ----------------------------------------------------------------------------- multi-head canonical MLP
+HEADS_MIN, HEADS_MAX = 2, 8          # the head layer is one 32-row MFMA tile: up to 8 heads x 4 outputs
+
+
+def _chk_heads(n_heads):
+    n_heads = int(n_heads)
+    if not HEADS_MIN <= n_heads <= HEADS_MAX:
+        raise _lib.HnrfError(f'n_heads = {n_heads}: the multi-head canonical MLP is built for {HEADS_MIN}..{HEADS_MAX} heads')
+    return n_heads
+
+
+def canonical_heads_pack(weights, biases, n_heads, mode='f32', out=None):
+    """canonical_pack for the multi-head MLP (mlp_rgb_sigma.py:114-115): output_linear.0 is (4 n_heads, 256).  The image
+    is for canonical_heads / render_frame_heads only; a single head is packed by canonical_pack from its four rows."""
+    lib = _lib.load_heads()
+    m, H = MLP_MODES[mode], _chk_heads(n_heads)
+    _chk(*weights, *biases)
+    assert len(weights) == 9 and len(biases) == 9
+    shapes = [(256, 63)] + [(256, 256)] * 4 + [(256, 319)] + [(256, 256)] * 2 + [(4 * H, 256)]
+    for w, b, s in zip(weights, biases, shapes):
+        if tuple(w.shape) != s or b.numel() != s[0]:
+            raise _lib.HnrfError(f'canonical MLP layer shape {tuple(w.shape)} != {s}: only the default '
+                                 f'architecture (default.yaml:51-57) with {H} heads of depth 1 is built')
+    nbytes = lib.hnrf_canonical_packed_bytes(m)
+    if out is None or out.numel() * 4 < nbytes:
+        out = torch.empty((nbytes + 3) // 4, device=weights[0].device)
+    _lib.check(lib.hnrf_canonical_heads_pack(_ptr_array(weights), _ptr_array(biases), H, m, _ptr(out), _stream()),
+               'hnrf_canonical_heads_pack')
+    return out
+
+
+def canonical_heads(xyz, packed, n_heads, mode='f32'):
+    """K3 for every head of one trunk pass (mlp_rgb_sigma.py:180-193, head_id = -1).  xyz (...,3) -> raw (H,...,4)."""
+    lib = _lib.load_heads()
+    _chk(xyz, packed)
+    H, P = _chk_heads(n_heads), xyz.numel() // 3
+    raw = torch.empty(H, *xyz.shape[:-1], 4, device=xyz.device)
+    _lib.check(lib.hnrf_canonical_heads_fwd(_ptr(xyz), _ptr(packed), _mode_arg(mode), P, H, _ptr(raw), _stream()),
+               'hnrf_canonical_heads_fwd')
+    return raw
+
+
+def canonical_heads_sparse(xyz, packed, n_heads, idx, count, mode='f32', raw=None):
+    lib = _lib.load_heads()
+    _chk(xyz, packed)
+    H, P = _chk_heads(n_heads), xyz.numel() // 3
+    if raw is None:
+        raw = torch.zeros(H, *xyz.shape[:-1], 4, device=xyz.device)
+    _chk(raw)
+    assert raw.numel() == H * P * 4
+    _lib.check(lib.hnrf_canonical_heads_fwd_sparse(_ptr(xyz), _ptr(packed), _mode_arg(mode), P, H, _ptr(idx), _ptr(count),
+                                                   _ptr(raw), _stream()), 'hnrf_canonical_heads_fwd_sparse')
+    return raw
+
+
+HEAD_KEYS = ('rgb', 'alpha', 'depth', 'weights_on_rays', 'rgb_on_rays', 'cnl_xyz', 'cnl_rgb', 'cnl_weight')
+
+
+def render_frame_heads(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w,
+                       nr_packed, cnl_packed, bgcolor, n_samples, chunk, n_heads, mode='f16x3', diagnostics=True,
+                       cull_eps=0.0, workspace=None, overlap=True, mlp_event_log=None):
+    """render_frame for every head of a multi-head image (hnrf_render_frame_heads_fwd; network.py:570-601): the MLP
+    trunks once per chunk, one compositing pass per head.  Returns (dict, workspace): the HEAD_KEYS are lists of n_heads
+    whole-frame tensors, xyz_on_rays is the same tensor n_heads times, backward_motion_weights and offsets are tensors."""
+    lib = _lib.load_heads()
+    H = _chk_heads(n_heads)
+    N, S, B, G = rays_o.shape[0], int(n_samples), motion_Rs.shape[0], vol.shape[-1]
+    dev = rays_o.device
+    chunk = int(chunk)
+    args, workspace = _render_args((rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
+                                    hann_w, nr_packed, cnl_packed, bgcolor), workspace,
+                                   lib.hnrf_render_frame_heads_workspace_bytes(min(chunk, max(N, 1)), S, H))
+    shapes = output_shapes(S, B, diagnostics)
+    # one allocation per key, head-major: out[k][h] is a contiguous whole-frame tensor
+    stacked = {k: torch.empty((H, N) + shapes[k], device=dev) for k in HEAD_KEYS if k in shapes}
+    single = {k: torch.empty((N,) + v, device=dev) for k, v in shapes.items() if k not in HEAD_KEYS}
+    arr = lambda k: (ctypes.c_void_p * H)(*[stacked[k][h].data_ptr() for h in range(H)]) if k in stacked else None
+    side, ev_arr, mlp_arr, pairs = _frame_sync_args(dev, N, chunk, overlap, mlp_event_log is not None)
+    _lib.check(lib.hnrf_render_frame_heads_fwd(
+        *map(_ptr, args), _mode_arg(mode), float(cull_eps), N, S, B, G, chunk, H, _ptr(workspace),
+        workspace.numel() * workspace.element_size(), *[arr(k) for k in HEAD_KEYS], _ptr(single.get('xyz_on_rays')),
+        _ptr(single.get('backward_motion_weights')), _ptr(single.get('offsets')),
+        side.cuda_stream if side is not None else None, ev_arr, mlp_arr, _stream()), 'hnrf_render_frame_heads_fwd')
+    if side is not None:
+        for t in args[:10] + (workspace, single.get('backward_motion_weights')):      # (as in render_frame)
+            if t is not None:
+                t.record_stream(side)
+    if mlp_event_log is not None:
+        mlp_event_log.extend(pairs)
+    out = {k: list(v.unbind(0)) for k, v in stacked.items()}
+    out.update(single)
+    if 'xyz_on_rays' in out:
+        out['xyz_on_rays'] = [out['xyz_on_rays']] * H
+    return out, workspace
 
 
 def nonrigid_sparse(x_skel, hann_w, packed, idx, count, mode='f32'):

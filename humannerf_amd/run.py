@@ -9,6 +9,8 @@ render.ImageWriter / MetricsWriter on worker threads.
                                   side by side, PSNR (SSIM, LPIPS) per image and averaged
   run_freeview   run.py:67-170    one training frame seen from a camera orbiting the subject
   run_tpose      run.py:178-183   the canonical pose on a turntable, non-rigid motion off
+  run_heads      run.py:76-81, 219-225   the three loops above for a multi-head canonical MLP with cfg.test.head_id = -1:
+                                  every frame rendered once, head i written to ``<load_net><tag>_h<i>/<folder>``
   run_mesh       (no counterpart) the canonical body as a coloured triangle mesh, and that mesh skinned into frames
   run_mesh_render (no counterpart) the movement / freeview / tpose sequences as rasterised pictures of that mesh: a preview
   run_surface_points  run.py:388-404   cfg.test.save_3d_together: one canonical surface point per ray of every movement
@@ -219,6 +221,96 @@ def run_tpose(network, subject, total_frames=None, render_folder_name=None, logd
                             folder, logdir, rank, world, device)
     finally:
         cfg.ignore_non_rigid_motions = old
+
+
+def run_heads(network, subject, kind='movement', frame_idx=None, total_frames=None, render_folder_name=None, logdir=None,
+              device=None, test_num=-1, metrics=None, lpips_fn=None, image_size=None, src_type='zju_mocap'):
+    """Every head of a multi-head canonical MLP (run.py:76-81, :219-225 with cfg.test.head_id = -1): each frame of the
+    ``kind`` = 'movement' | 'freeview' | 'tpose' sequence is rendered ONCE with ``head_id = -1`` -- the trunks of both
+    MLPs once, one compositing pass per head -- and head i's picture goes to ``<logdir>/<load_net><eval_output_tag>_h<i>/
+    <folder>/NAME.png``, as the reference names them; 'movement' also writes ``<folder>-metrics.perimg.txt /
+    .average.txt`` per head (MetricsWriter on the delivered images).  Frames leave through render.FrameOutbox and
+    render.ImageWriter like those of the other loops.  The f16-range verdict of a frame is waited for before its pictures
+    are handed over (one wait per frame; with cfg.amd.on_f16_range = 'f32' a frame out of range is rendered again with
+    the exact kernels first).  Returns a list of per-head result dicts {'image_dir', 'stack', 'metrics'}.
+    cfg.amd.video and cfg.amd.maps are not built for this loop: ValueError."""
+    import torch
+    from .config import amd_option, check_amd_options
+    check_amd_options()
+    if amd_option('video', 'none') != 'none':
+        raise ValueError("run_heads: cfg.amd.video = %r is not built for the all-heads loop (set it to 'none')"
+                         % (amd_option('video', 'none'),))
+    if amd_option('maps', []):
+        raise ValueError('run_heads: cfg.amd.maps = %r is not built for the all-heads loop (set it to [])'
+                         % (list(amd_option('maps', [])),))
+    H = getattr(network, 'head_num', 0)
+    if not H:
+        raise ValueError('run_heads: the canonical MLP has a single head (canonical_mlp.multihead.enable is off)')
+    if kind not in ('movement', 'freeview', 'tpose'):
+        raise ValueError("run_heads: kind must be 'movement', 'freeview' or 'tpose', got %r" % (kind,))
+    device = device or next(network.parameters()).device
+    keep = cfg.perturb, cfg.ignore_non_rigid_motions, cfg.get('show_truth', False)
+    if kind == 'movement':
+        cfg.show_truth = True
+        n = len(subject) if test_num < 0 else min(test_num, len(subject))
+        frames = _Frames(n, lambda i: subject.movement_frame(i, load_image=True, device=device))
+        names = [str(subject.framelist[i]).replace('/', '-') for i in range(n)]
+        folder = render_folder_name or 'movement'
+    elif kind == 'freeview':
+        frame_idx = int(cfg.get('freeview', {}).get('frame_idx', 0)) if frame_idx is None else int(frame_idx)
+        n = int(cfg.get('render_frames', 100)) if total_frames is None else int(total_frames)
+        size = image_size if image_size is not None else subject.image_size(subject.framelist_all[frame_idx])
+        frames = _Frames(n, lambda i: subject.freeview_frame(i, n, train_frame_idx=frame_idx, src_type=src_type,
+                                                             image_size=size, bgcolor=cfg.bgcolor))
+        names = [None] * n
+        folder = render_folder_name or cfg.get('render_folder_name', '') or 'freeview_%d' % frame_idx
+    else:
+        n = int(cfg.get('render_frames', 100)) if total_frames is None else int(total_frames)
+        frames = _Frames(n, lambda i: subject.tpose_frame(i, n, image_size=image_size, bgcolor=cfg.bgcolor))
+        names = [None] * n
+        folder = render_folder_name or cfg.get('render_folder_name', '') or 'tpose'
+        cfg.ignore_non_rigid_motions = True
+    out_dirs = [_output_dir(logdir) + '_h%d' % h for h in range(H)]
+    writers = [render.ImageWriter(d, folder) for d in out_dirs]
+    mws = [render.MetricsWriter(d, folder, dataset=subject.dataset_path, metrics=metrics, lpips_fn=lpips_fn)
+           for d in out_dirs] if kind == 'movement' else None
+    outbox = render.FrameOutbox(device)
+    network.eval()
+    cfg.perturb = 0.                                                     # run.py:71, 214
+
+    def render_item(item):
+        with torch.no_grad():
+            res = network(**item['data'], head_id=-1, iter_val=float(cfg.eval_iter))
+        imgs = []
+        for h in range(H):
+            rgb8, a8, t8 = render.unpack_to_image(item['W'], item['H'], None, item['data']['bgcolor'] / 255., res['rgb'][h],
+                                                  res['alpha'][h], item['truth'] if h == 0 else None,
+                                                  ray_index=item['ray_index'])
+            imgs += [rgb8, a8] + ([t8] if t8 is not None and h == 0 and item['truth'] is not None else [])
+        return outbox.post(imgs), item['truth'] is not None
+
+    pre = render.FramePrefetcher(frames, list(range(n)), device, show_truth=kind == 'movement')
+    try:
+        for item in pre:
+            mode = network._mlp_mode()
+            parcel, has_truth = render_item(item)
+            network.check_f16_range(wait=True)                           # (raises, or switches the mode, on a range hit)
+            if network._mlp_mode() != mode:
+                parcel.discard()
+                parcel, has_truth = render_item(item)
+            arrs = parcel.collect()[0]
+            truth8 = arrs[2] if has_truth else None
+            per_head = [arrs[:2]] + [arrs[(3 if has_truth else 2) + 2 * (h - 1):][:2] for h in range(1, H)]
+            i = item['idx']
+            for h, (rgb8, alpha8) in enumerate(per_head):
+                writers[h].append(_panels(rgb8, alpha8, truth8), img_name=names[i])
+                if mws is not None and truth8 is not None:
+                    mws[h].append(name=names[i], pred=rgb8, target=truth8, mask=None)
+    finally:
+        pre.close()
+        cfg.perturb, cfg.ignore_non_rigid_motions, cfg.show_truth = keep
+    return [{'image_dir': os.path.join(out_dirs[h], folder), 'stack': writers[h].finalize(),
+             'metrics': mws[h].finalize() if mws is not None else None} for h in range(H)]
 
 
 def run_mesh(network, subject, frames=(), resolution=256, level=None, logdir=None):

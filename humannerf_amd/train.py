@@ -189,6 +189,9 @@ PROGRESS_ITERS = (100, 300, 1000, 2500)          # trainer.py:240
 
 class Trainer:
     def __init__(self, network, optimizer=None, lpips_fn=None, world_size=1, process_group=None, logdir=None):
+        if getattr(network, 'head_num', 0):
+            raise NotImplementedError('Trainer: a multi-head canonical MLP (%d heads) is built for inference only; its '
+                                      'checkpoints come from the reference trainer' % network.head_num)
         self.network = network.deploy_mlps_to_secondary_gpus()
         self.optimizer = optimizer if optimizer is not None else build_optimizer(network)
         self.lpips_fn = lpips_fn

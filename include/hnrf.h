@@ -780,6 +780,10 @@ int hnrf_image_metrics(const uint8_t* pred, const uint8_t* target, const uint8_t
  * version 13; contracts and declarations in hnrf_geometry.h. */
 #include "hnrf_geometry.h"
 
+/* ---- the multi-head canonical MLP (canonical_mlp.multihead, head_depth 1): pack, all heads of one trunk pass, and the
+ * frame with per-head outputs.  Additive to ABI version 13; contracts and declarations in hnrf_heads.h. */
+#include "hnrf_heads.h"
+
 #ifdef __cplusplus
 }
 #endif
