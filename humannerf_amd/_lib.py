@@ -12,11 +12,18 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('HNRF_LIB_PATH', os.path.join(_HERE, 'libhnrf.so'))   # override: diagnostic builds only
 
 HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf.h'))
-CLOUD_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_cloud.h'))   # included by hnrf.h
-VIDEO_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_video.h'))   # included by hnrf.h
-SEGMENT_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_segment.h'))   # included by hnrf.h
-GEOMETRY_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_geometry.h'))   # included by hnrf.h
-HEADS_HEADER_PATH = os.path.normpath(os.path.join(_HERE, '..', 'include', 'hnrf_heads.h'))   # included by hnrf.h
+
+# The additive headers (each included by hnrf.h): group -> (header file, what a library without its entries was "built
+# before").  Their entries are additive to ABI version 13, so a library of that version built before them (HNRF_LIB_PATH)
+# still loads; load_<group>() binds them and raises when they are missing.  <GROUP>_HEADER_PATH and <GROUP>_SIGNATURES
+# below come from this table, and load_all() -- the self-check of __graft_entry__.build() -- walks it.
+GROUPS = {
+    'cloud': ('hnrf_cloud.h', 'the surface-point and frame-distance kernels'),
+    'video': ('hnrf_video.h', 'the JPEG encoder'),
+    'segment': ('hnrf_segment.h', 'the body-part segmentation'),
+    'geometry': ('hnrf_geometry.h', 'the geometry maps'),
+    'heads': ('hnrf_heads.h', 'the multi-head canonical MLP'),
+}
 
 _SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float,
             'double': ctypes.c_double}
@@ -64,21 +71,19 @@ def _signatures(path=HEADER_PATH):
 
 # name -> (restype, argtypes), derived from the declarations of include/hnrf.h
 SIGNATURES = _signatures()
-# the surface-point / frame-distance entries of include/hnrf_cloud.h: additive to ABI version 13, so a library of that
-# version built before them (HNRF_LIB_PATH) still loads; load_cloud() binds them and raises when they are missing
-CLOUD_SIGNATURES = _signatures(CLOUD_HEADER_PATH)
 
-# the JPEG encoder's entries of include/hnrf_video.h: additive to ABI version 13 in the same way (load_video)
-VIDEO_SIGNATURES = _signatures(VIDEO_HEADER_PATH)
 
-# the body-part segmentation's entries of include/hnrf_segment.h: additive to ABI version 13 in the same way (load_segment)
-SEGMENT_SIGNATURES = _signatures(SEGMENT_HEADER_PATH)
+def _header(group):
+    path = os.path.normpath(os.path.join(_HERE, '..', 'include', GROUPS[group][0]))
+    return path, _signatures(path)
 
-# the geometry maps' entries of include/hnrf_geometry.h: additive to ABI version 13 in the same way (load_geometry)
-GEOMETRY_SIGNATURES = _signatures(GEOMETRY_HEADER_PATH)
 
-# the multi-head canonical MLP's entries of include/hnrf_heads.h: additive to ABI version 13 in the same way (load_heads)
-HEADS_SIGNATURES = _signatures(HEADS_HEADER_PATH)
+_HEADERS = {group: _header(group) for group in GROUPS}       # group -> (header path, its name -> (restype, argtypes))
+CLOUD_HEADER_PATH, CLOUD_SIGNATURES = _HEADERS['cloud']
+VIDEO_HEADER_PATH, VIDEO_SIGNATURES = _HEADERS['video']
+SEGMENT_HEADER_PATH, SEGMENT_SIGNATURES = _HEADERS['segment']
+GEOMETRY_HEADER_PATH, GEOMETRY_SIGNATURES = _HEADERS['geometry']
+HEADS_HEADER_PATH, HEADS_SIGNATURES = _HEADERS['heads']
 
 _lib = None
 
@@ -109,103 +114,54 @@ def load():
     return lib
 
 
-_cloud_bound = False
+_bound = set()
+
+
+def _bind(group, lib=None):
+    """load() plus the entries of the group's header, typed.  A library without them raises HnrfError.  ``lib``: a
+    library object to bind in the place of the loaded one (every time it is asked for)."""
+    header, phrase = GROUPS[group]
+    if lib is None and group in _bound:
+        return load()
+    target = load() if lib is None else lib
+    for name, (res, args) in _HEADERS[group][1].items():
+        try:
+            fn = getattr(target, name)
+        except AttributeError:
+            raise HnrfError(f'{LIB_PATH} does not export {name}: it was built before {phrase} '
+                            f'(include/{header}); rebuild it') from None
+        fn.restype = res
+        fn.argtypes = args
+    if lib is None:
+        _bound.add(group)
+    return target
 
 
 def load_cloud():
-    """load() plus the entries of include/hnrf_cloud.h, typed.  A library without them raises HnrfError."""
-    global _cloud_bound
-    lib = load()
-    if not _cloud_bound:
-        for name, (res, args) in CLOUD_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise HnrfError(f'{LIB_PATH} does not export {name}: it was built before the surface-point and '
-                                f'frame-distance kernels (include/hnrf_cloud.h); rebuild it') from None
-            fn.restype = res
-            fn.argtypes = args
-        _cloud_bound = True
-    return lib
-
-
-_video_bound = False
+    return _bind('cloud')
 
 
 def load_video():
-    """load() plus the entries of include/hnrf_video.h, typed.  A library without them raises HnrfError."""
-    global _video_bound
-    lib = load()
-    if not _video_bound:
-        for name, (res, args) in VIDEO_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise HnrfError(f'{LIB_PATH} does not export {name}: it was built before the JPEG encoder '
-                                f'(include/hnrf_video.h); rebuild it') from None
-            fn.restype = res
-            fn.argtypes = args
-        _video_bound = True
-    return lib
-
-
-_segment_bound = False
+    return _bind('video')
 
 
 def load_segment():
-    """load() plus the entries of include/hnrf_segment.h, typed.  A library without them raises HnrfError."""
-    global _segment_bound
-    lib = load()
-    if not _segment_bound:
-        for name, (res, args) in SEGMENT_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise HnrfError(f'{LIB_PATH} does not export {name}: it was built before the body-part segmentation '
-                                f'(include/hnrf_segment.h); rebuild it') from None
-            fn.restype = res
-            fn.argtypes = args
-        _segment_bound = True
-    return lib
-
-
-_geometry_bound = False
+    return _bind('segment')
 
 
 def load_geometry():
-    """load() plus the entries of include/hnrf_geometry.h, typed.  A library without them raises HnrfError."""
-    global _geometry_bound
-    lib = load()
-    if not _geometry_bound:
-        for name, (res, args) in GEOMETRY_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise HnrfError(f'{LIB_PATH} does not export {name}: it was built before the geometry maps '
-                                f'(include/hnrf_geometry.h); rebuild it') from None
-            fn.restype = res
-            fn.argtypes = args
-        _geometry_bound = True
-    return lib
-
-
-_heads_bound = False
+    return _bind('geometry')
 
 
 def load_heads():
-    """load() plus the entries of include/hnrf_heads.h, typed.  A library without them raises HnrfError."""
-    global _heads_bound
+    return _bind('heads')
+
+
+def load_all():
+    """load() plus every group of GROUPS (the self-check of __graft_entry__.build())."""
     lib = load()
-    if not _heads_bound:
-        for name, (res, args) in HEADS_SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError:
-                raise HnrfError(f'{LIB_PATH} does not export {name}: it was built before the multi-head canonical MLP '
-                                f'(include/hnrf_heads.h); rebuild it') from None
-            fn.restype = res
-            fn.argtypes = args
-        _heads_bound = True
+    for group in GROUPS:
+        _bind(group)
     return lib
 
 

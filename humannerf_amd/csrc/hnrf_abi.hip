@@ -59,9 +59,10 @@ struct Share {
     bool fused;
 };
 
-// All heads of a multi-head canonical image (hnrf_render_frame_heads_fwd): K3 writes the n planes raw [n][P][4] in one
-// launch, K4 runs once per plane into o[g].  Every o[g] carries the same xyz / bmw / offsets: those do not depend on the head.
-struct HeadsOut {
+// What K3 writes and K4 composites: the n planes raw [n][P][4] and the outputs o[g] of each.  n == 1: the chunk's own
+// raw (c.raw) and FrameOut; n >= 2: all heads of a multi-head canonical image (hnrf_render_frame_heads_fwd), written by
+// K3 in one launch.  Every o[g] carries the same xyz / bmw / offsets: those do not depend on the head.
+struct Planes {
     int n;
     float* raw;
     const FrameOut* o;
@@ -74,8 +75,9 @@ struct HeadsOut {
 // K2 and K3; the lean form then writes no xyz at all.
 int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w, const void* nr_packed,
                  const BakedGrid& off, const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t R,
-                 int S, const FrameOut& d, void* ev_start, void* ev_stop, hipStream_t st,
-                 const Share& sh = Share{nullptr, false}, const HeadsOut* hd = nullptr) {
+                 int S, const Planes& pl, void* ev_start, void* ev_stop, hipStream_t st,
+                 const Share& sh = Share{nullptr, false}) {
+    const FrameOut& d = pl.o[0];                                  // (K2's outputs: the same in every plane)
     const size_t P = (size_t)R * (size_t)S;
     const bool cull = cull_eps > 0.f, diag = d.weights != nullptr;
     int rc;
@@ -93,7 +95,7 @@ int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w,
     // d.offsets need no `diag ?` of their own)
     if (off.grid) {
         if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-        rc = baked_warp_sample(c.x_skel, off, BakedGrid{cnl.grid, cnl.N, cnl.bmin, cnl.bmax}, (int64_t)P, ci, cc, c.raw,
+        rc = baked_warp_sample(c.x_skel, off, BakedGrid{cnl.grid, cnl.N, cnl.bmin, cnl.bmax}, (int64_t)P, ci, cc, pl.raw,
                                d.xyz, d.offsets, st);
         if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
         if (rc) return rc;
@@ -108,25 +110,20 @@ int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w,
             HNRF_HIP(hipMemsetAsync(d.offsets, 0, P * 12, st));
         }
         if (ev_start) (void)hipEventRecord((hipEvent_t)ev_start, st);
-        rc = cnl.grid ? baked_sample(cnl_in, cnl.grid, cnl.N, cnl.bmin, cnl.bmax, (int64_t)P, ci, cc, c.raw, st)
-             : hd     ? hnrf_canonical_heads_fwd_sparse(cnl_in, cnl.packed, mode, (int64_t)P, hd->n, ci, cc, hd->raw, st)
-                      : hnrf_canonical_fwd_sparse(cnl_in, cnl.packed, mode, (int64_t)P, ci, cc, c.raw, st);
+        rc = cnl.grid  ? baked_sample(cnl_in, cnl.grid, cnl.N, cnl.bmin, cnl.bmax, (int64_t)P, ci, cc, pl.raw, st)
+             : pl.n > 1 ? hnrf_canonical_heads_fwd_sparse(cnl_in, cnl.packed, mode, (int64_t)P, pl.n, ci, cc, pl.raw, st)
+                        : hnrf_canonical_fwd_sparse(cnl_in, cnl.packed, mode, (int64_t)P, ci, cc, pl.raw, st);
         if (ev_stop) (void)hipEventRecord((hipEvent_t)ev_stop, st);
         if (rc) return rc;
     }
-    if (hd) {
-        for (int g = 0; g < hd->n; ++g) {
-            const FrameOut& o = hd->o[g];
-            if ((rc = hnrf_composite_fwd(hd->raw + (size_t)g * P * 4, c.mask, c.z_vals, rays_d, diag ? cnl_in : nullptr, bgcolor,
-                                         R, S, cull ? cull_eps : 0.f, o.rgb, o.alpha, o.depth, o.weights, o.rgb_on_rays,
-                                         o.cnl_xyz, o.cnl_rgb, o.cnl_weight, st)))
-                return rc;
-        }
-        return HNRF_OK;
+    for (int g = 0; g < pl.n; ++g) {
+        const FrameOut& o = pl.o[g];
+        if ((rc = hnrf_composite_fwd(pl.raw + (size_t)g * P * 4, c.mask, c.z_vals, rays_d, diag ? cnl_in : nullptr, bgcolor,
+                                     R, S, cull ? cull_eps : 0.f, o.rgb, o.alpha, o.depth, o.weights, o.rgb_on_rays,
+                                     o.cnl_xyz, o.cnl_rgb, o.cnl_weight, st)))
+            return rc;
     }
-    return hnrf_composite_fwd(c.raw, c.mask, c.z_vals, rays_d, diag ? cnl_in : nullptr, bgcolor, R, S,
-                              cull ? cull_eps : 0.f, d.rgb, d.alpha, d.depth, d.weights, d.rgb_on_rays, d.cnl_xyz,
-                              d.cnl_rgb, d.cnl_weight, st);
+    return HNRF_OK;
 }
 // the baked entries' grid arguments (the sampler launches from inside render_chunk without further checks)
 int check_source(const char* who, const CnlSource& cnl) {
@@ -165,8 +162,8 @@ int render_rays(const char* who, const Rays& rays, const WarpField& field, const
     const RenderCarve c = render_carve(workspace, R, S);
     hipStream_t st = (hipStream_t)stream;
     if (int rc = sample_warp(rays, field, R, S, c.z_vals, c.x_skel, c.mask, nullptr, nullptr, st)) return rc;
-    return render_chunk(c, rays.d, hann_w, nr_packed, off, cnl, bgcolor, mode, cull_eps, R, S, out, ev_mlp_start,
-                        ev_mlp_stop, st);
+    return render_chunk(c, rays.d, hann_w, nr_packed, off, cnl, bgcolor, mode, cull_eps, R, S, Planes{1, c.raw, &out},
+                        ev_mlp_start, ev_mlp_stop, st);
 }
 }  // namespace
 
@@ -221,24 +218,35 @@ extern "C" int hnrf_render_rays_baked_nr_fwd(const float* rays_o, const float* r
 // per-ray / per-sample results written straight into whole-frame buffers.  With a side stream the LBS warp (K1, an
 // L2-gather kernel without LDS) of chunk i+1 runs while the matrix-bound MLP kernels of chunk i own the CUs: K1 leaves
 // the critical path (3 % of a 512x512x128 frame).  Two workspaces alternate; the caller provides the events.
-extern "C" size_t hnrf_render_frame_workspace_bytes(int64_t chunk, int S) { return 2 * hnrf_render_workspace_bytes(chunk, S); }
-// + the representative slot behind the two chunk workspaces
-extern "C" size_t hnrf_render_frame_shared_workspace_bytes(int64_t chunk, int S) {
-    return hnrf_render_frame_workspace_bytes(chunk, S) + 256;
+//
+// The frame workspace for chunks of `rows` rays, the one statement of its size: the two chunk workspaces, behind them --
+// share -- the 256 bytes of the representative slot, or -- n_heads >= 2 -- the n_heads raw planes of one chunk (K3 and
+// the K4s of a chunk run on `stream` in order, so one set serves every chunk).
+static size_t frame_ws_bytes(int64_t rows, int S, bool share, int n_heads) {
+    return 2 * hnrf_render_workspace_bytes(rows, S) + (share ? 256 : 0) +
+           (n_heads ? align256((size_t)n_heads * (size_t)rows * (size_t)S * 16) : 0);
 }
-// + the n_heads raw planes of one chunk behind the two chunk workspaces (K3 and the K4s of a chunk run on `stream` in
-// order, so one set serves every chunk)
+extern "C" size_t hnrf_render_frame_workspace_bytes(int64_t chunk, int S) { return frame_ws_bytes(chunk, S, false, 0); }
+extern "C" size_t hnrf_render_frame_shared_workspace_bytes(int64_t chunk, int S) { return frame_ws_bytes(chunk, S, true, 0); }
 extern "C" size_t hnrf_render_frame_heads_workspace_bytes(int64_t chunk, int S, int n_heads) {
     if (chunk < 0 || S < 0 || n_heads < 2 || n_heads > 8) return 0;
-    return hnrf_render_frame_workspace_bytes(chunk, S) + align256((size_t)n_heads * (size_t)chunk * (size_t)S * 16);
+    return frame_ws_bytes(chunk, S, false, n_heads);
 }
 
 namespace {
+// What a frame entry asks for beside the plain frame.  Three types that do not convert into each other: a call site
+// that names them in the wrong order does not compile.  Shared inputs or heads, not both (the slot and the planes
+// start at the same byte behind the chunk workspaces).
+struct FrameOpts {
+    int* live_counts = nullptr;           // shared underflowing inputs: the live count of every chunk (null = off)
+    int n_heads = 0;                      // >= 2: every head of a multi-head canonical image, with
+    const FrameOut* head_out = nullptr;   // the whole-frame outputs of head g (head_out[0] is `out`)
+};
+
 int render_frame(const char* who, const Rays& rays, const WarpField& field, const float* hann_w, const void* nr_packed,
                  const BakedGrid& off, const CnlSource& cnl, const float* bgcolor, int mode, float cull_eps, int64_t N,
                  int S, int64_t chunk, void* workspace, size_t workspace_bytes, const FrameOut& out, void* side_stream,
-                 void* const* events, void* const* mlp_events, void* stream, int* live_counts = nullptr, int n_heads = 0,
-                 const FrameOut* head_out = nullptr) {
+                 void* const* events, void* const* mlp_events, void* stream, const FrameOpts& opt = {}) {
     HNRF_REQUIRE(workspace && out.rgb && out.alpha && out.depth, HNRF_E_ARG, "%s: null pointer", who);
     int src = check_source(who, cnl);
     if (src) return src;
@@ -246,22 +254,15 @@ int render_frame(const char* who, const Rays& rays, const WarpField& field, cons
     HNRF_REQUIRE(N >= 0 && chunk >= 1 && S >= 2, HNRF_E_ARG, "%s: bad dims", who);
     HNRF_REQUIRE(((uintptr_t)workspace & 255) == 0, HNRF_E_ARG, "%s: workspace must be 256-byte aligned", who);
     const int64_t cr = chunk < N ? chunk : (N > 0 ? N : 1);
-    const size_t ws_one = hnrf_render_workspace_bytes(cr, S);
-    HNRF_REQUIRE(workspace_bytes >= 2 * ws_one, HNRF_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who,
-                 workspace_bytes, 2 * ws_one);
+    const bool share = opt.live_counts != nullptr;
+    const size_t ws_one = hnrf_render_workspace_bytes(cr, S), ws_all = frame_ws_bytes(cr, S, share, opt.n_heads);
+    HNRF_REQUIRE(workspace_bytes >= ws_all, HNRF_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, ws_all);
     HNRF_REQUIRE(nr_packed == nullptr || hann_w != nullptr, HNRF_E_ARG, "%s: hann_w missing", who);
-    const size_t heads_bytes = n_heads ? align256((size_t)n_heads * (size_t)cr * (size_t)S * 16) : 0;
-    HNRF_REQUIRE(workspace_bytes >= 2 * ws_one + heads_bytes, HNRF_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who,
-                 workspace_bytes, 2 * ws_one + heads_bytes);
-    float* heads_raw = n_heads ? (float*)((char*)workspace + 2 * ws_one) : nullptr;
-    const bool share = live_counts != nullptr;
-    if (share) {
-        HNRF_REQUIRE((mode & HNRF_MLP_ARITH_MASK) == HNRF_MLP_F16X3 && nr_packed && cnl.packed && !cnl.grid && !off.grid &&
-                         cull_eps == 0.f, HNRF_E_UNSUPPORTED,
-                     "%s: shared inputs exist for HNRF_MLP_F16X3 with both MLPs and cull_eps == 0 only", who);
-        HNRF_REQUIRE(workspace_bytes >= 2 * ws_one + 256, HNRF_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who,
-                     workspace_bytes, 2 * ws_one + 256);
-    }
+    const int n_planes = opt.n_heads ? opt.n_heads : 1;
+    float* heads_raw = opt.n_heads ? (float*)((char*)workspace + 2 * ws_one) : nullptr;     // (null: the chunk's own raw)
+    HNRF_REQUIRE(!share || ((mode & HNRF_MLP_ARITH_MASK) == HNRF_MLP_F16X3 && nr_packed && cnl.packed && !cnl.grid &&
+                            !off.grid && cull_eps == 0.f), HNRF_E_UNSUPPORTED,
+                 "%s: shared inputs exist for HNRF_MLP_F16X3 with both MLPs and cull_eps == 0 only", who);
     const bool diag = out.weights != nullptr;
     HNRF_REQUIRE(!diag || (out.rgb_on_rays && out.cnl_xyz && out.cnl_rgb && out.cnl_weight && out.xyz && out.bmw &&
                            out.offsets), HNRF_E_ARG, "%s: the eight diagnostic outputs go together", who);
@@ -286,7 +287,7 @@ int render_frame(const char* who, const Rays& rays, const WarpField& field, cons
         Chunk k{R, rays.rows(r0, S), render_carve((char*)workspace + (size_t)(i & 1) * ws_one, R, S),
                 out.rows(r0, S, field.B), ShareOut{}};
         if (share)
-            k.sh = ShareOut{rep + 4, rep + 8, rep + 12, k.c.idx, live_counts + i, (float4*)k.c.raw, k.o.offsets, k.o.xyz};
+            k.sh = ShareOut{rep + 4, rep + 8, rep + 12, k.c.idx, opt.live_counts + i, (float4*)k.c.raw, k.o.offsets, k.o.xyz};
         return k;
     };
     auto warp = [&](int64_t i) {                                  // K1 of chunk i on the side stream
@@ -303,7 +304,7 @@ int render_frame(const char* who, const Rays& rays, const WarpField& field, cons
         // recorded behind that chunk's K4, the last reader of both.)
         const int rmode = mode & (HNRF_MLP_ARITH_MASK | HNRF_MLP_NO_RANGE_GUARD);
         HNRF_HIP(hipMemsetAsync(rep, 0, 64, st));
-        HNRF_HIP(hipMemsetAsync(live_counts, 0, (size_t)nchunk * sizeof(int), st));
+        HNRF_HIP(hipMemsetAsync(opt.live_counts, 0, (size_t)nchunk * sizeof(int), st));
         if ((rc = hnrf_nonrigid_fwd_sparse(rep, hann_w, nr_packed, rmode, 1, nullptr, nullptr, rep + 8, rep + 4, st))) return rc;
         if ((rc = hnrf_canonical_fwd_sparse(rep + 8, cnl.packed, rmode, 1, nullptr, nullptr, rep + 12, st))) return rc;
     }
@@ -329,12 +330,12 @@ int render_frame(const char* who, const Rays& rays, const WarpField& field, cons
         int cmode = mode & (HNRF_MLP_ARITH_MASK | HNRF_MLP_NO_RANGE_GUARD);
         if ((mode & HNRF_MLP_GUARD_ONE_CHUNK) && (int64_t)((unsigned)mode >> 16) % nchunk != i) cmode |= HNRF_MLP_NO_RANGE_GUARD;
         const Chunk k = chunk_at(i);
-        FrameOut ho[8];
-        for (int g = 0; g < n_heads; ++g) ho[g] = head_out[g].rows(i * chunk, S, field.B);
-        const HeadsOut hd{n_heads, heads_raw, ho};
-        if ((rc = render_chunk(k.c, k.rays.d, hann_w, nr_packed, off, cnl, bgcolor, cmode, cull_eps, k.R, S, k.o,
+        FrameOut po[8] = {k.o};                                   // the planes' rows of this chunk
+        for (int g = 1; g < n_planes; ++g) po[g] = opt.head_out[g].rows(i * chunk, S, field.B);
+        if ((rc = render_chunk(k.c, k.rays.d, hann_w, nr_packed, off, cnl, bgcolor, cmode, cull_eps, k.R, S,
+                               Planes{n_planes, heads_raw ? heads_raw : k.c.raw, po},
                                mlp_events ? mlp_events[2 * i] : nullptr, mlp_events ? mlp_events[2 * i + 1] : nullptr, st,
-                               Share{share ? &k.sh : nullptr, fused}, n_heads ? &hd : nullptr))) return rc;
+                               Share{share ? &k.sh : nullptr, fused}))) return rc;
         if (two) HNRF_HIP(hipEventRecord(ev_done[i & 1], st));
         if (!two && i + 1 < nchunk && (rc = warp(i + 1))) return rc;   // single stream: plain sequence
     }
@@ -390,7 +391,8 @@ extern "C" int hnrf_render_frame_heads_fwd(const float* rays_o, const float* ray
     return render_frame(who, Rays{rays_o, rays_d, near, far, t_rand},
                         WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, hann_w, nr_packed, kNoOffGrid,
                         CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor, mode, cull_eps, N, S, chunk,
-                        workspace, workspace_bytes, ho[0], side_stream, events, mlp_events, stream, nullptr, n_heads, ho);
+                        workspace, workspace_bytes, ho[0], side_stream, events, mlp_events, stream,
+                        FrameOpts{nullptr, n_heads, ho});
 }
 
 extern "C" int hnrf_render_frame_shared_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
@@ -410,7 +412,7 @@ extern "C" int hnrf_render_frame_shared_fwd(const float* rays_o, const float* ra
                         workspace, workspace_bytes,
                         FrameOut{rgb, alpha, depth, weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays,
                                  bmw, offsets},
-                        side_stream, events, mlp_events, stream, live_counts);
+                        side_stream, events, mlp_events, stream, FrameOpts{live_counts});
 }
 
 extern "C" int hnrf_render_frame_baked_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,

@@ -118,23 +118,30 @@ def nonrigid(x_skel, hann_w, packed, mode='f32', want_offsets=False, xyz_out=Non
     return xyz, offsets
 
 
-def canonical_pack(weights, biases, mode='f32', out=None):
-    """Pack pts_linears.{0..14} (8 layers) + output_linear.0."""
-    lib = _lib.load()
-    m = MLP_MODES[mode]
+def _canonical_pack(lib, weights, biases, m, out, n_heads=None):
+    """canonical_pack, and with ``n_heads`` canonical_heads_pack: the image of pts_linears.{0..14} (8 layers) +
+    output_linear.0, whose rows are the 4 outputs of the one head or of each of the ``n_heads``."""
     _chk(*weights, *biases)
     assert len(weights) == 9 and len(biases) == 9
-    shapes = [(256, 63)] + [(256, 256)] * 4 + [(256, 319)] + [(256, 256)] * 2 + [(4, 256)]
+    shapes = [(256, 63)] + [(256, 256)] * 4 + [(256, 319)] + [(256, 256)] * 2 + [(4 * (n_heads or 1), 256)]
     for w, b, s in zip(weights, biases, shapes):
         if tuple(w.shape) != s or b.numel() != s[0]:
-            raise _lib.HnrfError(f'canonical MLP layer shape {tuple(w.shape)} != {s}: only the default '
-                                 f'architecture (default.yaml:51-57) is built')
+            raise _lib.HnrfError(f'canonical MLP layer shape {tuple(w.shape)} != {s}: only the default architecture '
+                                 f'(default.yaml:51-57) {f"with {n_heads} heads of depth 1 " if n_heads else ""}is built')
     nbytes = lib.hnrf_canonical_packed_bytes(m)
     if out is None or out.numel() * 4 < nbytes:
         out = torch.empty((nbytes + 3) // 4, device=weights[0].device)
-    _lib.check(lib.hnrf_canonical_pack(_ptr_array(weights), _ptr_array(biases), m, _ptr(out), _stream()),
-               'hnrf_canonical_pack')
+    ptrs = _ptr_array(weights), _ptr_array(biases)
+    if n_heads:
+        _lib.check(lib.hnrf_canonical_heads_pack(*ptrs, n_heads, m, _ptr(out), _stream()), 'hnrf_canonical_heads_pack')
+    else:
+        _lib.check(lib.hnrf_canonical_pack(*ptrs, m, _ptr(out), _stream()), 'hnrf_canonical_pack')
     return out
+
+
+def canonical_pack(weights, biases, mode='f32', out=None):
+    """Pack pts_linears.{0..14} (8 layers) + output_linear.0."""
+    return _canonical_pack(_lib.load(), weights, biases, MLP_MODES[mode], out)
 
 
 def status_word(packed, which, mode):
@@ -319,29 +326,52 @@ def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, b
     of the samples per chunk that went through the MLPs, and the frame's sample count."""
     lib = _lib.load()
     _chk_baked_nr(baked, baked_nr)
-    N, S, B, G = rays_o.shape[0], int(n_samples), motion_Rs.shape[0], vol.shape[-1]
-    dev = rays_o.device
-    chunk = int(chunk)
     share = share_log is not None
     if share and (baked is not None or baked_nr is not None):
         raise _lib.HnrfError('render_frame: shared inputs exist with both MLPs only, not with a baked grid')
-    ws_bytes = lib.hnrf_render_frame_shared_workspace_bytes if share else lib.hnrf_render_frame_workspace_bytes
-    args, workspace = _render_args((rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
-                                    hann_w, nr_packed, cnl_packed, bgcolor), workspace,
-                                   ws_bytes(min(chunk, max(N, 1)), S))
-    out = {k: torch.empty((N,) + v, device=dev) for k, v in output_shapes(S, B, diagnostics).items()}
-    g = lambda k: _ptr(out.get(k))
-    side, ev_arr, mlp_arr, pairs = _frame_sync_args(dev, N, chunk, overlap, mlp_event_log is not None)
-    fn, name, ptrs = _render_entry(lib, 'frame', args, baked, baked_nr, share)
-    live = (torch.empty(max(1, -(-N // chunk)), dtype=torch.int32, device=dev),) if share else ()
-    _lib.check(fn(
-        *ptrs, _mode_arg(mode), float(cull_eps), N, S, B, G, chunk, _ptr(workspace),
-        workspace.numel() * workspace.element_size(), g('rgb'), g('alpha'), g('depth'),
-        g('weights_on_rays'), g('rgb_on_rays'), g('cnl_xyz'), g('cnl_rgb'), g('cnl_weight'), g('xyz_on_rays'),
-        g('backward_motion_weights'), g('offsets'), *map(_ptr, live), side.cuda_stream if side is not None else None,
-        ev_arr, mlp_arr, _stream()), name)
+    out, workspace, live = _frame_call(lib, (rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min,
+                                             bbox_scale, hann_w, nr_packed, cnl_packed, bgcolor), n_samples, chunk, mode,
+                                       diagnostics, cull_eps, workspace, overlap, mlp_event_log, baked, baked_nr, share)
     if share:
-        share_log.append((live[0], N * S))
+        share_log.append((live, rays_o.shape[0] * int(n_samples)))
+    return out, workspace
+
+
+HEAD_KEYS = ('rgb', 'alpha', 'depth', 'weights_on_rays', 'rgb_on_rays', 'cnl_xyz', 'cnl_rgb', 'cnl_weight')
+
+
+def _frame_call(lib, operands, n_samples, chunk, mode, diagnostics, cull_eps, workspace, overlap, mlp_event_log,
+                baked=None, baked_nr=None, share=False, n_heads=None):
+    """The one call of a frame entry, for render_frame and -- ``n_heads`` -- render_frame_heads: the workspace, the
+    whole-frame output tensors (with ``n_heads`` one allocation per HEAD_KEYS key, head-major: out[k][h] is a contiguous
+    whole-frame tensor), the stream and event arguments, the call, and what the side stream and the event log need
+    afterwards.  Returns (out, workspace, the live counts of ``share`` or None)."""
+    H = n_heads
+    N, S, B, G = operands[0].shape[0], int(n_samples), operands[5].shape[0], operands[7].shape[-1]
+    dev = operands[0].device
+    chunk = int(chunk)
+    rows = min(chunk, max(N, 1))
+    need = lib.hnrf_render_frame_heads_workspace_bytes(rows, S, H) if H else \
+        (lib.hnrf_render_frame_shared_workspace_bytes if share else lib.hnrf_render_frame_workspace_bytes)(rows, S)
+    args, workspace = _render_args(operands, workspace, need)
+    out = {k: torch.empty(((H, N) if H and k in HEAD_KEYS else (N,)) + v, device=dev)
+           for k, v in output_shapes(S, B, diagnostics).items()}
+
+    def ptr(k):             # (the heads entry takes the HEAD_KEYS as arrays of one pointer per head)
+        if H and k in HEAD_KEYS and k in out:
+            return (ctypes.c_void_p * H)(*[out[k][h].data_ptr() for h in range(H)])
+        return _ptr(out.get(k))
+
+    side, ev_arr, mlp_arr, pairs = _frame_sync_args(dev, N, chunk, overlap, mlp_event_log is not None)
+    if H:
+        fn, name, ptrs = lib.hnrf_render_frame_heads_fwd, 'hnrf_render_frame_heads_fwd', list(map(_ptr, args))
+    else:
+        fn, name, ptrs = _render_entry(lib, 'frame', args, baked, baked_nr, share)
+    live = torch.empty(max(1, -(-N // chunk)), dtype=torch.int32, device=dev) if share else None
+    _lib.check(fn(
+        *ptrs, _mode_arg(mode), float(cull_eps), N, S, B, G, chunk, *([H] if H else []), _ptr(workspace),
+        workspace.numel() * workspace.element_size(), *[ptr(k) for k in output_shapes(S, B)],
+        *([_ptr(live)] if share else []), side.cuda_stream if side is not None else None, ev_arr, mlp_arr, _stream()), name)
     if side is not None:
         # the side stream read the inputs and wrote backward_motion_weights / the workspace: keep the allocator from
         # handing those blocks out again before it is done (everything it did is also ordered on the main stream)
@@ -350,7 +380,7 @@ def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, b
                 t.record_stream(side)
     if mlp_event_log is not None:
         mlp_event_log.extend(pairs)
-    return out, workspace
+    return out, workspace, live
 
 
 def render_rays_term(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
@@ -677,19 +707,7 @@ def canonical_heads_pack(weights, biases, n_heads, mode='f32', out=None):
     is for canonical_heads / render_frame_heads only; a single head is packed by canonical_pack from its four rows."""
     lib = _lib.load_heads()
     m, H = MLP_MODES[mode], _chk_heads(n_heads)
-    _chk(*weights, *biases)
-    assert len(weights) == 9 and len(biases) == 9
-    shapes = [(256, 63)] + [(256, 256)] * 4 + [(256, 319)] + [(256, 256)] * 2 + [(4 * H, 256)]
-    for w, b, s in zip(weights, biases, shapes):
-        if tuple(w.shape) != s or b.numel() != s[0]:
-            raise _lib.HnrfError(f'canonical MLP layer shape {tuple(w.shape)} != {s}: only the default '
-                                 f'architecture (default.yaml:51-57) with {H} heads of depth 1 is built')
-    nbytes = lib.hnrf_canonical_packed_bytes(m)
-    if out is None or out.numel() * 4 < nbytes:
-        out = torch.empty((nbytes + 3) // 4, device=weights[0].device)
-    _lib.check(lib.hnrf_canonical_heads_pack(_ptr_array(weights), _ptr_array(biases), H, m, _ptr(out), _stream()),
-               'hnrf_canonical_heads_pack')
-    return out
+    return _canonical_pack(lib, weights, biases, m, out, H)
 
 
 def canonical_heads(xyz, packed, n_heads, mode='f32'):
@@ -716,9 +734,6 @@ def canonical_heads_sparse(xyz, packed, n_heads, idx, count, mode='f32', raw=Non
     return raw
 
 
-HEAD_KEYS = ('rgb', 'alpha', 'depth', 'weights_on_rays', 'rgb_on_rays', 'cnl_xyz', 'cnl_rgb', 'cnl_weight')
-
-
 def render_frame_heads(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w,
                        nr_packed, cnl_packed, bgcolor, n_samples, chunk, n_heads, mode='f16x3', diagnostics=True,
                        cull_eps=0.0, workspace=None, overlap=True, mlp_event_log=None):
@@ -727,31 +742,10 @@ def render_frame_heads(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, 
     whole-frame tensors, xyz_on_rays is the same tensor n_heads times, backward_motion_weights and offsets are tensors."""
     lib = _lib.load_heads()
     H = _chk_heads(n_heads)
-    N, S, B, G = rays_o.shape[0], int(n_samples), motion_Rs.shape[0], vol.shape[-1]
-    dev = rays_o.device
-    chunk = int(chunk)
-    args, workspace = _render_args((rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
-                                    hann_w, nr_packed, cnl_packed, bgcolor), workspace,
-                                   lib.hnrf_render_frame_heads_workspace_bytes(min(chunk, max(N, 1)), S, H))
-    shapes = output_shapes(S, B, diagnostics)
-    # one allocation per key, head-major: out[k][h] is a contiguous whole-frame tensor
-    stacked = {k: torch.empty((H, N) + shapes[k], device=dev) for k in HEAD_KEYS if k in shapes}
-    single = {k: torch.empty((N,) + v, device=dev) for k, v in shapes.items() if k not in HEAD_KEYS}
-    arr = lambda k: (ctypes.c_void_p * H)(*[stacked[k][h].data_ptr() for h in range(H)]) if k in stacked else None
-    side, ev_arr, mlp_arr, pairs = _frame_sync_args(dev, N, chunk, overlap, mlp_event_log is not None)
-    _lib.check(lib.hnrf_render_frame_heads_fwd(
-        *map(_ptr, args), _mode_arg(mode), float(cull_eps), N, S, B, G, chunk, H, _ptr(workspace),
-        workspace.numel() * workspace.element_size(), *[arr(k) for k in HEAD_KEYS], _ptr(single.get('xyz_on_rays')),
-        _ptr(single.get('backward_motion_weights')), _ptr(single.get('offsets')),
-        side.cuda_stream if side is not None else None, ev_arr, mlp_arr, _stream()), 'hnrf_render_frame_heads_fwd')
-    if side is not None:
-        for t in args[:10] + (workspace, single.get('backward_motion_weights')):      # (as in render_frame)
-            if t is not None:
-                t.record_stream(side)
-    if mlp_event_log is not None:
-        mlp_event_log.extend(pairs)
-    out = {k: list(v.unbind(0)) for k, v in stacked.items()}
-    out.update(single)
+    out, workspace, _ = _frame_call(lib, (rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
+                                          hann_w, nr_packed, cnl_packed, bgcolor), n_samples, chunk, mode, diagnostics,
+                                    cull_eps, workspace, overlap, mlp_event_log, n_heads=H)
+    out = {k: list(v.unbind(0)) if k in HEAD_KEYS else v for k, v in out.items()}
     if 'xyz_on_rays' in out:
         out['xyz_on_rays'] = [out['xyz_on_rays']] * H
     return out, workspace

@@ -31,6 +31,7 @@ video.merge_parts.
 With world > 1 every rank writes its own frames into the same folder; metrics are reduced by the caller
 (``MetricsWriter`` files are per rank: ``<folder>.rank<r>``).
 """
+import contextlib
 import os
 
 import numpy as np
@@ -55,6 +56,75 @@ class _Frames:
 
     def __getitem__(self, i):
         return self.make(i)
+
+
+def _sequence(subject, kind, load_image=True, device=None, test_num=-1, frame_idx=None, total_frames=None,
+              image_size=None, src_type='zju_mocap', numbered=False, square_tpose=False, prefix=''):
+    """(frames, names, default folder) of the ``kind`` = 'movement' | 'freeview' | 'tpose' sequence, for every loop below.
+    movement: the subject's first ``test_num`` frames (< 0: all) under their frame names, with their images (truth panel
+    and metrics; decoded for ``device``) or -- ``load_image`` False -- camera only at ``image_size`` / the image's own size.
+    freeview (freeview.py:172-280) and tpose (tpose.py): ``total_frames`` cameras (None: cfg.render_frames) on
+    cfg.bgcolor, like every non-train dataset the reference builds (create_dataset.py:40); names None, ``numbered``
+    '%06d'; ``src_type`` None: not handed on; ``square_tpose``: the T-pose camera gets the larger side of ``image_size``.
+    Default folder: ``prefix`` + movement / freeview_<frame_idx> / tpose; without a prefix cfg.render_folder_name goes
+    before the latter two."""
+    if kind == 'movement':
+        n = len(subject) if test_num < 0 else min(test_num, len(subject))
+        if load_image:
+            # camera-only rays: they come from the device generator, the truth pixels are picked on the device (the
+            # prefetcher thread of render_frames builds them: PNG decoding on the host, undistortion / composite / resize
+            # on the device when there is one)
+            make = lambda i: subject.movement_frame(i, load_image=True, device=device)
+        else:
+            size = lambda i: image_size if image_size is not None else subject.image_size(subject.framelist[i])
+            make = lambda i: subject.movement_frame(i, image_size=size(i))
+        return _Frames(n, make), [str(subject.framelist[i]).replace('/', '-') for i in range(n)], prefix + 'movement'
+    n = int(cfg.get('render_frames', 100)) if total_frames is None else int(total_frames)
+    if kind == 'freeview':
+        frame_idx = int(cfg.get('freeview', {}).get('frame_idx', 0)) if frame_idx is None else int(frame_idx)
+        if image_size is None:
+            image_size = subject.image_size(subject.framelist_all[frame_idx])
+        src = {} if src_type is None else {'src_type': src_type}
+        make = lambda i: subject.freeview_frame(i, n, train_frame_idx=frame_idx, image_size=image_size,
+                                                bgcolor=cfg.bgcolor, **src)
+        folder = 'freeview_%d' % frame_idx
+    else:
+        size = int(np.max(image_size)) if square_tpose and image_size is not None else image_size
+        make = lambda i: subject.tpose_frame(i, n, image_size=size, bgcolor=cfg.bgcolor)
+        folder = 'tpose'
+    folder = prefix + folder if prefix else cfg.get('render_folder_name', '') or folder
+    return _Frames(n, make), ['%06d' % i for i in range(n)] if numbered else [None] * n, folder
+
+
+_CFG_KEYS = ('perturb', 'ignore_non_rigid_motions', 'show_truth')
+
+
+@contextlib.contextmanager
+def _cfg_override(**values):
+    """cfg.perturb, cfg.ignore_non_rigid_motions, cfg.show_truth and ``diagnostics`` (cfg.amd['diagnostics']) set for the
+    block and put back behind it, an exception included.  An amd key that was not there is popped again (show_truth comes
+    back as False); without an amd node ``diagnostics`` does nothing."""
+    amd = cfg.get('amd', None)
+    if 'diagnostics' in values and amd is None:
+        del values['diagnostics']
+    assert set(values) <= set(_CFG_KEYS + ('diagnostics',)), sorted(values)
+    had_diag = 'diagnostics' in values and 'diagnostics' in amd
+    old = {k: amd.get(k) if k == 'diagnostics' else cfg.get(k, False) for k in values}
+    try:
+        for k, v in values.items():
+            if k == 'diagnostics':
+                amd[k] = v
+            else:
+                setattr(cfg, k, v)
+        yield
+    finally:
+        for k, v in old.items():
+            if k != 'diagnostics':
+                setattr(cfg, k, v)
+            elif had_diag:
+                amd[k] = v
+            else:
+                amd.pop(k, None)
 
 
 def _panels(rgb8, alpha8, truth8=None):
@@ -148,13 +218,9 @@ def _render_loop(network, frames, names, folder, logdir, rank, world, device, me
     if metrics is not None and on_device:
         extra.update(metrics=metrics.metrics, lpips_fn=lpips_fn,
                      on_metrics=lambda i, values: metrics.append_values(names[i], values))
-    old = cfg.perturb
-    cfg.perturb = 0.                                                   # run.py:71, 214
-    try:
+    with _cfg_override(perturb=0.):                                    # run.py:71, 214 (render_frames zeroes it as well)
         images = render.render_frames(network, frames, rank=rank, world=world, device=device, on_image=on_image,
                                       show_truth=True, **extra)
-    finally:
-        cfg.perturb = old
     stack = writer.finalize() if writer is not None else None
     averages = metrics.finalize() if metrics is not None else None
     result = {'frames': own, 'images': images, 'image_dir': os.path.join(out_dir, folder), 'stack': stack,
@@ -176,13 +242,8 @@ def run_movement(network, subject, render_folder_name='movement', logdir=None, r
     on_device = amd_option('metrics', 'host') == 'device'
     if on_device and device.type != 'cuda':
         raise ValueError("cfg.amd.metrics = 'device' needs a GPU, got device %s" % device)
-    cfg.show_truth = True
-    n = len(subject) if test_num < 0 else min(test_num, len(subject))
-    # camera-only frames: rays come from the device generator, the truth pixels are picked on the device
-    # (the prefetcher thread of render_frames builds them: PNG decoding on the host, undistortion / composite / resize on
-    # the device when there is one)
-    frames = _Frames(n, lambda i: subject.movement_frame(i, load_image=True, device=device))
-    names = [str(subject.framelist[i]).replace('/', '-') for i in range(n)]
+    cfg.show_truth = True                       # lasting, not an override: the reference's run.py:216 leaves it set too
+    frames, names, _ = _sequence(subject, 'movement', device=device, test_num=test_num)
     render_folder_name = _baked_folder(network, subject, render_folder_name)
     suffix = '' if world == 1 else '.rank%d' % rank
     mw = render.MetricsWriter(_output_dir(logdir), render_folder_name + suffix, dataset=subject.dataset_path,
@@ -194,33 +255,22 @@ def run_movement(network, subject, render_folder_name='movement', logdir=None, r
 def run_freeview(network, subject, frame_idx=None, total_frames=None, render_folder_name=None, logdir=None, rank=0,
                  world=1, device=None, image_size=None, src_type='zju_mocap'):
     """run.py:67-176 with data_type 'freeview' (freeview.py:172-280)."""
-    frame_idx = int(cfg.get('freeview', {}).get('frame_idx', 0)) if frame_idx is None else int(frame_idx)
-    total = int(cfg.get('render_frames', 100)) if total_frames is None else int(total_frames)
-    if image_size is None:
-        image_size = subject.image_size(subject.framelist_all[frame_idx])
-    # background: cfg.bgcolor, like every non-train dataset the reference builds (create_dataset.py:40)
-    frames = _Frames(total, lambda i: subject.freeview_frame(i, total, train_frame_idx=frame_idx, src_type=src_type,
-                                                             image_size=image_size, bgcolor=cfg.bgcolor))
-    folder = render_folder_name or cfg.get('render_folder_name', '') or 'freeview_%d' % frame_idx
-    folder = _baked_folder(network, subject, folder)
-    return _render_loop(network, frames, [None] * total if world == 1 else ['%06d' % i for i in range(total)], folder,
-                        logdir, rank, world, device)
+    # numbered: with world > 1 the frames are named %06d, else None (ImageWriter then numbers what it is given)
+    frames, names, folder = _sequence(subject, 'freeview', frame_idx=frame_idx, total_frames=total_frames,
+                                      image_size=image_size, src_type=src_type, numbered=world > 1)
+    folder = _baked_folder(network, subject, render_folder_name or folder)
+    return _render_loop(network, frames, names, folder, logdir, rank, world, device)
 
 
 def run_tpose(network, subject, total_frames=None, render_folder_name=None, logdir=None, rank=0, world=1, device=None,
               image_size=None):
     """run.py:178-183: the turntable of tpose.py with cfg.ignore_non_rigid_motions = True."""
-    total = int(cfg.get('render_frames', 100)) if total_frames is None else int(total_frames)
-    frames = _Frames(total, lambda i: subject.tpose_frame(i, total, image_size=image_size, bgcolor=cfg.bgcolor))
-    old = cfg.ignore_non_rigid_motions
-    cfg.ignore_non_rigid_motions = True
-    try:
-        folder = render_folder_name or cfg.get('render_folder_name', '') or 'tpose'
-        folder = _baked_folder(network, subject, folder)
-        return _render_loop(network, frames, [None] * total if world == 1 else ['%06d' % i for i in range(total)],
-                            folder, logdir, rank, world, device)
-    finally:
-        cfg.ignore_non_rigid_motions = old
+    # numbered: with world > 1 the frames are named %06d, else None (as in run_freeview)
+    frames, names, folder = _sequence(subject, 'tpose', total_frames=total_frames, image_size=image_size,
+                                      numbered=world > 1)
+    with _cfg_override(ignore_non_rigid_motions=True):
+        folder = _baked_folder(network, subject, render_folder_name or folder)
+        return _render_loop(network, frames, names, folder, logdir, rank, world, device)
 
 
 def run_heads(network, subject, kind='movement', frame_idx=None, total_frames=None, render_folder_name=None, logdir=None,
@@ -249,34 +299,19 @@ def run_heads(network, subject, kind='movement', frame_idx=None, total_frames=No
     if kind not in ('movement', 'freeview', 'tpose'):
         raise ValueError("run_heads: kind must be 'movement', 'freeview' or 'tpose', got %r" % (kind,))
     device = device or next(network.parameters()).device
-    keep = cfg.perturb, cfg.ignore_non_rigid_motions, cfg.get('show_truth', False)
-    if kind == 'movement':
-        cfg.show_truth = True
-        n = len(subject) if test_num < 0 else min(test_num, len(subject))
-        frames = _Frames(n, lambda i: subject.movement_frame(i, load_image=True, device=device))
-        names = [str(subject.framelist[i]).replace('/', '-') for i in range(n)]
-        folder = render_folder_name or 'movement'
-    elif kind == 'freeview':
-        frame_idx = int(cfg.get('freeview', {}).get('frame_idx', 0)) if frame_idx is None else int(frame_idx)
-        n = int(cfg.get('render_frames', 100)) if total_frames is None else int(total_frames)
-        size = image_size if image_size is not None else subject.image_size(subject.framelist_all[frame_idx])
-        frames = _Frames(n, lambda i: subject.freeview_frame(i, n, train_frame_idx=frame_idx, src_type=src_type,
-                                                             image_size=size, bgcolor=cfg.bgcolor))
-        names = [None] * n
-        folder = render_folder_name or cfg.get('render_folder_name', '') or 'freeview_%d' % frame_idx
-    else:
-        n = int(cfg.get('render_frames', 100)) if total_frames is None else int(total_frames)
-        frames = _Frames(n, lambda i: subject.tpose_frame(i, n, image_size=image_size, bgcolor=cfg.bgcolor))
-        names = [None] * n
-        folder = render_folder_name or cfg.get('render_folder_name', '') or 'tpose'
-        cfg.ignore_non_rigid_motions = True
+    frames, names, folder = _sequence(subject, kind, device=device, test_num=test_num, frame_idx=frame_idx,
+                                      total_frames=total_frames, image_size=image_size, src_type=src_type)
+    folder, n = render_folder_name or folder, len(frames)
+    # perturb: run.py:71, 214.  All three are put back behind the loop whatever the kind sets -- show_truth too, unlike
+    # run_movement's, and as False where cfg had none
+    override = dict(perturb=0., show_truth=kind == 'movement' or cfg.get('show_truth', False),
+                    ignore_non_rigid_motions=kind == 'tpose' or cfg.ignore_non_rigid_motions)
     out_dirs = [_output_dir(logdir) + '_h%d' % h for h in range(H)]
     writers = [render.ImageWriter(d, folder) for d in out_dirs]
     mws = [render.MetricsWriter(d, folder, dataset=subject.dataset_path, metrics=metrics, lpips_fn=lpips_fn)
            for d in out_dirs] if kind == 'movement' else None
     outbox = render.FrameOutbox(device)
     network.eval()
-    cfg.perturb = 0.                                                     # run.py:71, 214
 
     def render_item(item):
         with torch.no_grad():
@@ -290,7 +325,7 @@ def run_heads(network, subject, kind='movement', frame_idx=None, total_frames=No
         return outbox.post(imgs), item['truth'] is not None
 
     pre = render.FramePrefetcher(frames, list(range(n)), device, show_truth=kind == 'movement')
-    try:
+    with _cfg_override(**override), contextlib.closing(pre):
         for item in pre:
             mode = network._mlp_mode()
             parcel, has_truth = render_item(item)
@@ -306,9 +341,6 @@ def run_heads(network, subject, kind='movement', frame_idx=None, total_frames=No
                 writers[h].append(_panels(rgb8, alpha8, truth8), img_name=names[i])
                 if mws is not None and truth8 is not None:
                     mws[h].append(name=names[i], pred=rgb8, target=truth8, mask=None)
-    finally:
-        pre.close()
-        cfg.perturb, cfg.ignore_non_rigid_motions, cfg.show_truth = keep
     return [{'image_dir': os.path.join(out_dirs[h], folder), 'stack': writers[h].finalize(),
              'metrics': mws[h].finalize() if mws is not None else None} for h in range(H)]
 
@@ -352,27 +384,14 @@ def run_mesh_render(network, subject, kind='movement', resolution=256, level=Non
     verts, faces, colors = network.extract_canonical_mesh(
         bbox['min_xyz'], bbox['max_xyz'], subject.motion_weights_priors, resolution=resolution,
         level=network.MESH_LEVEL if level is None else level)
-    if kind == 'movement':
-        n = len(subject) if test_num < 0 else min(test_num, len(subject))
-        size = lambda i: image_size if image_size is not None else subject.image_size(subject.framelist[i])
-        frames = _Frames(n, lambda i: subject.movement_frame(i, image_size=size(i)))
-        names = [str(subject.framelist[i]).replace('/', '-') for i in range(n)]
-        folder = render_folder_name or 'mesh_movement'
-    elif kind == 'freeview':
-        frame_idx = int(cfg.get('freeview', {}).get('frame_idx', 0)) if frame_idx is None else int(frame_idx)
-        n = int(cfg.get('render_frames', 100)) if total_frames is None else int(total_frames)
-        if image_size is None:
-            image_size = subject.image_size(subject.framelist_all[frame_idx])
-        frames = _Frames(n, lambda i: subject.freeview_frame(i, n, train_frame_idx=frame_idx, image_size=image_size,
-                                                             bgcolor=cfg.bgcolor))
-        names = [None] * n
-        folder = render_folder_name or 'mesh_freeview_%d' % frame_idx
-    else:
-        n = int(cfg.get('render_frames', 100)) if total_frames is None else int(total_frames)
-        size = None if image_size is None else int(np.max(image_size))           # (the T-pose camera is square)
-        frames = _Frames(n, lambda i: subject.tpose_frame(i, n, image_size=size, bgcolor=cfg.bgcolor))
-        names = [None] * n
-        folder = render_folder_name or 'mesh_tpose'
+    # load_image=False: the movement frames carry image_size= and no image
+    # src_type=None: freeview_frame is called without src_type (its own default)
+    # square_tpose: the T-pose size is int(np.max(image_size)); the volume loops pass image_size through
+    # prefix: mesh_<...> folders, which cfg.render_folder_name does not rename
+    frames, names, folder = _sequence(subject, kind, load_image=False, test_num=test_num, frame_idx=frame_idx,
+                                      total_frames=total_frames, image_size=image_size, src_type=None,
+                                      square_tpose=True, prefix='mesh_')
+    folder, n = render_folder_name or folder, len(frames)
     device = verts.device
     vout = _VideoOut(os.path.join(_output_dir(logdir), folder), names, 0, 1, device)
     writer = None if vout.only else render.ImageWriter(_output_dir(logdir), folder)
@@ -427,30 +446,17 @@ def run_surface_points(network, subject, weight_threshold=None, render_folder_na
     device = device or next(network.parameters()).device
     if weight_threshold is None:
         weight_threshold = (cfg.get('test', None) or {}).get('weight_threshold', 0.3)
-    n = len(subject) if test_num < 0 else min(test_num, len(subject))
-    frames = _Frames(n, lambda i: subject.movement_frame(i, load_image=True, device=device))
-    own = list(range(rank, n, world))
+    frames, _, _ = _sequence(subject, 'movement', device=device, test_num=test_num)
+    own = list(range(rank, len(frames), world))
     writer = render.ImageWriter(_output_dir(logdir), render_folder_name, workers=1, keep_frames=False)
-    amd = cfg.get('amd', None)
-    old_perturb, had_diag, old_diag = cfg.perturb, amd is not None and 'diagnostics' in amd, (amd or {}).get('diagnostics')
-    cfg.perturb = 0.                                                   # run.py:214
-    if amd is not None:
-        amd['diagnostics'] = True
     network.eval()
     pre = render.FramePrefetcher(frames, own, device, show_truth=True)
-    try:
+    with _cfg_override(perturb=0., diagnostics=True), contextlib.closing(pre):          # perturb: run.py:214
         for item in pre:
             with torch.no_grad():
                 out = network(**item['data'], iter_val=float(cfg.eval_iter))
             rec = cloud.surface_records(out, item['truth'], item['ray_index'], item['W'], weight_threshold)
             writer.append_3d_together(str(subject.framelist[item['idx']]), rec)
-    finally:
-        pre.close()
-        cfg.perturb = old_perturb
-        if had_diag:
-            amd['diagnostics'] = old_diag
-        elif amd is not None:
-            amd.pop('diagnostics', None)
     records = dict(writer.name_3d_together)
     writer.finalize()
     path = getattr(writer, 'path_3d_together', None)
@@ -477,22 +483,13 @@ def run_compare_lbs_delta(network, subject, logdir=None, rank=0, world=1, device
     if device.type != 'cuda':
         raise ValueError('run_compare_lbs_delta: the offset map needs a GPU, got device %s' % device)
     on_device = amd_option('metrics', 'host') == 'device'
-    n = len(subject) if test_num < 0 else min(test_num, len(subject))
-    frames = _Frames(n, lambda i: subject.movement_frame(i, load_image=True, device=device))
-    names = [str(subject.framelist[i]).replace('/', '-') for i in range(n)]
+    frames, names, _ = _sequence(subject, 'movement', device=device, test_num=test_num)
     out_dir = _output_dir(logdir)
     suffix = '' if world == 1 else '.rank%d' % rank
-    amd = cfg.get('amd', None)
-    had_diag, old_diag = amd is not None and 'diagnostics' in amd, (amd or {}).get('diagnostics')
-    old_nr, old_truth = cfg.ignore_non_rigid_motions, cfg.get('show_truth', False)
-    if amd is not None:
-        amd['diagnostics'] = True
-    cfg.show_truth = True
     imgs = {'lbs': {}, 'full': {}}                  # frame -> (render, truth) / -> offset panel
     offset, scores = {}, {}
-    try:
+    with _cfg_override(diagnostics=True, show_truth=True):          # show_truth is put back, unlike run_movement's
         for tag, flag in (('lbs', True), ('full', False)):
-            cfg.ignore_non_rigid_motions = flag
             mw = render.MetricsWriter(os.path.join(out_dir, 'cmp_lbs_delta'), 'movement_%s%s' % (tag, suffix),
                                       dataset=subject.dataset_path, metrics=['psnr'])
 
@@ -506,17 +503,11 @@ def run_compare_lbs_delta(network, subject, logdir=None, rank=0, world=1, device
                 extra.update(metrics=['psnr'], on_metrics=lambda i, v, mw=mw: mw.append_values(names[i], v))
             if not flag:
                 extra.update(maps=['offset'], on_maps=lambda i, panels: offset.__setitem__(i, panels['offset']))
-            render.render_frames(network, frames, rank=rank, world=world, device=device, on_image=on_image,
-                                 show_truth=True, **extra)
+            with _cfg_override(ignore_non_rigid_motions=flag):
+                render.render_frames(network, frames, rank=rank, world=world, device=device, on_image=on_image,
+                                     show_truth=True, **extra)
             mw.finalize()
             scores[tag] = {k: v['psnr'] for k, v in mw.name2metrics.items()}
-    finally:
-        cfg.ignore_non_rigid_motions = old_nr
-        cfg.show_truth = old_truth
-        if had_diag:
-            amd['diagnostics'] = old_diag
-        elif amd is not None:
-            amd.pop('diagnostics', None)
     writer = render.ImageWriter(out_dir, os.path.join('cmp_lbs_delta', 'movement'), keep_frames=False)
     own = sorted(imgs['full'])
     paths = []
