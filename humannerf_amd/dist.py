@@ -11,6 +11,8 @@
 The reference has no distributed code at all (its only mechanism is
 nn.DataParallel over the two MLPs, network.py:68-72,115-119).
 """
+import weakref
+
 import torch
 import torch.distributed as dist
 
@@ -34,6 +36,14 @@ def gather_frames(local, n_frames, rank, world, dst=0):
     for d in objs:
         merged.update(d)
     return [merged[i] for i in range(n_frames)]
+
+
+def _weights_changed(network):
+    """The collectives write through ``.data``, which no version counter sees: tell a Network (weights_changed) that
+    what it keeps from frame to frame is out of date.  Other modules keep nothing."""
+    changed = getattr(network, 'weights_changed', None)
+    if changed is not None:
+        changed()
 
 
 class _MeanAllReduceGrad(torch.autograd.Function):
@@ -87,6 +97,7 @@ class GradientSync:
         # insurance against replicas drifting apart over 400 k iterations the decoder parameters are re-broadcast from
         # rank 0 every ``resync_every`` steps (254 MB / 1000 steps)
         self.resync_every, self.steps = int(resync_every), 0
+        self._network = weakref.ref(network)
         named = [(n, p) for n, p in network.named_parameters() if p.requires_grad]
         self.decoder = [p for n, p in named if 'mweight_vol_decoder' in n]
         self.small = [p for n, p in named if 'mweight_vol_decoder' not in n]
@@ -107,6 +118,7 @@ class GradientSync:
         with torch.no_grad():
             for t in list(network.parameters()) + list(network.buffers()):
                 dist.broadcast(t.data, src=src, group=self.group)
+        _weights_changed(network)
 
     # -- backward-time hook -------------------------------------------------------------------------------
     def volume_hook(self, vol, priors=None):
@@ -129,6 +141,7 @@ class GradientSync:
         if self.mode == 'volume' and self.resync_every > 0 and self.steps % self.resync_every == 0:
             for p in self.decoder:
                 dist.broadcast(p.data, src=0, group=self.group)
+            _weights_changed(self._network())
         for bi, bucket in enumerate(self.buckets):
             have = [p for p in bucket if p.grad is not None]
             n = sum(p.numel() for p in bucket)

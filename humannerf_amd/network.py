@@ -432,21 +432,33 @@ def hann_window_weights(iter_val, multires, kick_in_iter, full_band_iter):
     return (1. - torch.cos(math.pi * torch.clamp(alpha - k, min=0., max=1.))) / 2.
 
 
-def _versions(params):
-    return tuple((p.data_ptr(), p._version) for p in params)
-
-
 def _resident(tensors):
-    """What _still_resident recognises ``tensors`` by later: a weak reference and the ``_version`` of each."""
-    return tuple((weakref.ref(t), t._version) for t in tensors)
+    """What _still_resident recognises ``tensors`` by later: a weak reference, the ``data_ptr`` and the ``_version`` of
+    each.  THE rule of everything a Network keeps from frame to frame, for the frame's inputs (priors, bbox,
+    dst_posevec) and for the parameters alike:
+
+    * the weak reference is the identity: another object never matches, not even one that the allocator placed on the
+      freed address of the old one with an equal version counter (a replaced nn.Parameter), and a collected object can
+      never match again;
+    * ``data_ptr`` sees ``t.data = other`` and a move between devices, which leave object and counter alone;
+    * ``_version`` sees every in-place write autograd knows of: ``t.copy_()``, ``t.mul_()``, foreach ops on the
+      tensors themselves, torch's optimizers in their foreach and single-tensor forms, GroupedAdam.
+
+    What none of the three sees is a write through ``t.data`` / ``t.detach()`` (``p.data.copy_()``,
+    ``p.data[i] = v``, ``dist.broadcast(p.data)``, optimizers that update through detached views): for the parameters
+    that is Network.weights_changed(), which load_state_dict and a move of the module call themselves and whose effect
+    a train-path forward has (Network._weights_gen); for a frame's inputs the rule is to pass a fresh tensor, or to
+    write the tensor itself."""
+    return tuple((weakref.ref(t), t.data_ptr(), t._version) for t in tensors)
 
 
 def _still_resident(refs, tensors):
-    """True when ``tensors`` are the very objects ``refs`` = _resident(...) was built from, unwritten since: a driver
-    that keeps its per-subject tensors on the device hits without a look at their values, i.e. without a host
-    synchronisation.  Equal values in other objects do not count: the caller compares those once, or not at all."""
+    """True when ``tensors`` are the very objects ``refs`` = _resident(...) was built from, on the same memory and
+    unwritten since: a driver that keeps its per-subject tensors on the device hits without a look at their values,
+    i.e. without a host synchronisation.  Equal values in other objects do not count: the caller compares those once,
+    or not at all."""
     return refs is not None and len(refs) == len(tensors) \
-        and all(r() is t and v == t._version for (r, v), t in zip(refs, tensors))
+        and all(r() is t and ptr == t.data_ptr() and v == t._version for (r, ptr, v), t in zip(refs, tensors))
 
 
 def _vec3(a, dev):
@@ -543,8 +555,14 @@ class Network(nn.Module):
             self.pose_decoder = BodyPoseRefiner(
                 embedding_size=cfg.pose_decoder.embedding_size, mlp_width=cfg.pose_decoder.mlp_width,
                 mlp_depth=cfg.pose_decoder.mlp_depth, total_bones=cfg.total_bones)
-        self._cnl_pack = None     # (key, packed image)
-        # multi-head: head -> (key, packed image), -1 = the all-heads image; _cnl_pack is the entry used last.  The head
+        # Weight-keyed entries carry _resident(their parameters) next to a key of plain values (mode, head, resolution):
+        # weights_changed() drops them all.
+        self._cnl_pack = None     # (key, packed image, _resident(weights), serial number of the pack)
+        self._pack_serial = 0
+        # counts the train-path forwards: in every key, so that an entry built before one is out of date after it (it
+        # stays where it is, its buffers are used again)
+        self._weights_gen = 0
+        # multi-head: head -> such an entry, -1 = the all-heads image; _cnl_pack is the entry used last.  The head
         # that _canonical_packed() packs outside forward (select_head), None = not chosen; the last device tensor read
         # as a head_id (tensor, _version, value)
         self._cnl_head_packs = {}
@@ -552,13 +570,13 @@ class Network(nn.Module):
         self._head_id_seen = None
         self._nr_pack_buf = None
         self.f16_guard = InferenceRangeGuard()
-        self._vol_cache = None    # (key, priors, volume, _resident((priors,)))
-        # baked canonical grid (cfg.amd.canonical = 'baked'): dict(grid, bmin, bmax, key, injected, refs) or None;
-        # bake_count counts the bakes this network ran
+        self._vol_cache = None    # (_resident(decoder parameters), priors, volume, _resident((priors,)), _weights_gen)
+        # baked canonical grid (cfg.amd.canonical = 'baked'): dict(grid, bmin, bmax, key, weights, injected, refs) or
+        # None; bake_count counts the bakes this network ran
         self._baked = None
         self.bake_count = 0
         # baked non-rigid offset field of the current frame (cfg.amd.nonrigid = 'baked'): dict(grid, bmin, bmax, packed,
-        # key, refs) or None, the resident workspace of the bake, and the number of bakes this network ran
+        # key, weights, refs) or None, the resident workspace of the bake, and the number of bakes this network ran
         self._baked_nr = None
         self._nr_bake_ws = None
         self.nonrigid_bake_count = 0
@@ -578,6 +596,36 @@ class Network(nn.Module):
         return self
 
     # packed-weight caches ----------------------------------------------------
+    def weights_changed(self):
+        """Drop everything derived from the parameters -- the packed canonical images, the decoded weight volume, the
+        baked canonical grid (an injected one stays: set_baked_grid) and the frame's offset grid -- and restart the
+        f16-range guard's audit schedule: the next frame rebuilds from the parameters as they are then.  THE call after
+        any write the entries cannot see by themselves (_resident: writes through ``p.data`` / ``p.detach()``, e.g.
+        ``p.data.copy_()``, ``dist.broadcast(p.data)``, an optimizer that steps through detached views).
+        load_state_dict and every move / cast of the module (``to``, ``cpu``, ``cuda``, ``float``) call it themselves; a
+        train-path forward marks the entries out of date to the same effect (_weights_gen).  Host only: no device work,
+        no synchronisation."""
+        self._cnl_pack = None
+        self._cnl_head_packs.clear()
+        self._vol_cache = None
+        if self._baked is not None and not self._baked['injected']:
+            self._baked = None
+        self._baked_nr = None
+        self.f16_guard.restart_schedule()
+        return self
+
+    def load_state_dict(self, *args, **kwargs):
+        try:
+            return super().load_state_dict(*args, **kwargs)
+        finally:
+            self.weights_changed()               # (also after a load that raised half way)
+
+    def _apply(self, fn, *args, **kwargs):
+        try:
+            return super()._apply(fn, *args, **kwargs)
+        finally:
+            self.weights_changed()               # (a move frees the old storage: its address may come back)
+
     def _mlp_mode(self):
         return self.f16_guard.mode()
 
@@ -652,12 +700,16 @@ class Network(nn.Module):
         ws, bs = [l.weight for l in lin], [l.bias for l in lin]
         if self.head_num:
             return self._canonical_packed_head(ws, bs)
-        key = (self._mlp_mode(),) + _versions(ws + bs)
-        if self._cnl_pack is None or self._cnl_pack[0] != key:
+        key, ent = (self._mlp_mode(), self._weights_gen), self._cnl_pack
+        if ent is None or ent[0] != key or not _still_resident(ent[2], ws + bs):
             packed = ops.canonical_pack([w.detach() for w in ws], [b.detach() for b in bs], self._mlp_mode(),
-                                        out=None if self._cnl_pack is None else self._cnl_pack[1])
-            self._cnl_pack = (key, packed)
+                                        out=None if ent is None else ent[1])
+            self._cnl_pack = self._packed_entry(key, packed, ws + bs)
         return self._cnl_pack[1]
+
+    def _packed_entry(self, key, packed, params):
+        self._pack_serial += 1
+        return (key, packed, _resident(params), self._pack_serial)
 
     def _canonical_packed_head(self, ws, bs):
         """The image of the selected head (ops.canonical_pack on its four rows), or with head -1 the all-heads image
@@ -667,9 +719,9 @@ class Network(nn.Module):
             raise RuntimeError('multi-head canonical MLP (%d heads): call select_head(h) before evaluating it outside '
                                'forward (no head is used silently)' % self.head_num)
         mode = self._mlp_mode()
-        key = (mode, h) + _versions(ws + bs)
+        key = (mode, h, self._weights_gen)
         ent = self._cnl_head_packs.get(h)
-        if ent is None or ent[0] != key:
+        if ent is None or ent[0] != key or not _still_resident(ent[2], ws + bs):
             W, B = [w.detach() for w in ws], [b.detach() for b in bs]
             buf = None if ent is None else ent[1]
             if h < 0:
@@ -677,7 +729,7 @@ class Network(nn.Module):
             else:
                 W[8], B[8] = W[8][4 * h:4 * h + 4], B[8][4 * h:4 * h + 4]        # (whole rows: contiguous views)
                 packed = ops.canonical_pack(W, B, mode, out=buf)
-            ent = self._cnl_head_packs[h] = (key, packed)
+            ent = self._cnl_head_packs[h] = self._packed_entry(key, packed, ws + bs)
         self._cnl_pack = ent
         return ent[1]
 
@@ -691,8 +743,8 @@ class Network(nn.Module):
         """(B+1,G,G,G) softmax volume; cached across frames in eval mode."""
         params = list(self.mweight_vol_decoder.parameters())
         use_cache = (not self.training) and (not torch.is_grad_enabled()) and amd_option('cache_weight_volume', True)
-        key = _versions(params)
-        if use_cache and self._vol_cache is not None and self._vol_cache[0] == key \
+        if use_cache and self._vol_cache is not None and self._vol_cache[4] == self._weights_gen \
+                and _still_resident(self._vol_cache[0], params) \
                 and self._vol_cache[1].shape == priors.shape:
             # same tensor object as last frame (a driver that keeps the priors resident): no comparison, no host
             # synchronisation; a fresh tensor is compared by value (one device round trip per frame)
@@ -701,11 +753,11 @@ class Network(nn.Module):
             if torch.equal(self._vol_cache[1], priors):
                 # equal by value: remember THIS tensor, so that the frames that follow hit by identity (a render loop
                 # uploads the subject's priors once per loop; comparing every frame blocked the host for a whole frame)
-                self._vol_cache = self._vol_cache[:3] + (_resident((priors,)),)
+                self._vol_cache = self._vol_cache[:3] + (_resident((priors,)), self._weights_gen)
                 return self._vol_cache[2]
         vol = self.mweight_vol_decoder(motion_weights_priors=priors[None])[0].contiguous()
         if use_cache:
-            self._vol_cache = (key, priors.clone(), vol, _resident((priors,)))
+            self._vol_cache = (_resident(params), priors.clone(), vol, _resident((priors,)), self._weights_gen)
         return vol
 
     # forward -------------------------------------------------------------------
@@ -754,6 +806,10 @@ class Network(nn.Module):
     def _forward(self, rays, dst_Rs, dst_Ts, cnl_gtfms, motion_weights_priors, dst_posevec, near, far, iter_val,
                  cnl_bbox_min_xyz, cnl_bbox_scale_xyz, bgcolor, t_rand, **kwargs):
         train_path = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if train_path:
+            # a step follows, by whatever optimizer (torch's fused Adam leaves the version counters alone): the next
+            # inference frame rebuilds everything derived from the weights
+            self._weights_gen += 1
         all_heads = self.head_num and self._head == -1
         if self.head_num and train_path:
             raise NotImplementedError('multi-head canonical MLP: inference only (the training kernels have one head; '
@@ -851,7 +907,7 @@ class Network(nn.Module):
                 for k, v in out.items()}
 
     def _guard_plan(self, mode, n_rays):
-        return self.f16_guard.plan(mode, -(-n_rays // int(cfg.chunk)), None if self._cnl_pack is None else self._cnl_pack[0])
+        return self.f16_guard.plan(mode, -(-n_rays // int(cfg.chunk)), None if self._cnl_pack is None else self._cnl_pack[3])
 
     def _forward_frame(self, per_ray, per_frame, nr_packed, cnl_packed, bg, S, mode, diag, hann_host=None, baked=None,
                        baked_nr=None, nr_baked_on=None, all_heads=False):
@@ -974,8 +1030,10 @@ class Network(nn.Module):
         with torch.no_grad():
             N = baked_mod.check_resolution(amd_option('bake_resolution', 256) if resolution is None else resolution)
             dev = self._mesh_device()
-            bmin = _vec3(cnl_bbox_min_xyz, dev)
-            bmax = _vec3(cnl_bbox_max_xyz, dev) if cnl_bbox_max_xyz is not None \
+            # copies: the grid keeps the box it was baked over, whatever the caller writes into these tensors afterwards
+            # (_vec3 hands an fp32 device tensor back as it is; _baked_for_frame compares the frame's box with the kept one)
+            bmin = _vec3(cnl_bbox_min_xyz, dev).clone()
+            bmax = _vec3(cnl_bbox_max_xyz, dev).clone() if cnl_bbox_max_xyz is not None \
                 else (bmin + 2.0 / _vec3(cnl_bbox_scale_xyz, dev)).contiguous()
             grid, sat = self._canonical_pass(
                 lambda packed, mode: ops.bake_canonical(packed, bmin, bmax, N, mode, want_saturated=True))
@@ -985,8 +1043,8 @@ class Network(nn.Module):
                 warnings.warn('bake_canonical: %d canonical-MLP outputs beyond +-65504 were saturated in the f16 grid: '
                               'the baked render differs from the exact one there' % n_sat)
             self.bake_count += 1
-            self._baked = {'grid': grid, 'bmin': bmin, 'bmax': bmax, 'key': (_versions(self._cnl_tensors()), self._mlp_mode(), N, self._head),
-                           'injected': False, 'refs': None}
+            self._baked = {'grid': grid, 'bmin': bmin, 'bmax': bmax, 'key': (self._mlp_mode(), N, self._head, self._weights_gen),
+                           'weights': _resident(self._cnl_tensors()), 'injected': False, 'refs': None}
             return grid
 
     def set_baked_grid(self, grid, bbox_min, bbox_max, weights_hash=None):
@@ -1006,8 +1064,8 @@ class Network(nn.Module):
         N = baked_mod.check_resolution(g.shape[0])
         if tuple(g.shape) != (N, N, N, 4) or g.dtype != torch.float16:
             raise ValueError('set_baked_grid: grid must be float16 (N, N, N, 4), got %s %s' % (g.dtype, tuple(g.shape)))
-        self._baked = {'grid': g.to(dev).contiguous(), 'bmin': _vec3(bbox_min, dev), 'bmax': _vec3(bbox_max, dev), 'key': None,
-                       'injected': True, 'refs': None}
+        self._baked = {'grid': g.to(dev).contiguous(), 'bmin': _vec3(bbox_min, dev).clone(), 'bmax': _vec3(bbox_max, dev).clone(), 'key': None,
+                       'weights': None, 'injected': True, 'refs': None}
 
     # baked non-rigid offset field (no counterpart in the reference; humannerf_amd/baked.py) -------------------------
     def _nr_tensors(self):
@@ -1036,7 +1094,7 @@ class Network(nn.Module):
             grid = ops.bake_nonrigid(packed, hann, bmin, bmax, M, mode, workspace=self._nr_bake_ws[1])
             self.nonrigid_bake_count += 1
             self._baked_nr = {'grid': grid, 'bmin': bmin, 'bmax': bmax, 'packed': packed, 'mode': mode, 'key': None,
-                              'refs': None}
+                              'weights': None, 'refs': None}
             return grid
 
     def _baked_nr_for_frame(self, dst_posevec, iter_val, hann_host, bmin, bmax):
@@ -1046,15 +1104,16 @@ class Network(nn.Module):
         fresh bake (whose packed image is returned for the f16-range watch).  Identity only: a fresh ``dst_posevec``
         tensor re-bakes, nothing is compared by value, nothing synchronises."""
         M = int(amd_option('nonrigid_bake_resolution', 128))
-        key = (_versions(self._nr_tensors()), self._mlp_mode(), M, tuple(hann_host.tolist()),
-               iter_val < cfg.non_rigid_motion_mlp.kick_in_iter)
-        watched = (dst_posevec, bmin, bmax)
+        key = (self._mlp_mode(), M, tuple(hann_host.tolist()), iter_val < cfg.non_rigid_motion_mlp.kick_in_iter,
+               self._weights_gen)
+        watched, weights = (dst_posevec, bmin, bmax), self._nr_tensors()
         b = self._baked_nr
-        if b is not None and b['key'] == key and _still_resident(b['refs'], watched):
+        if b is not None and b['key'] == key and _still_resident(b['weights'], weights) \
+                and _still_resident(b['refs'], watched):
             return (b['grid'], b['bmin'], b['bmax']), None
         self.bake_nonrigid(dst_posevec, iter_val, (bmin, bmax), M)
         b = self._baked_nr
-        b['key'], b['refs'] = key, _resident(watched)
+        b['key'], b['weights'], b['refs'] = key, _resident(weights), _resident(watched)
         return (b['grid'], b['bmin'], b['bmax']), b['packed']
 
     def _baked_for_frame(self, bbox_min, bbox_max, bbox_scale):
@@ -1066,8 +1125,8 @@ class Network(nn.Module):
         if b is not None and b['injected']:
             return b['grid'], b['bmin'], b['bmax']
         box = (bbox_min, bbox_max if bbox_max is not None else bbox_scale)
-        key = (_versions(self._cnl_tensors()), self._mlp_mode(), int(amd_option('bake_resolution', 256)), self._head)
-        if b is not None and b['key'] == key:
+        key = (self._mlp_mode(), int(amd_option('bake_resolution', 256)), self._head, self._weights_gen)
+        if b is not None and b['key'] == key and _still_resident(b['weights'], self._cnl_tensors()):
             if _still_resident(b['refs'], box):
                 return b['grid'], b['bmin'], b['bmax']
             dev = b['bmin'].device
@@ -1076,7 +1135,7 @@ class Network(nn.Module):
             if torch.equal(bmin, b['bmin']) and torch.equal(bmax, b['bmax']):
                 b['refs'] = _resident(box)
                 return b['grid'], b['bmin'], b['bmax']
-        self.bake_canonical(bbox_min, bbox_max, key[2], bbox_scale)
+        self.bake_canonical(bbox_min, bbox_max, key[1], bbox_scale)
         b = self._baked
         b['refs'] = _resident(box)
         return b['grid'], b['bmin'], b['bmax']
