@@ -25,6 +25,13 @@ GROUPS = {
     'heads': ('hnrf_heads.h', 'the multi-head canonical MLP'),
 }
 
+# Headers added after the five above, of the same shape and bound in the same way, but by _bind_late / load_late():
+# GROUPS and _bind stay what libraries and callers of ABI version 13 know them as.  build() calls load_late() after
+# load_all().
+LATE_GROUPS = {
+    'skin': ('hnrf_skin.h', 'the skinned glTF export'),
+}
+
 _SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float,
             'double': ctypes.c_double}
 _DECL = re.compile(r'([\w\s]+?[\s*]+)(hnrf_\w+)\s*\(([^()]*)\)\s*;')
@@ -73,8 +80,8 @@ def _signatures(path=HEADER_PATH):
 SIGNATURES = _signatures()
 
 
-def _header(group):
-    path = os.path.normpath(os.path.join(_HERE, '..', 'include', GROUPS[group][0]))
+def _header(group, table=GROUPS):
+    path = os.path.normpath(os.path.join(_HERE, '..', 'include', table[group][0]))
     return path, _signatures(path)
 
 
@@ -84,6 +91,8 @@ VIDEO_HEADER_PATH, VIDEO_SIGNATURES = _HEADERS['video']
 SEGMENT_HEADER_PATH, SEGMENT_SIGNATURES = _HEADERS['segment']
 GEOMETRY_HEADER_PATH, GEOMETRY_SIGNATURES = _HEADERS['geometry']
 HEADS_HEADER_PATH, HEADS_SIGNATURES = _HEADERS['heads']
+_LATE_HEADERS = {group: _header(group, LATE_GROUPS) for group in LATE_GROUPS}
+SKIN_HEADER_PATH, SKIN_SIGNATURES = _LATE_HEADERS['skin']
 
 _lib = None
 
@@ -120,11 +129,20 @@ _bound = set()
 def _bind(group, lib=None):
     """load() plus the entries of the group's header, typed.  A library without them raises HnrfError.  ``lib``: a
     library object to bind in the place of the loaded one (every time it is asked for)."""
-    header, phrase = GROUPS[group]
+    return _bind_table(group, lib, GROUPS, _HEADERS)
+
+
+def _bind_late(group, lib=None):
+    """_bind for a group of LATE_GROUPS."""
+    return _bind_table(group, lib, LATE_GROUPS, _LATE_HEADERS)
+
+
+def _bind_table(group, lib, table, headers):
+    header, phrase = table[group]
     if lib is None and group in _bound:
         return load()
     target = load() if lib is None else lib
-    for name, (res, args) in _HEADERS[group][1].items():
+    for name, (res, args) in headers[group][1].items():
         try:
             fn = getattr(target, name)
         except AttributeError:
@@ -155,6 +173,18 @@ def load_geometry():
 
 def load_heads():
     return _bind('heads')
+
+
+def load_skin(lib=None):
+    return _bind_late('skin', lib)
+
+
+def load_late():
+    """load() plus every group of LATE_GROUPS (the second half of the self-check of __graft_entry__.build())."""
+    lib = load()
+    for group in LATE_GROUPS:
+        _bind_late(group)
+    return lib
 
 
 def load_all():

@@ -1190,6 +1190,15 @@ class Network(nn.Module):
         verts, faces = mesh.mesh_from_density(density, cnl_bbox_min_xyz, cnl_bbox_max_xyz, level)
         return verts, faces, self.vertex_colors(verts)
 
+    def refiner_rvec(self, frame, iter_val=1e7):
+        """The pose refiner's axis-angle corrections (23, 3) for a frame dict (dst_posevec), as frame_motion applies them
+        (dst_Rs[i] <- dst_Rs[i] Rodrigues(rvec[i - 1])); None when iter_val is below its kick_in_iter or it is off."""
+        if not self._refines_pose(float(iter_val)):
+            return None
+        with torch.no_grad():
+            posevec = torch.as_tensor(frame['dst_posevec']).to(device=self._mesh_device(), dtype=torch.float32)
+            return self.pose_decoder.rvec(posevec[None])
+
     def frame_motion(self, frame, iter_val=1e7):
         """The motion basis (B,3,3), (B,3) and weight volume forward computes for a frame dict (dst_Rs, dst_Ts,
         cnl_gtfms, motion_weights_priors, dst_posevec), the pose refiner applied when iter_val >= its kick_in_iter."""
@@ -1197,8 +1206,7 @@ class Network(nn.Module):
         t = lambda k: torch.as_tensor(frame[k]).to(device=dev, dtype=torch.float32)
         with torch.no_grad():
             dst_Rs, dst_Ts, cnl_gtfms = t('dst_Rs'), t('dst_Ts'), t('cnl_gtfms')
-            rvec = self.pose_decoder.rvec(t('dst_posevec')[None]) if self._refines_pose(float(iter_val)) else None
-            motion_Rs, motion_Ts = motion_basis(dst_Rs, dst_Ts, cnl_gtfms, rvec)
+            motion_Rs, motion_Ts = motion_basis(dst_Rs, dst_Ts, cnl_gtfms, self.refiner_rvec(frame, iter_val))
             vol = self._weight_volume(t('motion_weights_priors'))
         return motion_Rs.contiguous(), motion_Ts.contiguous(), vol
 
@@ -1214,6 +1222,25 @@ class Network(nn.Module):
         with torch.no_grad():
             verts = verts.to(device=self._mesh_device(), dtype=torch.float32).contiguous()
             return ops.forward_skin(verts, motion_Rs, motion_Ts, vol, bmin, scale)
+
+    def skin_weights(self, verts, frame=None, k=4, motion_weights_priors=None, cnl_bbox_min_xyz=None,
+                     cnl_bbox_scale_xyz=None):
+        """The bone weights pose_vertices blends canonical vertices (V, 3) with, as data (hnrf_skin_weights): the k
+        (4 or 8) largest per vertex of the weight volume forward uses, normalised -- what a skinned mesh file holds.
+        ``frame``: a frame dict (motion_weights_priors, cnl_bbox_min_xyz, cnl_bbox_scale_xyz; the weights do not depend
+        on the pose), or give the three by keyword.  Returns (joints (V, k) uint8, weights (V, k) fp32, kept (V,) fp32
+        = the sum of the k selected weights before normalisation) on the device."""
+        from . import skin
+        frame = frame or {}
+        pick = lambda given, key: frame[key] if given is None else given
+        dev = self._mesh_device()
+        bmin = _vec3(pick(cnl_bbox_min_xyz, 'cnl_bbox_min_xyz'), dev)
+        scale = _vec3(pick(cnl_bbox_scale_xyz, 'cnl_bbox_scale_xyz'), dev)
+        with torch.no_grad():
+            priors = torch.as_tensor(pick(motion_weights_priors, 'motion_weights_priors'))
+            vol = self._weight_volume(priors.to(device=dev, dtype=torch.float32))
+            verts = verts.to(device=dev, dtype=torch.float32).contiguous()
+            return skin.skin_weights(verts, vol, bmin, scale, k=k)
 
     def render_mesh(self, verts, faces, colors, frame, iter_val=1e7, posed=False, **raster_options):
         """A picture of the mesh in a frame's pose and camera (humannerf_amd.raster, hnrf_raster_mesh): the canonical

@@ -1114,6 +1114,42 @@ def forward_skin(verts, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale):
     return out
 
 
+def _chk_skin_k(k):
+    k = int(k)
+    if k not in (4, 8):
+        raise _lib.HnrfError(f'{k} influences per vertex: glTF skinning is built for 4 or 8')
+    return k
+
+
+def skin_weights(verts, vol, n_bones, bbox_min, bbox_scale, k=4):
+    """hnrf_skin_weights: the k largest of the first ``n_bones`` channels of vol at verts (V, 3), normalised ->
+    joints (V, k) uint8, weights (V, k) fp32, kept (V,) fp32 (the sum of the selected weights)."""
+    lib = _lib.load_skin()
+    _chk(verts, vol, bbox_min, bbox_scale)
+    k, B, G, V = _chk_skin_k(k), int(n_bones), vol.shape[-1], verts.shape[0]
+    assert vol.shape[0] >= B and verts.dim() == 2 and verts.shape[1] == 3
+    joints = torch.empty(V, k, dtype=torch.uint8, device=verts.device)
+    weights = torch.empty(V, k, device=verts.device)
+    kept = torch.empty(V, device=verts.device)
+    _lib.check(lib.hnrf_skin_weights(_ptr(verts), V, _ptr(vol), B, G, _ptr(bbox_min), _ptr(bbox_scale), k, _ptr(joints),
+                                     _ptr(weights), _ptr(kept), _stream()), 'hnrf_skin_weights')
+    return joints, weights, kept
+
+
+def skin_lbs(verts, joints, weights, mats):
+    """hnrf_skin_lbs: out (V, 3) = sum_k weights[:, k] (mats[joints[:, k]] (x, 1)); mats (B, 3, 4)."""
+    lib = _lib.load_skin()
+    _chk(verts, weights, mats)
+    _chk_dev(joints, torch.uint8, 'joints')
+    V, k = verts.shape[0], _chk_skin_k(weights.shape[-1])
+    assert verts.dim() == 2 and verts.shape[1] == 3 and tuple(joints.shape) == (V, k) == tuple(weights.shape)
+    assert mats.dim() == 3 and tuple(mats.shape[1:]) == (3, 4)
+    out = torch.empty_like(verts)
+    _lib.check(lib.hnrf_skin_lbs(_ptr(verts), V, _ptr(joints), _ptr(weights), k, _ptr(mats), mats.shape[0], _ptr(out),
+                                 _stream()), 'hnrf_skin_lbs')
+    return out
+
+
 _raster_ws = {}                       # (V, F, H, W, device) -> workspace of the last call of that shape
 
 

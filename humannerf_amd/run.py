@@ -12,6 +12,8 @@ render.ImageWriter / MetricsWriter on worker threads.
   run_heads      run.py:76-81, 219-225   the three loops above for a multi-head canonical MLP with cfg.test.head_id = -1:
                                   every frame rendered once, head i written to ``<load_net><tag>_h<i>/<folder>``
   run_mesh       (no counterpart) the canonical body as a coloured triangle mesh, and that mesh skinned into frames
+  run_gltf       (no counterpart) that mesh, its skeleton, its 4 or 8 largest bone weights per vertex and the movement as
+                                  ONE animated glTF 2.0 binary, with the skinning error of the truncation per frame
   run_mesh_render (no counterpart) the movement / freeview / tpose sequences as rasterised pictures of that mesh: a preview
   run_surface_points  run.py:388-404   cfg.test.save_3d_together: one canonical surface point per ray of every movement
                                   frame, collected as ``name-2-3d.bin``
@@ -367,6 +369,63 @@ def run_mesh(network, subject, frames=(), resolution=256, level=None, logdir=Non
         written[name] = os.path.join(out_dir, name + '.ply')
         mesh.write_ply(written[name], network.pose_vertices(verts, frame).cpu().numpy(), faces_h, colors_h)
     return written
+
+
+def run_gltf(network, subject, frames=None, resolution=256, level=None, influences=4, fps=30, up='+z', logdir=None,
+             iter_val=1e7):
+    """The avatar as ONE skinned, animated glTF 2.0 binary, ``<out>/mesh/avatar.glb`` (humannerf_amd/gltf.py): the
+    canonical mesh of run_mesh with its vertex colours, the 24-joint skeleton, the ``influences`` (4 or 8) largest bone
+    weights of every vertex (Network.skin_weights) and one animation over ``frames`` (indices into subject.framelist or
+    frame names; None: the whole framelist; the camera entries are not used) at ``fps``.  ``up``: the up axis of the
+    subject's world, '+z' (ZJU-MoCap, the default), '+y' or '-y'.  The pose refiner acts as in Network.pose_vertices
+    (``iter_val`` against its kick-in).  The non-rigid offsets are not in the file: skinning cannot represent them.
+
+    For every frame the device compares what a viewer will compute, skin.skin_lbs of the truncated weights with the
+    frame's joint matrices, with the exact forward skin Network.pose_vertices.  Returns {'path', 'V', 'F', 'frames',
+    'kept': {'min', 'mean'} (the sum of the selected weights before normalisation), 'skin_error': {'max', 'mean',
+    'per_frame': [{'max', 'mean'}, ...]}} -- distances in metres: the answer to "are 4 influences enough for this
+    checkpoint".  Single rank."""
+    import torch
+    from . import gltf, skin
+    out_dir = os.path.join(_output_dir(logdir), 'mesh')
+    os.makedirs(out_dir, exist_ok=True)
+    bbox = subject.canonical_bbox
+    verts, faces, colors = network.extract_canonical_mesh(
+        bbox['min_xyz'], bbox['max_xyz'], subject.motion_weights_priors, resolution=resolution,
+        level=network.MESH_LEVEL if level is None else level)
+    if verts.shape[0] == 0 or faces.shape[0] == 0:
+        raise ValueError('run_gltf: the canonical mesh is empty at this level (Network.MESH_LEVEL is not checked on a '
+                         'trained checkpoint: pick the level per checkpoint)')
+    device = verts.device
+    idxs = [subject.framelist.index(f) if isinstance(f, str) else int(f)
+            for f in (range(len(subject)) if frames is None else frames)]
+    # the subject's priors, uploaded once: Network keeps the weight volume of a resident tensor without comparing it
+    priors = torch.as_tensor(subject.motion_weights_priors).to(device=device, dtype=torch.float32)
+    first = dict(subject.movement_frame(idxs[0] if idxs else 0, image_size=(1, 1)), motion_weights_priors=priors)
+    joints, weights, kept = network.skin_weights(verts, first, k=influences)
+    dst_Rs, dst_Ts, Rh, Th, errs = [], [], [], [], []
+    for idx in idxs:
+        frame = dict(subject.movement_frame(idx, image_size=(1, 1)), motion_weights_priors=priors)
+        info = subject.mesh_infos[subject.framelist[idx]]
+        rvec = network.refiner_rvec(frame, iter_val)
+        dst_Rs.append(gltf.refined_rotations(frame['dst_Rs'], None if rvec is None else rvec.cpu().numpy()))
+        dst_Ts.append(frame['dst_Ts'])
+        Rh.append(info['Rh'])
+        Th.append(info['Th'])
+        motion_Rs, motion_Ts, _ = network.frame_motion(frame, iter_val)
+        d = skin.skin_lbs(verts, joints, weights, skin.joint_matrices(motion_Rs, motion_Ts)) \
+            - network.pose_vertices(verts, frame, iter_val)
+        d = torch.sqrt((d * d).sum(1))
+        errs.append(torch.stack([d.max(), d.mean()]))
+    path = os.path.join(out_dir, 'avatar.glb')
+    gltf.write_glb(path, verts, faces, colors, joints, weights, subject.cnl_gtfms,
+                   dst_Rs=np.stack(dst_Rs) if idxs else None, dst_Ts=np.stack(dst_Ts) if idxs else None,
+                   Rh=np.stack(Rh) if idxs else None, Th=np.stack(Th) if idxs else None, fps=fps, up=up)
+    per = torch.stack(errs).cpu().numpy().astype(np.float64) if idxs else np.zeros((0, 2))
+    return {'path': path, 'V': int(verts.shape[0]), 'F': int(faces.shape[0]), 'frames': idxs,
+            'kept': {'min': float(kept.min()), 'mean': float(kept.mean())},
+            'skin_error': {'max': float(per[:, 0].max()) if idxs else 0.0, 'mean': float(per[:, 1].mean()) if idxs else 0.0,
+                           'per_frame': [{'max': float(a), 'mean': float(b)} for a, b in per]}}
 
 
 def run_mesh_render(network, subject, kind='movement', resolution=256, level=None, logdir=None, render_folder_name=None,

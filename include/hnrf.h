@@ -784,6 +784,10 @@ int hnrf_image_metrics(const uint8_t* pred, const uint8_t* target, const uint8_t
  * frame with per-head outputs.  Additive to ABI version 13; contracts and declarations in hnrf_heads.h. */
 #include "hnrf_heads.h"
 
+/* ---- the skinned glTF export: the K largest bone weights of every vertex, normalised, and the skinning sum a glTF
+ * viewer performs with them.  Additive to ABI version 13; contracts and declarations in hnrf_skin.h. */
+#include "hnrf_skin.h"
+
 #ifdef __cplusplus
 }
 #endif
