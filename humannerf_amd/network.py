@@ -20,7 +20,6 @@ in PyTorch-ROCm.
 Only the default-config branches are implemented; anything else raises.
 """
 import math
-import weakref
 
 import torch
 import torch.nn as nn
@@ -29,6 +28,7 @@ import torch.nn.functional as F
 from . import ops
 from .autograd import RenderRays
 from .config import cfg, amd_option, check_amd_options
+from .kept import Kept, _resident, _still_resident     # noqa: F401  (the rule keeps its name here for its importers)
 from .range_guard import ActivationRangeError, InferenceRangeGuard     # noqa: F401  (the error's importers look here)
 
 SMPL_PARENT = [-1, 0, 0, 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 9, 9, 12, 13, 14, 16,
@@ -432,35 +432,6 @@ def hann_window_weights(iter_val, multires, kick_in_iter, full_band_iter):
     return (1. - torch.cos(math.pi * torch.clamp(alpha - k, min=0., max=1.))) / 2.
 
 
-def _resident(tensors):
-    """What _still_resident recognises ``tensors`` by later: a weak reference, the ``data_ptr`` and the ``_version`` of
-    each.  THE rule of everything a Network keeps from frame to frame, for the frame's inputs (priors, bbox,
-    dst_posevec) and for the parameters alike:
-
-    * the weak reference is the identity: another object never matches, not even one that the allocator placed on the
-      freed address of the old one with an equal version counter (a replaced nn.Parameter), and a collected object can
-      never match again;
-    * ``data_ptr`` sees ``t.data = other`` and a move between devices, which leave object and counter alone;
-    * ``_version`` sees every in-place write autograd knows of: ``t.copy_()``, ``t.mul_()``, foreach ops on the
-      tensors themselves, torch's optimizers in their foreach and single-tensor forms, GroupedAdam.
-
-    What none of the three sees is a write through ``t.data`` / ``t.detach()`` (``p.data.copy_()``,
-    ``p.data[i] = v``, ``dist.broadcast(p.data)``, optimizers that update through detached views): for the parameters
-    that is Network.weights_changed(), which load_state_dict and a move of the module call themselves and whose effect
-    a train-path forward has (Network._weights_gen); for a frame's inputs the rule is to pass a fresh tensor, or to
-    write the tensor itself."""
-    return tuple((weakref.ref(t), t.data_ptr(), t._version) for t in tensors)
-
-
-def _still_resident(refs, tensors):
-    """True when ``tensors`` are the very objects ``refs`` = _resident(...) was built from, on the same memory and
-    unwritten since: a driver that keeps its per-subject tensors on the device hits without a look at their values,
-    i.e. without a host synchronisation.  Equal values in other objects do not count: the caller compares those once,
-    or not at all."""
-    return refs is not None and len(refs) == len(tensors) \
-        and all(r() is t and ptr == t.data_ptr() and v == t._version for (r, ptr, v), t in zip(refs, tensors))
-
-
 def _vec3(a, dev):
     return torch.as_tensor(a).to(device=dev, dtype=torch.float32).reshape(3).contiguous()
 
@@ -555,29 +526,23 @@ class Network(nn.Module):
             self.pose_decoder = BodyPoseRefiner(
                 embedding_size=cfg.pose_decoder.embedding_size, mlp_width=cfg.pose_decoder.mlp_width,
                 mlp_depth=cfg.pose_decoder.mlp_depth, total_bones=cfg.total_bones)
-        # Weight-keyed entries carry _resident(their parameters) next to a key of plain values (mode, head, resolution):
-        # weights_changed() drops them all.
-        self._cnl_pack = None     # (key, packed image, _resident(weights), serial number of the pack)
+        # Everything kept from frame to frame is one kept.Kept each, by name: ('pack', head) the packed canonical images
+        # (head None = the single-head network, -1 = the all-heads image), 'vol' the decoded weight volume, 'baked' the
+        # canonical grid (cfg.amd.canonical = 'baked'), 'baked_nr' the frame's offset grid (cfg.amd.nonrigid = 'baked'),
+        # 'head_id' the last device tensor read as a head_id.  weights_changed() drops all that is not injected.
+        self._kept = {}
+        # the name of the packed image used last (its serial number goes to the f16-range guard), and the packs so far
+        self._pack_last = None
         self._pack_serial = 0
-        # counts the train-path forwards: in every key, so that an entry built before one is out of date after it (it
-        # stays where it is, its buffers are used again)
+        # counts the train-path forwards: compared by every entry's weights test, so that an entry built before one is
+        # out of date after it (it stays where it is, its buffers are used again)
         self._weights_gen = 0
-        # multi-head: head -> such an entry, -1 = the all-heads image; _cnl_pack is the entry used last.  The head
-        # that _canonical_packed() packs outside forward (select_head), None = not chosen; the last device tensor read
-        # as a head_id (tensor, _version, value)
-        self._cnl_head_packs = {}
+        # the head that _canonical_packed() packs outside forward (select_head), None = not chosen
         self._head = None
-        self._head_id_seen = None
         self._nr_pack_buf = None
         self.f16_guard = InferenceRangeGuard()
-        self._vol_cache = None    # (_resident(decoder parameters), priors, volume, _resident((priors,)), _weights_gen)
-        # baked canonical grid (cfg.amd.canonical = 'baked'): dict(grid, bmin, bmax, key, weights, injected, refs) or
-        # None; bake_count counts the bakes this network ran
-        self._baked = None
+        # the bakes this network ran, and the resident workspace of the offset grid's bake
         self.bake_count = 0
-        # baked non-rigid offset field of the current frame (cfg.amd.nonrigid = 'baked'): dict(grid, bmin, bmax, packed,
-        # key, weights, refs) or None, the resident workspace of the bake, and the number of bakes this network ran
-        self._baked_nr = None
         self._nr_bake_ws = None
         self.nonrigid_bake_count = 0
         self._workspace = None
@@ -600,19 +565,18 @@ class Network(nn.Module):
         """Drop everything derived from the parameters -- the packed canonical images, the decoded weight volume, the
         baked canonical grid (an injected one stays: set_baked_grid) and the frame's offset grid -- and restart the
         f16-range guard's audit schedule: the next frame rebuilds from the parameters as they are then.  THE call after
-        any write the entries cannot see by themselves (_resident: writes through ``p.data`` / ``p.detach()``, e.g.
+        any write the entries cannot see by themselves (kept._resident: writes through ``p.data`` / ``p.detach()``, e.g.
         ``p.data.copy_()``, ``dist.broadcast(p.data)``, an optimizer that steps through detached views).
         load_state_dict and every move / cast of the module (``to``, ``cpu``, ``cuda``, ``float``) call it themselves; a
         train-path forward marks the entries out of date to the same effect (_weights_gen).  Host only: no device work,
         no synchronisation."""
-        self._cnl_pack = None
-        self._cnl_head_packs.clear()
-        self._vol_cache = None
-        if self._baked is not None and not self._baked['injected']:
-            self._baked = None
-        self._baked_nr = None
+        self._drop(lambda e: not e.injected)
         self.f16_guard.restart_schedule()
         return self
+
+    def _drop(self, which):
+        for name in [n for n, e in self._kept.items() if which(e)]:
+            del self._kept[name]
 
     def load_state_dict(self, *args, **kwargs):
         try:
@@ -639,8 +603,7 @@ class Network(nn.Module):
         loops call this once after their last frame).  Returns True when one of them left the range."""
         hit = self.f16_guard.check(wait, upto)
         if any(hit):
-            self._cnl_pack = None                               # (a fresh pack clears the canonical image's word)
-            self._cnl_head_packs.clear()
+            self._drop(lambda e: e.packed is not None)          # (a fresh pack clears the canonical image's word)
         return self.f16_guard.act(*hit)
 
     def _canonical_pass(self, op):
@@ -673,7 +636,7 @@ class Network(nn.Module):
 
     def _resolve_head(self, head_id):
         """forward's ``head_id`` as an int: -1 = all heads, None = the selected head.  A tensor on the host is read there;
-        one on the device is read back once and remembered by identity and ``_version``, not once per frame."""
+        one on the device is read back once and remembered by the resident-tensor rule, not once per frame."""
         if head_id is None:
             if self._head is None:
                 raise RuntimeError('multi-head canonical MLP (%d heads): pass head_id (0..%d, or -1 for all heads) or call '
@@ -685,10 +648,13 @@ class Network(nn.Module):
             if head_id.device.type == 'cpu':
                 h = int(head_id.reshape(()).item())
             else:
-                seen = self._head_id_seen
-                if seen is None or seen[0] is not head_id or seen[1] != head_id._version:
-                    seen = self._head_id_seen = (head_id, head_id._version, int(head_id.reshape(()).item()))
-                h = seen[2]
+                # read back once per (object, data_ptr, _version), by identity only.  Injected: the caller's value, nothing
+                # derived from the weights, so weights_changed() costs no further read-back
+                seen = self._kept.get('head_id')
+                if seen is None or not seen.fed_by((head_id,)):
+                    seen = self._kept['head_id'] = Kept(inputs=(head_id,), injected=True,
+                                                        value=int(head_id.reshape(()).item()))
+                h = seen.value
         else:
             h = int(head_id)
         if not -1 <= h < self.head_num:
@@ -696,42 +662,30 @@ class Network(nn.Module):
         return h
 
     def _canonical_packed(self):
-        lin = self.cnl_mlp.module.linears()
-        ws, bs = [l.weight for l in lin], [l.bias for l in lin]
-        if self.head_num:
-            return self._canonical_packed_head(ws, bs)
-        key, ent = (self._mlp_mode(), self._weights_gen), self._cnl_pack
-        if ent is None or ent[0] != key or not _still_resident(ent[2], ws + bs):
-            packed = ops.canonical_pack([w.detach() for w in ws], [b.detach() for b in bs], self._mlp_mode(),
-                                        out=None if ent is None else ent[1])
-            self._cnl_pack = self._packed_entry(key, packed, ws + bs)
-        return self._cnl_pack[1]
-
-    def _packed_entry(self, key, packed, params):
-        self._pack_serial += 1
-        return (key, packed, _resident(params), self._pack_serial)
-
-    def _canonical_packed_head(self, ws, bs):
-        """The image of the selected head (ops.canonical_pack on its four rows), or with head -1 the all-heads image
-        (ops.canonical_heads_pack); one cached image per head, the head in its key."""
-        h = self._head
-        if h is None:
+        """The packed canonical image: of all rows on the single-head network (no head: None in the key), else of the
+        selected head (ops.canonical_pack on its four rows) or with head -1 the all-heads image
+        (ops.canonical_heads_pack); one kept image per head, the head in its key."""
+        h = self._head if self.head_num else None
+        if self.head_num and h is None:
             raise RuntimeError('multi-head canonical MLP (%d heads): call select_head(h) before evaluating it outside '
                                'forward (no head is used silently)' % self.head_num)
-        mode = self._mlp_mode()
-        key = (mode, h, self._weights_gen)
-        ent = self._cnl_head_packs.get(h)
-        if ent is None or ent[0] != key or not _still_resident(ent[2], ws + bs):
+        lin = self.cnl_mlp.module.linears()
+        ws, bs = [l.weight for l in lin], [l.bias for l in lin]
+        mode, name = self._mlp_mode(), ('pack', h)
+        ent = self._kept.get(name)
+        if ent is None or not ent.built_from((mode, h), self._weights_gen, ws + bs):
             W, B = [w.detach() for w in ws], [b.detach() for b in bs]
-            buf = None if ent is None else ent[1]
-            if h < 0:
+            buf = None if ent is None else ent.packed                   # (a stale image's buffer is packed into again)
+            if h is not None and h < 0:
                 packed = ops.canonical_heads_pack(W, B, self.head_num, mode, out=buf)
             else:
-                W[8], B[8] = W[8][4 * h:4 * h + 4], B[8][4 * h:4 * h + 4]        # (whole rows: contiguous views)
+                if h is not None:
+                    W[8], B[8] = W[8][4 * h:4 * h + 4], B[8][4 * h:4 * h + 4]    # (whole rows: contiguous views)
                 packed = ops.canonical_pack(W, B, mode, out=buf)
-            ent = self._cnl_head_packs[h] = self._packed_entry(key, packed, ws + bs)
-        self._cnl_pack = ent
-        return ent[1]
+            self._pack_serial += 1                                      # (every pack takes the next serial)
+            ent = self._kept[name] = Kept((mode, h), self._weights_gen, ws + bs, packed=packed, serial=self._pack_serial)
+        self._pack_last = name                                          # (_guard_plan: the serial of the image used last)
+        return ent.packed
 
     def _nonrigid_packed(self, cond):
         lin = self.non_rigid_mlp.module.linears()
@@ -742,22 +696,19 @@ class Network(nn.Module):
     def _weight_volume(self, priors):
         """(B+1,G,G,G) softmax volume; cached across frames in eval mode."""
         params = list(self.mweight_vol_decoder.parameters())
+        # consulted and stored only in eval mode, with grad disabled and the option on: otherwise the entry is left alone
         use_cache = (not self.training) and (not torch.is_grad_enabled()) and amd_option('cache_weight_volume', True)
-        if use_cache and self._vol_cache is not None and self._vol_cache[4] == self._weights_gen \
-                and _still_resident(self._vol_cache[0], params) \
-                and self._vol_cache[1].shape == priors.shape:
-            # same tensor object as last frame (a driver that keeps the priors resident): no comparison, no host
-            # synchronisation; a fresh tensor is compared by value (one device round trip per frame)
-            if _still_resident(self._vol_cache[3], (priors,)):
-                return self._vol_cache[2]
-            if torch.equal(self._vol_cache[1], priors):
-                # equal by value: remember THIS tensor, so that the frames that follow hit by identity (a render loop
-                # uploads the subject's priors once per loop; comparing every frame blocked the host for a whole frame)
-                self._vol_cache = self._vol_cache[:3] + (_resident((priors,)), self._weights_gen)
-                return self._vol_cache[2]
+        e = self._kept.get('vol') if use_cache else None
+        # The kept priors (a clone) are compared by shape first.  Then the ladder: the same tensor object as last frame (a
+        # driver that keeps the priors resident) hits without a comparison, i.e. without a host synchronisation; a fresh
+        # tensor is compared by value once (a device round trip) and THIS tensor is remembered, so that the frames that
+        # follow hit by identity (a render loop uploads the subject's priors once per loop)
+        if e is not None and e.built_from(None, self._weights_gen, params) and e.priors.shape == priors.shape \
+                and e.fed_by((priors,), lambda: torch.equal(e.priors, priors)):
+            return e.vol
         vol = self.mweight_vol_decoder(motion_weights_priors=priors[None])[0].contiguous()
         if use_cache:
-            self._vol_cache = (_resident(params), priors.clone(), vol, _resident((priors,)), self._weights_gen)
+            self._kept['vol'] = Kept(None, self._weights_gen, params, (priors,), priors=priors.clone(), vol=vol)
         return vol
 
     # forward -------------------------------------------------------------------
@@ -907,7 +858,8 @@ class Network(nn.Module):
                 for k, v in out.items()}
 
     def _guard_plan(self, mode, n_rays):
-        return self.f16_guard.plan(mode, -(-n_rays // int(cfg.chunk)), None if self._cnl_pack is None else self._cnl_pack[3])
+        last = self._kept.get(self._pack_last)
+        return self.f16_guard.plan(mode, -(-n_rays // int(cfg.chunk)), None if last is None else last.serial)
 
     def _forward_frame(self, per_ray, per_frame, nr_packed, cnl_packed, bg, S, mode, diag, hann_host=None, baked=None,
                        baked_nr=None, nr_baked_on=None, all_heads=False):
@@ -1043,9 +995,16 @@ class Network(nn.Module):
                 warnings.warn('bake_canonical: %d canonical-MLP outputs beyond +-65504 were saturated in the f16 grid: '
                               'the baked render differs from the exact one there' % n_sat)
             self.bake_count += 1
-            self._baked = {'grid': grid, 'bmin': bmin, 'bmax': bmax, 'key': (self._mlp_mode(), N, self._head, self._weights_gen),
-                           'weights': _resident(self._cnl_tensors()), 'injected': False, 'refs': None}
+            # key: mode, resolution, selected head.  No input objects remembered: the next frame compares its box by value once
+            self._kept['baked'] = Kept((self._mlp_mode(), N, self._head), self._weights_gen, self._cnl_tensors(),
+                                       grid=grid, bmin=bmin, bmax=bmax)
             return grid
+
+    @property
+    def baked_resolution(self):
+        """The resolution N of the canonical grid kept for forward (baked or injected), None without one."""
+        b = self._kept.get('baked')
+        return None if b is None else b.grid.shape[0]
 
     def set_baked_grid(self, grid, bbox_min, bbox_max, weights_hash=None):
         """Use ``grid`` (float16 (N, N, N, 4), array or tensor; baked.load_grid, or any field on the lattice) over
@@ -1053,7 +1012,7 @@ class Network(nn.Module):
         happens to the weights; ``weights_hash`` (the one stored with a saved grid), when given, must be this network's
         canonical_weights_hash().  ``grid`` None drops the cached grid."""
         if grid is None:
-            self._baked = None
+            self._kept.pop('baked', None)
             return
         if weights_hash is not None and weights_hash != self.canonical_weights_hash():
             raise ValueError('set_baked_grid: the grid was baked from other canonical weights (hash %s..., this network '
@@ -1064,8 +1023,9 @@ class Network(nn.Module):
         N = baked_mod.check_resolution(g.shape[0])
         if tuple(g.shape) != (N, N, N, 4) or g.dtype != torch.float16:
             raise ValueError('set_baked_grid: grid must be float16 (N, N, N, 4), got %s %s' % (g.dtype, tuple(g.shape)))
-        self._baked = {'grid': g.to(dev).contiguous(), 'bmin': _vec3(bbox_min, dev).clone(), 'bmax': _vec3(bbox_max, dev).clone(), 'key': None,
-                       'weights': None, 'injected': True, 'refs': None}
+        # injected: no key, no weights -- weights_changed() leaves it, _baked_for_frame returns it unconditionally
+        self._kept['baked'] = Kept(injected=True, grid=g.to(dev).contiguous(), bmin=_vec3(bbox_min, dev).clone(),
+                                   bmax=_vec3(bbox_max, dev).clone())
 
     # baked non-rigid offset field (no counterpart in the reference; humannerf_amd/baked.py) -------------------------
     def _nr_tensors(self):
@@ -1080,6 +1040,11 @@ class Network(nn.Module):
         the device and keeps it for forward (cfg.amd.nonrigid = 'baked').  Nothing is read back: no host
         synchronisation (forward calls this once per frame); the f16-range verdict of the packed image travels with
         forward's watch, and offsets beyond +-65504 m are saturated uncounted."""
+        return self._bake_nonrigid(dst_posevec, iter_val, box, resolution).grid
+
+    def _bake_nonrigid(self, dst_posevec, iter_val, box, resolution, key=None, watched=None):
+        """bake_nonrigid, returning the entry it keeps.  ``key`` / ``watched``: what _baked_nr_for_frame recognises the
+        grid by; a direct call has neither, so no frame hits its grid."""
         from . import baked as baked_mod
         with torch.no_grad():
             M = baked_mod.check_resolution(amd_option('nonrigid_bake_resolution', 128) if resolution is None else resolution)
@@ -1087,58 +1052,51 @@ class Network(nn.Module):
             bmin, bmax = _vec3(box[0], dev), _vec3(box[1], dev)
             posevec = torch.as_tensor(dst_posevec).to(device=dev, dtype=torch.float32).reshape(-1)
             _, cond, _, hann, _ = self._conditioning(posevec, float(iter_val), dev, True, want_rvec=False)
-            mode = self._mlp_mode()
             packed = self._nonrigid_packed(cond)
             if self._nr_bake_ws is None or self._nr_bake_ws[0] != (M, dev):
                 self._nr_bake_ws = ((M, dev), ops.bake_nonrigid_workspace(M, dev))
-            grid = ops.bake_nonrigid(packed, hann, bmin, bmax, M, mode, workspace=self._nr_bake_ws[1])
+            grid = ops.bake_nonrigid(packed, hann, bmin, bmax, M, self._mlp_mode(), workspace=self._nr_bake_ws[1])
             self.nonrigid_bake_count += 1
-            self._baked_nr = {'grid': grid, 'bmin': bmin, 'bmax': bmax, 'packed': packed, 'mode': mode, 'key': None,
-                              'weights': None, 'refs': None}
-            return grid
+            b = self._kept['baked_nr'] = Kept(key, self._weights_gen, self._nr_tensors(), watched, grid=grid, bmin=bmin,
+                                              bmax=bmax, nr_packed=packed)
+            return b
 
     def _baked_nr_for_frame(self, dst_posevec, iter_val, hann_host, bmin, bmax):
         """((off_grid, bmin, bmax), packed image or None) for an inference frame: the grid of the last frame when its
-        key -- non-rigid parameter versions, mlp_mode, M, the host-side Hann weights, whether the condition code is
-        zeroed -- is unchanged and box and ``dst_posevec`` are the same tensor objects at the same ``_version``; else a
-        fresh bake (whose packed image is returned for the f16-range watch).  Identity only: a fresh ``dst_posevec``
-        tensor re-bakes, nothing is compared by value, nothing synchronises."""
+        key -- mlp_mode, M, the host-side Hann weights, whether the condition code is zeroed -- and the non-rigid
+        parameters are unchanged and box and ``dst_posevec`` are the same tensor objects at the same ``_version``; else
+        a fresh bake (whose packed image is returned for the f16-range watch, and only then).  Identity only: a fresh
+        ``dst_posevec`` tensor re-bakes, nothing is compared by value, nothing synchronises."""
         M = int(amd_option('nonrigid_bake_resolution', 128))
-        key = (self._mlp_mode(), M, tuple(hann_host.tolist()), iter_val < cfg.non_rigid_motion_mlp.kick_in_iter,
-               self._weights_gen)
-        watched, weights = (dst_posevec, bmin, bmax), self._nr_tensors()
-        b = self._baked_nr
-        if b is not None and b['key'] == key and _still_resident(b['weights'], weights) \
-                and _still_resident(b['refs'], watched):
-            return (b['grid'], b['bmin'], b['bmax']), None
-        self.bake_nonrigid(dst_posevec, iter_val, (bmin, bmax), M)
-        b = self._baked_nr
-        b['key'], b['weights'], b['refs'] = key, _resident(weights), _resident(watched)
-        return (b['grid'], b['bmin'], b['bmax']), b['packed']
+        key = (self._mlp_mode(), M, tuple(hann_host.tolist()), iter_val < cfg.non_rigid_motion_mlp.kick_in_iter)
+        watched = (dst_posevec, bmin, bmax)
+        b = self._kept.get('baked_nr')
+        if b is not None and b.built_from(key, self._weights_gen, self._nr_tensors()) and b.fed_by(watched):
+            return (b.grid, b.bmin, b.bmax), None
+        b = self._bake_nonrigid(dst_posevec, iter_val, (bmin, bmax), M, key, watched)
+        return (b.grid, b.bmin, b.bmax), b.nr_packed
 
     def _baked_for_frame(self, bbox_min, bbox_max, bbox_scale):
-        """(grid, bmin, bmax) for an inference frame: the injected grid; else the cached one when its key (canonical
-        weight versions, mode, N) and box match; else a fresh bake over the frame's box.  The box is compared like the
-        priors of _weight_volume: the same tensor objects as last frame hit without a look at their values (a render
-        loop keeps them resident), fresh tensors are compared by value once (a device round trip) and remembered."""
-        b = self._baked
-        if b is not None and b['injected']:
-            return b['grid'], b['bmin'], b['bmax']
-        box = (bbox_min, bbox_max if bbox_max is not None else bbox_scale)
-        key = (self._mlp_mode(), int(amd_option('bake_resolution', 256)), self._head, self._weights_gen)
-        if b is not None and b['key'] == key and _still_resident(b['weights'], self._cnl_tensors()):
-            if _still_resident(b['refs'], box):
-                return b['grid'], b['bmin'], b['bmax']
-            dev = b['bmin'].device
-            bmin = _vec3(bbox_min, dev)
-            bmax = _vec3(bbox_max, dev) if bbox_max is not None else bmin + 2.0 / _vec3(bbox_scale, dev)
-            if torch.equal(bmin, b['bmin']) and torch.equal(bmax, b['bmax']):
-                b['refs'] = _resident(box)
-                return b['grid'], b['bmin'], b['bmax']
-        self.bake_canonical(bbox_min, bbox_max, key[1], bbox_scale)
-        b = self._baked
-        b['refs'] = _resident(box)
-        return b['grid'], b['bmin'], b['bmax']
+        """(grid, bmin, bmax) for an inference frame: the injected grid, unconditionally; else the kept one when its key
+        (mode, N, selected head), the canonical weights and the box match; else a fresh bake over the frame's box.  The
+        box is compared like the priors of _weight_volume: the same tensor objects as last frame hit without a look at
+        their values (a render loop keeps them resident), fresh tensors are compared by value once (a device round trip)
+        and remembered."""
+        b = self._kept.get('baked')
+        if b is None or not b.injected:
+            box = (bbox_min, bbox_max if bbox_max is not None else bbox_scale)
+            key = (self._mlp_mode(), int(amd_option('bake_resolution', 256)), self._head)
+
+            def same_box():
+                bmin = _vec3(bbox_min, b.bmin.device)
+                bmax = _vec3(bbox_max, bmin.device) if bbox_max is not None else bmin + 2.0 / _vec3(bbox_scale, bmin.device)
+                return torch.equal(bmin, b.bmin) and torch.equal(bmax, b.bmax)
+
+            if b is None or not (b.built_from(key, self._weights_gen, self._cnl_tensors()) and b.fed_by(box, same_box)):
+                self.bake_canonical(bbox_min, bbox_max, key[1], bbox_scale)
+                b = self._kept['baked']
+                b.remember(box)
+        return b.grid, b.bmin, b.bmax
 
     # mesh extraction (no counterpart in the reference) ------------------------------------------------------------
     # Density at which the canonical surface is cut.  NOT checked on a trained checkpoint (none can be obtained

@@ -174,14 +174,12 @@ def _baked_folder(network, subject, folder):
     _, nonrigid, nr_M = check_amd_options()
     if amd_option('canonical', 'mlp') != 'baked':
         return folder
-    b = getattr(network, '_baked', None)
-    if b is None or not b['injected']:
-        bbox = subject.canonical_bbox
-        mn, mx = bbox['min_xyz'].astype('float32'), bbox['max_xyz'].astype('float32')
-        import torch
-        with torch.no_grad():
-            network._baked_for_frame(torch.from_numpy(mn), torch.from_numpy(mx), None)
-    folder = '%s_baked_%d' % (folder, network._baked['grid'].shape[0])
+    bbox = subject.canonical_bbox
+    mn, mx = bbox['min_xyz'].astype('float32'), bbox['max_xyz'].astype('float32')
+    import torch
+    with torch.no_grad():
+        network._baked_for_frame(torch.from_numpy(mn), torch.from_numpy(mx), None)    # (an injected grid: returned as it is)
+    folder = '%s_baked_%d' % (folder, network.baked_resolution)
     if nonrigid == 'baked' and not cfg.ignore_non_rigid_motions:
         folder += '_nr%d' % nr_M                # the per-frame offset grid (cfg.amd.nonrigid = 'baked'): baked by forward
     return folder

@@ -39,13 +39,8 @@ for iter_val in (100.0, 7000.0, 20000.0, 1e7):
     for name, opts, frames in PATHS:
         for k, v in dict(DEFAULTS, **opts).items():
             setattr(cfg.amd, k, v)
-        net._cnl_pack = None                             # (a fresh pack, audit schedule and grids for every path)
-        if hasattr(net, 'f16_guard'):
-            net.f16_guard.restart_schedule()
-        else:
-            net._guard_state = None                      # (a checkout from before the guard left Network)
+        net.weights_changed()                            # (a fresh pack, audit schedule and grids for every path)
         net.set_baked_grid(None, None, None)
-        net._baked_nr = None
         for f in range(frames):
             with torch.no_grad():
                 out = net(**data, iter_val=iter_val)

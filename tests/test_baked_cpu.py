@@ -139,7 +139,7 @@ def test_grid_files_round_trip_and_the_weight_hash_is_checked(tmp_path):
     assert np.array_equal(back['bbox_min'], lo) and np.array_equal(back['bbox_max'], hi)
     assert back['N'] == N and back['mode'] == 'f16x3' and back['weights_hash'] == h
     net.set_baked_grid(back['grid'], back['bbox_min'], back['bbox_max'], weights_hash=back['weights_hash'])
-    assert net._baked['injected'] and torch.equal(net._baked['grid'], torch.from_numpy(grid))
+    assert net._kept['baked'].injected and torch.equal(net._kept['baked'].grid, torch.from_numpy(grid))
     with torch.no_grad():
         net.cnl_mlp.module.output_linear[0].bias[3] += 1.0
     assert net.canonical_weights_hash() != h

@@ -232,7 +232,7 @@ def test_network_refuses_baked_offsets_without_a_baked_canonical():
     """Option handling of Network.forward, without a GPU: the inconsistent pair raises before anything is launched."""
     from humannerf_amd.network import Network
     net = Network().eval()
-    assert net.nonrigid_bake_count == 0 and net._baked_nr is None
+    assert net.nonrigid_bake_count == 0 and 'baked_nr' not in net._kept
     fr = scene.synthetic_frame(H=8, W=8)
     keys = ['rays', 'near', 'far', 'dst_Rs', 'dst_Ts', 'cnl_gtfms', 'motion_weights_priors', 'dst_posevec',
             'cnl_bbox_min_xyz', 'cnl_bbox_scale_xyz', 'bgcolor']

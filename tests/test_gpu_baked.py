@@ -238,7 +238,7 @@ def test_baked_frame_against_the_oracle(net, golden_case, state):
             d = frame_to_gpu(fr)
             out = net(**d, iter_val=m['iter_val'])
             assert net.check_f16_range(wait=True) is False
-            grid, bmin, bmax = (net._baked[k].cpu().numpy() for k in ('grid', 'bmin', 'bmax'))
+            grid, bmin, bmax = (getattr(net._kept['baked'], k).cpu().numpy() for k in ('grid', 'bmin', 'bmax'))
             k1, _, _, _ = frame_parts(net, fr, use_nonrigid=False)
             z, _, mask, _ = ops.sample_warp(*k1, m['N_samples'])
     finally:
@@ -303,7 +303,7 @@ def test_network_forward_with_the_baked_option(net, state, frame):
             # another resolution is another key
             cfg.amd.bake_resolution = 24
             net(**d, iter_val=1e7)
-            assert net.bake_count == c0 + 4 and net._baked['grid'].shape[0] == 24
+            assert net.bake_count == c0 + 4 and net._kept['baked'].grid.shape[0] == 24
             # an injected analytic grid is used as it is, and never re-baked
             vals = torch.tensor([0.0, 1.0, -1.0, 50.0])
             const = vals.half().expand(16, 16, 16, 4).contiguous()
@@ -339,12 +339,12 @@ def test_network_forward_with_the_baked_option(net, state, frame):
         assert tb['rgb'].requires_grad and net.bake_count == c1
         assert all(same_bits(tb[k].detach(), tm[k].detach()) for k in ('rgb', 'alpha', 'depth'))
         # back at 'mlp' with a grid still cached: the exact path, as of a network that never baked
-        assert net._baked is not None
+        assert 'baked' in net._kept
         with torch.no_grad():
             back = net(**d, iter_val=1e7)
             never = load_net(state)
             ref = never(**d, iter_val=1e7)
-        assert never.bake_count == 0 and never._baked is None
+        assert never.bake_count == 0 and 'baked' not in never._kept
         assert all(same_bits(back[k], ref[k]) for k in ref) and all(same_bits(back[k], exact[k]) for k in exact)
     finally:
         with torch.no_grad():
@@ -405,10 +405,10 @@ def test_the_grid_converges_to_the_mlp(state, frame):
         for N in (128, 32, 16):
             cfg.amd.bake_resolution = N
             out = n(**d, iter_val=1e7)
-            assert n._baked['grid'].shape[0] == N
+            assert n._kept['baked'].grid.shape[0] == N
             err[N] = float((out['rgb'] - exact['rgb']).abs().max())
             if N == 128:
-                floor = 4 * 2.0 ** -11 * float(n._baked['grid'].float().abs().max()) / 4
+                floor = 4 * 2.0 ** -11 * float(n._kept['baked'].grid.float().abs().max()) / 4
     coarse = 32 if err[32] > floor else 16
     print('max |d rgb|: N=128 %.3e, N=32 %.3e, N=16 %.3e; f16 floor %.3e; coarse grid %d'
           % (err[128], err[32], err[16], floor, coarse))

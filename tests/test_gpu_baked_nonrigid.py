@@ -209,7 +209,7 @@ def test_network_forward_with_both_options_baked(net, state, frame, convergence)
             c0, b0 = net.nonrigid_bake_count, net.bake_count
             first = net(**d, iter_val=1e7)
             assert net.nonrigid_bake_count == c0 + 1 and net.bake_count == b0
-            assert net._baked_nr['grid'].shape == (32, 32, 32, 4)
+            assert net._kept['baked_nr'].grid.shape == (32, 32, 32, 4)
             assert set(first) == set(exact) == KEYS11
             assert all(first[k].shape == exact[k].shape and first[k].dtype == exact[k].dtype for k in exact)
             assert same_bits(first['backward_motion_weights'], exact['backward_motion_weights'])     # K1 stays exact
@@ -242,7 +242,7 @@ def test_network_forward_with_both_options_baked(net, state, frame, convergence)
             assert net.nonrigid_bake_count == c0 + 6 and all(same_bits(first[k], other[k]) for k in first)
             cfg.amd.nonrigid_bake_resolution = 24                                   # another M is another key
             net(**fresh, iter_val=1e7)
-            assert net.nonrigid_bake_count == c0 + 7 and net._baked_nr['grid'].shape[0] == 24
+            assert net.nonrigid_bake_count == c0 + 7 and net._kept['baked_nr'].grid.shape[0] == 24
             cfg.amd.nonrigid_bake_resolution = 32
             assert net.bake_count == b0                                             # (the canonical grid never moved)
             # the lean form: the same picture

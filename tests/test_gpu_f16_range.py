@@ -521,7 +521,7 @@ def test_render_frames_under_each_policy(policy, hot_net, monkeypatch):
         want = render.render_frames(net, frames)
         cfg.amd.mlp_mode, cfg.amd.on_f16_range = 'f16x3', policy
         net.f16_guard.reset()
-        net._cnl_pack = None
+        net._drop(lambda e: e.packed is not None)
         monkeypatch.setattr(net, 'forward', counting)
         if policy == 'raise':
             with pytest.raises(ActivationRangeError):
@@ -543,4 +543,4 @@ def test_render_frames_under_each_policy(policy, hot_net, monkeypatch):
     finally:
         cfg.amd.diagnostics, cfg.amd.mlp_mode, cfg.amd.on_f16_range = True, 'f16x3', 'raise'
         net.f16_guard.reset()
-        net._cnl_pack = None
+        net._drop(lambda e: e.packed is not None)

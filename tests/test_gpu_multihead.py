@@ -252,7 +252,7 @@ def test_frame_all_heads(mode, diag, heads_net, heads_frame, fixture_npz):
         hid = torch.tensor(1, device=dev())
         a = net(**heads_frame, head_id=hid)
         b = net(**heads_frame, head_id=hid)
-        assert net._head_id_seen[0] is hid and torch.equal(a['rgb'], every['rgb'][1]) and torch.equal(b['rgb'], a['rgb'])
+        assert net._kept['head_id'].inputs[0][0]() is hid and torch.equal(a['rgb'], every['rgb'][1]) and torch.equal(b['rgb'], a['rgb'])
 
 
 def test_frame_all_heads_direct_abi(heads_net, heads_frame):

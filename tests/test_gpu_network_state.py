@@ -518,10 +518,10 @@ def test_bake_resolution_change(world, monkeypatch):
         before = render(live, batch)
         cfg.amd.bake_resolution = 24
         fine = twice(live, batch, cold_frame(live, batch), monkeypatch, first={'bake': 1})
-        assert live._baked['grid'].shape[0] == 24 and moved(fine, before) > MOVED
+        assert live._kept['baked'].grid.shape[0] == 24 and moved(fine, before) > MOVED
         cfg.amd.bake_resolution = 16
         back = twice(live, batch, cold_pair(live, batch), monkeypatch, first={'bake': 1})
-        assert live._baked['grid'].shape[0] == 16 and same(back, before)
+        assert live._kept['baked'].grid.shape[0] == 16 and same(back, before)
 
 
 def test_select_head_with_a_grid_cached(world, monkeypatch):
@@ -546,11 +546,11 @@ def test_head_id_device_tensor_edited_in_place(world, monkeypatch):
         live = new_net(world.states['heads'])
         hid = torch.tensor(0, device=DEV)
         before = render(live, batch, head_id=hid)
-        assert same(render(live, batch, head_id=hid), before) and live._head_id_seen[0] is hid
+        assert same(render(live, batch, head_id=hid), before) and live._kept['head_id'].inputs[0][0]() is hid
         hid.fill_(2)
         want = cold_pair(live, batch, head_id=2)
         after = twice(live, batch, want, monkeypatch, head_id=hid, first={'pack': 1})
-        assert live._head_id_seen[2] == 2 and moved(after, before) > MOVED
+        assert live._kept['head_id'].value == 2 and moved(after, before) > MOVED
 
 
 def test_injected_grid_is_never_rebaked(world, monkeypatch):
@@ -571,10 +571,10 @@ def test_injected_grid_is_never_rebaked(world, monkeypatch):
         cold.set_baked_grid(grid, *box)
         want = render(cold, batch)
         after = twice(live, batch, want, monkeypatch, first={'pack': 1, 'decode': 1})     # (everything but the grid)
-        assert same(after, before) and live.bake_count == 1 and live._baked['injected']
+        assert same(after, before) and live.bake_count == 1 and live._kept['baked'].injected
         live.set_baked_grid(None, None, None)
         baked = twice(live, batch, cold_pair(live, batch), monkeypatch, first={'bake': 1})
-        assert moved(baked, before) > MOVED and live._baked['grid'].shape[0] == 16
+        assert moved(baked, before) > MOVED and live._kept['baked'].grid.shape[0] == 16
 
 
 def test_samples_and_chunk_change_on_one_workspace(world, monkeypatch):

@@ -194,7 +194,7 @@ def test_f16_range_guard_of_inference(which, diag, gpu_net, golden_frame, seeded
             sd[which].copy_(torch.from_numpy(seeded_params[which]))
         cfg.amd.on_f16_range, cfg.amd.diagnostics, cfg.perturb = 'raise', True, 1.0
         gpu_net.f16_guard.reset()
-        gpu_net._cnl_pack = None
+        gpu_net._drop(lambda e: e.packed is not None)
 
 
 def test_lean_path_equals_diagnostic_path(gpu_net, golden_frame, monkeypatch):

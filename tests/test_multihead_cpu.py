@@ -104,7 +104,7 @@ def test_head_selection_and_pack_keys(net3, monkeypatch):
 
     monkeypatch.setattr(ops, 'canonical_pack', single)
     monkeypatch.setattr(ops, 'canonical_heads_pack', heads)
-    net3._cnl_head_packs.clear()
+    net3._drop(lambda e: e.packed is not None)
     net3.select_head(None)
     with pytest.raises(RuntimeError, match='select_head'):
         net3._canonical_packed()
@@ -116,14 +116,14 @@ def test_head_selection_and_pack_keys(net3, monkeypatch):
         kind, shape, wp, bp, out = calls[-1]
         assert (kind, shape, out) == ('single', (4, 256), None)
         assert wp == W.data_ptr() + 4 * h * 256 * 4 and bp == b.data_ptr() + 4 * h * 4
-        assert net3._cnl_pack[0][:2] == (net3._mlp_mode(), h) and net3._cnl_pack[1] is images[h]
+        assert net3._kept[net3._pack_last].key == (net3._mlp_mode(), h) and net3._kept[net3._pack_last].packed is images[h]
     n = len(calls)
     for h in (0, 1, 2):                                             # every head keeps its image: nothing is packed again
         assert net3.select_head(h)._canonical_packed() is images[h]
     assert len(calls) == n
     net3._head = -1                                                 # what forward(head_id=-1) sets for the frame
     every = net3._canonical_packed()
-    assert calls[-1][:3] == ('heads', (12, 256), 3) and net3._cnl_pack[0][1] == -1
+    assert calls[-1][:3] == ('heads', (12, 256), 3) and net3._kept[net3._pack_last].key[1] == -1
     assert all(every is not v for v in images.values())
     with torch.no_grad():
         W.add_(0)                                                   # a weight update: the key's versions change

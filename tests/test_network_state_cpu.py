@@ -72,6 +72,7 @@ def test_weight_keyed_entries_follow_the_rule(net, monkeypatch):
     load_state_dict, a move or cast of the module) and which do not (nothing, and a write through ``.data`` without
     weights_changed -- the documented blind spot)."""
     from humannerf_amd import ops
+    from humannerf_amd.kept import Kept
     packs, decodes = [], []
     monkeypatch.setattr(ops, 'canonical_pack', lambda ws, bs, mode='f32', out=None: packs.append(out) or torch.zeros(4))
     dec = net.mweight_vol_decoder
@@ -101,7 +102,7 @@ def test_weight_keyed_entries_follow_the_rule(net, monkeypatch):
     head.weight.data.mul_(1.5)                                       # unseen ...
     assert rebuilt() == (0, 0)
     assert net.weights_changed() is net                              # ... until the documented call
-    assert net._cnl_pack is None and net._vol_cache is None
+    assert ('pack', None) not in net._kept and 'vol' not in net._kept
     assert rebuilt() == (1, 1) and rebuilt() == (0, 0)
     old_w, old_e = head.weight, dec.const_embedding
     head.weight, dec.const_embedding = _alias(old_w), _alias(old_e)  # replaced Parameters at the old (data_ptr, _version)
@@ -111,27 +112,168 @@ def test_weight_keyed_entries_follow_the_rule(net, monkeypatch):
     assert rebuilt() == (0, 0)
     # load_state_dict and Module._apply (every move and cast) drop the entries themselves, at once
     net.load_state_dict(net.state_dict())
-    assert net._cnl_pack is None and net._vol_cache is None
+    assert ('pack', None) not in net._kept and 'vol' not in net._kept
     assert rebuilt() == (1, 1) and rebuilt() == (0, 0)
     net.load_state_dict(net.state_dict(), assign=True)
-    assert net._cnl_pack is None and net._vol_cache is None
+    assert ('pack', None) not in net._kept and 'vol' not in net._kept
     assert rebuilt() == (1, 1) and rebuilt() == (0, 0)
     net.float()
-    assert net._cnl_pack is None and net._vol_cache is None
+    assert ('pack', None) not in net._kept and 'vol' not in net._kept
     assert rebuilt() == (1, 1) and rebuilt() == (0, 0)
     # an injected grid outlives weights_changed, a baked one does not
-    net._baked = {'injected': False}
-    net._baked_nr = {}
+    net._kept['baked'], net._kept['baked_nr'] = Kept(), Kept()
     net.weights_changed()
-    assert net._baked is None and net._baked_nr is None
-    net._baked = {'injected': True}
+    assert 'baked' not in net._kept and 'baked_nr' not in net._kept
+    injected = net._kept['baked'] = Kept(injected=True)
     net.weights_changed()
-    assert net._baked == {'injected': True}
-    net._baked = None
+    assert net._kept['baked'] is injected
+    net.set_baked_grid(None, None, None)
+    assert 'baked' not in net._kept
     # the guard's audit schedule restarts with the weights
     net.f16_guard._schedule = ['k', 3]
     net.weights_changed()
     assert net.f16_guard._schedule is None
+
+
+def test_kept_entry_alone():
+    """kept.Kept without a Network: the weights test fails on another key, another generation and each of the three ways
+    _still_resident fails; the input ladder hits by identity without a comparison, compares fresh tensors once and then
+    hits by identity, and without the callable never matches fresh tensors."""
+    from humannerf_amd.kept import Kept
+    p, q = torch.nn.Parameter(torch.arange(6.)), torch.nn.Parameter(torch.ones(3))
+    key = ('f16x3', 1)
+    e = Kept(key, 4, [p, q])
+    assert e.built_from(key, 4, [p, q])
+    assert not e.built_from(('f16x3', 2), 4, [p, q])                 # another key
+    assert not e.built_from(key, 5, [p, q])                          # another weights generation
+    assert not e.built_from(key, 4, [p, _alias(q)])                  # another object at an equal (data_ptr, _version)
+    with torch.no_grad():
+        q.add_(0)
+    assert not e.built_from(key, 4, [p, q])                          # a later _version
+    e = Kept(key, 4, [p, q])
+    assert e.built_from(key, 4, [p, q])
+    p.data = p.data.clone()
+    assert not e.built_from(key, 4, [p, q])                          # another data_ptr
+    assert not Kept(key, 4).built_from(key, 4, [])                   # built from no weights (injected): never
+    with pytest.raises(TypeError):
+        Kept(key, 4, image=torch.zeros(4))                           # (payload has its names)
+
+    def never():
+        raise AssertionError('compared by value')
+
+    asked = []
+    a, b = torch.arange(3.), torch.ones(3)
+    e = Kept(inputs=(a, b), value=7)
+    assert e.value == 7 and e.packed is None and not e.injected
+    assert e.fed_by((a, b), never)                                   # identity: the callable is not asked
+    a2, b2 = a.clone(), b.clone()
+    assert not e.fed_by((a2, b2), lambda: asked.append(0) or False) and e.fed_by((a, b), never)     # (unequal: kept as it was)
+    assert e.fed_by((a2, b2), lambda: asked.append(1) or True) and asked == [0, 1]                  # asked once ...
+    assert e.fed_by((a2, b2), never) and not e.fed_by((a, b))        # ... then these objects hit, the old ones do not
+    assert not e.fed_by((a2.clone(), b2.clone())) and not e.fed_by((a2.clone(), b2.clone()))        # no callable: never
+    assert e.fed_by((a2, b2), never)
+    a2.add_(0)
+    assert not e.fed_by((a2, b2))                                    # written in place
+    e = Kept()
+    assert not e.fed_by((a, b))                                      # nothing remembered
+    e.remember((a, b))
+    assert e.fed_by((a, b), never)
+
+
+from test_multihead_cpu import net3                                  # noqa: E402,F401  (the 3-head Network on the CPU)
+
+PRIORS = torch.ones(25, 2, 2, 2)
+
+
+def _stubbed(net, monkeypatch):
+    """The packers and the decoder of ``net`` replaced by counters: (the ``out=`` of every pack, an item per decode)."""
+    from humannerf_amd import ops
+    packs, decodes = [], []
+    monkeypatch.setattr(ops, 'canonical_pack', lambda ws, bs, mode='f32', out=None: packs.append(out) or torch.zeros(4))
+    monkeypatch.setattr(ops, 'canonical_heads_pack',
+                        lambda ws, bs, n_heads, mode='f32', out=None: packs.append(out) or torch.zeros(4))
+    monkeypatch.setattr(net.mweight_vol_decoder, 'forward',
+                        lambda motion_weights_priors, **_: decodes.append(1) or torch.zeros(1, 25, 2, 2, 2))
+    return packs, decodes
+
+
+def _fill(net):
+    """An entry of every kind ``net`` can hold, none injected: the packed images (every head and the all-heads image of
+    a multi-head network) and the weight volume through their sites; the two grids, a head id, another image and one
+    of no kind at all planted.  Returns the heads packed."""
+    from humannerf_amd.kept import Kept
+    heads = list(range(-1, net.head_num)) if net.head_num else [None]
+    net.eval()
+    with torch.no_grad():
+        for h in heads:
+            net._head = h
+            net._canonical_packed()
+        net._head = None
+        net._weight_volume(PRIORS)
+    gen = net._weights_gen
+    net._kept['baked'] = Kept(('f16x3', 16, None), gen, net._cnl_tensors(), grid=torch.zeros(2, 2, 2, 4))
+    net._kept['baked_nr'] = Kept(('f16x3', 16), gen, net._nr_tensors(), grid=torch.zeros(2, 2, 2, 4), nr_packed=torch.zeros(4))
+    net._kept['head_id'] = Kept(inputs=(PRIORS,), value=1)
+    net._kept['another image'] = Kept(('f16x3', 9), gen, net._cnl_tensors(), packed=torch.zeros(4), serial=0)
+    net._kept['a seventh'] = Kept()
+    return heads
+
+
+@pytest.mark.parametrize('which', ['net', 'net3'])
+def test_no_entry_can_be_forgotten(which, request, monkeypatch):
+    """weights_changed() leaves nothing that is not injected, check_f16_range() after a hit no packed canonical image
+    and everything else -- whatever the entries are called: the network's own collection is what is looked through."""
+    from humannerf_amd.kept import Kept
+    net = request.getfixturevalue(which)
+    _stubbed(net, monkeypatch)
+    net.weights_changed()
+    heads = _fill(net)
+    assert {('pack', h) for h in heads} | {'vol'} <= set(net._kept) and len(net._kept) == len(heads) + 6
+    injected = net._kept['baked'] = Kept(injected=True, grid=torch.zeros(2, 2, 2, 4))
+    assert net.weights_changed() is net
+    assert all(e.injected for e in net._kept.values()) and list(net._kept.items()) == [('baked', injected)]
+    net.set_baked_grid(None, None, None)
+    # the canonical-image drop after a hit of the f16-range guard
+    _fill(net)
+    others = {n: e for n, e in net._kept.items() if e.packed is None}
+    assert set(others) == {'vol', 'baked', 'baked_nr', 'head_id', 'a seventh'} and len(net._kept) == len(heads) + 6
+    monkeypatch.setattr(net.f16_guard, 'check', lambda wait=True, upto=None: (True, False))
+    monkeypatch.setattr(net.f16_guard, 'act', lambda *hit: any(hit))
+    monkeypatch.setattr(net.f16_guard, 'plan', lambda mode, n_chunks, weights_key: weights_key)
+    assert net._guard_plan('f16x3', 1) == net._kept[('pack', heads[-1])].serial == net._pack_serial   # (the image used last)
+    assert net.check_f16_range() is True
+    assert all(e.packed is None for e in net._kept.values())        # selected head, other heads, all heads: gone
+    assert net._kept == others and net._kept['baked_nr'].nr_packed is not None and net._kept['vol'].vol is not None
+    assert net._guard_plan('f16x3', 1) is None                      # (the image used last is gone: no serial)
+    net.weights_changed()
+    assert net._kept == {}
+
+
+@pytest.mark.parametrize('which', ['net', 'net3'])
+def test_a_generation_step_alone_outdates_every_weight_keyed_entry(which, request, monkeypatch):
+    """``_weights_gen += 1``, what a train-path _forward does, and nothing else: every entry built from weights misses
+    its weights test, the packed images are packed again into their own buffers, the volume is decoded again."""
+    net = request.getfixturevalue(which)
+    packs, decodes = _stubbed(net, monkeypatch)
+    net.weights_changed()
+    heads = _fill(net)
+    images = [net._kept[('pack', h)].packed for h in heads]
+    assert (len(packs), len(decodes)) == (len(heads), 1) and all(out is None for out in packs)
+    _fill(net)
+    assert (len(packs), len(decodes)) == (len(heads), 1)             # unchanged: every site hits
+    keyed = {n: e for n, e in net._kept.items() if e.weights is not None}
+    assert set(keyed) == {('pack', h) for h in heads} | {'vol', 'baked', 'baked_nr', 'another image'}
+    params = {n: [ref() for ref, _, _ in e.weights] for n, e in keyed.items()}
+    assert all(e.built_from(e.key, net._weights_gen, params[n]) for n, e in keyed.items())
+    net._weights_gen += 1
+    assert not any(e.built_from(e.key, net._weights_gen, params[n]) for n, e in keyed.items())
+    _fill(net)
+    assert len(decodes) == 2 and len(packs) == 2 * len(heads)
+    assert all(out is image for out, image in zip(packs[len(heads):], images))     # (each image's buffer is used again)
+    assert all(net._kept[('pack', h)].gen == net._weights_gen for h in heads) and net._kept['vol'].gen == net._weights_gen
+    _fill(net)
+    assert (len(packs), len(decodes)) == (2 * len(heads), 2)
+    net.weights_changed()
 
 
 def test_broadcasts_tell_the_network(tmp_path):
