@@ -51,8 +51,9 @@ struct CnlSource {
 constexpr BakedGrid kNoOffGrid{nullptr, 0, nullptr, nullptr};
 
 // Shared underflowing inputs (hnrf.h, hnrf_render_frame_shared_fwd): the chunk's ShareOut -- c_off / c_xyz / c_raw in the
-// frame's representative slot (16 floats: x = +0 at [0..2], c_off at [4..6], c_xyz at [8..10], c_raw at [12..15]), the
-// chunk's live count.  out null = off.  fused: K1 has already classified (hnrf_sample_warp_share_fwd): idx, the count
+// frame's representative slot (x = +0 at floats [0..2], c_off at [4..6], c_xyz at [8..10], c_raw [n][4] from [12]: 44
+// floats of the slot's 64 with the 8 planes of hnrf_render_frame_heads_shared_fwd), the chunk's live count and its
+// planes.  out null = off.  fused: K1 has already classified (hnrf_sample_warp_share_fwd): idx, the count
 // and the fills are written; otherwise hnrf_share_compact runs here.
 struct Share {
     const ShareOut* out;
@@ -220,11 +221,17 @@ extern "C" int hnrf_render_rays_baked_nr_fwd(const float* rays_o, const float* r
 // the critical path (3 % of a 512x512x128 frame).  Two workspaces alternate; the caller provides the events.
 //
 // The frame workspace for chunks of `rows` rays, the one statement of its size: the two chunk workspaces, behind them --
-// share -- the 256 bytes of the representative slot, or -- n_heads >= 2 -- the n_heads raw planes of one chunk (K3 and
-// the K4s of a chunk run on `stream` in order, so one set serves every chunk).
+// share -- the 256 bytes of the representative slot, and -- n_heads >= 2 -- the n_heads raw planes of one chunk.  K3 and
+// the K4s of a chunk run on `stream` in order, so one set of planes serves every chunk -- unless the inputs are shared:
+// then K1 of chunk i+1 fills the shared rows of its planes on the side stream while the K4s of chunk i still read
+// theirs, and two sets alternate like the chunk workspaces (set i & 1; K1 of chunk i+1 waits for ev_done of chunk i-1,
+// the last reader of that set).
+static size_t plane_set_bytes(int64_t rows, int S, int n_heads) {
+    return align256((size_t)n_heads * (size_t)rows * (size_t)S * 16);
+}
 static size_t frame_ws_bytes(int64_t rows, int S, bool share, int n_heads) {
     return 2 * hnrf_render_workspace_bytes(rows, S) + (share ? 256 : 0) +
-           (n_heads ? align256((size_t)n_heads * (size_t)rows * (size_t)S * 16) : 0);
+           (n_heads ? (share ? 2 : 1) * plane_set_bytes(rows, S, n_heads) : 0);
 }
 extern "C" size_t hnrf_render_frame_workspace_bytes(int64_t chunk, int S) { return frame_ws_bytes(chunk, S, false, 0); }
 extern "C" size_t hnrf_render_frame_shared_workspace_bytes(int64_t chunk, int S) { return frame_ws_bytes(chunk, S, true, 0); }
@@ -232,11 +239,15 @@ extern "C" size_t hnrf_render_frame_heads_workspace_bytes(int64_t chunk, int S, 
     if (chunk < 0 || S < 0 || n_heads < 2 || n_heads > 8) return 0;
     return frame_ws_bytes(chunk, S, false, n_heads);
 }
+extern "C" size_t hnrf_render_frame_heads_shared_workspace_bytes(int64_t chunk, int S, int n_heads) {
+    if (chunk < 0 || S < 0 || n_heads < 2 || n_heads > 8) return 0;
+    return frame_ws_bytes(chunk, S, true, n_heads);
+}
 
 namespace {
 // What a frame entry asks for beside the plain frame.  Three types that do not convert into each other: a call site
-// that names them in the wrong order does not compile.  Shared inputs or heads, not both (the slot and the planes
-// start at the same byte behind the chunk workspaces).
+// that names them in the wrong order does not compile.  Shared inputs and heads go together
+// (hnrf_render_frame_heads_shared_fwd): the slot first, the planes -- two sets then, frame_ws_bytes -- behind it.
 struct FrameOpts {
     int* live_counts = nullptr;           // shared underflowing inputs: the live count of every chunk (null = off)
     int n_heads = 0;                      // >= 2: every head of a multi-head canonical image, with
@@ -259,7 +270,9 @@ int render_frame(const char* who, const Rays& rays, const WarpField& field, cons
     HNRF_REQUIRE(workspace_bytes >= ws_all, HNRF_E_WORKSPACE, "%s: workspace %zu < %zu bytes", who, workspace_bytes, ws_all);
     HNRF_REQUIRE(nr_packed == nullptr || hann_w != nullptr, HNRF_E_ARG, "%s: hann_w missing", who);
     const int n_planes = opt.n_heads ? opt.n_heads : 1;
-    float* heads_raw = opt.n_heads ? (float*)((char*)workspace + 2 * ws_one) : nullptr;     // (null: the chunk's own raw)
+    // the planes of chunk i (null: the chunk's own raw)
+    char* const heads_raw = opt.n_heads ? (char*)workspace + 2 * ws_one + (share ? 256 : 0) : nullptr;
+    const size_t heads_set = share ? plane_set_bytes(cr, S, n_planes) : 0;
     HNRF_REQUIRE(!share || ((mode & HNRF_MLP_ARITH_MASK) == HNRF_MLP_F16X3 && nr_packed && cnl.packed && !cnl.grid &&
                             !off.grid && cull_eps == 0.f), HNRF_E_UNSUPPORTED,
                  "%s: shared inputs exist for HNRF_MLP_F16X3 with both MLPs and cull_eps == 0 only", who);
@@ -281,13 +294,16 @@ int render_frame(const char* who, const Rays& rays, const WarpField& field, cons
         RenderCarve c;
         FrameOut o;
         ShareOut sh;
+        float* raw;                                               // its n_planes raw planes, R S float4s apart
     };
     auto chunk_at = [&](int64_t i) {
         const int64_t r0 = i * chunk, R = (N - r0 < chunk) ? N - r0 : chunk;
         Chunk k{R, rays.rows(r0, S), render_carve((char*)workspace + (size_t)(i & 1) * ws_one, R, S),
-                out.rows(r0, S, field.B), ShareOut{}};
+                out.rows(r0, S, field.B), ShareOut{}, nullptr};
+        k.raw = heads_raw ? (float*)(heads_raw + (size_t)(i & 1) * heads_set) : k.c.raw;
         if (share)
-            k.sh = ShareOut{rep + 4, rep + 8, rep + 12, k.c.idx, opt.live_counts + i, (float4*)k.c.raw, k.o.offsets, k.o.xyz};
+            k.sh = ShareOut{rep + 4, rep + 8, rep + 12, k.c.idx, opt.live_counts + i, (float4*)k.raw, k.o.offsets, k.o.xyz,
+                            n_planes, R * (int64_t)S};
         return k;
     };
     auto warp = [&](int64_t i) {                                  // K1 of chunk i on the side stream
@@ -300,13 +316,17 @@ int render_frame(const char* who, const Rays& rays, const WarpField& field, cons
         // the representative x = (+0, +0, +0) through the chunks' kernel instances (guarded unless no chunk is: the
         // guard sees the shared class through it), once per frame; no mlp_events around it.  In front of K1 of chunk 0
         // and of ev_in: the fused K1 reads c_off / c_xyz / c_raw and counts into live_counts, on either stream.  (K1 of
-        // chunk i+1 writes idx and the raw fills of the workspace chunk i-1 used: it waits for ev_done of chunk i-1,
-        // recorded behind that chunk's K4, the last reader of both.)
+        // chunk i+1 writes idx and the raw fills of the workspace -- with heads: of the plane set -- chunk i-1 used: it
+        // waits for ev_done of chunk i-1, recorded behind that chunk's last K4, the last reader of both.)  With heads K3
+        // writes the representative's P = 1 planes 4 floats apart: c_raw [n][4].
         const int rmode = mode & (HNRF_MLP_ARITH_MASK | HNRF_MLP_NO_RANGE_GUARD);
         HNRF_HIP(hipMemsetAsync(rep, 0, 64, st));
         HNRF_HIP(hipMemsetAsync(opt.live_counts, 0, (size_t)nchunk * sizeof(int), st));
         if ((rc = hnrf_nonrigid_fwd_sparse(rep, hann_w, nr_packed, rmode, 1, nullptr, nullptr, rep + 8, rep + 4, st))) return rc;
-        if ((rc = hnrf_canonical_fwd_sparse(rep + 8, cnl.packed, rmode, 1, nullptr, nullptr, rep + 12, st))) return rc;
+        if ((rc = opt.n_heads ? hnrf_canonical_heads_fwd_sparse(rep + 8, cnl.packed, rmode, 1, opt.n_heads, nullptr, nullptr,
+                                                                rep + 12, st)
+                              : hnrf_canonical_fwd_sparse(rep + 8, cnl.packed, rmode, 1, nullptr, nullptr, rep + 12, st)))
+            return rc;
     }
     if (two) {
         ev_in = (hipEvent_t)events[0];
@@ -333,7 +353,7 @@ int render_frame(const char* who, const Rays& rays, const WarpField& field, cons
         FrameOut po[8] = {k.o};                                   // the planes' rows of this chunk
         for (int g = 1; g < n_planes; ++g) po[g] = opt.head_out[g].rows(i * chunk, S, field.B);
         if ((rc = render_chunk(k.c, k.rays.d, hann_w, nr_packed, off, cnl, bgcolor, cmode, cull_eps, k.R, S,
-                               Planes{n_planes, heads_raw ? heads_raw : k.c.raw, po},
+                               Planes{n_planes, k.raw, po},
                                mlp_events ? mlp_events[2 * i] : nullptr, mlp_events ? mlp_events[2 * i + 1] : nullptr, st,
                                Share{share ? &k.sh : nullptr, fused}))) return rc;
         if (two) HNRF_HIP(hipEventRecord(ev_done[i & 1], st));
@@ -362,18 +382,15 @@ extern "C" int hnrf_render_frame_fwd(const float* rays_o, const float* rays_d, c
                         side_stream, events, mlp_events, stream);
 }
 
-extern "C" int hnrf_render_frame_heads_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
-                                           const float* t_rand, const float* motion_Rs, const float* motion_Ts,
-                                           const float* vol, const float* bbox_min, const float* bbox_scale,
-                                           const float* hann_w, const void* nr_packed, const void* cnl_packed,
-                                           const float* bgcolor, int mode, float cull_eps, int64_t N, int S, int B, int G,
-                                           int64_t chunk, int n_heads, void* workspace, size_t workspace_bytes,
-                                           float* const* rgb, float* const* alpha, float* const* depth,
-                                           float* const* weights_on_rays, float* const* rgb_on_rays, float* const* cnl_xyz,
-                                           float* const* cnl_rgb, float* const* cnl_weight, float* xyz_on_rays, float* bmw,
-                                           float* offsets, void* side_stream, void* const* events,
-                                           void* const* mlp_events, void* stream) {
-    const char* who = "hnrf_render_frame_heads_fwd";
+// hnrf_render_frame_heads_fwd and -- live_counts -- hnrf_render_frame_heads_shared_fwd: the per-head planes checked and
+// bundled, then the frame
+static int frame_heads(const char* who, const Rays& rays, const WarpField& field, const float* hann_w, const void* nr_packed,
+                       const void* cnl_packed, const float* bgcolor, int mode, float cull_eps, int64_t N, int S,
+                       int64_t chunk, int n_heads, void* workspace, size_t workspace_bytes, float* const* rgb,
+                       float* const* alpha, float* const* depth, float* const* weights_on_rays, float* const* rgb_on_rays,
+                       float* const* cnl_xyz, float* const* cnl_rgb, float* const* cnl_weight, float* xyz_on_rays, float* bmw,
+                       float* offsets, int* live_counts, void* side_stream, void* const* events, void* const* mlp_events,
+                       void* stream) {
     HNRF_REQUIRE(n_heads >= 2 && n_heads <= 8, HNRF_E_ARG, "%s: n_heads=%d outside 2..8", who, n_heads);
     HNRF_REQUIRE(rgb && alpha && depth, HNRF_E_ARG, "%s: null output array", who);
     const bool diag = weights_on_rays != nullptr;
@@ -388,11 +405,43 @@ extern "C" int hnrf_render_frame_heads_fwd(const float* rays_o, const float* ray
                                 cnl_weight[g], xyz_on_rays, bmw, offsets}
                      : FrameOut{rgb[g], alpha[g], depth[g], nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, bmw, nullptr};
     }
-    return render_frame(who, Rays{rays_o, rays_d, near, far, t_rand},
-                        WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, hann_w, nr_packed, kNoOffGrid,
-                        CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr}, bgcolor, mode, cull_eps, N, S, chunk,
-                        workspace, workspace_bytes, ho[0], side_stream, events, mlp_events, stream,
-                        FrameOpts{nullptr, n_heads, ho});
+    return render_frame(who, rays, field, hann_w, nr_packed, kNoOffGrid, CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr},
+                        bgcolor, mode, cull_eps, N, S, chunk, workspace, workspace_bytes, ho[0], side_stream, events,
+                        mlp_events, stream, FrameOpts{live_counts, n_heads, ho});
+}
+
+extern "C" int hnrf_render_frame_heads_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                           const float* t_rand, const float* motion_Rs, const float* motion_Ts,
+                                           const float* vol, const float* bbox_min, const float* bbox_scale,
+                                           const float* hann_w, const void* nr_packed, const void* cnl_packed,
+                                           const float* bgcolor, int mode, float cull_eps, int64_t N, int S, int B, int G,
+                                           int64_t chunk, int n_heads, void* workspace, size_t workspace_bytes,
+                                           float* const* rgb, float* const* alpha, float* const* depth,
+                                           float* const* weights_on_rays, float* const* rgb_on_rays, float* const* cnl_xyz,
+                                           float* const* cnl_rgb, float* const* cnl_weight, float* xyz_on_rays, float* bmw,
+                                           float* offsets, void* side_stream, void* const* events,
+                                           void* const* mlp_events, void* stream) {
+    return frame_heads("hnrf_render_frame_heads_fwd", Rays{rays_o, rays_d, near, far, t_rand},
+                       WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, hann_w, nr_packed, cnl_packed,
+                       bgcolor, mode, cull_eps, N, S, chunk, n_heads, workspace, workspace_bytes, rgb, alpha, depth,
+                       weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays, bmw, offsets, nullptr,
+                       side_stream, events, mlp_events, stream);
+}
+
+extern "C" int hnrf_render_frame_heads_shared_fwd(
+    const float* rays_o, const float* rays_d, const float* near, const float* far, const float* t_rand,
+    const float* motion_Rs, const float* motion_Ts, const float* vol, const float* bbox_min, const float* bbox_scale,
+    const float* hann_w, const void* nr_packed, const void* cnl_packed, const float* bgcolor, int mode, float cull_eps,
+    int64_t N, int S, int B, int G, int64_t chunk, int n_heads, void* workspace, size_t workspace_bytes, float* const* rgb,
+    float* const* alpha, float* const* depth, float* const* weights_on_rays, float* const* rgb_on_rays,
+    float* const* cnl_xyz, float* const* cnl_rgb, float* const* cnl_weight, float* xyz_on_rays, float* bmw, float* offsets,
+    int* live_counts, void* side_stream, void* const* events, void* const* mlp_events, void* stream) {
+    HNRF_REQUIRE(live_counts, HNRF_E_ARG, "hnrf_render_frame_heads_shared_fwd: null live_counts");
+    return frame_heads("hnrf_render_frame_heads_shared_fwd", Rays{rays_o, rays_d, near, far, t_rand},
+                       WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, hann_w, nr_packed, cnl_packed,
+                       bgcolor, mode, cull_eps, N, S, chunk, n_heads, workspace, workspace_bytes, rgb, alpha, depth,
+                       weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays, bmw, offsets, live_counts,
+                       side_stream, events, mlp_events, stream);
 }
 
 extern "C" int hnrf_render_frame_shared_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,

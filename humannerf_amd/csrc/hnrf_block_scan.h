@@ -63,15 +63,23 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int* total) {
 // Shared underflowing inputs (the predicate: hnrf.h, hnrf_share_compact): the representative's results c_off / c_xyz /
 // c_raw, the list of live samples idx[0 .. *count) and the rows the shared samples' results go to.  offsets / xyz
 // nullable (the lean form reads neither).  *count must be 0 before the first block runs.
+// n raw planes (1..8; the heads of a multi-head canonical image, hnrf_heads_shared.h): c_raw is [n][4], plane g starts
+// at raw + g * plane_stride (in float4s) and a shared sample gets c_raw[g] in plane g.  The predicate, the list, offsets
+// and xyz do not depend on the head: one of each.
 struct ShareOut {
     const float *c_off, *c_xyz, *c_raw;
     int *idx, *count;
     float4* raw;
     float *offsets, *xyz;
+    int n = 1;
+    int64_t plane_stride = 0;
 };
 
-// Sample p with x_skel = x: shared or live (in_range false: neither).  A live sample goes onto the list; a shared one
-// gets the representative's results, which are its own bit for bit.
+// Sample p with x_skel = x: shared or live (in_range false: neither).  A live sample goes onto the list once (no plane
+// row of it is touched); a shared one gets the representative's results, which are its own bit for bit.  PLANES: the
+// sh.n planes in a run-time loop, one float4 store each; without it the single plane's code is what it was before
+// planes existed (sh.n and sh.plane_stride are not read).
+template <bool PLANES = false>
 __device__ __forceinline__ void share_classify(bool in_range, int64_t p, const float (&x)[3], const ShareOut& sh) {
 #pragma clang fp contract(off)
     bool shared = in_range;
@@ -82,7 +90,13 @@ __device__ __forceinline__ void share_classify(bool in_range, int64_t p, const f
     const int slot = block_append(keep, sh.count);
     if (keep) sh.idx[slot] = (int)p;
     if (shared) {
-        sh.raw[p] = make_float4(sh.c_raw[0], sh.c_raw[1], sh.c_raw[2], sh.c_raw[3]);
+        if constexpr (PLANES) {
+            for (int g = 0; g < sh.n; ++g)                                 // (c_raw: wave-uniform addresses, scalar loads)
+                sh.raw[(int64_t)g * sh.plane_stride + p] =
+                    make_float4(sh.c_raw[4 * g], sh.c_raw[4 * g + 1], sh.c_raw[4 * g + 2], sh.c_raw[4 * g + 3]);
+        } else {
+            sh.raw[p] = make_float4(sh.c_raw[0], sh.c_raw[1], sh.c_raw[2], sh.c_raw[3]);
+        }
         if (sh.offsets) {
 #pragma unroll
             for (int a = 0; a < 3; ++a) {

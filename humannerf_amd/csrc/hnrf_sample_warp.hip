@@ -20,10 +20,11 @@ struct __attribute__((packed, aligned(4))) f32x2u { float x, y; };
 
 // SHARE: the block classifies its samples while it still has their x_skel in registers (share_classify;
 // hnrf_sample_warp_share_fwd, hnrf.h): one atomic per block, issued while the CU's other resident blocks are in their
-// bone loops, instead of a second pass whose blocks do little else than wait for theirs.
+// bone loops, instead of a second pass whose blocks do little else than wait for theirs.  SHARE = 2: into the n raw
+// planes of a multi-head frame (hnrf_sample_warp_share_heads_fwd, hnrf_heads_shared.h); 1 is the single-plane code.
 // BT: the bone count as a compile-time constant (24 = the SMPL skeleton of every config of the reference; 0 = read B at
 // run time).  With BT the four-bone trips lose their per-bone `b < B` branches.
-template <bool WRITE_BMW, int BT, bool SHARE = false>
+template <bool WRITE_BMW, int BT, int SHARE = 0>
 __global__ __launch_bounds__(256) void sample_warp_kernel(
     const float* __restrict__ rays_o, const float* __restrict__ rays_d,
     const float* __restrict__ near, const float* __restrict__ far,
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(256) void sample_warp_kernel(
         x_skel[p * 3 + 2] = xs[2];
         fg_mask[p] = wsum;
     }
-    if constexpr (SHARE) share_classify(in_range, p, xs, sh);
+    if constexpr (SHARE != 0) share_classify<SHARE == 2>(in_range, p, xs, sh);
     if (bmw4) {                                        // (block-uniform: no thread has left the kernel)
         __syncthreads();
         const int64_t base = (int64_t)blockIdx.x * 256;
@@ -179,6 +180,7 @@ __global__ __launch_bounds__(256) void compact_kernel(const float* __restrict__ 
 // Samples whose K2 / K3 inputs underflow to those of x_skel = (+0, +0, +0) (the predicate: hnrf.h, hnrf_share_compact):
 // such a sample's offsets / xyz / raw are the representative's c_off / c_xyz / c_raw bit for bit, so they are written
 // here and the MLPs run on the rest, idx[0..count) in compact_kernel's order.
+template <bool PLANES>
 __global__ __launch_bounds__(256) void share_compact_kernel(const float* __restrict__ x_skel, int64_t P, ShareOut sh) {
     const int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const bool in_range = p < P;
@@ -187,30 +189,60 @@ __global__ __launch_bounds__(256) void share_compact_kernel(const float* __restr
 #pragma unroll
         for (int a = 0; a < 3; ++a) x[a] = x_skel[p * 3 + a];
     }
-    share_classify(in_range, p, x, sh);
+    share_classify<PLANES>(in_range, p, x, sh);
 }
 
 int share_compact(const float* x_skel, int64_t P, const ShareOut& sh, hipStream_t st) {
     if (P == 0) return HNRF_OK;
-    hipLaunchKernelGGL(share_compact_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, x_skel, P, sh);
-    return check_launch("hnrf_share_compact");
+    const dim3 grid((unsigned)((P + 255) / 256));
+    if (sh.n > 1) hipLaunchKernelGGL(share_compact_kernel<true>, grid, dim3(256), 0, st, x_skel, P, sh);
+    else hipLaunchKernelGGL(share_compact_kernel<false>, grid, dim3(256), 0, st, x_skel, P, sh);
+    return check_launch(sh.n > 1 ? "hnrf_share_compact_heads" : "hnrf_share_compact");
 }
 
 }  // namespace hnrf
 
-extern "C" int hnrf_share_compact(const float* x_skel, const float* c_off, const float* c_xyz, const float* c_raw,
-                                  int64_t P, int* idx, int* count, float* offsets, float* xyz, float* raw, void* stream) {
-    using namespace hnrf;
-    HNRF_REQUIRE(x_skel && c_off && c_xyz && c_raw && idx && count && raw, HNRF_E_ARG, "hnrf_share_compact: null pointer");
-    HNRF_REQUIRE((offsets == nullptr) == (xyz == nullptr), HNRF_E_ARG, "hnrf_share_compact: offsets and xyz go together");
-    HNRF_REQUIRE(P >= 0 && P < 2147483647LL, HNRF_E_ARG, "hnrf_share_compact: bad P");
-    HNRF_REQUIRE(((uintptr_t)raw & 15) == 0, HNRF_E_ARG, "hnrf_share_compact: raw must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
+namespace {
+using namespace hnrf;
+// The share arguments of the four classification entries, checked, *count zeroed, as a ShareOut: one plane, or --
+// n_heads >= 2 -- the head-major planes raw [n_heads][P][4] of the *_heads entries (hnrf_heads_shared.h).
+int share_args(const char* who, const float* c_off, const float* c_xyz, const float* c_raw, int64_t P, int n_heads,
+               int* idx, int* count, float* offsets, float* xyz, float* raw, hipStream_t st, ShareOut* sh) {
+    HNRF_REQUIRE(n_heads == 0 || (n_heads >= 2 && n_heads <= 8), HNRF_E_ARG, "%s: n_heads=%d outside 2..8", who, n_heads);
+    HNRF_REQUIRE(c_off && c_xyz && c_raw && idx && count && raw, HNRF_E_ARG, "%s: null pointer", who);
+    HNRF_REQUIRE((offsets == nullptr) == (xyz == nullptr), HNRF_E_ARG, "%s: offsets and xyz go together", who);
+    HNRF_REQUIRE(((uintptr_t)raw & 15) == 0, HNRF_E_ARG, "%s: raw must be 16-byte aligned", who);
     if (hipMemsetAsync(count, 0, sizeof(int), st) != hipSuccess) {
-        set_error("hnrf_share_compact: memset failed");
+        set_error("%s: memset failed", who);
         return HNRF_E_LAUNCH;
     }
-    return share_compact(x_skel, P, ShareOut{c_off, c_xyz, c_raw, idx, count, (float4*)raw, offsets, xyz}, st);
+    *sh = ShareOut{c_off, c_xyz, c_raw, idx, count, (float4*)raw, offsets, xyz, n_heads ? n_heads : 1, P};
+    return HNRF_OK;
+}
+
+int share_compact_entry(const char* who, const float* x_skel, const float* c_off, const float* c_xyz, const float* c_raw,
+                        int64_t P, int n_heads, int* idx, int* count, float* offsets, float* xyz, float* raw, void* stream) {
+    HNRF_REQUIRE(x_skel, HNRF_E_ARG, "%s: null pointer", who);
+    HNRF_REQUIRE(P >= 0 && P < 2147483647LL, HNRF_E_ARG, "%s: bad P", who);
+    ShareOut sh;
+    if (int rc = share_args(who, c_off, c_xyz, c_raw, P, n_heads, idx, count, offsets, xyz, raw, (hipStream_t)stream, &sh))
+        return rc;
+    return share_compact(x_skel, P, sh, (hipStream_t)stream);
+}
+}  // namespace
+
+extern "C" int hnrf_share_compact(const float* x_skel, const float* c_off, const float* c_xyz, const float* c_raw,
+                                  int64_t P, int* idx, int* count, float* offsets, float* xyz, float* raw, void* stream) {
+    return share_compact_entry("hnrf_share_compact", x_skel, c_off, c_xyz, c_raw, P, 0, idx, count, offsets, xyz, raw, stream);
+}
+
+extern "C" int hnrf_share_compact_heads(const float* x_skel, const float* c_off, const float* c_xyz, const float* c_raw,
+                                        int64_t P, int n_heads, int* idx, int* count, float* offsets, float* xyz,
+                                        float* raw, void* stream) {
+    using namespace hnrf;
+    HNRF_REQUIRE(n_heads != 0, HNRF_E_ARG, "hnrf_share_compact_heads: n_heads=0 outside 2..8");
+    return share_compact_entry("hnrf_share_compact_heads", x_skel, c_off, c_xyz, c_raw, P, n_heads, idx, count, offsets, xyz,
+                               raw, stream);
 }
 
 extern "C" int hnrf_compact_samples(const float* fg_mask, float eps, int64_t P, int* idx, int* count, void* stream) {
@@ -230,7 +262,9 @@ extern "C" int hnrf_compact_samples(const float* fg_mask, float eps, int64_t P, 
 namespace hnrf {
 int sample_warp(const Rays& rays, const WarpField& f, int64_t R, int S, float* z_vals, float* x_skel, float* fg_mask,
                 float* bmw, const ShareOut* sh, hipStream_t st) {
-    const char* who = sh ? "hnrf_sample_warp_share_fwd" : "hnrf_sample_warp_fwd";
+    const char* who = !sh          ? "hnrf_sample_warp_fwd"
+                      : sh->n > 1 ? "hnrf_sample_warp_share_heads_fwd"
+                                  : "hnrf_sample_warp_share_fwd";
     const int B = f.B, G = f.G;
     HNRF_REQUIRE(rays.o && rays.d && rays.near && rays.far && f.Rs && f.Ts && f.vol && f.bbox_min && f.bbox_scale,
                  HNRF_E_ARG, "%s: null input pointer", who);
@@ -248,9 +282,10 @@ int sample_warp(const Rays& rays, const WarpField& f, int64_t R, int S, float* z
     hipLaunchKernelGGL((sample_warp_kernel<W, BT_, SH_>), dim3((unsigned)blocks), dim3(256), 0, st, rays.o, rays.d,  \
                        rays.near, rays.far, rays.t_rand, f.Rs, f.Ts, f.vol, f.bbox_min, f.bbox_scale, P, S, B, G,     \
                        z_vals, x_skel, fg_mask, bmw, so)
-    if (sh) { if (bmw) HNRF_K1(true, 24, true); else HNRF_K1(false, 24, true); }
-    else if (bmw) { if (B == 24) HNRF_K1(true, 24, false); else HNRF_K1(true, 0, false); }
-    else { if (B == 24) HNRF_K1(false, 24, false); else HNRF_K1(false, 0, false); }
+    if (sh && sh->n > 1) { if (bmw) HNRF_K1(true, 24, 2); else HNRF_K1(false, 24, 2); }
+    else if (sh) { if (bmw) HNRF_K1(true, 24, 1); else HNRF_K1(false, 24, 1); }
+    else if (bmw) { if (B == 24) HNRF_K1(true, 24, 0); else HNRF_K1(true, 0, 0); }
+    else { if (B == 24) HNRF_K1(false, 24, 0); else HNRF_K1(false, 0, 0); }
 #undef HNRF_K1
     return check_launch(who);
 }
@@ -268,6 +303,22 @@ extern "C" int hnrf_sample_warp_fwd(const float* rays_o, const float* rays_d,
                        R, S, z_vals, x_skel, fg_mask, bmw, nullptr, (hipStream_t)stream);
 }
 
+namespace {
+// hnrf_sample_warp_share_fwd and -- n_heads planes -- hnrf_sample_warp_share_heads_fwd
+int sample_warp_share_entry(const char* who, const Rays& rays, const WarpField& f, int64_t R, int S, float* z_vals,
+                            float* x_skel, float* fg_mask, float* bmw, const float* c_off, const float* c_xyz,
+                            const float* c_raw, int n_heads, int* idx, int* count, float* offsets, float* xyz, float* raw,
+                            void* stream) {
+    HNRF_REQUIRE(f.B == 24, HNRF_E_UNSUPPORTED, "%s: the fused classification exists for 24 bones only (B=%d)", who, f.B);
+    HNRF_REQUIRE(R >= 0 && S >= 2 && R * (int64_t)S < 2147483647LL, HNRF_E_ARG, "%s: bad R=%lld S=%d", who, (long long)R, S);
+    ShareOut sh;
+    if (int rc = share_args(who, c_off, c_xyz, c_raw, R * (int64_t)S, n_heads, idx, count, offsets, xyz, raw,
+                            (hipStream_t)stream, &sh))
+        return rc;
+    return sample_warp(rays, f, R, S, z_vals, x_skel, fg_mask, bmw, &sh, (hipStream_t)stream);
+}
+}  // namespace
+
 extern "C" int hnrf_sample_warp_share_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
                                           const float* t_rand, const float* motion_Rs, const float* motion_Ts,
                                           const float* vol, const float* bbox_min, const float* bbox_scale, int64_t R,
@@ -275,18 +326,21 @@ extern "C" int hnrf_sample_warp_share_fwd(const float* rays_o, const float* rays
                                           const float* c_off, const float* c_xyz, const float* c_raw, int* idx, int* count,
                                           float* offsets, float* xyz, float* raw, void* stream) {
     using namespace hnrf;
-    const char* who = "hnrf_sample_warp_share_fwd";
-    HNRF_REQUIRE(B == 24, HNRF_E_UNSUPPORTED, "%s: the fused classification exists for 24 bones only (B=%d)", who, B);
-    HNRF_REQUIRE(c_off && c_xyz && c_raw && idx && count && raw, HNRF_E_ARG, "%s: null pointer", who);
-    HNRF_REQUIRE((offsets == nullptr) == (xyz == nullptr), HNRF_E_ARG, "%s: offsets and xyz go together", who);
-    HNRF_REQUIRE(R >= 0 && S >= 2 && R * (int64_t)S < 2147483647LL, HNRF_E_ARG, "%s: bad R=%lld S=%d", who, (long long)R, S);
-    HNRF_REQUIRE(((uintptr_t)raw & 15) == 0, HNRF_E_ARG, "%s: raw must be 16-byte aligned", who);
-    hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(count, 0, sizeof(int), st) != hipSuccess) {
-        set_error("%s: memset failed", who);
-        return HNRF_E_LAUNCH;
-    }
-    const ShareOut sh{c_off, c_xyz, c_raw, idx, count, (float4*)raw, offsets, xyz};
-    return sample_warp(Rays{rays_o, rays_d, near, far, t_rand}, WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G},
-                       R, S, z_vals, x_skel, fg_mask, bmw, &sh, st);
+    return sample_warp_share_entry("hnrf_sample_warp_share_fwd", Rays{rays_o, rays_d, near, far, t_rand},
+                                   WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, R, S, z_vals, x_skel,
+                                   fg_mask, bmw, c_off, c_xyz, c_raw, 0, idx, count, offsets, xyz, raw, stream);
+}
+
+extern "C" int hnrf_sample_warp_share_heads_fwd(const float* rays_o, const float* rays_d, const float* near,
+                                                const float* far, const float* t_rand, const float* motion_Rs,
+                                                const float* motion_Ts, const float* vol, const float* bbox_min,
+                                                const float* bbox_scale, int64_t R, int S, int B, int G, float* z_vals,
+                                                float* x_skel, float* fg_mask, float* bmw, const float* c_off,
+                                                const float* c_xyz, const float* c_raw, int n_heads, int* idx, int* count,
+                                                float* offsets, float* xyz, float* raw, void* stream) {
+    using namespace hnrf;
+    HNRF_REQUIRE(n_heads != 0, HNRF_E_ARG, "hnrf_sample_warp_share_heads_fwd: n_heads=0 outside 2..8");
+    return sample_warp_share_entry("hnrf_sample_warp_share_heads_fwd", Rays{rays_o, rays_d, near, far, t_rand},
+                                   WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, R, S, z_vals, x_skel,
+                                   fg_mask, bmw, c_off, c_xyz, c_raw, n_heads, idx, count, offsets, xyz, raw, stream);
 }

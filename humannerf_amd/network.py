@@ -826,7 +826,8 @@ class Network(nn.Module):
                                           "head's transmittance")
             if nr_from_grid:
                 raise NotImplementedError("head_id = -1 with cfg.amd.nonrigid = 'baked'")
-            out = self._forward_frame(per_ray, per_frame, nr_packed, cnl_packed, bg, S, mode, diag, all_heads=True)
+            out = self._forward_frame(per_ray, per_frame, nr_packed, cnl_packed, bg, S, mode, diag, hann_host,
+                                      all_heads=True)
         elif train_path:
             out = self._forward_chunks(per_ray, per_frame, bg, S, mode, diag,
                                        train=(cond, not ignore_nr, nr_inputs_are_zero))
@@ -866,20 +867,22 @@ class Network(nn.Module):
         """Inference, the whole frame in one library call -- chunk loop of network.py:330-352, results straight into
         whole-frame tensors (the reference concatenates per-chunk results: one more pass over 17 KB per ray);
         optionally K1 of the next chunk on a side stream under the MLP kernels of the current one
-        (cfg.amd.overlap_warp).  ``all_heads``: every head (hnrf_render_frame_heads_fwd) -- the trunks of both MLPs once
-        per chunk, one compositing pass per head; the shared evaluation of underflowing inputs is bypassed."""
+        (cfg.amd.overlap_warp).  ``all_heads``: every head (hnrf_render_frame_heads_fwd, with the shared evaluation of
+        underflowing inputs hnrf_render_frame_heads_shared_fwd) -- the trunks of both MLPs once per chunk, one compositing
+        pass per head."""
         gmode, guarded = self._guard_plan(mode, per_ray[0].shape[0])
         cull_eps = 0.0 if diag else float(amd_option('cull_eps', 0.0))
         common = dict(diagnostics=diag, cull_eps=cull_eps, workspace=self._workspace,
                       overlap=bool(amd_option('overlap_warp', False)), mlp_event_log=self.mlp_event_log)
         # one evaluation for the samples whose inputs underflow to those of x_skel = 0 (hnrf.h, hnrf_share_compact;
         # its threshold assumes Hann weights <= 1: checked on the host copy, nothing waits for the device)
-        share = (not all_heads and bool(amd_option('share_underflow', True)) and mode == 'f16x3' and nr_packed is not None
+        share = (bool(amd_option('share_underflow', True)) and mode == 'f16x3' and nr_packed is not None
                  and baked is None and cull_eps == 0.0 and float(hann_host.max()) <= 1.0)
         share_log = [] if share else None
         if all_heads:
             out, self._workspace = ops.render_frame_heads(*per_ray, *per_frame, nr_packed, cnl_packed, bg, S,
-                                                          int(cfg.chunk), self.head_num, gmode, **common)
+                                                          int(cfg.chunk), self.head_num, gmode, share_log=share_log,
+                                                          **common)
         else:
             out, self._workspace = ops.render_frame(*per_ray, *per_frame, nr_packed, cnl_packed, bg, S, int(cfg.chunk),
                                                     gmode, baked=baked, baked_nr=baked_nr, share_log=share_log, **common)

@@ -345,14 +345,18 @@ def _frame_call(lib, operands, n_samples, chunk, mode, diagnostics, cull_eps, wo
     """The one call of a frame entry, for render_frame and -- ``n_heads`` -- render_frame_heads: the workspace, the
     whole-frame output tensors (with ``n_heads`` one allocation per HEAD_KEYS key, head-major: out[k][h] is a contiguous
     whole-frame tensor), the stream and event arguments, the call, and what the side stream and the event log need
-    afterwards.  Returns (out, workspace, the live counts of ``share`` or None)."""
+    afterwards.  ``share`` with ``n_heads``: hnrf_render_frame_heads_shared_fwd (``lib`` has its header bound).  Returns
+    (out, workspace, the live counts of ``share`` or None)."""
     H = n_heads
     N, S, B, G = operands[0].shape[0], int(n_samples), operands[5].shape[0], operands[7].shape[-1]
     dev = operands[0].device
     chunk = int(chunk)
     rows = min(chunk, max(N, 1))
-    need = lib.hnrf_render_frame_heads_workspace_bytes(rows, S, H) if H else \
-        (lib.hnrf_render_frame_shared_workspace_bytes if share else lib.hnrf_render_frame_workspace_bytes)(rows, S)
+    if H:
+        stem = 'hnrf_render_frame_heads_shared' if share else 'hnrf_render_frame_heads'
+        need = getattr(lib, stem + '_workspace_bytes')(rows, S, H)
+    else:
+        need = (lib.hnrf_render_frame_shared_workspace_bytes if share else lib.hnrf_render_frame_workspace_bytes)(rows, S)
     args, workspace = _render_args(operands, workspace, need)
     out = {k: torch.empty(((H, N) if H and k in HEAD_KEYS else (N,)) + v, device=dev)
            for k, v in output_shapes(S, B, diagnostics).items()}
@@ -364,7 +368,7 @@ def _frame_call(lib, operands, n_samples, chunk, mode, diagnostics, cull_eps, wo
 
     side, ev_arr, mlp_arr, pairs = _frame_sync_args(dev, N, chunk, overlap, mlp_event_log is not None)
     if H:
-        fn, name, ptrs = lib.hnrf_render_frame_heads_fwd, 'hnrf_render_frame_heads_fwd', list(map(_ptr, args))
+        fn, name, ptrs = getattr(lib, stem + '_fwd'), stem + '_fwd', list(map(_ptr, args))
     else:
         fn, name, ptrs = _render_entry(lib, 'frame', args, baked, baked_nr, share)
     live = torch.empty(max(1, -(-N // chunk)), dtype=torch.int32, device=dev) if share else None
@@ -736,15 +740,20 @@ def canonical_heads_sparse(xyz, packed, n_heads, idx, count, mode='f32', raw=Non
 
 def render_frame_heads(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w,
                        nr_packed, cnl_packed, bgcolor, n_samples, chunk, n_heads, mode='f16x3', diagnostics=True,
-                       cull_eps=0.0, workspace=None, overlap=True, mlp_event_log=None):
+                       cull_eps=0.0, workspace=None, overlap=True, mlp_event_log=None, share_log=None):
     """render_frame for every head of a multi-head image (hnrf_render_frame_heads_fwd; network.py:570-601): the MLP
     trunks once per chunk, one compositing pass per head.  Returns (dict, workspace): the HEAD_KEYS are lists of n_heads
-    whole-frame tensors, xyz_on_rays is the same tensor n_heads times, backward_motion_weights and offsets are tensors."""
-    lib = _lib.load_heads()
+    whole-frame tensors, xyz_on_rays is the same tensor n_heads times, backward_motion_weights and offsets are tensors.
+    ``share_log``: as in render_frame -- a list selects hnrf_render_frame_heads_shared_fwd and receives (live_counts,
+    samples); a live sample counts once, not once per head."""
+    share = share_log is not None
+    lib = _lib.load_heads_shared() if share else _lib.load_heads()
     H = _chk_heads(n_heads)
-    out, workspace, _ = _frame_call(lib, (rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
-                                          hann_w, nr_packed, cnl_packed, bgcolor), n_samples, chunk, mode, diagnostics,
-                                    cull_eps, workspace, overlap, mlp_event_log, n_heads=H)
+    out, workspace, live = _frame_call(lib, (rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min,
+                                             bbox_scale, hann_w, nr_packed, cnl_packed, bgcolor), n_samples, chunk, mode,
+                                       diagnostics, cull_eps, workspace, overlap, mlp_event_log, share=share, n_heads=H)
+    if share:
+        share_log.append((live, rays_o.shape[0] * int(n_samples)))
     out = {k: list(v.unbind(0)) if k in HEAD_KEYS else v for k, v in out.items()}
     if 'xyz_on_rays' in out:
         out['xyz_on_rays'] = [out['xyz_on_rays']] * H

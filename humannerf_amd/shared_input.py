@@ -28,3 +28,18 @@ def shared_mask(x_skel, c_off, c_xyz):
 def live_indices(x_skel, c_off, c_xyz):
     """Sorted flat indices of the samples the MLPs still evaluate (the device list holds the same set, in block order)."""
     return np.flatnonzero(~shared_mask(np.asarray(x_skel, dtype=np.float32).reshape(-1, 3), c_off, c_xyz))
+
+
+def fill_planes(x_skel, c_off, c_xyz, c_raw, planes):
+    """The twin of hnrf_share_compact_heads (include/hnrf_heads_shared.h): ``planes`` (H, P, 4) float32, written in
+    place -- row p of plane g becomes c_raw[g] (H, 4) where sample p is shared, and no row of a live sample is touched
+    in any plane.  Returns the live list (sorted; each live sample once, whatever H is)."""
+    c_raw = np.asarray(c_raw, dtype=np.float32)
+    H, P = planes.shape[:2]
+    if planes.dtype != np.float32 or planes.shape != (H, P, 4) or c_raw.shape != (H, 4):
+        raise ValueError('fill_planes: planes (H, P, 4) float32 and c_raw (H, 4), got %s %s and %s'
+                         % (planes.dtype, planes.shape, c_raw.shape))
+    m = shared_mask(np.asarray(x_skel, dtype=np.float32).reshape(P, 3), c_off, c_xyz)
+    for g in range(H):
+        planes[g, m] = c_raw[g]
+    return np.flatnonzero(~m)

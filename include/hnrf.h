@@ -788,6 +788,11 @@ int hnrf_image_metrics(const uint8_t* pred, const uint8_t* target, const uint8_t
  * viewer performs with them.  Additive to ABI version 13; contracts and declarations in hnrf_skin.h. */
 #include "hnrf_skin.h"
 
+/* ---- every head of a multi-head canonical image with the shared evaluation of underflowing inputs: the n-plane
+ * classification, stand-alone and fused into K1, and the frame entry that joins it with the all-heads K3.  Additive to
+ * ABI version 13; contracts and declarations in hnrf_heads_shared.h. */
+#include "hnrf_heads_shared.h"
+
 #ifdef __cplusplus
 }
 #endif

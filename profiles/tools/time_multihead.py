@@ -5,8 +5,9 @@
           libhnrf.so built from the parent commit -- of the parent, interleaved in the same process on the same inputs;
           both arithmetics.  Accepted: all-heads / parent single-head <= 1.05 (f16x3).
   frame   the bench frame (512 x 512 rays x 128 samples, bench.py's camera): forward(head_id=-1) against the H frames
-          forward(head_id=h), with cfg.amd.share_underflow on and off (the all-heads path bypasses the shared
-          evaluation either way), 11-output and lean form.
+          forward(head_id=h), with cfg.amd.share_underflow on and off (when profiles/multihead.txt was taken the
+          all-heads path bypassed the shared evaluation either way; since then it shares:
+          time_multihead_shared.py), 11-output and lean form.
 
     python profiles/tools/time_multihead.py [--heads 4] [--iters 20] [--warmup 3] [--parent-lib PATH] [--step kernel|frame]
 
