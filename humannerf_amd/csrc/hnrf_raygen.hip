@@ -162,7 +162,9 @@ extern "C" int hnrf_gen_rays(const float* Kinv, const float* R, const float* T, 
                      workspace,
                  HNRF_E_ARG, "hnrf_gen_rays: null pointer");
     HNRF_REQUIRE(H > 0 && W > 0 && (int64_t)H * W < 2147483647LL, HNRF_E_ARG, "hnrf_gen_rays: bad image size %dx%d", H, W);
-    HNRF_REQUIRE(workspace_bytes >= hnrf_gen_rays_workspace_bytes(H, W), HNRF_E_ARG, "hnrf_gen_rays: workspace too small");
+    HNRF_REQUIRE(((uintptr_t)workspace & 255) == 0, HNRF_E_ARG, "hnrf_gen_rays: workspace must be 256-byte aligned");
+    HNRF_REQUIRE(workspace_bytes >= hnrf_gen_rays_workspace_bytes(H, W), HNRF_E_WORKSPACE,
+                 "hnrf_gen_rays: workspace %zu < %zu bytes", workspace_bytes, hnrf_gen_rays_workspace_bytes(H, W));
     const int nblk = (int)(((int64_t)H * W + 255) / 256);
     hipStream_t st = (hipStream_t)stream;
     int* blk = (int*)workspace;

@@ -454,7 +454,8 @@ int hnrf_nonrigid_bwd(const float* x_skel, const float* hann_w, const float* d_x
  *  is applied inside), all float32 device pointers.  Outputs, in pixel order: ray_mask [H*W] (1 = the ray crosses
  *  the box), and for the *count kept rays rays_o / rays_d [count,3] (direction un-normalised, components clamped
  *  to 1e-5 like the reference), near / far [count].  Size the ray buffers for H*W; their entries from *count on
- *  are not written. */
+ *  are not written.  workspace: hnrf_gen_rays_workspace_bytes(H, W) bytes, 256-byte aligned like every other workspace
+ *  (HNRF_E_ARG otherwise; a smaller one is HNRF_E_WORKSPACE); nothing is written when the call is refused. */
 size_t hnrf_gen_rays_workspace_bytes(int H, int W);
 int hnrf_gen_rays(const float* Kinv, const float* R, const float* T, const float* bbox_min, const float* bbox_max,
                   int H, int W, float* rays_o, float* rays_d, float* near, float* far, uint8_t* ray_mask,

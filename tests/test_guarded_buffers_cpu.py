@@ -1,0 +1,146 @@
+"""tests/guarded_buffers.py on CPU tensors: every violation the GPU tests of tests/test_gpu_buffer_bounds.py rely on is
+planted here by hand and must be reported with its offset, and a clean run must pass.  Nothing is planted in a kernel:
+this file is the evidence that those checks have teeth."""
+import numpy as np
+import pytest
+import torch
+
+from tests import guarded_buffers as gb
+
+P, B = 777, 7                       # 777 rows of 7 floats: 21 756 bytes, off every 16-byte and 256-byte boundary
+
+
+def _kernel(buf, rows=None):
+    """A well-behaved 'kernel': writes row r of the [P][B] float interior with r + column / 8, on ``rows`` or all."""
+    v = buf.view(torch.float32, P, B)
+    want = torch.arange(P, dtype=torch.float32)[:, None] + torch.arange(B, dtype=torch.float32)[None] / 8
+    if rows is None:
+        v.copy_(want)
+    else:
+        v[rows] = want[rows]
+
+
+@pytest.mark.parametrize('fill', gb.FILLS)
+@pytest.mark.parametrize('nbytes', [0, 1, 3, 4, 255, 256, P * B * 4, 37 * 53])
+def test_layout_and_clean_run(nbytes, fill):
+    g = gb.GuardedBuffer(nbytes, fill, name='clean')
+    assert g.ptr % 256 == 0 and g.start >= gb.GUARD and g.bytes.numel() - g.start - nbytes >= gb.GUARD
+    assert g.interior_bytes().numel() == nbytes
+    assert bool((g.interior_bytes() == (fill & 0xFF)).all())
+    g.interior_bytes().fill_(0x5A)                                  # every interior byte written, nothing else
+    assert g.violations() == []
+    g.check()
+    if nbytes % 4 == 0:
+        assert g.view(torch.int32).numel() == nbytes // 4
+
+
+@pytest.mark.parametrize('fill', gb.FILLS)
+def test_write_one_element_past_the_end(fill):
+    g = gb.GuardedBuffer(P * B * 4, fill, name='out')
+    _kernel(g)
+    g.check()
+    g.words[(g.start + g.nbytes) // 4] = 0x3F800000                 # element P * B of a float view
+    assert g.violations() == [('back', 0 if fill else 2)]           # 1.0f = 00 00 80 3F: over zeros bytes 2, 3 differ
+    with pytest.raises(gb.GuardViolation, match=r"out: back guard written at byte \+%d from the interior's end" % (0 if fill else 2)):
+        g.check()
+
+
+@pytest.mark.parametrize('fill', gb.FILLS)
+def test_write_one_byte_past_a_ragged_end(fill):
+    """An interior of 37 x 53 bytes (a ray mask) ends inside a word: the byte behind it is guard."""
+    g = gb.GuardedBuffer(37 * 53, fill, name='mask')
+    g.interior_bytes().fill_(1)
+    g.check()
+    g.bytes[g.start + g.nbytes] = 1
+    assert g.violations() == [('back', 0)]
+    g.bytes[g.start + g.nbytes] = fill & 0xFF
+    g.bytes[g.start + g.nbytes + 2] = 1                             # the last ragged byte of that word
+    assert g.violations() == [('back', 2)]
+
+
+@pytest.mark.parametrize('fill', gb.FILLS)
+def test_write_one_element_before_the_start(fill):
+    g = gb.GuardedBuffer(P * B * 4, fill, name='out')
+    _kernel(g)
+    g.words[g.start // 4 - 1] = 0x12345678
+    assert g.violations() == [('front', -4)]
+    with pytest.raises(gb.GuardViolation, match=r"out: front guard written at byte -4 from the interior's start"):
+        g.check()
+
+
+@pytest.mark.parametrize('fill', gb.FILLS)
+def test_write_at_the_far_end_of_the_back_guard(fill):
+    g = gb.GuardedBuffer(P * B * 4, fill, name='out')
+    _kernel(g)
+    g.words[(g.start + g.nbytes + gb.GUARD) // 4 - 1] = 0x12345678  # the last word of the 64 KiB behind the interior
+    assert g.violations() == [('back', gb.GUARD - 4)]
+    with pytest.raises(gb.GuardViolation, match=r'\+%d from' % (gb.GUARD - 4)):
+        g.check()
+    h = gb.GuardedBuffer(P * B * 4, fill)
+    h.words[0] = 0x12345678                                         # and the far end of the front guard
+    assert h.violations() == [('front', -h.start)] and h.start >= gb.GUARD
+
+
+def test_an_element_never_written_differs_between_the_fills():
+    a, b = (gb.GuardedBuffer(P * B * 4, f, name='raw') for f in gb.FILLS)
+    for g in (a, b):
+        _kernel(g)
+    gb.same_bits(a, b)                                              # the clean run
+    a, b = (gb.GuardedBuffer(P * B * 4, f, name='raw') for f in gb.FILLS)
+    rows = torch.ones(P, dtype=torch.bool)
+    rows[P - 1] = False                                             # the 'kernel' forgets its last tail row
+    for g in (a, b):
+        _kernel(g, rows)
+        g.check()                                                   # (no guard sees that)
+    with pytest.raises(gb.GuardViolation, match='raw: byte %d of the interior differs' % ((P - 1) * B * 4)):
+        gb.same_bits(a, b)
+    gb.same_bits(a, b, rows=rows, n_rows=P, row_bytes=B * 4)        # on the rows it wrote the two runs agree
+    with pytest.raises(gb.GuardViolation, match='byte %d ' % ((P - 1) * B * 4)):
+        gb.same_bits(a, b, rows=torch.tensor([3, P - 1]), n_rows=P, row_bytes=B * 4)
+
+
+def test_a_result_that_depends_on_bytes_behind_an_input_differs_between_the_fills():
+    """An input placed in a guarded buffer: a 'kernel' that reads one element past its end computes something else
+    under each fill."""
+    x = torch.arange(P, dtype=torch.float32)
+    outs = []
+    for f in gb.FILLS:
+        g = gb.place(x, f, name='x')
+        assert torch.equal(g.view(torch.float32), x) and g.nbytes == 4 * P
+        o = gb.GuardedBuffer(4 * P, f, name='y')
+        wide = g.words[g.start // 4:g.start // 4 + P + 1]          # reads x[p + 1]: one past the end at p = P - 1
+        o.view(torch.int32).copy_(wide[:-1] ^ wide[1:])
+        g.check(), o.check()
+        outs.append(o)
+    with pytest.raises(gb.GuardViolation, match='y: byte %d ' % (4 * (P - 1))):
+        gb.same_bits(*outs)
+
+
+@pytest.mark.parametrize('fill', gb.FILLS)
+def test_a_row_that_must_stay_untouched(fill):
+    g = gb.GuardedBuffer(P * B * 4, fill, name='raw')
+    listed = torch.zeros(P, dtype=torch.bool)
+    listed[torch.from_numpy(np.random.RandomState(1).permutation(P)[:129])] = True
+    _kernel(g, listed)
+    g.rows_hold_fill(~listed, P, B * 4)                             # the clean run
+    g.rows_hold_fill((~listed).nonzero().reshape(-1), P, B * 4)     # (indices as well as a mask)
+    r = int((~listed).nonzero()[5])
+    g.view(torch.float32, P, B)[r, B - 1] = 2.5
+    with pytest.raises(gb.GuardViolation, match=r'raw: row %d \(of %d, %d bytes each\) was written' % (r, P, B * 4)):
+        g.rows_hold_fill(~listed, P, B * 4)
+    with pytest.raises(gb.GuardViolation, match='raw: interior written at byte'):
+        g.holds_fill()
+    h = gb.GuardedBuffer(P * B * 4, fill, name='ws')
+    h.holds_fill()                                                  # a refused call leaves everything
+    # planes: plane 1 of [2][P][B] starts at byte offset P * B * 4
+    k = gb.GuardedBuffer(2 * P * B * 4, fill, name='planes')
+    k.view(torch.float32, 2, P, B)[1, 7] = 1.0
+    k.rows_hold_fill(torch.ones(P, dtype=torch.bool), P, B * 4)
+    with pytest.raises(gb.GuardViolation, match='row 7 '):
+        k.rows_hold_fill(torch.ones(P, dtype=torch.bool), P, B * 4, offset=P * B * 4)
+
+
+def test_misaligned_interior_for_the_refusal_cases():
+    g = gb.GuardedBuffer(1024, gb.FILLS[0], misalign=128)
+    assert g.ptr % 256 == 128
+    g.check()
