@@ -38,6 +38,7 @@ LATE_GROUPS = {
 # load_open() after load_late().
 OPEN_GROUPS = {
     'heads_shared': ('hnrf_heads_shared.h', 'the shared evaluation for all heads'),
+    'normals': ('hnrf_normals.h', 'the density-gradient normals'),
 }
 
 _SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float,
@@ -103,6 +104,7 @@ _LATE_HEADERS = {group: _header(group, LATE_GROUPS) for group in LATE_GROUPS}
 SKIN_HEADER_PATH, SKIN_SIGNATURES = _LATE_HEADERS['skin']
 _OPEN_HEADERS = {group: _header(group, OPEN_GROUPS) for group in OPEN_GROUPS}
 HEADS_SHARED_HEADER_PATH, HEADS_SHARED_SIGNATURES = _OPEN_HEADERS['heads_shared']
+NORMALS_HEADER_PATH, NORMALS_SIGNATURES = _OPEN_HEADERS['normals']
 
 _lib = None
 
@@ -191,6 +193,10 @@ def load_skin(lib=None):
 
 def load_heads_shared(lib=None):
     return _bind_table('heads_shared', lib, OPEN_GROUPS, _OPEN_HEADERS)
+
+
+def load_normals(lib=None):
+    return _bind_table('normals', lib, OPEN_GROUPS, _OPEN_HEADERS)
 
 
 def load_open():

@@ -211,6 +211,13 @@ _DEFAULTS = {
         # the surface distance the maps are made of: 'expected' = depth / alpha, 'median' = the depth of the sample where
         # the cumulative weight reaches half of its total (needs diagnostics = True)
         'maps_surface': 'expected',
+        # where the 'normal' and 'shaded' panels take their normals from: 'screen' = differences of the rendered surface
+        # distance (nothing changes); 'gradient' = the gradient of the density at the ray's samples (Network.ray_normals,
+        # include/hnrf_normals.h: the training kernels run over the kept samples; one device count is read back per
+        # frame).  'gradient' needs diagnostics = True
+        'maps_normals': 'screen',
+        # 'gradient': a sample takes part in its ray's normal iff its compositing weight is >= this; finite and > 0
+        'normal_weight_min': 1e-4,
         # gc.freeze() at the start of the training / render loops (config.quiet_gc)
         'freeze_gc': True,
     },
@@ -257,7 +264,8 @@ def check_amd_options(node=None):
     (video 'none' / 'mjpeg' / 'mjpeg_only', video_quality an integer in [1, 100], video_fps an integer >= 1), or
     video = 'mjpeg_only' with metrics = 'host' (the host route needs the images that mode does not copy), or maps that
     is no list of distinct names out of 'depth' / 'normal' / 'shaded' / 'offset', a maps_surface that is not 'expected' or
-    'median', or 'offset' / 'median' asked for with diagnostics off."""
+    'median', or 'offset' / 'median' asked for with diagnostics off, or a maps_normals that is not 'screen' or
+    'gradient', a normal_weight_min that is not finite and > 0, or 'gradient' with diagnostics off."""
     get = amd_option if node is None else (lambda k: node.get(k, _DEFAULTS['amd'][k]))
     if not isinstance(get('share_underflow'), bool):
         raise ValueError('cfg.amd.share_underflow must be True or False, got %r' % (get('share_underflow'),))
@@ -284,6 +292,14 @@ def check_amd_options(node=None):
         raise ValueError("cfg.amd.maps with 'offset', and cfg.amd.maps_surface = 'median', need cfg.amd.diagnostics = True "
                          "(got cfg.amd.maps = %r, cfg.amd.maps_surface = %r): the lean form returns neither the per-sample "
                          "weights nor the offsets" % (list(maps), surface))
+    normals, wmin = get('maps_normals'), get('normal_weight_min')
+    if normals not in ('screen', 'gradient'):
+        raise ValueError("cfg.amd.maps_normals must be 'screen' or 'gradient', got %r" % (normals,))
+    if isinstance(wmin, bool) or not isinstance(wmin, (int, float)) or not (wmin > 0 and wmin < float('inf')):
+        raise ValueError('cfg.amd.normal_weight_min must be finite and > 0, got %r' % (wmin,))
+    if normals == 'gradient' and not get('diagnostics'):
+        raise ValueError("cfg.amd.maps_normals = 'gradient' needs cfg.amd.diagnostics = True (got cfg.amd.maps = %r): the "
+                         "lean form returns neither the per-sample weights nor the bone weights" % (list(maps),))
     canonical, nonrigid, M = get('canonical'), get('nonrigid'), get('nonrigid_bake_resolution')
     if canonical not in ('mlp', 'baked'):
         raise ValueError("cfg.amd.canonical must be 'mlp' or 'baked', got %r" % (canonical,))

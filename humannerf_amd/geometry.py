@@ -1,9 +1,16 @@
 """Geometry maps of a rendered frame: depth, normal, shaded and non-rigid-offset panels (include/hnrf_geometry.h,
 csrc/hnrf_geometry.hip).
 
-The normals are SCREEN-SPACE DIFFERENCES OF THE RENDERED SURFACE DISTANCE -- the per-ray depth the compositing kernel
-already returns, turned into a point per pixel and differenced along the image axes.  They cost no network evaluation
-and are the same for the exact, culled and baked paths; they are not the gradient of the density.
+By default (cfg.amd.maps_normals = 'screen') the normals are SCREEN-SPACE DIFFERENCES OF THE RENDERED SURFACE DISTANCE --
+the per-ray depth the compositing kernel already returns, turned into a point per pixel and differenced along the image
+axes.  They cost no network evaluation and are the same for the exact, culled and baked paths; they are not the gradient
+of the density.  With cfg.amd.maps_normals = 'gradient' the 'normal' and 'shaded' panels are painted from
+DENSITY-GRADIENT normals instead (include/hnrf_normals.h, csrc/hnrf_normals.hip): Network.ray_normals runs the training
+kernels over the samples that carry weight and hnrf_ray_normals blends their unit normals per ray; the same gradient
+gives meshes and glTF files their vertex normals (Network.vertex_normals).
+
+  ray_normals_host, normal_panels_host,          the numpy twins of hnrf_normals.h, bit for bit
+  field_normals_host
 
   ray_surface_host, pixel_rays_host, maps_host   the numpy twins: the second statement of every formula of the header,
                                                  bit for bit (fp32, every operation rounded on its own, the header's
@@ -213,6 +220,153 @@ def maps_host(rays_o, rays_d, surf, pix2ray, H, W, want=OUTPUTS, surface=0, alph
     return {k: np.ascontiguousarray(v) for k, v in res.items()}
 
 
+# ------------------------------------------------------------------------- numpy twins of include/hnrf_normals.h
+def _len3_host(v):
+    """sqrt(fl(fl(fl(v0 v0) + fl(v1 v1)) + fl(v2 v2))) of (..., 3) fp32."""
+    return np.sqrt((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2]).astype(_F)
+
+
+def ray_normals_host(weights, bmw, motion_Rs, idx, g, alpha, alpha_min=0.5):
+    """hnrf_ray_normals in numpy: weights (R, S), bmw (R, S, B), motion_Rs (B, 3, 3), idx (n,) the kept samples as flat
+    indices (distinct, in any order), g (n, 3) the skeleton-space density gradient at them, row k for idx[k], alpha (R,)
+    -> (normal (R, 3) fp32, nvalid (R,) uint8)."""
+    w = np.asarray(weights, dtype=_F)
+    R, S = w.shape
+    m = np.asarray(bmw, dtype=_F).reshape(R * S, -1)
+    Rs = np.asarray(motion_Rs, dtype=_F).reshape(-1, 9)
+    B = Rs.shape[0]
+    idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+    g = np.asarray(g, dtype=_F).reshape(-1, 3)[:idx.size]
+    inside = (idx >= 0) & (idx < R * S)
+    idx, g = idx[inside], g[inside]
+    contrib = np.zeros((R * S, 3), _F)
+    with np.errstate(all='ignore'):
+        A = np.zeros((idx.size, 9), _F)
+        mk = m[idx]
+        for b in range(B):
+            A = A + mk[:, b, None] * Rs[b][None, :]
+        v = np.stack([-((A[:, j] * g[:, 0] + A[:, 3 + j] * g[:, 1]) + A[:, 6 + j] * g[:, 2]) for j in range(3)], -1).astype(_F)
+        ln = _len3_host(v)
+        good = (ln > 0) & np.isfinite(ln)
+        u = v / np.where(good, ln, _F(1))[:, None]
+        # (a sample that contributes nothing adds +0: acc starts at +0 and a sum never rounds to -0, so acc is unchanged)
+        contrib[idx] = np.where(good[:, None], w.reshape(-1)[idx][:, None] * u, _F(0))
+        contrib = contrib.reshape(R, S, 3)
+        acc = np.zeros((R, 64, 3), _F)
+        for s0 in range(0, S, 64):
+            n = min(64, S - s0)
+            acc[:, :n] = acc[:, :n] + contrib[:, s0:s0 + n]
+        lanes = np.arange(64)
+        for off in (32, 16, 8, 4, 2, 1):
+            acc = acc + acc[:, lanes ^ off]
+        N = acc[:, 0]
+        L = _len3_host(N)
+        a = np.asarray(alpha, _F).reshape(-1)
+        ok = np.isfinite(a) & (a >= _F(alpha_min)) & (L > 0) & np.isfinite(L)
+        normal = np.where(ok[:, None], N / np.where(ok, L, _F(1))[:, None], _F(0)).astype(_F)
+    return np.ascontiguousarray(normal), ok.astype(np.uint8)
+
+
+NORMAL_OUTPUTS = ('normal', 'nvalid', 'normal8', 'shaded8')
+
+
+def normal_panels_host(rays_d, ray_normal, ray_nvalid, valid, pix2ray, H, W, want=NORMAL_OUTPUTS, surface=0, alpha=None,
+                       M=None, bgcolor=None, ambient=AMBIENT, albedo=ALBEDO):
+    """hnrf_normal_panels in numpy: per-ray normals (ray_normals_host), the valid bits of ray_surface_host and pix2ray
+    -> {name: array} for ``want`` out of NORMAL_OUTPUTS."""
+    d = np.asarray(rays_d, _F).reshape(-1, 3)
+    N = d.shape[0]
+    p2r = np.asarray(pix2ray, np.int64).reshape(H, W)
+    has_ray = (p2r >= 0) & (p2r < N)
+    r = np.where(has_ray, p2r, 0)
+    if N == 0:
+        d, rn, rv, valid = np.zeros((1, 3), _F), np.zeros((1, 3), _F), np.zeros(1, np.uint8), np.zeros(1, np.uint8)
+    else:
+        rn, rv = np.asarray(ray_normal, _F).reshape(-1, 3), np.asarray(ray_nvalid, np.uint8).reshape(-1)
+        valid = np.asarray(valid, np.uint8).reshape(-1)
+    ok = has_ray & (((valid[r] >> surface) & 1) == 1)
+    has = ok & (rv[r] != 0)
+    ambient, albedo = _F(ambient), _F(albedo)
+    bg = np.asarray(bgcolor, _F).reshape(3)
+    bg8 = q8_host(bg)
+    res = {}
+    with np.errstate(all='ignore'):
+        n = np.where(has[..., None], rn[r], _F(0)).astype(_F)
+        if 'normal' in want:
+            res['normal'] = n
+        if 'nvalid' in want:
+            res['nvalid'] = has.astype(np.uint8)
+        if 'normal8' in want:
+            m = np.asarray(M, _F).reshape(3, 3)
+            mn = np.stack([(m[i, 0] * n[..., 0] + m[i, 1] * n[..., 1]) + m[i, 2] * n[..., 2] for i in range(3)], -1)
+            res['normal8'] = np.where(has[..., None], q8_host(_F(0.5) + _F(0.5) * mn), bg8)
+        if 'shaded8' in want:
+            dr = d[r]
+            nd = ((n[..., 0] * dr[..., 0] + n[..., 1] * dr[..., 1]) + n[..., 2] * dr[..., 2]).astype(_F)
+            dl = np.sqrt((dr[..., 0] * dr[..., 0] + dr[..., 1] * dr[..., 1]) + dr[..., 2] * dr[..., 2]).astype(_F)
+            a = np.asarray(alpha, _F).reshape(-1)[r] if N else np.zeros((H, W), _F)
+            s = np.where(has, ambient + (_F(1) - ambient) * (np.abs(nd) / dl), ambient).astype(_F)
+            ga, na = (s * albedo) * a, _F(1) - a
+            col = np.stack([ga + na * bg[i] for i in range(3)], -1)
+            res['shaded8'] = np.where(ok[..., None], q8_host(col), bg8)
+    return {k: np.ascontiguousarray(v) for k, v in res.items()}
+
+
+def trilinear_gradient_host(verts, vol, bbox_min, bbox_scale, n_bones=None):
+    """fg (V,) and grad fg (V, 3) of hnrf_field_normals: the summed trilinear bone weights at canonical points and the
+    analytic derivative of the trilinear weights, fp32, in the header's order."""
+    from . import skin
+    v = np.asarray(verts, _F).reshape(-1, 3)
+    vol = np.asarray(vol, _F)
+    bmin, bscale = np.asarray(bbox_min, _F).reshape(3), np.asarray(bbox_scale, _F).reshape(3)
+    B, G = (vol.shape[0] if n_bones is None else int(n_bones)), vol.shape[-1]
+    gm1 = _F(G - 1)
+    off, cw = skin._trilinear_host(v, bmin, bscale, G)
+    u, e = [], []
+    with np.errstate(all='ignore'):
+        for a in range(3):
+            i = (((v[:, a] - bmin[a]) * bscale[a] - _F(1)) + _F(1)) * _F(0.5) * gm1
+            f0 = np.floor(i)
+            w1, w0 = i - f0, (f0 + _F(1)) - i
+            x0 = np.fmin(np.fmax(f0, _F(-2)), gm1 + _F(1)).astype(np.int64)
+            in0, in1 = (x0 >= 0) & (x0 < G), (x0 + 1 >= 0) & (x0 + 1 < G)
+            u.append((np.where(in0, w0, _F(0)).astype(_F), np.where(in1, w1, _F(0)).astype(_F)))
+            e.append((np.where(in0, _F(-1), _F(0)).astype(_F), np.where(in1, _F(1), _F(0)).astype(_F)))
+        flat = vol[:B].reshape(B, -1)
+        fg = np.zeros(len(v), _F)
+        Gr = np.zeros((len(v), 3), _F)
+        for b in range(B):
+            w = np.zeros(len(v), _F)
+            wd = np.zeros((len(v), 3), _F)
+            for k in range(8):
+                dx, dy, dz = k & 1, (k >> 1) & 1, (k >> 2) & 1
+                c = flat[b, off[:, k]]
+                w = w + c * cw[:, k]
+                wd[:, 0] = wd[:, 0] + c * (e[0][dx] * u[1][dy] * u[2][dz])
+                wd[:, 1] = wd[:, 1] + c * (u[0][dx] * e[1][dy] * u[2][dz])
+                wd[:, 2] = wd[:, 2] + c * (u[0][dx] * u[1][dy] * e[2][dz])
+            fg = fg + w
+            Gr = Gr + wd
+        grad = (Gr * ((bscale * _F(0.5)) * gm1)[None, :]).astype(_F)
+    return fg, grad
+
+
+def field_normals_host(verts, g, sigma, vol, bbox_min, bbox_scale, n_bones=None):
+    """hnrf_field_normals in numpy: the unit normal -grad D / |grad D| of D = relu(sigma) fg at canonical points
+    (V, 3), from grad sigma ``g`` (V, 3) and ``sigma`` (V,) there; 0 where the length is 0 or not finite."""
+    fg, gfg = trilinear_gradient_host(verts, vol, bbox_min, bbox_scale, n_bones)
+    g, sg = np.asarray(g, _F).reshape(-1, 3), np.asarray(sigma, _F).reshape(-1)
+    with np.errstate(all='ignore'):
+        pos = sg > 0
+        sr = np.where(pos, sg, _F(0)).astype(_F)
+        gs = np.where(pos[:, None], g, _F(0)).astype(_F)
+        D = (fg[:, None] * gs + sr[:, None] * gfg).astype(_F)
+        ln = _len3_host(D)
+        ok = (ln > 0) & np.isfinite(ln)
+        n = np.where(ok[:, None], -(D / np.where(ok, ln, _F(1))[:, None]), _F(0)).astype(_F)
+    return np.ascontiguousarray(n)
+
+
 # -------------------------------------------------------------------------------------------------- the device entry
 def check_maps(maps, surface='expected', diagnostics=True):
     """The panel names and the surface a caller asks for; ValueError names what is wrong."""
@@ -250,7 +404,7 @@ def _workspace(H, W, N, device):
 
 
 def frame_maps(data, out, H, W, ray_index, maps=MAP_NAMES, surface='expected', alpha_min=0.5, edge=0.05, M=None,
-               truth8=None):
+               truth8=None, ray_normals=None):
     """The panels of one rendered frame on the device.  ``data``: the frame's inputs as the network got them (``rays``
     (2, N, 3), ``near``, ``far``, ``bgcolor`` in 0..255); ``out``: what the network returned (``alpha``, ``depth`` and,
     with cfg.amd.diagnostics, ``weights_on_rays`` and ``offsets``); ``ray_index`` (N,) int64 the flat pixel of every ray;
@@ -259,7 +413,10 @@ def frame_maps(data, out, H, W, ray_index, maps=MAP_NAMES, surface='expected', a
     (H, W, 3) fp32 (the unit normals in world space; 'normal' is the 8-bit panel), ``nvalid`` (H, W) uint8, ``t`` (N,)
     and ``status`` (1,) int32 (not read back: 0 = fine, 1 = a ray index outside the image, and then nothing was
     written).  The panels are fresh tensors; normal_world, nvalid and t live in
-    a workspace per (H, W, N) that the next frame of that size overwrites.  Nothing here synchronises."""
+    a workspace per (H, W, N) that the next frame of that size overwrites.  Nothing here synchronises.
+    ``ray_normals``: (normal (N, 3), nvalid (N,) uint8) of Network.ray_normals -- the 'normal' and 'shaded' panels,
+    normal_world and nvalid then come from hnrf_normal_panels (density-gradient normals, not flipped towards the
+    camera); 'depth' and 'offset' stay as they are."""
     import torch
     from . import ops
     if float(cfg.perturb) > 0.:
@@ -291,6 +448,23 @@ def frame_maps(data, out, H, W, ray_index, maps=MAP_NAMES, surface='expected', a
             ws['lohi'].zero_()
     Mt = ws['eye'] if M is None else torch.as_tensor(M, dtype=torch.float32).to(dev).contiguous()
     names = {'depth': 'depth8', 'normal': 'normal8', 'shaded': 'shaded8', 'offset': 'offset8'}
+    if ray_normals is not None:
+        # normal, nvalid and the two panels made of normals from the per-ray normals; depth and offset as ever
+        rn, rv = ray_normals
+        other = [names[m] for m in maps if m in ('depth', 'offset')]
+        res = ops.geometry_maps(rays_o, rays_d, surf, ws['pix2ray'], H, W, other, surface=int(median),
+                                alpha=out['alpha'].reshape(-1), edge=edge, M=Mt, bgcolor=bg, lohi=ws['lohi'],
+                                truth8=truth8 if want_woff else None, status=ws['status']) if other else {}
+        res.update(ops.normal_panels(rays_d, rn.reshape(-1, 3).contiguous(), rv.reshape(-1).contiguous(), surf['valid'],
+                                     ws['pix2ray'], H, W,
+                                     ['normal', 'nvalid'] + [names[m] for m in maps if m in ('normal', 'shaded')],
+                                     surface=int(median), alpha=out['alpha'].reshape(-1).contiguous(), M=Mt, bgcolor=bg,
+                                     ambient=AMBIENT, albedo=ALBEDO, status=ws['status'],
+                                     out={'normal': ws['normal'], 'nvalid': ws['nvalid']}))
+        ret = {m: res[names[m]] for m in maps}
+        ret.update(normal_world=res['normal'], nvalid=res['nvalid'], t=surf['t_med' if median else 't_exp'],
+                   status=ws['status'])
+        return ret
     res = ops.geometry_maps(rays_o, rays_d, surf, ws['pix2ray'], H, W, ['normal', 'nvalid'] + [names[m] for m in maps],
                             surface=int(median), alpha=out['alpha'].reshape(-1), edge=edge, M=Mt, bgcolor=bg,
                             lohi=ws['lohi'], truth8=truth8 if want_woff else None, status=ws['status'],

@@ -9,14 +9,16 @@ The forward skinning of this package is, term for term, what glTF calls skinning
 so the file holds the canonical mesh and its vertex colours once, a 24-joint skeleton, per-vertex weights (the K
 largest of skin.skin_weights, K = 4 or 8) and one animation with a quaternion per joint per frame.  What it does NOT
 hold: the non-rigid offsets (skinning cannot represent them; the export is the geometry class of run.run_mesh and the
-mesh preview), the weights beyond the K largest (run.run_gltf measures what that costs), normals, textures, cameras.
+mesh preview), the weights beyond the K largest (run.run_gltf measures what that costs), textures, cameras.  Normals
+are optional (``write_glb(normals=...)``: the density-gradient normals of Network.vertex_normals, bind pose); without
+them a viewer shades every face flat.
 
 Layout of the file (``write_glb``):
 
 - container: 12-byte header, a JSON chunk padded with spaces and a BIN chunk padded with zeros, each to 4 bytes;
 - one buffer; indices UNSIGNED_INT; POSITION VEC3 FLOAT with min / max; COLOR_0 VEC4 UNSIGNED_BYTE normalised, alpha
   255, quantised like mesh.write_ply; JOINTS_0 VEC4 UNSIGNED_BYTE, WEIGHTS_0 VEC4 FLOAT (JOINTS_1 / WEIGHTS_1 when
-  K = 8); every bufferView starts on a multiple of 4 and is tightly packed;
+  K = 8); with normals NORMAL VEC3 FLOAT behind them; every bufferView starts on a multiple of 4 and is tightly packed;
 - material: KHR_materials_unlit, white -- the vertex colours are radiance the network already shaded;
 - nodes: ``root`` (static: the up-axis rotation into glTF's +Y-up world) > ``global`` (the frame's Rh / Th: x_world =
   R(Rh) x + Th) > ``joint_00`` .. ``joint_23`` along scene.SMPL_PARENT, rest translation = the canonical
@@ -168,14 +170,16 @@ def _np(a, dtype):
 
 
 def write_glb(path, verts, faces, colors, joints, weights, cnl_gtfms, dst_Rs=None, dst_Ts=None, Rh=None, Th=None,
-              fps=30, up='+z', parent=SMPL_PARENT, name='avatar'):
+              fps=30, up='+z', parent=SMPL_PARENT, name='avatar', normals=None):
     """Write the skinned, animated avatar (layout: the module's docstring).
 
     verts (V, 3) canonical; faces (F, 3); colors (V, 3) in [0, 1] or uint8; joints (V, K) uint8 and weights (V, K),
     K = 4 or 8 (skin.skin_weights); cnl_gtfms (J, 4, 4), the canonical global transforms (pure translations).
     Animation of T frames (dst_Rs None or T = 0: none is written): dst_Rs (T, J, 3, 3) the local rotations, the pose
     refiner already applied where it acts (refined_rotations); dst_Ts (T, J, 3); Rh (T, 3) axis-angle and Th (T, 3) of
-    the ``global`` node (None: identity / zero).  Returns the number of bytes written."""
+    the ``global`` node (None: identity / zero).  ``normals`` (V, 3): unit vectors in the bind pose, written as the
+    NORMAL attribute behind the weights (a zero vector, where the field has no gradient, stays zero); None: the file is
+    what it is without the argument, byte for byte.  Returns the number of bytes written."""
     from .dataset import rodrigues_cv
     from .mesh import _u8_colors
     if up not in UP:
@@ -207,6 +211,11 @@ def write_glb(path, verts, faces, colors, joints, weights, cnl_gtfms, dst_Rs=Non
     for s in range(K // 4):
         prim['attributes']['JOINTS_%d' % s] = buf.accessor(jn[:, 4 * s:4 * s + 4], UBYTE, 'VEC4', ARRAY_BUFFER)
         prim['attributes']['WEIGHTS_%d' % s] = buf.accessor(wt[:, 4 * s:4 * s + 4], FLOAT, 'VEC4', ARRAY_BUFFER)
+    if normals is not None:
+        nrm = np.ascontiguousarray(_np(normals, np.float32)).reshape(-1, 3)
+        if nrm.shape[0] != V or not np.isfinite(nrm).all():
+            raise ValueError('write_glb: normals must be (V, 3) and finite')
+        prim['attributes']['NORMAL'] = buf.accessor(nrm, FLOAT, 'VEC3', ARRAY_BUFFER)
 
     # nodes: 0 root, 1 global, 2 .. J + 1 the joints, J + 2 the mesh
     ROOT, GLOBAL, JOINT0, MESH = 0, 1, 2, J + 2
@@ -304,7 +313,12 @@ def read_glb(path):
             raise ValueError('%s: an accessor runs past its bufferView' % path)
         arr = np.ndarray((a['count'], nc), dtype=dt, buffer=blob, offset=start, strides=(stride, dt.itemsize)).copy()
         arrays.append(arr[:, 0] if nc == 1 else arr)
-    return {'json': doc, 'accessors': arrays, 'bin': blob}
+    res = {'json': doc, 'accessors': arrays, 'bin': blob}
+    for m in doc.get('meshes', []):
+        for p in m.get('primitives', []):
+            if 'NORMAL' in p.get('attributes', {}) and 'normals' not in res:
+                res['normals'] = arrays[p['attributes']['NORMAL']]          # (V, 3) float32 of the first such primitive
+    return res
 
 
 def _local_matrix(node, override):

@@ -181,17 +181,24 @@ def _u8_colors(colors):
     return np.clip(np.rint(c.astype(np.float64) * 255.0), 0, 255).astype(np.uint8)
 
 
-def write_ply(path, verts, faces, colors=None):
-    """Binary little-endian PLY: float x y z (+ uchar red green blue), faces as 'list uchar int'.  ``colors`` in
-    [0, 1] (float) or uint8."""
+def write_ply(path, verts, faces, colors=None, normals=None):
+    """Binary little-endian PLY: float x y z (+ float nx ny nz) (+ uchar red green blue), faces as 'list uchar int'.
+    ``colors`` in [0, 1] (float) or uint8; ``normals`` (V, 3) float.  Without ``normals`` the file is what it always was."""
     v = np.ascontiguousarray(_host(verts)).reshape(-1, 3)
     f = np.asarray(faces.detach().cpu().numpy() if hasattr(faces, 'detach') else faces, dtype=np.int32).reshape(-1, 3)
     vfields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')]
+    if normals is not None:
+        nrm = np.ascontiguousarray(_host(normals)).reshape(-1, 3)
+        if nrm.shape[0] != v.shape[0]:
+            raise ValueError('write_ply: %d normals for %d vertices' % (nrm.shape[0], v.shape[0]))
+        vfields += [('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')]
     if colors is not None:
         col = colors.detach().cpu().numpy() if hasattr(colors, 'detach') else colors
         vfields += [('red', 'u1'), ('green', 'u1'), ('blue', 'u1')]
     vrec = np.empty(v.shape[0], dtype=vfields)
     vrec['x'], vrec['y'], vrec['z'] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        vrec['nx'], vrec['ny'], vrec['nz'] = nrm[:, 0], nrm[:, 1], nrm[:, 2]
     if colors is not None:
         c8 = _u8_colors(col).reshape(-1, 3)
         vrec['red'], vrec['green'], vrec['blue'] = c8[:, 0], c8[:, 1], c8[:, 2]
@@ -199,6 +206,8 @@ def write_ply(path, verts, faces, colors=None):
     frec['n'], frec['i'] = 3, f
     header = ['ply', 'format binary_little_endian 1.0', 'element vertex %d' % v.shape[0],
               'property float x', 'property float y', 'property float z']
+    if normals is not None:
+        header += ['property float nx', 'property float ny', 'property float nz']
     if colors is not None:
         header += ['property uchar red', 'property uchar green', 'property uchar blue']
     header += ['element face %d' % f.shape[0], 'property list uchar int vertex_indices', 'end_header']
@@ -208,8 +217,9 @@ def write_ply(path, verts, faces, colors=None):
         fh.write(frec.tobytes())
 
 
-def read_ply(path):
-    """Reads what ``write_ply`` writes: (verts (V,3) float32, faces (F,3) int32, colors (V,3) uint8 or None)."""
+def read_ply(path, want_normals=False):
+    """Reads what ``write_ply`` writes: (verts (V,3) float32, faces (F,3) int32, colors (V,3) uint8 or None), and with
+    ``want_normals`` a fourth entry, normals (V,3) float32 or None."""
     with open(path, 'rb') as fh:
         data = fh.read()
     end = data.index(b'end_header\n') + len(b'end_header\n')
@@ -223,7 +233,9 @@ def read_ply(path):
             nv = int(l.split()[2])
         elif l.startswith('element face '):
             nf = int(l.split()[2])
-    vfields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')] + ([('r', 'u1'), ('g', 'u1'), ('b', 'u1')] if has_color else [])
+    has_normal = any(l == 'property float nx' for l in lines)
+    vfields = [('x', '<f4'), ('y', '<f4'), ('z', '<f4')] + ([('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4')] if has_normal else []) \
+        + ([('r', 'u1'), ('g', 'u1'), ('b', 'u1')] if has_color else [])
     vrec = np.frombuffer(data, dtype=vfields, count=nv, offset=end)
     off = end + vrec.nbytes
     frec = np.frombuffer(data, dtype=[('n', 'u1'), ('i', '<i4', (3,))], count=nf, offset=off)
@@ -231,6 +243,9 @@ def read_ply(path):
         raise ValueError('%s: only triangles are read' % path)
     verts = np.stack([vrec['x'], vrec['y'], vrec['z']], axis=1)
     colors = np.stack([vrec['r'], vrec['g'], vrec['b']], axis=1) if has_color else None
+    if want_normals:
+        normals = np.stack([vrec['nx'], vrec['ny'], vrec['nz']], axis=1) if has_normal else None
+        return verts, np.ascontiguousarray(frec['i']).reshape(-1, 3), colors, normals
     return verts, np.ascontiguousarray(frec['i']).reshape(-1, 3), colors
 
 

@@ -546,6 +546,9 @@ class Network(nn.Module):
         self._nr_bake_ws = None
         self.nonrigid_bake_count = 0
         self._workspace = None
+        # the gradient pass's chunk workspace (ops.density_gradient fills it) and the slot table of hnrf_ray_normals
+        self._gradient_ws = {}
+        self._normals_ws = None
         # cfg.amd.share_underflow: (live counts per chunk on the device, samples) of the last frame, None = path off
         self._share_last = None
         # set by train.Trainer when world_size > 1: dist.GradientSync whose volume_hook averages the weight-volume
@@ -1150,6 +1153,141 @@ class Network(nn.Module):
                                               cnl_bbox_scale_xyz)
         verts, faces = mesh.mesh_from_density(density, cnl_bbox_min_xyz, cnl_bbox_max_xyz, level)
         return verts, faces, self.vertex_colors(verts)
+
+    # density-gradient normals (no counterpart in the reference; include/hnrf_normals.h) --------------------------
+    def _bwd_packed(self, which):
+        """The backward image (hnrf_*_bwd_pack) of the 'canonical' or the 'nonrigid' MLP that density_gradient's dX chain
+        reads: one kept entry per (mode, head), built from the weights as the forward images are, not once per call."""
+        mode = self._mlp_mode()
+        if which == 'canonical':
+            h = self._head if self.head_num else None
+            lin = self.cnl_mlp.module.linears()
+        else:
+            h, lin = None, self.non_rigid_mlp.module.linears()
+        ws, name = [l.weight for l in lin], ('pack_bwd', which, h)
+        ent = self._kept.get(name)
+        if ent is None or not ent.built_from((mode, h), self._weights_gen, ws):
+            W = [w.detach() for w in ws]
+            if h is not None:
+                W[8] = W[8][4 * h:4 * h + 4]
+            pack = ops.canonical_bwd_pack if which == 'canonical' else ops.nonrigid_bwd_pack
+            ent = self._kept[name] = Kept((mode, h), self._weights_gen, ws,
+                                          packed=pack(W, mode, out=None if ent is None else ent.packed))
+        return ent.packed
+
+    def _gradient_head(self, what):
+        if self.head_num and (self._head is None or self._head < 0):
+            raise RuntimeError('multi-head canonical MLP (%d heads): call select_head(h) before %s (the gradient is one '
+                               "head's; all heads at once are not built)" % (self.head_num, what))
+
+    def _density_gradient(self, pts, warp=None):
+        """ops.density_gradient with this network's images and its one resident workspace.  ``warp``: (x_skel, hann_w,
+        nr_packed)."""
+        if warp is not None:
+            warp = tuple(warp) + (self._bwd_packed('nonrigid'),)
+        return ops.density_gradient(pts, self._canonical_packed(), self._bwd_packed('canonical'), self._mlp_mode(),
+                                    warp=warp, workspace=self._gradient_ws)
+
+    def density_gradient(self, points, frame=None, iter_val=1e7):
+        """The gradient of the density with respect to position at ``points`` (P, 3), by the training kernels
+        (ops.density_gradient) in _mlp_mode(): (g (P, 3), sigma (P,)) on the device.  ``points`` are canonical; given
+        ``frame`` (a frame dict: dst_posevec) they are skeleton-space points of that frame and the non-rigid chain is
+        included: g = (I + J_offset)^T grad sigma at x_skel + offset (with cfg.ignore_non_rigid_motions there is no
+        offset).  A multi-head network uses the selected head; head -1 raises."""
+        self._gradient_head('density_gradient')
+        dev = self._mesh_device()
+        with torch.no_grad():
+            pts = torch.as_tensor(points).to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+            if frame is None or bool(cfg.ignore_non_rigid_motions):
+                return self._density_gradient(pts)
+            posevec = torch.as_tensor(frame['dst_posevec']).to(device=dev, dtype=torch.float32).reshape(-1)
+            _, cond, _, hann_w, _ = self._conditioning(posevec, float(iter_val), dev, True, want_rvec=False)
+            return self._density_gradient(None, (pts, hann_w, self._nonrigid_packed(cond)))
+
+    def ray_normals(self, data, out, alpha_min=0.5, weight_min=None, iter_val=1e7, want_parts=False):
+        """One observation-space normal per ray of a rendered frame from the gradient of the density (hnrf_ray_normals):
+        (normal (N, 3) fp32, nvalid (N,) uint8) on the device.  ``data``: the frame's inputs as forward got them;
+        ``out``: what forward returned with cfg.amd.diagnostics (weights_on_rays, backward_motion_weights, xyz_on_rays,
+        alpha); ``weight_min`` (default cfg.amd.normal_weight_min): a sample takes part iff its compositing weight is
+        >= it.  Defined for cfg.perturb == 0: the samples are then the render's own.
+
+        The steps: hnrf_compact_samples over the weights; x_skel of the kept samples from hnrf_sample_warp_fwd run again
+        on the frame's rays, chunk by chunk (xyz_on_rays - offsets is not x_skel in fp32); the gradient pass with the
+        non-rigid chain behind it; hnrf_ray_normals.  The chain is skipped -- the gradient is taken at xyz_on_rays --
+        with cfg.ignore_non_rigid_motions, and below non_rigid_motion_mlp.kick_in_iter, where forward feeds the MLP
+        zeros and the offset is a per-frame constant (unless the offsets came from a baked grid).  The MLPs are always
+        evaluated, also with cfg.amd.canonical = 'baked': the normals are the exact field's.
+
+        ONE device count is read back per frame -- the number of kept samples, because the training kernels take their
+        sample count from the host: unlike the rest of a frame this call waits for the device.  ``want_parts``: also
+        return dict(idx, count, n: the kept samples; x: the points the gradient was taken at, skeleton-space when
+        ``chain``; g: the gradients)."""
+        self._gradient_head('ray_normals')
+        if float(cfg.perturb) > 0.:
+            raise ValueError('ray normals are defined for cfg.perturb == 0 only (got %r): the samples of the render are '
+                             'not reproduced otherwise' % (cfg.perturb,))
+        for k in ('weights_on_rays', 'backward_motion_weights', 'xyz_on_rays'):
+            if k not in out:
+                raise ValueError('ray_normals needs %r of a frame rendered with cfg.amd.diagnostics = True' % k)
+        weight_min = float(amd_option('normal_weight_min', 1e-4) if weight_min is None else weight_min)
+        iter_val = float(iter_val)
+        f32 = lambda t: torch.as_tensor(t).to(dtype=torch.float32)
+        with torch.no_grad():
+            S = int(out['weights_on_rays'].shape[-1])
+            w = f32(out['weights_on_rays']).reshape(-1, S).contiguous()
+            N, dev = w.shape[0], w.device
+            bmw = f32(out['backward_motion_weights']).reshape(N, S, -1).contiguous()
+            alpha = f32(out['alpha']).reshape(-1).contiguous()
+            idx, count = ops.compact_samples(w, weight_min)
+            n = int(count.item()) if N else 0                     # THE read-back: the training kernels take P from the host
+            kept = idx[:n].long()
+            dst_posevec = f32(data['dst_posevec']).to(dev)
+            ignore_nr = bool(cfg.ignore_non_rigid_motions)
+            rvec, cond, _, hann_w, nr_zero = self._conditioning(dst_posevec, iter_val, dev, True, want_hann=not ignore_nr)
+            motion_Rs, motion_Ts = motion_basis(f32(data['dst_Rs']).to(dev), f32(data['dst_Ts']).to(dev),
+                                                f32(data['cnl_gtfms']).to(dev), rvec)
+            motion_Rs = motion_Rs.contiguous()
+            chain = not (ignore_nr or (nr_zero and amd_option('nonrigid', 'mlp') != 'baked'))
+            if not chain:
+                xs = f32(out['xyz_on_rays']).reshape(-1, 3)[kept].contiguous()
+                g, _ = self._density_gradient(xs)
+            else:
+                vol = self._weight_volume(f32(data['motion_weights_priors']).to(dev))
+                rays = data['rays']
+                per_ray = (f32(rays[0]).reshape(-1, 3).contiguous(), f32(rays[1]).reshape(-1, 3).contiguous(),
+                           f32(data['near']).reshape(-1).contiguous(), f32(data['far']).reshape(-1).contiguous())
+                bmin, bscale = f32(data['cnl_bbox_min_xyz']).contiguous(), f32(data['cnl_bbox_scale_xyz']).contiguous()
+                xs = torch.zeros(n, 3, device=dev)
+                chunk = int(cfg.chunk)
+                for r0 in range(0, N, chunk):
+                    part = [t[r0:r0 + chunk] for t in per_ray]
+                    x_skel = ops.sample_warp(*part, None, motion_Rs, motion_Ts.contiguous(), vol, bmin, bscale, S)[1]
+                    local = kept - r0 * S
+                    inside = (local >= 0) & (local < x_skel.shape[0] * S)
+                    xs = torch.where(inside[:, None], x_skel.reshape(-1, 3)[local.clamp(0, x_skel.shape[0] * S - 1)], xs)
+                g, _ = self._density_gradient(None, (xs, hann_w, self._nonrigid_packed(cond)))
+            if self._normals_ws is None or self._normals_ws.numel() < N * S or self._normals_ws.device != dev:
+                self._normals_ws = torch.empty(max(N * S, 1), dtype=torch.int32, device=dev)
+            normal, nvalid = ops.ray_normals(w, bmw, motion_Rs, idx, count, g, alpha, alpha_min, workspace=self._normals_ws)
+        if want_parts:
+            return normal, nvalid, dict(idx=idx, count=count, n=n, g=g, x=xs, chain=chain)
+        return normal, nvalid
+
+    def vertex_normals(self, verts, motion_weights_priors, cnl_bbox_min_xyz, cnl_bbox_max_xyz, cnl_bbox_scale_xyz=None,
+                       want_parts=False):
+        """Unit normals (V, 3) of the surface extract_canonical_mesh cuts at canonical vertices (V, 3): -grad D / |grad D|
+        of the gated density D = relu(sigma) fg of canonical_density_grid (hnrf_field_normals), grad sigma from
+        density_gradient and grad fg from the weight volume's trilinear weights.  0 where the gradient vanishes.
+        ``want_parts``: (normals, g, sigma, vol)."""
+        self._gradient_head('vertex_normals')
+        with torch.no_grad():
+            dev = self._mesh_device()
+            bmin, _, scale = self._mesh_bbox(cnl_bbox_min_xyz, cnl_bbox_max_xyz, cnl_bbox_scale_xyz)
+            vol = self._weight_volume(torch.as_tensor(motion_weights_priors).to(device=dev, dtype=torch.float32))
+            verts = torch.as_tensor(verts).to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+            g, sigma = self._density_gradient(verts)
+            normals = ops.field_normals(verts, g, sigma, vol, vol.shape[0] - 1, bmin, scale)   # (the background channel is last)
+        return (normals, g, sigma, vol) if want_parts else normals
 
     def refiner_rvec(self, frame, iter_val=1e7):
         """The pose refiner's axis-angle corrections (23, 3) for a frame dict (dst_posevec), as frame_motion applies them

@@ -1655,3 +1655,234 @@ def geometry_maps(rays_o, rays_d, surf, pix2ray, H, W, want, surface=0, alpha=No
                                           float(ambient), float(albedo), _ptr(truth8), _ptr(status),
                                           *[_ptr(res.get(k)) for k in GEOMETRY_OUTPUTS], _stream()), 'hnrf_geometry_maps')
     return res
+
+
+# ------------------------------------------------------------------------------------------ density-gradient normals
+def canonical_bwd_pack(weights, mode='f32', out=None):
+    """hnrf_canonical_bwd_pack: the transposed image of the 9 canonical nn.Linear weights the dX chain reads, for a
+    caller that keeps it (canonical_bwd packs one per call).  ``out``: a buffer of a former pack to write into."""
+    lib = _lib.load()
+    _chk(*weights)
+    assert len(weights) == 9
+    m = MLP_MODES[mode]
+    nbytes = lib.hnrf_canonical_bwd_packed_bytes(m)
+    if out is None or out.numel() * 4 < nbytes:
+        out = torch.empty((nbytes + 3) // 4, device=weights[0].device)
+    _lib.check(lib.hnrf_canonical_bwd_pack(_ptr_array(weights), m, _ptr(out), _stream()), 'hnrf_canonical_bwd_pack')
+    return out
+
+
+def nonrigid_bwd_pack(weights, mode='f32', out=None):
+    """hnrf_nonrigid_bwd_pack: as canonical_bwd_pack, of the 7 non-rigid nn.Linear weights."""
+    lib = _lib.load()
+    _chk(*weights)
+    assert len(weights) == 7
+    m = MLP_MODES[mode]
+    nbytes = lib.hnrf_nonrigid_bwd_packed_bytes(m)
+    if out is None or out.numel() * 4 < nbytes:
+        out = torch.empty((nbytes + 3) // 4, device=weights[0].device)
+    _lib.check(lib.hnrf_nonrigid_bwd_pack(_ptr_array(weights), m, _ptr(out), _stream()), 'hnrf_nonrigid_bwd_pack')
+    return out
+
+
+GRADIENT_CHUNK = 16384
+# bytes of workspace per sample of a chunk, 'f32' and 'f16x3' alike (both save fp32 activations):
+#   canonical  raw 16 + pe 252 + acts 8192 + relu_bits 256 + d_raw 16 + dZ 8192
+#   non-rigid  xyz 12 + offsets 12 + pe 144 + acts 3072 + relu_bits 96 + dZ 3072
+GRADIENT_BYTES_CANONICAL, GRADIENT_BYTES_NONRIGID = 16924, 6408
+
+
+def _gradient_workspace(ws, C, with_warp, dev):
+    key = (int(C), str(dev))
+    if ws.get('key') != key:
+        ws.clear()
+        ws['key'] = key
+        f = lambda n: torch.empty(n, device=dev)
+        i = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
+        d_raw = torch.zeros(C, 4, device=dev)
+        d_raw[:, 3] = 1.0
+        ws.update(raw=f(C * 4), pe=f(C * 63), acts=f(8 * C * 256), bits=i(8 * C * 8), dZ=f(8 * C * 256), d_raw=d_raw,
+                  one=torch.ones(1, device=dev), amax=torch.zeros(1, device=dev))
+    if with_warp and 'nr_acts' not in ws:
+        f = lambda n: torch.empty(n, device=dev)
+        ws.update(nr_xyz=f(C * 3), nr_off=f(C * 3), nr_pe=f(C * 36), nr_acts=f(6 * C * 128),
+                  nr_bits=torch.empty(6 * C * 4, dtype=torch.int32, device=dev), nr_dZ=f(6 * C * 128))
+    return ws
+
+
+def density_gradient(xyz, cnl_packed, cnl_weights, mode='f32', warp=None, workspace=None, chunk=GRADIENT_CHUNK):
+    """The gradient of the canonical MLP's density with respect to position, by the training kernels: g (P, 3) fp32 and
+    sigma (P,) (the pre-activation density, raw[:, 3]).
+
+    ``xyz`` (P, 3): canonical points; ``cnl_packed``: the forward image (canonical_pack) of ``mode`` ('f32' | 'f16x3');
+    ``cnl_weights``: the backward image (canonical_bwd_pack: one tensor, what a caller keeps) or the 9 nn.Linear
+    weights, packed here then.  The forward is hnrf_canonical_fwd_train, the backward hnrf_canonical_bwd with
+    d_raw = (0, 0, 0, 1) in every row and d_raw_amax = 1, a resident one-element tensor.
+
+    ``warp`` = (x_skel (P, 3), hann_w (6,), nr_packed, nr_weights (the backward image or the 7 weights)): the points are
+    skeleton-space points, xyz = hnrf_nonrigid_fwd_train(x_skel) (``xyz`` is ignored: pass None) and the result is
+    hnrf_nonrigid_bwd's d_x_skel = d_xyz + J_offset^T d_xyz, with d_xyz_amax the maximum magnitude of d_xyz over ALL P
+    samples, reduced on the device and never read back.  For that the pass has two phases: the canonical gradients of
+    every chunk first, the non-rigid chain of every chunk behind them (its forward runs a second time for the sign
+    masks) -- so that the result does not depend on ``chunk``, bit for bit, in 'f16x3' too.
+
+    The MLP kernels write activations and per-layer gradients nobody wants here, so the pass runs over at most ``chunk``
+    samples at a time through ``workspace``, a dict the caller keeps (filled here; {} or None = a fresh one).  It takes
+    GRADIENT_BYTES_CANONICAL = 16924 bytes per sample of a chunk in either mode, and GRADIENT_BYTES_NONRIGID = 6408 more
+    with ``warp`` (277 MB and 382 MB at the default chunk of 16384).  Nothing synchronises."""
+    lib = _lib.load()
+    if mode not in MLP_MODES:
+        raise _lib.HnrfError("density_gradient: mode must be 'f32' or 'f16x3', got %r" % (mode,))
+    m = TRAIN_MODES[mode]
+    C = int(chunk)
+    if C < 1:
+        raise _lib.HnrfError('density_gradient: chunk must be >= 1, got %r' % (chunk,))
+    if warp is not None:
+        x_skel, hann_w, nr_packed, nr_weights = warp
+        _chk(x_skel, hann_w, nr_packed)
+        x_skel = x_skel.reshape(-1, 3)
+        P, dev = x_skel.shape[0], x_skel.device
+    else:
+        _chk(xyz)
+        xyz = xyz.reshape(-1, 3)
+        P, dev = xyz.shape[0], xyz.device
+    _chk(cnl_packed)
+    g, sigma = torch.empty(P, 3, device=dev), torch.empty(P, device=dev)
+    if P == 0:
+        return g, sigma
+    if not torch.is_tensor(cnl_weights):
+        cnl_weights = canonical_bwd_pack(list(cnl_weights), mode)
+    _chk(cnl_weights)
+    if warp is not None:
+        if not torch.is_tensor(nr_weights):
+            nr_weights = nonrigid_bwd_pack(list(nr_weights), mode)
+        _chk(nr_weights)
+    ws = _gradient_workspace({} if workspace is None else workspace, min(C, max(P, 1)) if workspace is None else C,
+                             warp is not None, dev)
+    C = ws['key'][0]
+    st = _stream()
+    with torch.cuda.device(dev):
+        for i in range(0, P, C):
+            n = min(C, P - i)
+            if warp is not None:
+                _lib.check(lib.hnrf_nonrigid_fwd_train(_ptr(x_skel[i:i + n]), _ptr(hann_w), _ptr(nr_packed), m, n,
+                                                       _ptr(ws['nr_xyz']), _ptr(ws['nr_off']), _ptr(ws['nr_pe']),
+                                                       _ptr(ws['nr_acts']), ws['nr_bits'].data_ptr(), st),
+                           'hnrf_nonrigid_fwd_train')
+                pts = ws['nr_xyz']
+            else:
+                pts = xyz[i:i + n]
+            _lib.check(lib.hnrf_canonical_fwd_train(_ptr(pts), _ptr(cnl_packed), m, n, _ptr(ws['raw']), _ptr(ws['pe']),
+                                                    _ptr(ws['acts']), ws['bits'].data_ptr(), st), 'hnrf_canonical_fwd_train')
+            _lib.check(lib.hnrf_canonical_bwd(_ptr(pts), _ptr(ws['d_raw']), ws['bits'].data_ptr(), _ptr(cnl_weights), m,
+                                              _ptr(ws['one']), n, _ptr(ws['dZ']), _ptr(g[i:i + n]), 0, st),
+                       'hnrf_canonical_bwd')
+            sigma[i:i + n].copy_(ws['raw'][:4 * n].view(n, 4)[:, 3])
+        if warp is not None:
+            d_xyz = g.clone()
+            torch.amax(d_xyz.abs().reshape(-1), dim=0, keepdim=True, out=ws['amax'])
+            for i in range(0, P, C):
+                n = min(C, P - i)
+                _lib.check(lib.hnrf_nonrigid_fwd_train(_ptr(x_skel[i:i + n]), _ptr(hann_w), _ptr(nr_packed), m, n,
+                                                       _ptr(ws['nr_xyz']), _ptr(ws['nr_off']), _ptr(ws['nr_pe']),
+                                                       _ptr(ws['nr_acts']), ws['nr_bits'].data_ptr(), st),
+                           'hnrf_nonrigid_fwd_train')
+                _lib.check(lib.hnrf_nonrigid_bwd(_ptr(x_skel[i:i + n]), _ptr(hann_w), _ptr(d_xyz[i:i + n]),
+                                                 ws['nr_bits'].data_ptr(), _ptr(nr_weights), m, _ptr(ws['amax']), n,
+                                                 _ptr(ws['nr_dZ']), _ptr(g[i:i + n]), 0, st), 'hnrf_nonrigid_bwd')
+    return g, sigma
+
+
+def ray_normals(weights, bmw, motion_Rs, idx, count, g, alpha, alpha_min=0.5, workspace=None, out=None):
+    """hnrf_ray_normals (include/hnrf_normals.h): weights (R, S), bmw (R, S, B), motion_Rs (B, 3, 3), idx / count from
+    compact_samples(weights, weight_min), g (n, 3) the gradient at the first n kept samples, alpha (R,) -> (normal (R, 3),
+    nvalid (R,) uint8).  ``workspace``: an int32 tensor of R S elements to use as the slot table; ``out``: (normal,
+    nvalid) to write into."""
+    lib = _lib.load_normals()
+    _chk(weights, bmw, motion_Rs, g, alpha)
+    _chk_dev(idx, torch.int32, 'ray_normals: idx')
+    _chk_dev(count, torch.int32, 'ray_normals: count')
+    if weights.dim() != 2 or bmw.dim() != 3 or bmw.shape[:2] != weights.shape or motion_Rs.shape != (bmw.shape[2], 3, 3) \
+            or g.dim() != 2 or g.shape[1] != 3 or alpha.shape != (weights.shape[0],):
+        raise _lib.HnrfError('ray_normals: weights (R, S), bmw (R, S, B), motion_Rs (B, 3, 3), g (n, 3), alpha (R,) '
+                             'expected, got %s %s %s %s %s' % (tuple(weights.shape), tuple(bmw.shape),
+                                                               tuple(motion_Rs.shape), tuple(g.shape), tuple(alpha.shape)))
+    R, S = weights.shape
+    dev = weights.device
+    n_max = min(int(g.shape[0]), int(idx.numel()))
+    need = lib.hnrf_ray_normals_workspace_bytes(R, S)
+    if workspace is None or workspace.numel() * 4 < need:
+        workspace = torch.empty(max((need + 3) // 4, 1), dtype=torch.int32, device=dev)
+    _chk_dev(workspace, torch.int32, 'ray_normals: workspace')
+    normal, nvalid = out if out is not None else (torch.empty(R, 3, device=dev), torch.empty(R, dtype=torch.uint8, device=dev))
+    _chk(normal)
+    _chk_dev(nvalid, torch.uint8, 'ray_normals: nvalid')
+    if normal.numel() < 3 * R or nvalid.numel() < R:
+        raise _lib.HnrfError('ray_normals: an output is smaller than %d rays' % R)
+    with torch.cuda.device(dev):
+        _lib.check(lib.hnrf_ray_normals(_ptr(weights), _ptr(bmw), _ptr(motion_Rs), _ptr(idx), _ptr(count), n_max, _ptr(g),
+                                        _ptr(alpha), R, S, int(bmw.shape[2]), float(alpha_min), _ptr(workspace),
+                                        workspace.numel() * 4, _ptr(normal), _ptr(nvalid), _stream()), 'hnrf_ray_normals')
+    return normal, nvalid
+
+
+NORMAL_OUTPUTS = ('normal', 'nvalid', 'normal8', 'shaded8')
+
+
+def normal_panels(rays_d, ray_normal, ray_nvalid, valid, pix2ray, H, W, want, surface=0, alpha=None, M=None, bgcolor=None,
+                  ambient=0.25, albedo=0.8, status=None, out=None):
+    """hnrf_normal_panels: per-ray normals (ray_normals), ``valid`` of ray_surface and pix2ray of pixel_rays -> {name:
+    tensor} for ``want`` out of NORMAL_OUTPUTS: normal (H, W, 3) fp32, nvalid (H, W) uint8, normal8 / shaded8 (H, W, 3)
+    uint8.  ``out``: tensors to write into."""
+    lib = _lib.load_normals()
+    bad = [k for k in want if k not in NORMAL_OUTPUTS]
+    if bad:
+        raise _lib.HnrfError('normal_panels: unknown outputs %r (out of %r)' % (bad, NORMAL_OUTPUTS))
+    _chk(rays_d, ray_normal, alpha, M, bgcolor)
+    _chk_dev(pix2ray, torch.int32, 'normal_panels: pix2ray')
+    _chk_dev(ray_nvalid, torch.uint8, 'normal_panels: ray_nvalid')
+    _chk_dev(valid, torch.uint8, 'normal_panels: valid')
+    H, W, N, dev = int(H), int(W), rays_d.shape[0], rays_d.device
+    if rays_d.shape != (N, 3) or pix2ray.numel() < H * W or ray_normal.numel() < 3 * N or ray_nvalid.numel() < N or \
+            valid.numel() < N or (alpha is not None and alpha.numel() < N):
+        raise _lib.HnrfError('normal_panels: rays_d (N, 3), per-ray inputs of N = %d rays and pix2ray of H * W expected' % N)
+    for name, v, k in (('M', M, 9), ('bgcolor', bgcolor, 3)):
+        if v is not None and v.numel() != k:
+            raise _lib.HnrfError('normal_panels: %s must hold %d floats' % (name, k))
+    if status is not None:
+        _chk_dev(status, torch.int32, 'normal_panels: status')
+    out = {} if out is None else out
+    res = {}
+    for k in want:
+        shape, dtype = ((H, W, 3), torch.float32) if k == 'normal' else ((H, W), torch.uint8) if k == 'nvalid' else \
+            ((H, W, 3), torch.uint8)
+        t = out.get(k)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        _chk_dev(t, dtype, 'normal_panels: ' + k)
+        if tuple(t.shape) != shape:
+            raise _lib.HnrfError('normal_panels: %s must be %r, got %r' % (k, shape, tuple(t.shape)))
+        res[k] = t
+    with torch.cuda.device(dev):
+        _lib.check(lib.hnrf_normal_panels(_ptr(rays_d), _ptr(ray_normal), _ptr(ray_nvalid), _ptr(valid), int(surface),
+                                          _ptr(alpha), _ptr(pix2ray), N, H, W, _ptr(M), _ptr(bgcolor), float(ambient),
+                                          float(albedo), _ptr(status), *[_ptr(res.get(k)) for k in NORMAL_OUTPUTS],
+                                          _stream()), 'hnrf_normal_panels')
+    return res
+
+
+def field_normals(verts, g, sigma, vol, n_bones, bbox_min, bbox_scale):
+    """hnrf_field_normals: verts (V, 3) canonical, g (V, 3) and sigma (V,) of density_gradient there, vol (>= n_bones,
+    G, G, G) -> normal (V, 3): -grad D / |grad D| of D = relu(sigma) fg, 0 where the length is 0 or not finite."""
+    lib = _lib.load_normals()
+    _chk(verts, g, sigma, vol, bbox_min, bbox_scale)
+    V, G = verts.shape[0], vol.shape[-1]
+    if verts.shape != (V, 3) or g.shape != (V, 3) or sigma.shape != (V,) or vol.dim() != 4 or vol.shape[0] < n_bones or \
+            vol.shape[1] != G or vol.shape[2] != G or bbox_min.numel() != 3 or bbox_scale.numel() != 3:
+        raise _lib.HnrfError('field_normals: verts (V, 3), g (V, 3), sigma (V,), vol (>= B, G, G, G), bbox_min / '
+                             'bbox_scale (3,) expected')
+    normal = torch.empty(V, 3, device=verts.device)
+    with torch.cuda.device(verts.device):
+        _lib.check(lib.hnrf_field_normals(_ptr(verts), _ptr(g), _ptr(sigma), V, _ptr(vol), int(n_bones), G, _ptr(bbox_min),
+                                          _ptr(bbox_scale), _ptr(normal), _stream()), 'hnrf_field_normals')
+    return normal

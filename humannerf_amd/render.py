@@ -708,7 +708,9 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
     behind the other panels, so ``video`` encodes them too.  The normal panel is in the camera frame of the frame's
     ``E`` (the rasteriser's shade = 'normal'); 'offset' is painted where the truth has colour when the frame has one.
     A frame rendered again after an f16-range hit gets its maps again; with ``images='none'`` they go into the video
-    only.  ``on_image`` gets what it gets without maps."""
+    only.  ``on_image`` gets what it gets without maps.  With cfg.amd.maps_normals = 'gradient' the 'normal' and
+    'shaded' panels are painted from density-gradient normals (Network.ray_normals, which reads one device count back per
+    frame: such a loop waits for the device once per frame; 'screen', the default, never does)."""
     device = device or next(network.parameters()).device
     if images not in ('host', 'none'):
         raise ValueError("render_frames: images must be 'host' or 'none', got %r" % (images,))
@@ -724,6 +726,10 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
         from .config import amd_option
         maps_surface = amd_option('maps_surface', 'expected')
         geometry.check_maps(maps, maps_surface, bool(amd_option('diagnostics', True)))
+        gradient_normals = amd_option('maps_normals', 'screen') == 'gradient' and ('normal' in maps or 'shaded' in maps)
+        if gradient_normals and not amd_option('diagnostics', True):
+            raise ValueError("cfg.amd.maps_normals = 'gradient' needs cfg.amd.diagnostics = True: the lean form returns "
+                             "neither the per-sample weights nor the bone weights")
         if device.type != 'cuda':
             raise ValueError('render_frames: geometry maps need a GPU (got device %s); on the host use geometry.maps_host'
                              % device)
@@ -796,8 +802,13 @@ def render_frames(network, frames, rank=0, world=1, device=None, on_image=None, 
             mvec = torch.stack([vals[k] for k in metrics])
         gmaps = None
         if maps is not None:
+            extra = {}
+            if gradient_normals:
+                # (the one place of a frame that waits for the device: Network.ray_normals reads the kept count back)
+                extra['ray_normals'] = network.ray_normals(item['data'], res, iter_val=float(cfg.eval_iter))
             gm = geometry.frame_maps(item['data'], res, item['H'], item['W'], item['ray_index'], maps=maps,
-                                     surface=maps_surface, M=item.get('M'), truth8=t8 if item['truth'] is not None else None)
+                                     surface=maps_surface, M=item.get('M'), truth8=t8 if item['truth'] is not None else None,
+                                     **extra)
             gmaps = {m: gm[m] for m in maps}
         vid = None
         if video is not None:

@@ -345,11 +345,13 @@ def run_heads(network, subject, kind='movement', frame_idx=None, total_frames=No
              'metrics': mws[h].finalize() if mws is not None else None} for h in range(H)]
 
 
-def run_mesh(network, subject, frames=(), resolution=256, level=None, logdir=None):
+def run_mesh(network, subject, frames=(), resolution=256, level=None, logdir=None, normals=False):
     """Network.extract_canonical_mesh over the subject's canonical bbox, written as ``<out>/mesh/canonical.ply``, and
     for every entry of ``frames`` (index into subject.framelist, or frame name) that mesh posed with
     Network.pose_vertices, written as ``<out>/mesh/<frame_name>.ply`` (vertex colours of the canonical mesh; the
-    non-rigid offsets are not inverted).  ``level``: None = Network.MESH_LEVEL.  Returns {name: path}."""
+    non-rigid offsets are not inverted).  ``level``: None = Network.MESH_LEVEL.  ``normals``: ``canonical.ply`` also
+    holds the density-gradient normals of its vertices (Network.vertex_normals; the posed files do not: a posed normal
+    needs the skinning matrix of its vertex).  Returns {name: path}."""
     from . import mesh
     out_dir = os.path.join(_output_dir(logdir), 'mesh')
     os.makedirs(out_dir, exist_ok=True)
@@ -359,7 +361,11 @@ def run_mesh(network, subject, frames=(), resolution=256, level=None, logdir=Non
         level=network.MESH_LEVEL if level is None else level)
     faces_h, colors_h = faces.cpu().numpy(), colors.cpu().numpy()
     written = {'canonical': os.path.join(out_dir, 'canonical.ply')}
-    mesh.write_ply(written['canonical'], verts.cpu().numpy(), faces_h, colors_h)
+    if normals:
+        vn = network.vertex_normals(verts, subject.motion_weights_priors, bbox['min_xyz'], bbox['max_xyz'])
+        mesh.write_ply(written['canonical'], verts.cpu().numpy(), faces_h, colors_h, normals=vn.cpu().numpy())
+    else:
+        mesh.write_ply(written['canonical'], verts.cpu().numpy(), faces_h, colors_h)
     for f in frames:
         idx = subject.framelist.index(f) if isinstance(f, str) else int(f)
         frame = subject.movement_frame(idx, image_size=(1, 1))          # (the camera entries are not used)
@@ -370,13 +376,15 @@ def run_mesh(network, subject, frames=(), resolution=256, level=None, logdir=Non
 
 
 def run_gltf(network, subject, frames=None, resolution=256, level=None, influences=4, fps=30, up='+z', logdir=None,
-             iter_val=1e7):
+             iter_val=1e7, normals=False):
     """The avatar as ONE skinned, animated glTF 2.0 binary, ``<out>/mesh/avatar.glb`` (humannerf_amd/gltf.py): the
     canonical mesh of run_mesh with its vertex colours, the 24-joint skeleton, the ``influences`` (4 or 8) largest bone
     weights of every vertex (Network.skin_weights) and one animation over ``frames`` (indices into subject.framelist or
     frame names; None: the whole framelist; the camera entries are not used) at ``fps``.  ``up``: the up axis of the
     subject's world, '+z' (ZJU-MoCap, the default), '+y' or '-y'.  The pose refiner acts as in Network.pose_vertices
     (``iter_val`` against its kick-in).  The non-rigid offsets are not in the file: skinning cannot represent them.
+    ``normals``: the file also holds a NORMAL attribute, the density-gradient normals of the canonical vertices
+    (Network.vertex_normals), so that a viewer shades smoothly.
 
     For every frame the device compares what a viewer will compute, skin.skin_lbs of the truncated weights with the
     frame's joint matrices, with the exact forward skin Network.pose_vertices.  Returns {'path', 'V', 'F', 'frames',
@@ -418,7 +426,8 @@ def run_gltf(network, subject, frames=None, resolution=256, level=None, influenc
     path = os.path.join(out_dir, 'avatar.glb')
     gltf.write_glb(path, verts, faces, colors, joints, weights, subject.cnl_gtfms,
                    dst_Rs=np.stack(dst_Rs) if idxs else None, dst_Ts=np.stack(dst_Ts) if idxs else None,
-                   Rh=np.stack(Rh) if idxs else None, Th=np.stack(Th) if idxs else None, fps=fps, up=up)
+                   Rh=np.stack(Rh) if idxs else None, Th=np.stack(Th) if idxs else None, fps=fps, up=up,
+                   **(dict(normals=network.vertex_normals(verts, priors, bbox['min_xyz'], bbox['max_xyz'])) if normals else {}))
     per = torch.stack(errs).cpu().numpy().astype(np.float64) if idxs else np.zeros((0, 2))
     return {'path': path, 'V': int(verts.shape[0]), 'F': int(faces.shape[0]), 'frames': idxs,
             'kept': {'min': float(kept.min()), 'mean': float(kept.mean())},

@@ -794,6 +794,11 @@ int hnrf_image_metrics(const uint8_t* pred, const uint8_t* target, const uint8_t
  * ABI version 13; contracts and declarations in hnrf_heads_shared.h. */
 #include "hnrf_heads_shared.h"
 
+/* ---- density-gradient normals: one observation-space normal per ray from the gradients the training kernels return,
+ * the normal / shaded panels painted from them, and the normal of the gated density a mesh is cut from.  Additive to ABI
+ * version 13; contracts and declarations in hnrf_normals.h. */
+#include "hnrf_normals.h"
+
 #ifdef __cplusplus
 }
 #endif
