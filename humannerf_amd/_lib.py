@@ -39,6 +39,7 @@ LATE_GROUPS = {
 OPEN_GROUPS = {
     'heads_shared': ('hnrf_heads_shared.h', 'the shared evaluation for all heads'),
     'normals': ('hnrf_normals.h', 'the density-gradient normals'),
+    'heads_train': ('hnrf_heads_train.h', 'the multi-head training kernels'),
 }
 
 _SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float,
@@ -105,6 +106,7 @@ SKIN_HEADER_PATH, SKIN_SIGNATURES = _LATE_HEADERS['skin']
 _OPEN_HEADERS = {group: _header(group, OPEN_GROUPS) for group in OPEN_GROUPS}
 HEADS_SHARED_HEADER_PATH, HEADS_SHARED_SIGNATURES = _OPEN_HEADERS['heads_shared']
 NORMALS_HEADER_PATH, NORMALS_SIGNATURES = _OPEN_HEADERS['normals']
+HEADS_TRAIN_HEADER_PATH, HEADS_TRAIN_SIGNATURES = _OPEN_HEADERS['heads_train']
 
 _lib = None
 
@@ -197,6 +199,10 @@ def load_heads_shared(lib=None):
 
 def load_normals(lib=None):
     return _bind_table('normals', lib, OPEN_GROUPS, _OPEN_HEADERS)
+
+
+def load_heads_train(lib=None):
+    return _bind_table('heads_train', lib, OPEN_GROUPS, _OPEN_HEADERS)
 
 
 def load_open():

@@ -8,6 +8,7 @@ holding the whole output), K1'.  No library GEMM is left on the per-sample path.
 bases, the weight volume and all MLP parameters -- exactly the tensors through which the
 reference's four parameter groups receive gradient (last row).
 """
+import functools
 import math
 
 import torch
@@ -16,17 +17,30 @@ from . import ops
 from .config import amd_option
 
 
+def _head_grads(dY, width, dw):
+    """dW / db of the head layer.  dY [P, n_out]: one call of ``dw``.  dY [H][P][4] (multi-head canonical MLP): one call
+    per plane, written to rows 4h .. 4h+3 of the (4 H, width) gradient -- the head kernels take n_out <= 4."""
+    if dY.dim() == 2:
+        return dw(dY)
+    H = dY.shape[0]
+    gW, gb = dY.new_empty(4 * H, width), dY.new_empty(4 * H)
+    for h in range(H):
+        dw(dY[h], dW_out=gW[4 * h:4 * h + 4], db_out=gb[4 * h:4 * h + 4])
+    return gW, gb
+
+
 def _weight_grads(dZ, acts, pe, dY, weights, skip_layer, skip_order, amax=None, mode='f32'):
     """dW / db of every layer from the chain kernel's dZ [L][P][W], the saved activations and PE matrix.
-    dY: gradient at the (3- / 4-wide) head output.  mode 'f16x3' (with amax from the chain kernel) runs the
-    matrix-shaped layers on the split-f16 kernel; PE blocks and heads stay fp32."""
+    dY: gradient at the (3- / 4-wide) head output, or [H][P][4] head-major planes of a multi-head canonical MLP.
+    mode 'f16x3' (with amax from the chain kernel) runs the matrix-shaped layers on the split-f16 kernel; PE blocks
+    and heads stay fp32."""
     n_hidden = acts.shape[0]
     npe = pe.shape[1]
     gW, gb = [None] * (n_hidden + 1), [None] * (n_hidden + 1)
     am = (lambda l: amax[l]) if amax is not None else (lambda l: None)
     if amax is None:
         mode = 'f32'
-    gW[n_hidden], gb[n_hidden] = ops.mlp_dw(dY, acts[n_hidden - 1])
+    gW[n_hidden], gb[n_hidden] = _head_grads(dY, acts.shape[-1], lambda dy, **out: ops.mlp_dw(dy, acts[n_hidden - 1], **out))
     for l in range(n_hidden):
         if l == 0:
             gW[l], gb[l] = ops.mlp_dw(dZ[l], pe)
@@ -47,9 +61,9 @@ def _weight_grads_h(dZ, scale, acts, pe, dY, weights, skip_layer, skip_order, np
     (``npe`` real columns), dY fp32 [P, 3|4] at the head output.  Every layer runs on hnrf_mlp_dw_h (transposed LDS reads,
     one f16 MFMA per product, fp32 accumulation)."""
     n_hidden = acts.shape[0]
-    P = dY.shape[0]
+    P = dY.shape[-2]
     gW, gb = [None] * (n_hidden + 1), [None] * (n_hidden + 1)
-    gW[n_hidden], gb[n_hidden] = ops.mlp_dw_h(dY, acts[n_hidden - 1], P=P, x_blocked=True)
+    gW[n_hidden], gb[n_hidden] = _head_grads(dY, acts.shape[-1], lambda dy, **out: ops.mlp_dw_h(dy, acts[n_hidden - 1], P=P, x_blocked=True, **out))
     for l in range(n_hidden):
         sc = scale[l:l + 1]
         if l == 0:
@@ -148,7 +162,12 @@ class RenderRays(torch.autograd.Function):
     """rgb, alpha, depth[, 8 diagnostic outputs] = RenderRays.apply(consts..., motion_Rs, motion_Ts, vol, *mlp_params)
 
     With ``diag`` the other keys of the reference's return dict (network.py:776-789) come out too, as
-    non-differentiable tensors, in OUTPUT_KEYS order."""
+    non-differentiable tensors, in OUTPUT_KEYS order.
+
+    One body for n >= 1 planes.  n = 1 is the single-head canonical MLP.  With a (4 n, 256) output_linear.0, n >= 2,
+    every head is rendered from ONE pass through both trunks: the keys of ops.HEAD_KEYS come out head-major, [n, ...],
+    the backward takes [n, ...] gradients, and runs K4' per plane, the chain seeded with every plane's d_raw
+    (hnrf_canonical_heads_bwd), the hidden layers' weight gradients once and the head's once per plane."""
 
     OUTPUT_KEYS = tuple(ops.output_shapes(0, 0))
 
@@ -175,9 +194,21 @@ class RenderRays(torch.autograd.Function):
         else:
             xyz, pe_n, acts_n, bits_n = x_skel, None, None, None
             offsets = torch.zeros_like(x_skel) if diag else None            # network.py:276-277
-        cn_packed = ops.canonical_pack(cn_w, cn_b, mode)
-        raw, pe_c, acts_c, bits_c = ops.canonical_train(xyz, cn_packed, tmode)
-        out = ops.composite(raw, mask, z, rays_d, xyz if diag else None, bg, diagnostics=bool(diag))
+        n = cn_w[8].shape[0] // 4                                            # planes: heads of the canonical MLP
+        if n == 1:
+            cn_packed = ops.canonical_pack(cn_w, cn_b, mode)
+            raw, pe_c, acts_c, bits_c = ops.canonical_train(xyz, cn_packed, tmode)
+            out = ops.composite(raw, mask, z, rays_d, xyz if diag else None, bg, diagnostics=bool(diag))
+        else:
+            cn_packed = ops.canonical_heads_pack(cn_w, cn_b, n, mode)
+            raw, pe_c, acts_c, bits_c = ops.canonical_heads_train(xyz, cn_packed, n, tmode)      # raw [n, R, S, 4]
+            R, S = z.shape
+            out = {k: torch.empty((n, R) + v, device=z.device)
+                   for k, v in list(ops.output_shapes(S, 0, bool(diag)).items())[:8]}
+            for h in range(n):
+                ops.composite(raw[h], mask, z, rays_d, xyz if diag else None, bg, diagnostics=bool(diag),
+                              out={k: v[h] for k, v in out.items()})
+        ctx.n_planes = n
         ctx.use_nonrigid = use_nonrigid
         ctx.const_offset = const_offset is not None
         ctx.half = half
@@ -199,18 +230,30 @@ class RenderRays(torch.autograd.Function):
         cn_w = list(ctx.saved_tensors[28:37])
         P = z.numel()
         c = lambda t: None if t is None else t.contiguous()
-        d_raw, d_mask = ops.composite_bwd(raw, mask, z, rays_d, bg, c(g_rgb), c(g_alpha), c(g_depth))
+        n = ctx.n_planes
+        if n == 1:
+            d_raw, d_mask = ops.composite_bwd(raw, mask, z, rays_d, bg, c(g_rgb), c(g_alpha), c(g_depth))
+            d_raw = d_raw.view(P, 4)
+            chain = ops.canonical_bwd
+        else:
+            # K4' once per plane: d_raw [n, P, 4] head-major, the mask's gradient summed over the planes
+            gh = lambda t, h: None if t is None else t[h].contiguous()
+            d_raw, d_mask = torch.empty(n, P, 4, device=z.device), None
+            for h in range(n):
+                _, m_h = ops.composite_bwd(raw[h], mask, z, rays_d, bg, gh(g_rgb, h), gh(g_alpha, h), gh(g_depth, h),
+                                           d_raw_out=d_raw[h])
+                d_mask = m_h if d_mask is None else d_mask.add_(m_h)
+            chain = functools.partial(ops.canonical_heads_bwd, n_heads=n)
         # canonical MLP (skip layer 5 takes [PE63 | h]): dX chain with the PE backward fused, then the weight gradients
-        d_raw = d_raw.view(P, 4)
         _, chain_mode, dw_mode, _ = training_modes()
         guard = chain_mode != 'f32' or dw_mode != 'f32'
         if guard:
             range_guard.calls += 1
         if ctx.half:
-            dZc, d_xyz, sc_c = ops.canonical_bwd(xyz.reshape(P, 3), d_raw, bits_c, cn_w, 'f16x3h')
+            dZc, d_xyz, sc_c = chain(xyz.reshape(P, 3), d_raw, bits_c, cn_w, mode='f16x3h')
             gWc, gbc = _weight_grads_h(dZc, sc_c, acts_c, pe_c, d_raw, cn_w, skip_layer=5, skip_order='pe_first', npe=63)
         else:
-            dZc, d_xyz, amax_c = ops.canonical_bwd(xyz.reshape(P, 3), d_raw, bits_c, cn_w, chain_mode)
+            dZc, d_xyz, amax_c = chain(xyz.reshape(P, 3), d_raw, bits_c, cn_w, mode=chain_mode)
             gWc, gbc = _weight_grads(dZc, acts_c, pe_c, d_raw, cn_w, skip_layer=5, skip_order='pe_first', amax=amax_c,
                                      mode=dw_mode)
         dZc_keep = dZc if (guard and range_guard.due()) else None

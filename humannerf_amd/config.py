@@ -132,6 +132,12 @@ _DEFAULTS = {
         # every this many backward passes the saved activations and the incoming gradient are checked against the
         # range the split-f16 / f16 arithmetic assumes (autograd.OperandRangeGuard); 0 = never
         'train_check_every': 200,
+        # training a multi-head canonical MLP (canonical_mlp.multihead.enable, 2..8 heads of depth 1).  False: such a
+        # network is inference only -- Trainer and a training-mode forward raise.  True: a training-mode forward with
+        # head_id = h trains head h (the single-head kernels on rows 4h .. 4h+3 of output_linear.0; the other heads' rows
+        # get zero gradients), head_id = -1 renders and differentiates every head from one pass through both trunks
+        # (include/hnrf_heads_train.h), and Trainer reads batch['head_id'] (dataset.FrameStream: multihead.split)
+        'train_heads': False,
         # inference in 'f16x3' is fp32-accurate for hidden activations below 128 (and clamps them at 65504, the f16
         # range).  The kernels flag any beyond (status word of
         # the packed weight image, read back one frame late without a synchronisation); what Network.forward does when
@@ -222,6 +228,30 @@ _DEFAULTS = {
         'freeze_gc': True,
     },
 }
+
+
+# The top-level ``multihead`` node beside its head_num (default.yaml:372-382).  The node as a whole has no default here
+# (a config without it selects no multi-head network: network.canonical_head_num); these are what multihead_option
+# answers for a key the node does not carry.
+MULTIHEAD_DEFAULTS = {
+    'split': 'view',                                   # 'view' | 'random' | 'argmin' | path of a JSON {frame_name: head}
+    'argmin_cfg': {'selector_criteria': {'lpips': 1.0, 'mse': 0.2, 'ssim': 0.0},
+                   'unselected_lossweights': {'lpips': 0.0, 'mse': 0.0}},
+}
+
+
+def multihead_option(path, config=None):
+    """``multihead.<path>`` ('split', 'argmin_cfg.selector_criteria', ...) of ``config`` (default: cfg), with
+    MULTIHEAD_DEFAULTS where the node or the key is missing."""
+    def walk(node):
+        for part in path.split('.'):
+            if not hasattr(node, 'get') or node.get(part, None) is None:
+                return None
+            node = node[part]
+        return node
+    config = cfg if config is None else config
+    got = walk(config.get('multihead', None) if hasattr(config, 'get') else None)
+    return walk(MULTIHEAD_DEFAULTS) if got is None else got
 
 
 _GC_FROZEN = False

@@ -155,6 +155,8 @@ int canonical16_heads_fwd(const float* xyz, const void* packed, int64_t P, int n
                           const int* count, bool guard, hipStream_t st);
 int canonical16_fwd_train(const float* xyz, const void* packed, int64_t P, float* raw, float* pe_out, float* acts,
                           uint32_t* relu_bits, int half, hipStream_t st);
+int canonical16_heads_fwd_train(const float* xyz, const void* packed, int64_t P, int n_heads, float* raw, float* pe_out,
+                                float* acts, uint32_t* relu_bits, int half, hipStream_t st);
 int nonrigid16_fwd(const float* x_skel, const float* hann_w, const void* packed, int64_t P, float* xyz,
                    float* offsets, const int* idx, const int* count, bool guard, hipStream_t st);
 
@@ -165,6 +167,12 @@ size_t canonical16_bwd_bytes();
 int canonical16_bwd_pack(const float* const* w, void* packed, hipStream_t st);
 int canonical16_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed, int64_t P,
                     const float* d_raw_amax, float* dZ, float* d_xyz, float* dz_amax, int half, hipStream_t st);
+
+size_t canonical16_heads_bwd_bytes();
+int canonical16_heads_bwd_pack(const float* const* w, int n_heads, void* packed, hipStream_t st);
+int canonical16_heads_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed, int64_t P,
+                          int n_heads, const float* d_raw_amax, float* dZ, float* d_xyz, float* dz_amax, int half,
+                          hipStream_t st);
 
 size_t nonrigid16_bwd_bytes();
 int nonrigid16_bwd_pack(const float* const* w, void* packed, hipStream_t st);

@@ -187,9 +187,10 @@ __device__ __forceinline__ void ring_fill(const float4* __restrict__ wptr, float
 // K3.  grid = ceil(P / 128) workgroups of 4 independent waves x 32 samples.
 // SAVE (training forward): also writes the positional encoding pe_out [P,63] (reference column
 // order) and the 8 post-ReLU activation matrices acts [8][P][256] that the backward GEMMs read.
-// HEADS (inference, image of hnrf_canonical_heads_pack): raw is n_heads planes [n_heads][P][4]; rows 4g .. 4g+3 of the
+// HEADS (image of hnrf_canonical_heads_pack): raw is n_heads planes [n_heads][P][4]; rows 4g .. 4g+3 of the
 // ONE head tile are head g, which sits in o[4q .. 4q+3] of lane half h for g = 2 q + h (canonical_f16x3_kernel has the
-// same epilogue).  n_heads is read by the HEADS instance only.
+// same epilogue).  n_heads is read by the HEADS instances only.  SAVE && HEADS (hnrf_canonical_heads_fwd_train): the
+// trunk does not know the heads, so everything SAVE writes is what the single-head instance writes.
 template <bool SAVE, bool HEADS = false>
 __global__ __launch_bounds__(256) void canonical_f32_kernel(const float* __restrict__ xyz,
                                                             const float* __restrict__ packed, int64_t P,
@@ -197,7 +198,6 @@ __global__ __launch_bounds__(256) void canonical_f32_kernel(const float* __restr
                                                             float* __restrict__ acts, uint32_t* __restrict__ relu_bits,
                                                             const int* __restrict__ idx,
                                                             const int* __restrict__ count, int n_heads) {
-    static_assert(!(SAVE && HEADS), "the all-heads epilogue exists in the inference form only");
     const int lane = threadIdx.x & 63;
     const int h = lane >> 5;
     const int64_t plane = P;                  // HEADS: samples per plane (P becomes *count in a sparse launch)
@@ -536,6 +536,26 @@ extern "C" int hnrf_canonical_fwd_train(const float* xyz, const void* packed, in
     hipLaunchKernelGGL(canonical_f32_kernel<true>, dim3((unsigned)((P + 127) / 128)), dim3(256), 0,
                        (hipStream_t)stream, xyz, (const float*)packed, P, (float4*)raw, pe_out, acts, relu_bits, nullptr, nullptr, 1);
     return check_launch("hnrf_canonical_fwd_train");
+}
+
+extern "C" int hnrf_canonical_heads_fwd_train(const float* xyz, const void* packed, int mode, int64_t P, int n_heads,
+                                              float* raw, float* pe_out, float* acts, uint32_t* relu_bits, void* stream) {
+    HNRF_REQUIRE(xyz && packed && raw && pe_out && acts && relu_bits, HNRF_E_ARG,
+                 "hnrf_canonical_heads_fwd_train: null pointer");
+    HNRF_REQUIRE(n_heads >= 2 && n_heads <= 8, HNRF_E_ARG, "hnrf_canonical_heads_fwd_train: n_heads=%d outside 2..8", n_heads);
+    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3 || mode == HNRF_MLP_F16X3_H, HNRF_E_UNSUPPORTED,
+                 "hnrf_canonical_heads_fwd_train: mode %d not built", mode);
+    HNRF_REQUIRE(P >= 0 && (P + 127) / 128 < 2147483647LL, HNRF_E_ARG, "hnrf_canonical_heads_fwd_train: bad P");
+    HNRF_REQUIRE((((uintptr_t)packed | (uintptr_t)raw | (uintptr_t)acts) & 15) == 0, HNRF_E_ARG,
+                 "hnrf_canonical_heads_fwd_train: packed/raw/acts must be 16-byte aligned");
+    if (P == 0) return HNRF_OK;
+    if (mode != HNRF_MLP_F32)
+        return canonical16_heads_fwd_train(xyz, packed, P, n_heads, raw, pe_out, acts, relu_bits, mode == HNRF_MLP_F16X3_H,
+                                           (hipStream_t)stream);
+    hipLaunchKernelGGL((canonical_f32_kernel<true, true>), dim3((unsigned)((P + 127) / 128)), dim3(256), 0,
+                       (hipStream_t)stream, xyz, (const float*)packed, P, (float4*)raw, pe_out, acts, relu_bits, nullptr, nullptr,
+                       n_heads);
+    return check_launch("hnrf_canonical_heads_fwd_train");
 }
 
 extern "C" int hnrf_nonrigid_fwd(const float* x_skel, const float* hann_w, const void* packed, int mode, int64_t P,

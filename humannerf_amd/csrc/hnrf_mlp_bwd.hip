@@ -918,6 +918,8 @@ struct PackBwd {
     int row_kind;          // PE_NONE: row rho <-> in-feature col0 + rho;  else: rows in PE K-step order
     int col0;              // first forward in-feature column of this block
     int head;              // 1: K = the n_out (<= 4) head outputs on lane half 0 of steps 0..3
+                           // 2 (all heads, n_out = 4 H): head g = 2 q + h on lane half h of steps 4 q .. 4 q + 3, the
+                           //    order in which the forward's accumulator holds them (canonical_f32_kernel, HEADS)
     int64_t w_off;         // float offset in the image
 };
 
@@ -932,7 +934,8 @@ __global__ void pack_bwd_kernel(PackBwd d, float* __restrict__ packed) {
     const int t = (int)(gg / d.NG);
     const int h = lane >> 5;
     const int j = 4 * g + e;                                   // K-step
-    const int o = d.head ? ((h == 0 && j < d.n_out) ? j : -1) : hid_feat(j, h);
+    const int o = d.head == 2 ? (j < 16 ? 4 * (2 * (j >> 2) + h) + (j & 3) : -1)
+                : d.head    ? ((h == 0 && j < d.n_out) ? j : -1) : hid_feat(j, h);
     const int rho = 32 * t + (lane & 31);                      // output row of this stage
     int col;
     if (d.row_kind == PE_NONE) {
@@ -1013,6 +1016,9 @@ constexpr int64_t CB_L4 = CB_L5P + 2 * 32 * 256;                  // W4^T .. W1^
 constexpr int64_t CB_L0P = CB_L4 + 4 * CB_MID;                    // W0^T PE rows
 constexpr int64_t CB_END = CB_L0P + 2 * 32 * 256;
 constexpr int64_t CB_FLOATS = CB_END + PF * 256;                  // prefetch over-run pad
+// all-heads image (hnrf_canonical_heads_bwd_pack): the head stage has K = 4 H <= 32 = 4 groups; everything behind it
+// is the single-head image moved by the three extra groups per tile
+constexpr int64_t CBH_SHIFT = 8 * 3 * 256;
 constexpr int64_t NB_HEAD = 0;                                    // W6^T: 4 tiles x 1 group
 constexpr int64_t NB_MID = 4 * 16 * 256;
 constexpr int64_t NB_L5 = NB_HEAD + 4 * 1 * 256;                  // W5^T
@@ -1030,12 +1036,16 @@ __device__ __forceinline__ void ring_fill_b(const float4* __restrict__ wptr, flo
 
 // Canonical MLP.  relu_bits [8][P][2][4] (sign masks of the saved activations), d_raw [P,4]; writes
 // dZ [8][P][256], d_xyz [P,3].
+// HEADS (hnrf_canonical_heads_bwd, image of hnrf_canonical_heads_bwd_pack): d_raw is n_heads planes [n_heads][P][4] and
+// the chain starts from sum_g W_g^T d_raw_g: a head stage of 4 groups whose K-step 4 q + e contracts output e of head
+// 2 q + h on lane half h -- one float4 load per (q, half).  Everything below the head stage is the same code.
+template <bool HEADS = false>
 __global__ __launch_bounds__(256) void canonical_bwd_kernel(const float* __restrict__ xyz,
                                                             const float4* __restrict__ d_raw,
                                                             const uint32_t* __restrict__ relu_bits,
                                                             const float* __restrict__ packed, int64_t P,
                                                             float* __restrict__ dZ, float* __restrict__ d_xyz,
-                                                            float* __restrict__ dz_amax) {
+                                                            float* __restrict__ dz_amax, int n_heads) {
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int64_t slot = ((int64_t)blockIdx.x * 4 + (threadIdx.x >> 6)) * 32 + (lane & 31);
     const int64_t sample = slot < P ? slot : P - 1;            // clamped lanes compute, but never store
@@ -1044,8 +1054,18 @@ __global__ __launch_bounds__(256) void canonical_bwd_kernel(const float* __restr
     const bool live = slot < P;
     const int64_t stride = P * 256;
 
-    const float4 g = d_raw[sample];
-    const float in0[4] = {h ? 0.f : g.x, h ? 0.f : g.y, h ? 0.f : g.z, h ? 0.f : g.w};
+    constexpr int NG0 = HEADS ? 4 : 1;                         // groups of the head stage
+    float in0[4 * NG0];
+    if constexpr (HEADS) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const float4 g = 2 * q + h < n_heads ? d_raw[(int64_t)(2 * q + h) * P + sample] : float4{0.f, 0.f, 0.f, 0.f};
+            in0[4 * q] = g.x; in0[4 * q + 1] = g.y; in0[4 * q + 2] = g.z; in0[4 * q + 3] = g.w;
+        }
+    } else {
+        const float4 g = d_raw[sample];
+        in0[0] = h ? 0.f : g.x; in0[1] = h ? 0.f : g.y; in0[2] = h ? 0.f : g.z; in0[3] = h ? 0.f : g.w;
+    }
     const float4* wptr = reinterpret_cast<const float4*>(packed) + lane;
     float4 ring[PF];
     ring_fill_b(wptr, ring);
@@ -1054,9 +1074,9 @@ __global__ __launch_bounds__(256) void canonical_bwd_kernel(const float* __restr
     const uint32_t* act = relu_bits + 7 * bstride + sample * 8 + h * 4;
     float* dz = dZ + 7 * stride + sample * 256;
     float hA[128], hB[128], dpe[32], dpe0[32];
-    constexpr int C_PH = 8 % PF;                               // after the 8-group head every stage is a multiple of 64 groups
+    constexpr int C_PH = (8 * NG0) % PF;                       // after the 8 NG0-group head every stage is a multiple of 64 groups
     static_assert(64 % PF == 0, "stages must keep the ring phase");
-    bwd_stage<0, 8, 1>(wptr, ring, in0, hA, act, live ? dz : nullptr, h, am);                  // dZ7
+    bwd_stage<0, 8, NG0>(wptr, ring, in0, hA, act, live ? dz : nullptr, h, am);                // dZ7
 #pragma unroll 1
     for (int l = 7; l >= 6; --l) {                                                      // dZ6, dZ5
         act -= bstride;
@@ -1421,9 +1441,72 @@ extern "C" int hnrf_canonical_bwd(const float* xyz, const float* d_raw, const ui
         if (int rc = init_dz_amax(dz_amax, 8, mode == HNRF_MLP_F16X3 ? d_raw_amax : nullptr, (hipStream_t)stream, "hnrf_canonical_bwd (maxima)")) return rc;
     if (mode == HNRF_MLP_F16X3)
         return canonical16_bwd(xyz, d_raw, relu_bits, packed, P, d_raw_amax, dZ, d_xyz, dz_amax, 0, (hipStream_t)stream);
-    hipLaunchKernelGGL(canonical_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, xyz,
-                       (const float4*)d_raw, relu_bits, (const float*)packed, P, dZ, d_xyz, dz_amax);
+    hipLaunchKernelGGL(canonical_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, xyz,
+                       (const float4*)d_raw, relu_bits, (const float*)packed, P, dZ, d_xyz, dz_amax, 1);
     return check_launch("hnrf_canonical_bwd");
+}
+
+// ---- all heads (hnrf_heads_train.h)
+extern "C" size_t hnrf_canonical_heads_bwd_packed_bytes(int mode, int n_heads) {
+    if (n_heads < 2 || n_heads > 8) return 0;
+    if (mode == HNRF_MLP_F16X3) return canonical16_heads_bwd_bytes();
+    return mode == HNRF_MLP_F32 ? (size_t)(CB_FLOATS + CBH_SHIFT) * sizeof(float) : 0;
+}
+
+extern "C" int hnrf_canonical_heads_bwd_pack(const float* const* weights, int n_heads, int mode, void* packed,
+                                             void* stream) {
+    HNRF_REQUIRE(weights && packed, HNRF_E_ARG, "hnrf_canonical_heads_bwd_pack: null pointer");
+    HNRF_REQUIRE(n_heads >= 2 && n_heads <= 8, HNRF_E_ARG, "hnrf_canonical_heads_bwd_pack: n_heads=%d outside 2..8", n_heads);
+    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3, HNRF_E_UNSUPPORTED,
+                 "hnrf_canonical_heads_bwd_pack: mode %d not built", mode);
+    for (int i = 0; i < 9; ++i) HNRF_REQUIRE(weights[i], HNRF_E_ARG, "hnrf_canonical_heads_bwd_pack: null layer %d", i);
+    HNRF_REQUIRE(((uintptr_t)packed & 15) == 0, HNRF_E_ARG, "hnrf_canonical_heads_bwd_pack: packed must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == HNRF_MLP_F16X3) return canonical16_heads_bwd_pack(weights, n_heads, packed, st);
+    float* out = (float*)packed;
+    if (hipMemsetAsync(out + CBH_SHIFT + CB_END, 0, PF * 256 * sizeof(float), st) != hipSuccess) {
+        set_error("hnrf_canonical_heads_bwd_pack: memset failed");
+        return HNRF_E_LAUNCH;
+    }
+    int rc;
+    if ((rc = launch_pack_bwd(PackBwd{weights[8], 4 * n_heads, 256, 8, 4, PE_NONE, 0, 2, CB_HEAD}, out, st))) return rc;
+    out += CBH_SHIFT;
+    for (int l = 7; l >= 6; --l)
+        if ((rc = launch_pack_bwd(PackBwd{weights[l], 256, 256, 8, 32, PE_NONE, 0, 0, CB_L7 + (7 - l) * CB_MID}, out, st)))
+            return rc;
+    if ((rc = launch_pack_bwd(PackBwd{weights[5], 256, 319, 8, 32, PE_NONE, 63, 0, CB_L5H}, out, st))) return rc;
+    if ((rc = launch_pack_bwd(PackBwd{weights[5], 256, 319, 2, 32, PE_CANONICAL, 0, 0, CB_L5P}, out, st))) return rc;
+    for (int l = 4; l >= 1; --l)
+        if ((rc = launch_pack_bwd(PackBwd{weights[l], 256, 256, 8, 32, PE_NONE, 0, 0, CB_L4 + (4 - l) * CB_MID}, out, st)))
+            return rc;
+    return launch_pack_bwd(PackBwd{weights[0], 256, 63, 2, 32, PE_CANONICAL, 0, 0, CB_L0P}, out, st);
+}
+
+extern "C" int hnrf_canonical_heads_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed,
+                                        int mode, const float* d_raw_amax, int64_t P, int n_heads, float* dZ, float* d_xyz,
+                                        float* dz_amax, void* stream) {
+    HNRF_REQUIRE(xyz && d_raw && relu_bits && packed && dZ && d_xyz, HNRF_E_ARG, "hnrf_canonical_heads_bwd: null pointer");
+    HNRF_REQUIRE(n_heads >= 2 && n_heads <= 8, HNRF_E_ARG, "hnrf_canonical_heads_bwd: n_heads=%d outside 2..8", n_heads);
+    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3 || mode == HNRF_MLP_F16X3_H, HNRF_E_UNSUPPORTED,
+                 "hnrf_canonical_heads_bwd: mode %d not built", mode);
+    HNRF_REQUIRE(mode == HNRF_MLP_F32 || d_raw_amax, HNRF_E_ARG,
+                 "hnrf_canonical_heads_bwd: HNRF_MLP_F16X3 needs d_raw_amax (device scalar >= max |d_raw| over all planes)");
+    HNRF_REQUIRE(mode != HNRF_MLP_F16X3_H || dz_amax, HNRF_E_ARG, "hnrf_canonical_heads_bwd: HNRF_MLP_F16X3_H needs dz_amax ([8] scales out)");
+    HNRF_REQUIRE(P >= 0, HNRF_E_ARG, "hnrf_canonical_heads_bwd: bad P");
+    HNRF_REQUIRE((((uintptr_t)d_raw | (uintptr_t)relu_bits | (uintptr_t)dZ | (uintptr_t)packed) & 15) == 0, HNRF_E_ARG,
+                 "hnrf_canonical_heads_bwd: d_raw, relu_bits, dZ, packed must be 16-byte aligned");
+    if (P == 0) return HNRF_OK;
+    const int64_t blocks = (P + 127) / 128;
+    HNRF_REQUIRE(blocks < 2147483647LL, HNRF_E_ARG, "hnrf_canonical_heads_bwd: too many samples");
+    if (mode == HNRF_MLP_F16X3_H)
+        return canonical16_heads_bwd(xyz, d_raw, relu_bits, packed, P, n_heads, d_raw_amax, dZ, d_xyz, dz_amax, 1, (hipStream_t)stream);
+    if (dz_amax)
+        if (int rc = init_dz_amax(dz_amax, 8, mode == HNRF_MLP_F16X3 ? d_raw_amax : nullptr, (hipStream_t)stream, "hnrf_canonical_heads_bwd (maxima)")) return rc;
+    if (mode == HNRF_MLP_F16X3)
+        return canonical16_heads_bwd(xyz, d_raw, relu_bits, packed, P, n_heads, d_raw_amax, dZ, d_xyz, dz_amax, 0, (hipStream_t)stream);
+    hipLaunchKernelGGL(canonical_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, xyz,
+                       (const float4*)d_raw, relu_bits, (const float*)packed, P, dZ, d_xyz, dz_amax, n_heads);
+    return check_launch("hnrf_canonical_heads_bwd");
 }
 
 extern "C" int hnrf_nonrigid_bwd(const float* x_skel, const float* hann_w, const float* d_xyz,

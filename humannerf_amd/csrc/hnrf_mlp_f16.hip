@@ -866,7 +866,7 @@ __device__ __forceinline__ void stash_pe(const Pipe& p, int ks, const float (&v)
 // SAVE (training forward): also writes pe_out [P,63], acts [8][P][256] (fp32 post-ReLU values, as combined in the
 // epilogue) and relu_bits [8][P][8] like canonical_f32_kernel<true>; no sparse form.  SAVE == SV_ACT_H: acts and
 // pe_out are f16 matrices ([8][P][256], [P][64] with column 63 zero) for hnrf_mlp_dw_h.
-// HEADS (inference, multi-head image of canonical16_pack): raw is n_heads planes [n_heads][P][4]; the head layer is the
+// HEADS (multi-head image of canonical16_pack; with SAVE: hnrf_canonical_heads_fwd_train): raw is n_heads planes [n_heads][P][4]; the head layer is the
 // same ONE 32-row tile, of which rows 0 .. 4 n_heads - 1 now hold weights.  In the 32x32 accumulator lane half h holds
 // rows 8 (r >> 2) + 4 h + (r & 3) in last[r]: head g = 2 q + h sits in last[4q .. 4q+3] of half h, and each half stores
 // its heads as one float4 per head -- no further MFMA, no LDS.  Head g equals the single-head kernel on the image packed
@@ -879,7 +879,6 @@ __global__ __launch_bounds__(256) void canonical_f16x3_kernel(const float* __res
                                                               const int* __restrict__ count,
                                                               float* __restrict__ pe_out, float* __restrict__ acts,
                                                               uint32_t* __restrict__ relu_bits, int n_heads) {
-    static_assert(!HEADS || SAVE == SV_NONE, "the all-heads epilogue exists in the inference form only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int64_t plane = P;                                  // HEADS: samples per plane (P becomes *count in a sparse launch)
     // sparse launch: only the `*count` samples listed in idx are evaluated (hnrf_compact_samples)
@@ -1207,6 +1206,8 @@ struct PackBwd16 {
     int row_kind;          // PE16_NONE: row rho <-> column col0 + rho; else rows in PE argument order
     int col0;
     int head;              // 1: K = the n_out (<= 4) head outputs, elements 0..3 of lane half 0 of k-step 0
+                           // 2 (all heads, n_out = 4 H, NK = 2): head g = 2 q + h on lane half h, elements 4 (q & 1) ..
+                           //    of k-step q >> 1 -- the order in which the forward's accumulator holds the heads
     int64_t off;           // byte offset of the stage's first slab
     const float* amax;     // device: max |W| of this layer; the image is stored x 2^layer_exponent(amax)
 };
@@ -1263,7 +1264,8 @@ __global__ void pack_bwd16_kernel(PackBwdSet16 set, char* __restrict__ packed) {
     _Float16 outv[2];
     for (int e = 0; e < 2; ++e) {
         const int j = j0 + e;
-        const int o = d.head ? ((ks == 0 && h == 0 && j < d.n_out) ? j : -1) : hid_feat16(ks, j, h);
+        const int o = d.head == 2 ? 4 * (2 * (2 * ks + (j >> 2)) + h) + (j & 3)
+                    : d.head    ? ((ks == 0 && h == 0 && j < d.n_out) ? j : -1) : hid_feat16(ks, j, h);
         float w = 0.f;
         if (o >= 0 && o < d.n_out && col >= 0 && col < d.n_in) w = ldexpf(d.W[(int64_t)o * d.n_in + col], kexp);
         const _Float16 hi = (_Float16)w;
@@ -1283,6 +1285,10 @@ constexpr int64_t CB16_L5P = CB16_L7 + 3 * CB16_FULL;
 constexpr int64_t CB16_L4 = CB16_L5P + CB16_PE;
 constexpr int64_t CB16_L0P = CB16_L4 + 4 * CB16_FULL;
 constexpr int64_t CB16_BYTES = CB16_L0P + CB16_PE;            // followed by float amax[9] (layer_amax_kernel), 256 bytes
+// all-heads image (canonical16_heads_bwd_pack): the head stage has K = 4 H <= 32 = TWO k-steps (8 tiles x 4 blocks, for
+// every H: the second k-step of H <= 4 is zeros, 24 of the chain's 6 528 MFMAs per wave, and the head slab is then a
+// 32-block slab like every other); everything behind it is the single-head image moved by 16 KiB
+constexpr int64_t CB16H_SHIFT = 16 * KB;
 
 __device__ __forceinline__ void chain_amax(SaveCtx& sc, float* __restrict__ slot) {
     float m = sc.amax;
@@ -1294,26 +1300,29 @@ __device__ __forceinline__ void chain_amax(SaveCtx& sc, float* __restrict__ slot
 
 // HALF: dZ is an f16 matrix holding the chain's SCALED values (dz_scale[l] = the power of two dZ_l was multiplied by, for
 // hnrf_mlp_dw_h); otherwise fp32, un-scaled, with the per-layer maxima in dz_amax.
-template <bool HALF>
+// HEADS (hnrf_canonical_heads_bwd, image of canonical16_heads_bwd_pack): d_raw is n_heads planes [n_heads][P][4], the head
+// stage contracts all of them (two k-steps from the stash); d_raw_amax bounds every plane.
+template <bool HALF, bool HEADS = false>
 __global__ __launch_bounds__(256) void canonical_bwd16_kernel(const float* __restrict__ xyz,
                                                               const float4* __restrict__ d_raw,
                                                               const uint32_t* __restrict__ relu_bits,
                                                               const char* __restrict__ packed, int64_t P,
                                                               const float* __restrict__ d_raw_amax,
                                                               float* __restrict__ dZ, float* __restrict__ d_xyz,
-                                                              float* __restrict__ dz_amax) {
+                                                              float* __restrict__ dz_amax, int n_heads) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int SV = HALF ? SV_DZ_H : SV_DZ;
-    // slabs: head (16 blocks), then 32-block slabs; the first THREE are put in flight here (the head stage has
-    // only 8 k-steps to issue DMA pieces from, one short of a 32-block slab)
-    Pipe p = pipe_start(packed, 0, CNL16_BIAS_LDS, CNL16_SLAB, 16, 32, smem);
+    // slabs: head (16 blocks; HEADS: 32), then 32-block slabs; the first THREE are put in flight here (the single-head
+    // head stage has only 8 k-steps to issue DMA pieces from, one short of a 32-block slab; the HEADS one has 16 and
+    // keeps the same plan: it issues no piece either, nb1 = nb2 = 0)
+    Pipe p = pipe_start(packed, 0, CNL16_BIAS_LDS, CNL16_SLAB, HEADS ? 32 : 16, 32, smem);
     slab_issue(p.gi, p.lds_base + p.ring_off + 2 * CNL16_SLAB, 32, p.wave);
     p.gi += 32 * 1024;
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int64_t slot = ((int64_t)blockIdx.x * 4 + p.wave) * 32 + (lane & 31);
     const int64_t sample = slot < P ? slot : P - 1;            // lanes past P repeat sample P-1 (same values stored)
     const int64_t stride = P * 256, bstride = P * 8;
-    const float* wmax = reinterpret_cast<const float*>(packed + CB16_BYTES);
+    const float* wmax = reinterpret_cast<const float*>(packed + CB16_BYTES + (HEADS ? CB16H_SHIFT : 0));
     auto kt = [&](int l) { return layer_exponent(wmax[l]); };          // weights of layer l are stored x 2^kt(l)
 
     // non-finite incoming gradient (an overflowed loss): the scale would be undefined -- gradients of zero scale come
@@ -1324,8 +1333,19 @@ __global__ __launch_bounds__(256) void canonical_bwd16_kernel(const float* __res
     const float scale = (am_in == am_in && am_in < 3.0e38f) ? ldexpf(1.0f, 2 - ex) : __builtin_nanf("");
     // HALF: lanes past P must leave zeros in the blocked dZ (the weight-gradient kernel reads whole blocks): a zero
     // incoming gradient does that for every stage
-    const float4 g = (HALF && slot >= P) ? float4{0.f, 0.f, 0.f, 0.f} : d_raw[sample];
-    {
+    if constexpr (HEADS) {
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {                        // element 4 e + i of k-step ks: output i of head 2 (2 ks + e) + h
+            const int g0 = 4 * ks + h, g1 = g0 + 2;
+            const bool dead = HALF && slot >= P;
+            const float4 a = (dead || g0 >= n_heads) ? float4{0.f, 0.f, 0.f, 0.f} : d_raw[(int64_t)g0 * P + sample];
+            const float4 b = (dead || g1 >= n_heads) ? float4{0.f, 0.f, 0.f, 0.f} : d_raw[(int64_t)g1 * P + sample];
+            const float v[8] = {a.x * scale, a.y * scale, a.z * scale, a.w * scale,
+                                b.x * scale, b.y * scale, b.z * scale, b.w * scale};
+            stash_pe(p, ks, v);
+        }
+    } else {
+        const float4 g = (HALF && slot >= P) ? float4{0.f, 0.f, 0.f, 0.f} : d_raw[sample];
         const float v[8] = {h ? 0.f : g.x * scale, h ? 0.f : g.y * scale, h ? 0.f : g.z * scale, h ? 0.f : g.w * scale,
                             0.f, 0.f, 0.f, 0.f};
         stash_pe(p, 0, v);
@@ -1362,7 +1382,7 @@ __global__ __launch_bounds__(256) void canonical_bwd16_kernel(const float* __res
     h16x8 dh[4], dl[4];
     float last[16];
     load_mask();
-    layer16<8, 8, 1, 0, false, SV>(p, 0, 0, hB_h, hB_l, hA_h, hA_l, last, &sc);                // dZ7 (hB unused: NKB = 0)
+    layer16<8, 8, HEADS ? 2 : 1, 0, false, SV>(p, 0, 0, hB_h, hB_l, hA_h, hA_l, last, &sc);    // dZ7 (hB unused: NKB = 0)
     next_stage(7);
 #pragma unroll 1
     for (int m = 6; m >= 5; --m) {                                                             // dZ6, dZ5
@@ -1635,6 +1655,21 @@ int canonical16_fwd_train(const float* xyz, const void* packed, int64_t P, float
                                                       nullptr, nullptr, pe_out, acts, relu_bits, 1);
 }
 
+// all heads on the activation-saving instances: what SAVE writes does not depend on the heads
+int canonical16_heads_fwd_train(const float* xyz, const void* packed, int64_t P, int n_heads, float* raw, float* pe_out,
+                                float* acts, uint32_t* relu_bits, int half, hipStream_t st) {
+    constexpr int lds = CNL16_BIAS_LDS + PE_STASH + RING * CNL16_SLAB;
+    const dim3 grid((unsigned)((P + 127) / 128));
+    const char* what = "hnrf_canonical_heads_fwd_train (f16x3)";
+    if (half)
+        return launch_lds<canonical_f16x3_kernel<SV_ACT_H, false, true>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed,
+                                                                         P, (float4*)raw, nullptr, nullptr, pe_out, acts,
+                                                                         relu_bits, n_heads);
+    return launch_lds<canonical_f16x3_kernel<SV_ACT, false, true>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
+                                                                   (float4*)raw, nullptr, nullptr, pe_out, acts, relu_bits,
+                                                                   n_heads);
+}
+
 int nonrigid16_fwd(const float* x_skel, const float* hann_w, const void* packed, int64_t P, float* xyz,
                    float* offsets, const int* idx, const int* count, bool guard, hipStream_t st) {
     constexpr int lds2 = NR16_BIAS_LDS + NR16X2_STASH + RING * NR16X2_SLAB;
@@ -1717,9 +1752,46 @@ int canonical16_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_b
     const char* what = "hnrf_canonical_bwd (f16x3)";
     if (half)
         return launch_lds<canonical_bwd16_kernel<true>>(what, grid, dim3(256), lds, st, xyz, (const float4*)d_raw, relu_bits,
-                                                        (const char*)packed, P, d_raw_amax, dZ, d_xyz, dz_amax);
+                                                        (const char*)packed, P, d_raw_amax, dZ, d_xyz, dz_amax, 1);
     return launch_lds<canonical_bwd16_kernel<false>>(what, grid, dim3(256), lds, st, xyz, (const float4*)d_raw, relu_bits,
-                                                     (const char*)packed, P, d_raw_amax, dZ, d_xyz, dz_amax);
+                                                     (const char*)packed, P, d_raw_amax, dZ, d_xyz, dz_amax, 1);
+}
+
+// ---- all heads: the transposed image whose head stage contracts 4 n_heads outputs, and the chain on it
+size_t canonical16_heads_bwd_bytes() { return (size_t)(CB16_BYTES + CB16H_SHIFT) + 256; }
+
+int canonical16_heads_bwd_pack(const float* const* w, int n_heads, void* packed, hipStream_t st) {
+    char* out = (char*)packed;
+    float* kexp = reinterpret_cast<float*>(out + CB16H_SHIFT + CB16_BYTES);
+    // (the head layer's maximum is taken over all heads: one exponent for the stage that sums them)
+    const int sizes[9] = {256 * 63, 256 * 256, 256 * 256, 256 * 256, 256 * 256, 256 * 319, 256 * 256, 256 * 256,
+                          4 * n_heads * 256};
+    int rc;
+    if ((rc = launch_layer_amax(w, sizes, 9, kexp, st))) return rc;
+    PackBwd16 d[10];
+    int n = 0;
+    const int64_t sh = CB16H_SHIFT;
+    d[n++] = PackBwd16{w[8], 4 * n_heads, 256, 8, 2, PE16_NONE, 0, 2, CB16_HEAD, kexp + 8};
+    for (int l = 7; l >= 6; --l) d[n++] = PackBwd16{w[l], 256, 256, 8, 16, PE16_NONE, 0, 0, sh + CB16_L7 + (7 - l) * CB16_FULL, kexp + l};
+    d[n++] = PackBwd16{w[5], 256, 319, 8, 16, PE16_NONE, 63, 0, sh + CB16_L7 + 2 * CB16_FULL, kexp + 5};
+    d[n++] = PackBwd16{w[5], 256, 319, 2, 16, PE16_CANONICAL, 0, 0, sh + CB16_L5P, kexp + 5};
+    for (int l = 4; l >= 1; --l) d[n++] = PackBwd16{w[l], 256, 256, 8, 16, PE16_NONE, 0, 0, sh + CB16_L4 + (4 - l) * CB16_FULL, kexp + l};
+    d[n++] = PackBwd16{w[0], 256, 63, 2, 16, PE16_CANONICAL, 0, 0, sh + CB16_L0P, kexp};
+    return launch_pack_bwd16(d, n, out, st);
+}
+
+int canonical16_heads_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed, int64_t P,
+                          int n_heads, const float* d_raw_amax, float* dZ, float* d_xyz, float* dz_amax, int half,
+                          hipStream_t st) {
+    constexpr int lds = CNL16_BIAS_LDS + PE_STASH + RING * CNL16_SLAB;
+    const dim3 grid((unsigned)((P + 127) / 128));
+    const char* what = "hnrf_canonical_heads_bwd (f16x3)";
+    if (half)
+        return launch_lds<canonical_bwd16_kernel<true, true>>(what, grid, dim3(256), lds, st, xyz, (const float4*)d_raw,
+                                                              relu_bits, (const char*)packed, P, d_raw_amax, dZ, d_xyz,
+                                                              dz_amax, n_heads);
+    return launch_lds<canonical_bwd16_kernel<false, true>>(what, grid, dim3(256), lds, st, xyz, (const float4*)d_raw, relu_bits,
+                                                           (const char*)packed, P, d_raw_amax, dZ, d_xyz, dz_amax, n_heads);
 }
 
 size_t nonrigid16_bwd_bytes() { return (size_t)NB16_BYTES + 256; }

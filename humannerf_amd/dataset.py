@@ -36,7 +36,7 @@ import pickle
 import numpy as np
 
 from . import imageproc, scene
-from .config import cfg
+from .config import amd_option, cfg, multihead_option
 
 # ------------------------------------------------------------------------------------------------ safe pickle reader
 _NUMPY_GLOBALS = {
@@ -154,6 +154,54 @@ ROT_CAM_PARAMS = {'zju_mocap': {'rotate_axis': 'z', 'inv_angle': True},
                   'wild': {'rotate_axis': 'y', 'inv_angle': False}}            # freeview.py:26-29
 
 
+# ------------------------------------------------------------------------------------------------ heads
+def parse_view_from_frame(frame_name):
+    """train.py:200-209: 'frame_000008_view_03' -> 3, 'Camera_B4/000438' -> 4, anything else view 0."""
+    if 'view' in frame_name:
+        return int(frame_name.split('view_')[1][:2])
+    if 'Camera' in frame_name:
+        return int(frame_name.split('/')[0].split('Camera_B')[1])
+    return 0
+
+
+def multihead_enabled():
+    return bool(cfg.get('canonical_mlp', {}).get('multihead', {}).get('enable', False))
+
+
+class HeadAssignment:
+    """``head_id`` of the items of a multi-head run (train.py:489-537), by ``multihead.split``: 'view' = the index of the
+    frame's view among the sorted views of ``framelist``; 'random' = np.random.randint(head_num) per item; 'argmin' = -1
+    (every head is rendered and the loss picks one); the path of a JSON file {frame_name: head} = what it says (the
+    reference's branch, train.py:83-86, cannot run as committed -- a typo in the attribute it reads; this is its evident
+    intent).  Items in image mode follow cfg.test.head_id (default -1) whatever the split."""
+
+    def __init__(self, framelist):
+        import json
+        self.split = str(multihead_option('split'))
+        self.views = sorted(set(parse_view_from_frame(f) for f in framelist))
+        self.table = None
+        if self.split not in ('view', 'random', 'argmin'):
+            if not os.path.isfile(self.split):
+                raise ValueError("multihead.split = %r: not 'view', 'random', 'argmin' or a JSON file" % (self.split,))
+            with open(self.split, 'r') as f:
+                self.table = json.load(f)
+
+    def train(self, frame_name, rng=None):
+        """patch mode; ``rng``: a numpy Generator for the 'random' draw (None: the global generator, as the reference)."""
+        if self.split == 'view':
+            return self.views.index(parse_view_from_frame(frame_name))
+        if self.split == 'argmin':
+            return -1
+        if self.split == 'random':
+            n = int(cfg.multihead.head_num)
+            return int(np.random.randint(n) if rng is None else rng.integers(n))
+        return int(self.table[frame_name])
+
+    @staticmethod
+    def image():
+        return int(cfg.get('test', {}).get('head_id', -1))
+
+
 # ------------------------------------------------------------------------------------------------ subject
 class Subject:
     """Everything the reference's Dataset.__init__ loads for one prepared subject directory."""
@@ -182,6 +230,17 @@ class Subject:
         self.framelist = frames[::skip]
         if maxframes > 0:
             self.framelist = self.framelist[:maxframes]
+        self._heads = None
+
+    def head_assignment(self):
+        """The HeadAssignment of this subject's frames under the current multihead.split, or None -- items then carry no
+        head_id -- for a single-head configuration and while cfg.amd.train_heads is off (nothing changes without the
+        switch)."""
+        if not (multihead_enabled() and amd_option('train_heads', False)):
+            return None
+        if self._heads is None or self._heads.split != str(multihead_option('split')):
+            self._heads = HeadAssignment(self.framelist)
+        return self._heads
 
     def __len__(self):
         return len(self.framelist)
@@ -247,6 +306,8 @@ class Subject:
             out['raw_rgbs'] = img
             if host_rays:
                 out['target_rgbs'] = img.reshape(-1, 3)[out['ray_mask']]
+        if self.head_assignment() is not None:
+            out['head_id'] = HeadAssignment.image()
         return out
 
     def freeview_frame(self, idx, total_frames, train_frame_idx=0, src_type='zju_mocap', bgcolor=None, host_rays=False,
@@ -308,6 +369,9 @@ class Subject:
                'patch_div_indices': div, 'patch_masks': pinfo['mask'], 'target_patches': targets,
                'target_rgbs': img.reshape(-1, 3)[ray_mask][sel], 'resize_parity': flag}
         out.update(self._skeleton_entries(info))
+        heads = self.head_assignment()
+        if heads is not None:
+            out['head_id'] = heads.train(name)
         return out
 
     # -- images -------------------------------------------------------------------------------------------------
@@ -460,6 +524,9 @@ class DeviceFrameCache:
                'patch_div_indices': torch.from_numpy(div), 'patch_masks': masks_d, 'target_patches': targets,
                'target_rgbs': targets.reshape(-1, 3).index_select(0, flat_d), 'resize_parity': ent['parity']}
         out.update(ent['skeleton'])
+        heads = self.subject.head_assignment()
+        if heads is not None:
+            out['head_id'] = torch.as_tensor(heads.train(ent['name'], rng))     # (on the host: the network reads it there)
         return out
 
 
@@ -544,7 +611,8 @@ class FrameStream:
         if self.cache is not None:
             exclude = ('frame_name', 'img_width', 'img_height', 'resize_parity')
             return {k: v for k, v in item.items() if k not in exclude}
-        return to_device(item, self.device, pinned=True) if self.device is not None else item
+        # (head_id, where items carry one, stays on the host: the network reads it there)
+        return to_device(item, self.device, pinned=True, host_keys=('patch_div_indices', 'head_id')) if self.device is not None else item
 
     def close(self):
         with self._cv:

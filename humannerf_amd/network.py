@@ -765,9 +765,10 @@ class Network(nn.Module):
             # inference frame rebuilds everything derived from the weights
             self._weights_gen += 1
         all_heads = self.head_num and self._head == -1
-        if self.head_num and train_path:
+        if self.head_num and train_path and not amd_option('train_heads', False):
             raise NotImplementedError('multi-head canonical MLP: inference only (the training kernels have one head; '
-                                      'checkpoints come from the reference trainer) -- call forward under torch.no_grad()')
+                                      'checkpoints come from the reference trainer) -- call forward under torch.no_grad(), '
+                                      'or set cfg.amd.train_heads = True to train it')
         if self.f16_guard.pending:
             self.check_f16_range(wait=False)       # the previous frames' f16-range verdicts (may switch the mode, or raise)
         iter_val = float(iter_val)
@@ -819,7 +820,7 @@ class Network(nn.Module):
                    for k, v in ops.output_shapes(S, self.total_bones, diag or train_path).items()}
             if all_heads:
                 out = self._heads_lists(out)
-        elif all_heads:
+        elif all_heads and not train_path:
             # every head of one trunk pass: the exact MLP path only
             if canonical == 'baked':
                 raise NotImplementedError("head_id = -1 with cfg.amd.canonical = 'baked': a baked grid holds one head "
@@ -832,8 +833,12 @@ class Network(nn.Module):
             out = self._forward_frame(per_ray, per_frame, nr_packed, cnl_packed, bg, S, mode, diag, hann_host,
                                       all_heads=True)
         elif train_path:
+            # (cfg.amd.train_heads: head h >= 0 trains on the single-head kernels, -1 on the all-heads ones)
             out = self._forward_chunks(per_ray, per_frame, bg, S, mode, diag,
                                        train=(cond, not ignore_nr, nr_inputs_are_zero))
+            if all_heads:      # the reference's list shapes, like the inference path's
+                out = {k: list(v.unbind(0)) if k in ops.HEAD_KEYS else ([v] * self.head_num if k == 'xyz_on_rays' else v)
+                       for k, v in out.items()}
         else:
             baked, baked_nr, nr_baked_on = None, None, None
             if canonical == 'baked':                             # (training ignores the option: _render_rays_train)
@@ -917,7 +922,9 @@ class Network(nn.Module):
                                                term_eps=term_eps, cull_eps=cull_eps, workspace=self._workspace))
         if train is None and mode == 'f16x3' and guarded != set():
             self.f16_guard.watch(packs[1], packs[0], mode)
-        return {k: (torch.cat([c[k] for c in chunks], 0) if len(chunks) > 1 else chunks[0][k]) for k in chunks[0]}
+        # (all heads in training: the per-head keys come head-major, [H, rays, ...])
+        ray_dim = lambda k: 1 if train is not None and self.head_num and self._head == -1 and k in ops.HEAD_KEYS else 0
+        return {k: (torch.cat([c[k] for c in chunks], ray_dim(k)) if len(chunks) > 1 else chunks[0][k]) for k in chunks[0]}
 
     def shared_sample_share(self):
         """Share of the last frame's samples that took the shared evaluation of cfg.amd.share_underflow instead of a pass
@@ -953,7 +960,13 @@ class Network(nn.Module):
         cn = self.cnl_mlp.module.linears()
         if hann_w is None:
             hann_w = torch.ones(6, device=rays_o.device)
-        params = [l.weight for l in nr] + [l.bias for l in nr] + [l.weight for l in cn] + [l.bias for l in cn]
+        cn_w, cn_b = [l.weight for l in cn], [l.bias for l in cn]
+        if self.head_num and self._head >= 0:
+            # one head of a multi-head MLP (cfg.amd.train_heads): views of its four rows, as select_head packs them --
+            # autograd leaves zeros in the other heads' rows, like the reference's slice (mlp_rgb_sigma.py:189-191)
+            rows = slice(4 * self._head, 4 * self._head + 4)
+            cn_w[8], cn_b[8] = cn_w[8][rows], cn_b[8][rows]
+        params = [l.weight for l in nr] + [l.bias for l in nr] + cn_w + cn_b
         const_offset = None
         if use_nonrigid and nr_inputs_are_zero:
             # before non_rigid_motion_mlp.kick_in_iter the MLP is fed zeros at every sample (condition code x 0,

@@ -448,11 +448,13 @@ def nonrigid_train(x_skel, hann_w, packed, mode='f32'):
     return xyz, offsets, pe, acts, bits
 
 
-def composite_bwd(raw, fg_mask, z_vals, rays_d, bgcolor, g_rgb, g_alpha=None, g_depth=None):
+def composite_bwd(raw, fg_mask, z_vals, rays_d, bgcolor, g_rgb, g_alpha=None, g_depth=None, d_raw_out=None):
+    """K4'.  ``d_raw_out``: a contiguous tensor of raw's size to write d_raw into (one plane of a multi-head d_raw)."""
     lib = _lib.load()
-    _chk(raw, fg_mask, z_vals, rays_d, bgcolor, g_rgb, g_alpha, g_depth)
+    _chk(raw, fg_mask, z_vals, rays_d, bgcolor, g_rgb, g_alpha, g_depth, d_raw_out)
     R, S = z_vals.shape
-    d_raw, d_mask = torch.empty_like(raw), torch.empty_like(fg_mask)
+    assert d_raw_out is None or d_raw_out.numel() == raw.numel()
+    d_raw, d_mask = torch.empty_like(raw) if d_raw_out is None else d_raw_out, torch.empty_like(fg_mask)
     _lib.check(lib.hnrf_composite_bwd(_ptr(raw), _ptr(fg_mask), _ptr(z_vals), _ptr(rays_d), _ptr(bgcolor), _ptr(g_rgb),
                                       _ptr(g_alpha), _ptr(g_depth), R, S, _ptr(d_raw), _ptr(d_mask), _stream()),
                'hnrf_composite_bwd')
@@ -520,11 +522,19 @@ def nonrigid_bwd(x_skel, hann_w, d_xyz, bits, weights, mode='f32'):
 _dw_ws = {}
 
 
-def mlp_dw(dZ, X, dW_out=None, want_db=True, mode='f32', dz_amax=None):
+def _db_buffer(db_out, n_out, want_db, device):
+    if db_out is None:
+        return torch.empty(n_out, device=device) if want_db else None
+    assert db_out.dtype == torch.float32 and db_out.is_cuda and db_out.is_contiguous() and db_out.numel() == n_out
+    return db_out
+
+
+def mlp_dw(dZ, X, dW_out=None, want_db=True, mode='f32', dz_amax=None, db_out=None):
     """dW = dZ^T X (and db = column sums of dZ) for one nn.Linear: dZ [P, n_out], X [P, n_in], row-major views
     whose last dimension is contiguous.  ``dW_out``: optional [n_out, >= n_in] view to write into (row stride kept).
     mode 'f16x3' (matrix-shaped layers only, others fall back to fp32 MFMA) needs ``dz_amax``: a device scalar
-    tensor whose maximum bounds |dZ| (one row of the chain kernels' amax output)."""
+    tensor whose maximum bounds |dZ| (one row of the chain kernels' amax output).  ``db_out``: optional contiguous
+    [n_out] view for db (the rows of one head in a multi-head gradient)."""
     lib = _lib.load()
     assert dZ.dtype == torch.float32 and X.dtype == torch.float32 and dZ.is_cuda and X.is_cuda
     assert dZ.dim() == 2 and X.dim() == 2 and dZ.stride(1) == 1 and X.stride(1) == 1 and dZ.shape[0] == X.shape[0]
@@ -533,7 +543,7 @@ def mlp_dw(dZ, X, dW_out=None, want_db=True, mode='f32', dz_amax=None):
     if dW_out is None:
         dW_out = torch.empty(n_out, n_in, device=dZ.device)
     assert dW_out.stride(1) == 1 and dW_out.shape[0] == n_out and dW_out.shape[1] == n_in
-    db = torch.empty(n_out, device=dZ.device) if want_db else None
+    db = _db_buffer(db_out, n_out, want_db, dZ.device)
     need = lib.hnrf_mlp_dw_workspace_bytes(P, n_out, n_in)
     if need == 0:
         raise _lib.HnrfError('hnrf_mlp_dw: shape (%d, %d, %d) not built' % (P, n_out, n_in))
@@ -550,7 +560,8 @@ def mlp_dw(dZ, X, dW_out=None, want_db=True, mode='f32', dz_amax=None):
     return dW_out, db
 
 
-def mlp_dw_h(dZ, X, dW_out=None, want_db=True, dz_scale=None, n_in=None, P=None, z_blocked=False, x_blocked=False):
+def mlp_dw_h(dZ, X, dW_out=None, want_db=True, dz_scale=None, n_in=None, P=None, z_blocked=False, x_blocked=False,
+             db_out=None):
     """hnrf_mlp_dw_h: dW = dZ^T X / scale (and db) from f16 operands.  dZ [P, n_out] f16 (n_out 128 | 256) or, for a
     head, fp32 [P, n_out <= 4]; X [P, >= n_in] f16 whose rows are zero-padded to 64 / 128 / 256 columns; ``n_in``:
     columns of dW (default X.shape[1]); dz_scale: device scalar the stored dZ was multiplied by.  ``z_blocked`` /
@@ -568,7 +579,7 @@ def mlp_dw_h(dZ, X, dW_out=None, want_db=True, dz_scale=None, n_in=None, P=None,
     if dW_out is None:
         dW_out = torch.empty(n_out, n_in, device=dZ.device)
     assert dW_out.stride(1) == 1 and dW_out.shape[0] == n_out and dW_out.shape[1] == n_in and dW_out.dtype == torch.float32
-    db = torch.empty(n_out, device=dZ.device) if want_db else None
+    db = _db_buffer(db_out, n_out, want_db, dZ.device)
     need = lib.hnrf_mlp_dw_h_workspace_bytes(P, n_out, n_in)
     if need == 0:
         raise _lib.HnrfError('hnrf_mlp_dw_h: shape (%d, %d, %d) not built' % (P, n_out, n_in))
@@ -1886,3 +1897,44 @@ def field_normals(verts, g, sigma, vol, n_bones, bbox_min, bbox_scale):
         _lib.check(lib.hnrf_field_normals(_ptr(verts), _ptr(g), _ptr(sigma), V, _ptr(vol), int(n_bones), G, _ptr(bbox_min),
                                           _ptr(bbox_scale), _ptr(normal), _stream()), 'hnrf_field_normals')
     return normal
+
+
+# -------------------------------------------------------------------------- training the multi-head canonical MLP
+def canonical_heads_train(xyz, packed, n_heads, mode='f32'):
+    """hnrf_canonical_heads_fwd_train: canonical_train on the image of canonical_heads_pack.  raw (H,...,4) head-major;
+    pe, acts and the sign masks are canonical_train's (the trunk does not know the heads)."""
+    lib = _lib.load_heads_train()
+    _chk(xyz, packed)
+    H, P = _chk_heads(n_heads), xyz.numel() // 3
+    dev = xyz.device
+    half = mode == 'f16x3h'
+    raw = torch.empty(H, *xyz.shape[:-1], 4, device=dev)
+    pe = torch.empty(P, 64, device=dev, dtype=torch.float16) if half else torch.empty(P, 63, device=dev)
+    acts = torch.empty(8, (P + 127) // 128 * 128, 256, device=dev, dtype=torch.float16) if half else torch.empty(8, P, 256, device=dev)
+    bits = torch.empty(8, P, 8, dtype=torch.int32, device=dev)
+    _lib.check(lib.hnrf_canonical_heads_fwd_train(_ptr(xyz), _ptr(packed), TRAIN_MODES[mode], P, H, _ptr(raw), _ptr(pe),
+                                                  _ptr(acts), bits.data_ptr(), _stream()), 'hnrf_canonical_heads_fwd_train')
+    return raw, pe, acts, bits
+
+
+def canonical_heads_bwd(xyz, d_raw, bits, weights, n_heads, mode='f32'):
+    """canonical_bwd seeded with every head's gradient: d_raw (H,P,4) head-major, weights[8] (4 H, 256).  Returns what
+    canonical_bwd returns; the bound of the incoming gradient is taken over all planes."""
+    lib = _lib.load_heads_train()
+    _chk(xyz, d_raw, *weights)
+    H, P = _chk_heads(n_heads), xyz.numel() // 3
+    assert bits.shape == (8, P, 8) and bits.dtype == torch.int32 and bits.is_contiguous()
+    assert d_raw.numel() == 4 * P * H and len(weights) == 9 and tuple(weights[8].shape) == (4 * H, 256)
+    half = mode == 'f16x3h'
+    m = MLP_MODES['f16x3' if half else mode]
+    packed = torch.empty((lib.hnrf_canonical_heads_bwd_packed_bytes(m, H) + 3) // 4, device=xyz.device)
+    _lib.check(lib.hnrf_canonical_heads_bwd_pack(_ptr_array(weights), H, m, _ptr(packed), _stream()),
+               'hnrf_canonical_heads_bwd_pack')
+    d_raw_amax = d_raw.abs().amax().reshape(1) if mode != 'f32' else None
+    dZ = torch.empty(8, (P + 127) // 128 * 128, 256, device=xyz.device, dtype=torch.float16) if half else torch.empty(8, P, 256, device=xyz.device)
+    d_xyz = torch.empty(P, 3, device=xyz.device)
+    amax = torch.empty(8, device=xyz.device) if half else torch.empty(8, 64, device=xyz.device)
+    _lib.check(lib.hnrf_canonical_heads_bwd(_ptr(xyz), _ptr(d_raw), bits.data_ptr(), _ptr(packed), TRAIN_MODES[mode],
+                                            _ptr(d_raw_amax), P, H, _ptr(dZ), _ptr(d_xyz), _ptr(amax), _stream()),
+               'hnrf_canonical_heads_bwd')
+    return dZ, d_xyz, amax

@@ -30,7 +30,7 @@ import warnings
 import torch
 
 from . import dist as hdist
-from .config import cfg, amd_option, quiet_gc
+from .config import cfg, amd_option, multihead_option, quiet_gc
 
 
 def customized_lr_names():
@@ -184,14 +184,65 @@ def image_loss(rgb, target, lpips_fn=None):
     return total, parts
 
 
+def _loss_term(name, rgb, target, lpips_fn):
+    """One un-weighted term of get_img_rebuild_loss (trainer.py:97-113).  'lpips' without an ``lpips_fn`` is 0, as the
+    reference's is with a zero weight (see Trainer.objective)."""
+    if name == 'mse':
+        return torch.mean((rgb - target) ** 2)
+    if name == 'l1':
+        return torch.mean(torch.abs(rgb - target))
+    if name == 'lpips':
+        if lpips_fn is None:
+            return rgb.new_zeros(())
+        return torch.mean(lpips_fn(rgb.permute(0, 3, 1, 2) * 2. - 1., target.permute(0, 3, 1, 2) * 2. - 1.))
+    raise KeyError('unknown loss term %r' % (name,))
+
+
+def heads_image_loss(rgbs, target, lpips_fn=None):
+    """The loss of multihead.split = 'argmin' (trainer.py:124-160) for a list of per-head images ``rgbs``: every head's
+    terms, a selection criterion per head (multihead.argmin_cfg.selector_criteria, weights > 0), best_head = the argmin of
+    the criteria (np.argmin: the first of equals); the best head's terms are weighted by cfg.train.lossweights, every
+    other head's by argmin_cfg.unselected_lossweights (all zero by default: those heads then receive a zero gradient, but
+    stay in the graph).  Returns (total, parts, best_head); parts holds '<name>_head<h>' for every head and weight > 0
+    (weighted by lossweights, as the reference logs them), '<name>' of the best head, and 'best_head'.
+    A selector_criteria.ssim > 0 raises NotImplementedError: the reference computes it with skimage on the host, and
+    parity of that branch is unpinned.  One host read (the criteria) per call."""
+    weights = {k: v for k, v in cfg.train.lossweights.items() if v > 0}
+    unselected = dict(multihead_option('argmin_cfg.unselected_lossweights'))
+    criteria_w = {k: v for k, v in dict(multihead_option('argmin_cfg.selector_criteria')).items() if v > 0}
+    if 'ssim' in criteria_w:
+        raise NotImplementedError('multihead.argmin_cfg.selector_criteria.ssim = %g: the SSIM criterion is not built (the '
+                                  'reference computes it with skimage on the host; set it to 0)' % criteria_w['ssim'])
+    names = list(weights) + [k for k in list(unselected) + list(criteria_w) if k not in weights]
+    terms = [{k: _loss_term(k, rgb, target, lpips_fn) for k in names} for rgb in rgbs]
+    if not criteria_w:
+        raise ValueError('multihead.argmin_cfg.selector_criteria has no weight > 0: nothing to select a head by')
+    criteria = torch.stack([sum(w * t[k].detach() for k, w in criteria_w.items()) for t in terms])
+    best = int(criteria.cpu().numpy().argmin())
+    parts = {}
+    for h, t in enumerate(terms):
+        parts.update({'%s_head%d' % (k, h): w * t[k] for k, w in weights.items()})
+    parts.update({k: w * terms[best][k] for k, w in weights.items()})
+    total = 0.0
+    for k, w in weights.items():
+        total = total + w * terms[best][k]
+    for h, t in enumerate(terms):
+        if h != best:
+            for k, w in unselected.items():
+                total = total + w * t[k]
+    parts['best_head'] = best
+    return total, parts, best
+
+
 PROGRESS_ITERS = (100, 300, 1000, 2500)          # trainer.py:240
 
 
 class Trainer:
     def __init__(self, network, optimizer=None, lpips_fn=None, world_size=1, process_group=None, logdir=None):
-        if getattr(network, 'head_num', 0):
+        if getattr(network, 'head_num', 0) and not amd_option('train_heads', False):
             raise NotImplementedError('Trainer: a multi-head canonical MLP (%d heads) is built for inference only; its '
-                                      'checkpoints come from the reference trainer' % network.head_num)
+                                      'checkpoints come from the reference trainer (cfg.amd.train_heads = True trains it '
+                                      'here)' % network.head_num)
         self.network = network.deploy_mlps_to_secondary_gpus()
         self.optimizer = optimizer if optimizer is not None else build_optimizer(network)
         self.lpips_fn = lpips_fn
@@ -209,6 +260,7 @@ class Trainer:
                           '(set lossweights.lpips = 0 to silence this)' % (weights['lpips'], self.objective))
         self.iter = 1
         self.start_iter = 1
+        self.best_head = None                # the head the last 'argmin' step selected
         quiet_gc()
 
     # ------------------------------------------------------------------------------------------ one iteration
@@ -217,16 +269,21 @@ class Trainer:
         (rank-averaged) gradients in ``.grad``."""
         self.network.train()
         self.optimizer.zero_grad(set_to_none=True)
-        out = self.network(**batch, iter_val=float(self.iter))
+        out = self.network(**batch, iter_val=float(self.iter))      # (a multi-head network reads batch['head_id'])
         if 'patch_masks' in batch:
-            pred = unpack_patches(out['rgb'], batch['patch_masks'], batch['bgcolor'] / 255.,
-                                  batch['target_patches'], batch['patch_div_indices'])
-            loss, parts = image_loss(pred, batch['target_patches'], self.lpips_fn)
+            unpack = lambda rgb: unpack_patches(rgb, batch['patch_masks'], batch['bgcolor'] / 255.,
+                                                batch['target_patches'], batch['patch_div_indices'])
+            target, lpips_fn = batch['target_patches'], self.lpips_fn
         else:                                # flat rays with per-ray targets
-            loss, parts = image_loss(out['rgb'][None, None], batch['target_rgbs'][None, None], None)
+            unpack = lambda rgb: rgb[None, None]
+            target, lpips_fn = batch['target_rgbs'][None, None], None
+        if isinstance(out['rgb'], list):     # head_id = -1, multihead.split = 'argmin' (trainer.py:124-160)
+            loss, parts, self.best_head = heads_image_loss([unpack(rgb) for rgb in out['rgb']], target, lpips_fn)
+        else:
+            loss, parts = image_loss(unpack(out['rgb']), target, lpips_fn)
         loss.backward()
         self.grad_sync.reduce()
-        return loss.detach(), {k: v.detach() for k, v in parts.items()}
+        return loss.detach(), {k: v.detach() if torch.is_tensor(v) else v for k, v in parts.items()}
 
     def optimizer_step(self):
         """Adam update, learning-rate decay, iteration counter (trainer.py:219, 253-255)."""
@@ -316,12 +373,46 @@ def make_progress_fn(frames, logdir, device=None, imgs_per_row=4):
     """The reference's Trainer.progress (trainer.py:271-350) as a ``progress_fn`` for Trainer.train: renders ``frames``
     (per-frame dicts like the 'progress' dataset yields: 16 frames in image mode, each with ``target_rgbs``) with the
     current weights, puts render and truth side by side, tiles them and writes ``prog_{iter:06}.jpg`` into ``logdir``.
-    Returns True when a rendered image is empty (all background) during the first 5000 iterations, like the reference."""
+    Returns True when a rendered image is empty (all background) during the first 5000 iterations, like the reference.
+    A multi-head network (cfg.amd.train_heads) writes one mosaic per head, ``prog_{iter:06}_head{h}.jpg``, from ONE
+    ``head_id = -1`` render per frame (trainer.py:276-335)."""
     import numpy as np
     from . import render
 
+    def progress_heads(trainer):
+        import contextlib
+        from PIL import Image
+        net, H = trainer.network, trainer.network.head_num
+        dev = device or next(net.parameters()).device
+        pairs, empty, outbox = [dict() for _ in range(H)], False, render.FrameOutbox(dev)
+        bg = np.array(cfg.bgcolor, dtype=np.float32)
+        pre = render.FramePrefetcher(frames, list(range(len(frames))), dev, show_truth=True)
+        with contextlib.closing(pre):
+            for item in pre:
+                with torch.no_grad():
+                    res = net(**item['data'], head_id=-1, iter_val=float(trainer.iter))   # the CURRENT iteration (trainer.py:293)
+                imgs, truth = [], item['truth']
+                for h in range(H):
+                    rgb8, a8, t8 = render.unpack_to_image(item['W'], item['H'], None, item['data']['bgcolor'] / 255.,
+                                                          res['rgb'][h], res['alpha'][h], truth if h == 0 else None,
+                                                          ray_index=item['ray_index'])
+                    imgs += [rgb8, a8] + ([t8] if h == 0 and truth is not None else [])
+                arrs = outbox.post(imgs).collect()[0]
+                net.check_f16_range(wait=True)
+                t8 = arrs[2] if truth is not None else None
+                for h in range(H):
+                    rgb8, a8 = arrs[:2] if h == 0 else arrs[(3 if truth is not None else 2) + 2 * (h - 1):][:2]
+                    pairs[h][item['idx']] = np.concatenate([rgb8, t8 if t8 is not None else a8], axis=1)
+                    empty = empty or (trainer.iter <= 5000 and bool(np.allclose(rgb8, bg, atol=5.)))
+        for h in range(H):
+            tiled = render.tile_images([pairs[h][i] for i in sorted(pairs[h])], imgs_per_row=imgs_per_row)
+            Image.fromarray(tiled).save(os.path.join(logdir, 'prog_%06d_head%d.jpg' % (trainer.iter, h)))
+        return empty
+
     def progress(trainer):
         os.makedirs(logdir, exist_ok=True)
+        if getattr(trainer.network, 'head_num', 0):
+            return progress_heads(trainer)
         pairs, empty = {}, False
 
         def on_image(i, rgb8, a8, t8=None):

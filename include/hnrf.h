@@ -799,6 +799,11 @@ int hnrf_image_metrics(const uint8_t* pred, const uint8_t* target, const uint8_t
  * version 13; contracts and declarations in hnrf_normals.h. */
 #include "hnrf_normals.h"
 
+/* ---- training the multi-head canonical MLP: the all-heads epilogue on the activation-saving forward, the transposed
+ * image with a 4 H-wide head stage, and the backward chain seeded with every head's gradient.  Additive to ABI version
+ * 13; contracts and declarations in hnrf_heads_train.h. */
+#include "hnrf_heads_train.h"
+
 #ifdef __cplusplus
 }
 #endif
