@@ -1232,7 +1232,8 @@ extern "C" int hnrf_mlp_dw(const float* dZ, int64_t ldz, const float* X, int64_t
                  "hnrf_mlp_dw: shape P=%lld n_out=%d n_in=%d not built (n_out 128|256 with n_in 128|256|<=64; n_out <= 4 with n_in 128|256)",
                  (long long)P, n_out, n_in);
     HNRF_REQUIRE(ldz >= n_out && ldx >= n_in && ldw >= n_in, HNRF_E_ARG, "hnrf_mlp_dw: row stride below width");
-    HNRF_REQUIRE(workspace_bytes >= hnrf_mlp_dw_workspace_bytes(P, n_out, n_in), HNRF_E_ARG,
+    HNRF_REQUIRE(((uintptr_t)workspace & 255) == 0, HNRF_E_ARG, "hnrf_mlp_dw: workspace must be 256-byte aligned");
+    HNRF_REQUIRE(workspace_bytes >= hnrf_mlp_dw_workspace_bytes(P, n_out, n_in), HNRF_E_WORKSPACE,
                  "hnrf_mlp_dw: workspace too small");
     if (n_in > 64 && n_out > 4)
         HNRF_REQUIRE(((uintptr_t)X & 15) == 0 && ldx % 4 == 0, HNRF_E_ARG,
@@ -1287,7 +1288,8 @@ extern "C" int hnrf_mlp_dw_h(const void* dZ, int64_t ldz, const void* X, int64_t
     HNRF_REQUIRE(P > 0 && dwh_plan(P, n_out, n_in, pl), HNRF_E_UNSUPPORTED,
                  "hnrf_mlp_dw_h: shape P=%lld n_out=%d n_in=%d not built (n_out 128|256 with n_in 128|256|<=64; n_out <= 4 "
                  "with n_in 128|256)", (long long)P, n_out, n_in);
-    HNRF_REQUIRE(workspace_bytes >= hnrf_mlp_dw_h_workspace_bytes(P, n_out, n_in), HNRF_E_ARG,
+    HNRF_REQUIRE(((uintptr_t)workspace & 255) == 0, HNRF_E_ARG, "hnrf_mlp_dw_h: workspace must be 256-byte aligned");
+    HNRF_REQUIRE(workspace_bytes >= hnrf_mlp_dw_h_workspace_bytes(P, n_out, n_in), HNRF_E_WORKSPACE,
                  "hnrf_mlp_dw_h: workspace too small");
     float* part = (float*)workspace;
     float* dbpart = part + (size_t)pl.nsplit * pl.now * pl.nip;

@@ -1707,7 +1707,8 @@ size_t canonical16_bwd_bytes() { return (size_t)CB16_BYTES + 256; }
 static int launch_layer_amax(const float* const* w, const int* n, int count, float* out, hipStream_t st) {
     LayerSet ls;
     for (int i = 0; i < 9; ++i) { ls.w[i] = i < count ? w[i] : nullptr; ls.n[i] = i < count ? n[i] : 0; }
-    if (hipMemsetAsync(out, 0, 64, st) != hipSuccess) {
+    // all 256 bytes the image reserves behind its blocks: *_bwd_packed_bytes counts them, so they are written
+    if (hipMemsetAsync(out, 0, 256, st) != hipSuccess) {
         set_error("hnrf pack (layer maxima): memset failed");
         return HNRF_E_LAUNCH;
     }

@@ -376,6 +376,7 @@ extern "C" int hnrf_motion_basis_bwd(const float* g_Rs, const float* g_Ts, const
     HNRF_REQUIRE(g_Rs && g_Ts && dst_Rs && dst_Ts && cnl_gtfms && saved && d_dst_Rs && d_dst_Ts, HNRF_E_ARG,
                  "hnrf_motion_basis_bwd: null pointer");
     HNRF_REQUIRE(B == POSE_B, HNRF_E_UNSUPPORTED, "hnrf_motion_basis_bwd: %d bones (the SMPL tree has 24)", B);
+    HNRF_REQUIRE(((uintptr_t)saved & 7) == 0, HNRF_E_ARG, "hnrf_motion_basis_bwd: saved must be 8-byte aligned");
     hipLaunchKernelGGL(motion_basis_bwd_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, g_Rs, g_Ts, (const float*)nullptr,
                        dst_Rs, dst_Ts, cnl_gtfms, (const double*)saved, (float*)nullptr, d_dst_Rs, d_dst_Ts);
     return check_launch("hnrf_motion_basis_bwd");
@@ -397,6 +398,7 @@ extern "C" int hnrf_refined_motion_basis_bwd(const float* g_Rs, const float* g_T
     HNRF_REQUIRE(g_Rs && g_Ts && rvec && dst_Rs && dst_Ts && cnl_gtfms && saved && d_rvec && d_dst_Rs && d_dst_Ts, HNRF_E_ARG,
                  "hnrf_refined_motion_basis_bwd: null pointer");
     HNRF_REQUIRE(B == POSE_B, HNRF_E_UNSUPPORTED, "hnrf_refined_motion_basis_bwd: %d bones (the SMPL tree has 24)", B);
+    HNRF_REQUIRE(((uintptr_t)saved & 7) == 0, HNRF_E_ARG, "hnrf_refined_motion_basis_bwd: saved must be 8-byte aligned");
     hipLaunchKernelGGL(motion_basis_bwd_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, g_Rs, g_Ts, rvec, dst_Rs, dst_Ts,
                        cnl_gtfms, (const double*)saved, d_rvec, d_dst_Rs, d_dst_Ts);
     return check_launch("hnrf_refined_motion_basis_bwd");

@@ -1917,6 +1917,21 @@ def canonical_heads_train(xyz, packed, n_heads, mode='f32'):
     return raw, pe, acts, bits
 
 
+def canonical_heads_bwd_pack(weights, n_heads, mode='f32', out=None):
+    """hnrf_canonical_heads_bwd_pack: as canonical_bwd_pack, with weights[8] (4 H, 256)."""
+    lib = _lib.load_heads_train()
+    _chk(*weights)
+    H = _chk_heads(n_heads)
+    assert len(weights) == 9 and tuple(weights[8].shape) == (4 * H, 256)
+    m = MLP_MODES[mode]
+    nbytes = lib.hnrf_canonical_heads_bwd_packed_bytes(m, H)
+    if out is None or out.numel() * 4 < nbytes:
+        out = torch.empty((nbytes + 3) // 4, device=weights[0].device)
+    _lib.check(lib.hnrf_canonical_heads_bwd_pack(_ptr_array(weights), H, m, _ptr(out), _stream()),
+               'hnrf_canonical_heads_bwd_pack')
+    return out
+
+
 def canonical_heads_bwd(xyz, d_raw, bits, weights, n_heads, mode='f32'):
     """canonical_bwd seeded with every head's gradient: d_raw (H,P,4) head-major, weights[8] (4 H, 256).  Returns what
     canonical_bwd returns; the bound of the incoming gradient is taken over all planes."""
@@ -1926,10 +1941,7 @@ def canonical_heads_bwd(xyz, d_raw, bits, weights, n_heads, mode='f32'):
     assert bits.shape == (8, P, 8) and bits.dtype == torch.int32 and bits.is_contiguous()
     assert d_raw.numel() == 4 * P * H and len(weights) == 9 and tuple(weights[8].shape) == (4 * H, 256)
     half = mode == 'f16x3h'
-    m = MLP_MODES['f16x3' if half else mode]
-    packed = torch.empty((lib.hnrf_canonical_heads_bwd_packed_bytes(m, H) + 3) // 4, device=xyz.device)
-    _lib.check(lib.hnrf_canonical_heads_bwd_pack(_ptr_array(weights), H, m, _ptr(packed), _stream()),
-               'hnrf_canonical_heads_bwd_pack')
+    packed = canonical_heads_bwd_pack(weights, H, 'f16x3' if half else mode)
     d_raw_amax = d_raw.abs().amax().reshape(1) if mode != 'f32' else None
     dZ = torch.empty(8, (P + 127) // 128 * 128, 256, device=xyz.device, dtype=torch.float16) if half else torch.empty(8, P, 256, device=xyz.device)
     d_xyz = torch.empty(P, 3, device=xyz.device)

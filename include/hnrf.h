@@ -339,7 +339,8 @@ int hnrf_sample_warp_bwd(const float* rays_o, const float* rays_d, const float* 
  * single-wave kernel each (in PyTorch: 23 dependent 4x4 matmuls, a batched inverse and their autograd twins).
  *  dst_Rs [24,3,3], dst_Ts [24,3], cnl_gtfms [24,4,4] -> Rs [24,3,3], Ts [24,3] = (cnl_gtfms_i A_i^-1)[:3,:3 | :3,3],
  *  A_i = A_parent(i) [R_i | T_i] along the SMPL tree; fp64 internally.  saved (nullable): hnrf_motion_basis_saved_bytes()
- *  bytes, 8-byte aligned, for the backward.  B must be 24.
+ *  bytes, 8-byte aligned, for the backward.  B must be 24.  A saved that is not 8-byte aligned is HNRF_E_ARG, another B
+ *  HNRF_E_UNSUPPORTED, in all four entries; nothing is written when a call is refused.
  *  bwd: g_Rs, g_Ts (gradients at the outputs) -> d_dst_Rs [24,3,3], d_dst_Ts [24,3]. */
 size_t hnrf_motion_basis_saved_bytes(void);
 int hnrf_motion_basis_fwd(const float* dst_Rs, const float* dst_Ts, const float* cnl_gtfms, int B, float* Rs, float* Ts,
@@ -365,7 +366,8 @@ int hnrf_refined_motion_basis_bwd(const float* g_Rs, const float* g_Ts, const fl
  *  the backward reads them and uses the rest as scratch.
  *  fwd: x [dims[0]] -> out [dims[layers]].
  *  bwd: g_out [dims[layers]] -> dW[l] (out, in), db[l] (HOST arrays of device pointers); d_x_parts (nullable): [8][256]
- *  floats whose first ceil(dims[1] / 32) rows sum to d_x (columns < dims[0]). */
+ *  floats whose first ceil(dims[1] / 32) rows sum to d_x (columns < dims[0]); the other rows and the columns from
+ *  dims[0] on are not written. */
 size_t hnrf_pose_mlp_saved_bytes(int layers);
 int hnrf_pose_mlp_fwd(const float* x, const float* const* W, const float* const* b, const int* dims, int layers, float* out,
                       float* saved, void* stream);
@@ -382,7 +384,11 @@ int hnrf_pose_mlp_bwd(const float* g_out, const float* x, const float* const* W,
  *  mode HNRF_MLP_F32: fp32 MFMA.  HNRF_MLP_F16X3: split-f16 MFMA at fp32-class accuracy for the matrix-shaped
  *  layers (n_out, n_in in {128, 256}; other shapes silently use the fp32 kernels); needs dz_amax = n_amax device
  *  floats whose maximum is >= max |dZ| (one row of hnrf_*_bwd's dz_amax), and |X| <= 65504.  Deterministic (fixed-order slice reduction).
- *  workspace: hnrf_mlp_dw_workspace_bytes (covers both modes). */
+ *  workspace: hnrf_mlp_dw_workspace_bytes (covers both modes), 256-byte aligned like every other workspace (HNRF_E_ARG
+ *  otherwise; a smaller one is HNRF_E_WORKSPACE); nothing is written when the call is refused.  Every slice partial the
+ *  reduction reads is written by the same call: the workspace needs no clearing between calls of different shapes.
+ *  Only the n_in columns of each of the n_out rows of dW are written: the other columns of a wider matrix keep what
+ *  they held. */
 size_t hnrf_mlp_dw_workspace_bytes(int64_t P, int n_out, int n_in);
 int hnrf_mlp_dw(const float* dZ, int64_t ldz, const float* X, int64_t ldx, int64_t P, int n_out, int n_in,
                 int mode, const float* dz_amax, int n_amax, float* dW, int64_t ldw, float* db, void* workspace,
@@ -395,7 +401,8 @@ int hnrf_mlp_dw(const float* dZ, int64_t ldz, const float* X, int64_t ldx, int64
  * fp32 accumulation over the samples; both operands reach the matrix pipe through gfx950's transposed LDS read
  * (ds_read_b64_tr_b16).  Each operand is rounded to 11 bits, unbiased: the relative error of a sum over N samples is
  * ~2^-12 / sqrt(N).  n_out <= 4 (heads): dZ is the fp32 [P, n_out] gradient at the head output, X the f16 activations.
- * Same shapes, workspace rules and determinism as hnrf_mlp_dw.
+ * Same shapes, workspace rules (hnrf_mlp_dw_h_workspace_bytes, 256-byte aligned: HNRF_E_ARG otherwise; a smaller one is
+ * HNRF_E_WORKSPACE; nothing is written when the call is refused) and determinism as hnrf_mlp_dw.
  * layout: 0 = both matrices row-major; HNRF_DWH_DZ_BLOCKED / HNRF_DWH_X_BLOCKED = the matrix is in the BLOCKED layout
  * the HNRF_MLP_F16X3_H training kernels write (32-sample blocks of [32-feature tile][4 groups][2][32 samples][4 halves],
  * layers padded to a multiple of 128 samples; row strides are ignored for it).  Built: none, dZ only, both. */
@@ -409,7 +416,8 @@ int hnrf_mlp_dw_h(const void* dZ, int64_t ldz, const void* X, int64_t ldx, int64
 /* Backward through all layers of one MLP (the dX chain of autograd over mlp_rgb_sigma.py / mlp_offset.py),
  * register-resident like the forward, with the backward of the positional encoding fused.
  *  *_bwd_pack: transposed weight image from the same nn.Linear weights hnrf_*_pack takes (re-pack after
- *  every parameter update).
+ *  every parameter update); it writes every one of the *_bwd_packed_bytes(mode) bytes (16-byte aligned), so that two
+ *  images of the same weights compare equal byte for byte.
  *  canonical: xyz [P,3], d_raw [P,4] (16-byte aligned), relu_bits [8][P][8] from hnrf_canonical_fwd_train ->
  *    dZ [8][P][256] (gradient at every hidden layer's pre-activation: the dZ operand of hnrf_mlp_dw) and
  *    d_xyz [P,3].
@@ -438,7 +446,8 @@ int hnrf_nonrigid_bwd_pack(const float* const* weights, int mode, void* packed, 
  *     ANY gradient tensor sees it.  Units whose ReLU is dead are masked by select and may stay 0.
  * The padding contract: rows 0 .. P-1 of dZ and d_xyz / d_x_skel and all of dz_amax are written whatever the buffers
  * held before; in HNRF_MLP_F16X3_H the padding rows P .. ceil(P / 128) * 128 - 1 of every blocked dZ layer are written
- * with ZEROS (hnrf_mlp_dw_h reads whole 128-sample blocks).  Nothing is read before it is written. */
+ * with ZEROS (hnrf_mlp_dw_h reads whole 128-sample blocks).  Nothing is read before it is written.  P == 0 returns
+ * HNRF_OK without a launch: nothing is written, dz_amax included. */
 int hnrf_canonical_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed,
                        int mode, const float* d_raw_amax, int64_t P, float* dZ, float* d_xyz, float* dz_amax,
                        void* stream);

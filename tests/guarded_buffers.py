@@ -1,7 +1,8 @@
 """Guarded buffers: what a test hands a kernel so that a store or a load outside the stated size is seen.
 
 One allocation holds a front guard of 64 KiB, a 256-byte aligned interior of EXACTLY the stated number of bytes, and a
-back guard of 64 KiB; all three are filled with one 32-bit pattern before the call.  Afterwards
+back guard of 64 KiB; all three are filled with one 32-bit pattern before the call.  (``guard``: another size for both
+guards, a multiple of 4.)  Afterwards
 
   - ``check()`` compares both guards with the pattern: a store outside the interior is reported with its byte offset
     from the interior's start or end;
@@ -13,7 +14,8 @@ back guard of 64 KiB; all three are filled with one 32-bit pattern before the ca
 The two patterns: 0xFFFFFFFF is a NaN as a float and -1 as an index or a count, 0x00000000 is zero.  There is no large
 positive pattern on purpose: a stale positive count would drive a kernel off its buffers, and these tests are there to
 detect, not to provoke.  64 KiB covers a full tile of the widest output row of the inference kernels (256 samples x 24
-bones x 4 bytes = 24 KiB).  Works on CPU tensors as on the device (tests/test_guarded_buffers_cpu.py)."""
+bones x 4 bytes = 24 KiB); the training kernels' file asks for 256 KiB: one 128-sample padding tile of a 256-wide fp32
+layer is 128 KiB.  Works on CPU tensors as on the device (tests/test_guarded_buffers_cpu.py)."""
 import torch
 
 GUARD = 64 * 1024
@@ -34,20 +36,20 @@ class GuardViolation(AssertionError):
 class GuardedBuffer:
     """``nbytes`` interior bytes between two guards, everything filled with the 32-bit ``fill``.  ``name`` appears in
     every report.  ``misalign``: extra bytes (a multiple of 4 below 256) by which the interior's start is moved off its
-    256-byte alignment, for the entries that must refuse such a pointer."""
+    256-byte alignment, for the entries that must refuse such a pointer.  ``guard``: bytes of each guard."""
 
-    def __init__(self, nbytes, fill, device='cpu', name='buffer', misalign=0):
-        nbytes = int(nbytes)
-        assert nbytes >= 0 and 0 <= misalign < ALIGN and misalign % 4 == 0
-        self.nbytes, self.fill, self.name = nbytes, fill & 0xFFFFFFFF, name
-        total = GUARD + 2 * ALIGN + (nbytes + 3) // 4 * 4 + GUARD
+    def __init__(self, nbytes, fill, device='cpu', name='buffer', misalign=0, guard=GUARD):
+        nbytes, guard = int(nbytes), int(guard)
+        assert nbytes >= 0 and 0 <= misalign < ALIGN and misalign % 4 == 0 and guard > 0 and guard % 4 == 0
+        self.nbytes, self.fill, self.name, self.guard = nbytes, fill & 0xFFFFFFFF, name, guard
+        total = guard + 2 * ALIGN + (nbytes + 3) // 4 * 4 + guard
         self.words = torch.empty(total // 4, dtype=torch.int32, device=device)
         self.words.fill_(as_i32(fill))
         base = self.words.data_ptr()
         assert base % 4 == 0
-        self.start = GUARD + (-(base + GUARD)) % ALIGN + misalign          # byte offset of the interior
+        self.start = guard + (-(base + guard)) % ALIGN + misalign          # byte offset of the interior
         self.bytes = self.words.view(torch.uint8)
-        assert self.start + nbytes + GUARD <= total and (self.ptr - misalign) % ALIGN == 0
+        assert self.start + nbytes + guard <= total and (self.ptr - misalign) % ALIGN == 0
 
     # ---------------------------------------------------------------- the interior
     @property
@@ -134,12 +136,12 @@ class GuardedBuffer:
                                  % (self.name, b - self.start, self.fill))
 
 
-def place(tensor, fill, device=None, name='input'):
+def place(tensor, fill, device=None, name='input', guard=GUARD):
     """A guarded buffer of exactly the bytes of ``tensor`` (contiguous), holding a copy of it: a kernel that reads past
     the end of this input reads the fill, and under the other fill it reads something else."""
     t = tensor.contiguous()
     device = t.device if device is None else device
-    g = GuardedBuffer(t.numel() * t.element_size(), fill, device, name)
+    g = GuardedBuffer(t.numel() * t.element_size(), fill, device, name, guard=guard)
     if t.numel():
         g.view(t.dtype).copy_(t.reshape(-1))
     return g

@@ -22,6 +22,7 @@ import torch
 
 from humannerf_amd import shared_input as si
 from tests import guarded_buffers as gb
+from tests.guarded_case import Case, T, _stream, bits, both, dev, eq, ok, same
 from tests import multihead_cases as mc
 from tests import test_render_kernel_refs as refs
 from tests.test_train_kernel_refs import CNL_NAMES, NR_NAMES
@@ -32,102 +33,11 @@ F = np.float32
 R0, S0 = 37, 21
 P0 = R0 * S0
 E_ARG, E_WORKSPACE = -1, -4
-STATUS_F16_RANGE = 1
 MODES = ['f32', 'f16x3']
 BMW = 'backward_motion_weights'
 # a representative of the seeded network's size for the share kernels (tests/test_gpu_shared_input.py); c_xyz = +0 + c_off
 C_OFF = np.array([-0.0686608, -0.00916304, 0.06966332], F)
 C_XYZ = (np.zeros(3, F) + C_OFF).astype(F)
-
-
-def dev():
-    assert torch.cuda.is_available(), 'GPU tests need an MI355X'
-    return torch.device('cuda:0')
-
-
-def T(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev())
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def bits(t):
-    t = t.contiguous()
-    return t.view(torch.int32 if t.element_size() == 4 else torch.uint8).reshape(-1)
-
-
-class Case:
-    """The buffers of one call under one fill: inputs (``put``: a copy of the array in a buffer of exactly its size),
-    packed images (``packed``) and outputs / workspaces (``new``).  ``done`` synchronises and checks (a) and (e)."""
-
-    def __init__(self, fill):
-        self.fill, self.g, self.orig, self.status = fill, {}, {}, {}
-
-    def put(self, name, a):
-        if a is None:
-            return None
-        t = (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev()).contiguous()
-        self.g[name] = gb.place(t, self.fill, name=name)
-        self.orig[name] = self.g[name].interior_bytes().clone()
-        return self.g[name].ptr
-
-    def packed(self, name, image):
-        """``image``: (tensor of the pack wrapper, exact byte size, byte offset of the status word or 0)."""
-        t, nbytes, off = image
-        ptr = self.put(name, t.view(torch.uint8)[:nbytes].clone())
-        self.status[name] = off
-        return ptr
-
-    def new(self, name, nbytes, misalign=0):
-        self.g[name] = gb.GuardedBuffer(nbytes, self.fill, dev(), name, misalign)
-        return self.g[name].ptr
-
-    def f(self, name, *shape):
-        return self.g[name].view(torch.float32, *shape)
-
-    def i(self, name, *shape):
-        return self.g[name].view(torch.int32, *shape)
-
-    def done(self):
-        torch.cuda.synchronize()
-        for g in self.g.values():
-            g.check()
-        for name, was in self.orig.items():
-            now = self.g[name].interior_bytes().clone()
-            off = self.status.get(name, 0)
-            if off:
-                old_w = int(was[off:off + 4].view(torch.int32))
-                new_w = int(now[off:off + 4].view(torch.int32))
-                assert new_w in (old_w, old_w | STATUS_F16_RANGE), (name, hex(old_w), hex(new_w))
-                now[off:off + 4] = was[off:off + 4]
-            assert torch.equal(now, was), 'input %s was written' % name
-        return self
-
-
-def both(fn):
-    """fn(case) under each fill -> the two finished cases."""
-    out = []
-    for fill in gb.FILLS:
-        c = Case(fill)
-        fn(c)
-        out.append(c.done())
-    return out
-
-
-def same(a, b, names, rows=None, n_rows=None, row_bytes=None, offset=0):
-    for n in names:
-        gb.same_bits(a.g[n], b.g[n], rows, n_rows, row_bytes, offset)
-
-
-def eq(c, name, t):
-    assert torch.equal(bits(c.g[name].view(torch.uint8 if t.element_size() == 1 else torch.int32)), bits(t)), name
-
-
-def ok(rc, what):
-    from humannerf_amd import _lib
-    _lib.check(rc, what)
 
 
 def lib_all():

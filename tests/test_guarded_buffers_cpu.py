@@ -140,6 +140,53 @@ def test_a_row_that_must_stay_untouched(fill):
         k.rows_hold_fill(torch.ones(P, dtype=torch.bool), P, B * 4, offset=P * B * 4)
 
 
+BIG_GUARD = 256 * 1024              # the guard of tests/test_gpu_train_buffer_bounds.py
+
+
+@pytest.mark.parametrize('fill', gb.FILLS)
+@pytest.mark.parametrize('nbytes', [0, 3, P * B * 4])
+def test_guard_size_argument_layout_and_clean_run(nbytes, fill):
+    for guard in (4, gb.GUARD, BIG_GUARD):
+        g = gb.GuardedBuffer(nbytes, fill, name='clean', guard=guard)
+        assert g.guard == guard and g.ptr % 256 == 0 and guard <= g.start < guard + 256
+        assert g.bytes.numel() - g.start - nbytes >= guard
+        g.interior_bytes().fill_(0x5A)
+        assert g.violations() == []
+        g.check()
+    assert gb.GuardedBuffer(nbytes, fill).guard == gb.GUARD          # the default stays 64 KiB
+    x = torch.arange(P, dtype=torch.float32)
+    h = gb.place(x, fill, name='x', guard=BIG_GUARD)
+    assert h.guard == BIG_GUARD and h.start >= BIG_GUARD and torch.equal(h.view(torch.float32), x)
+    h.check()
+    assert gb.place(x, fill).guard == gb.GUARD
+
+
+@pytest.mark.parametrize('fill', gb.FILLS)
+@pytest.mark.parametrize('side', ['back', 'front'])
+def test_a_write_one_padding_tile_away_needs_the_larger_guard(side, fill):
+    """A 'kernel' that writes one whole 128-sample tile of a 256-wide fp32 layer too many: its last element lies
+    128 KiB - 4 bytes behind the interior's end (or as far in front of its start).  The 64 KiB guard does not reach
+    there and reports nothing; the 256 KiB guard names the byte."""
+    tile = 128 * 256 * 4
+    assert gb.GUARD < tile <= BIG_GUARD
+    found = {}
+    for guard in (gb.GUARD, BIG_GUARD):
+        g = gb.GuardedBuffer(P * B * 4, fill, name='acts', guard=guard)
+        _kernel(g)
+        g.check()                                                   # the clean run passes at either size
+        at = g.start + g.nbytes + tile - 4 if side == 'back' else g.start - tile
+        if guard == BIG_GUARD:
+            g.words[at // 4] = 0x12345678
+        else:                   # the 64 KiB allocation ends before that byte: the store lands in somebody else's memory
+            assert not 0 <= at < g.bytes.numel()
+        found[guard] = g.violations()
+    assert found[gb.GUARD] == []
+    assert found[BIG_GUARD] == [('back', tile - 4) if side == 'back' else ('front', -tile)]
+    with pytest.raises(gb.GuardViolation, match=r"acts: %s guard written at byte %s from" %
+                       (side, r'\+%d' % (tile - 4) if side == 'back' else '-%d' % tile)):
+        g.check()
+
+
 def test_misaligned_interior_for_the_refusal_cases():
     g = gb.GuardedBuffer(1024, gb.FILLS[0], misalign=128)
     assert g.ptr % 256 == 128
