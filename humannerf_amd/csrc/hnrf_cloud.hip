@@ -275,10 +275,10 @@ using namespace hnrf;
 
 extern "C" int hnrf_surface_points(const float* weights, const float* xyz, const float* bmw, int64_t R, int S, int B,
                                    float* wxyz, float* wmax, int* lbs, void* stream) {
-    HNRF_REQUIRE(weights && xyz && bmw && wxyz && wmax && lbs, HNRF_E_ARG, "hnrf_surface_points: null pointer");
     HNRF_REQUIRE(R >= 0 && S >= 1 && B >= 1, HNRF_E_ARG, "hnrf_surface_points: bad dims R=%lld S=%d B=%d", (long long)R, S, B);
     HNRF_REQUIRE(S <= 512 && B <= 32, HNRF_E_UNSUPPORTED, "hnrf_surface_points: S=%d B=%d (S <= 512, B <= 32 built)", S, B);
-    if (R == 0) return HNRF_OK;
+    if (R == 0) return HNRF_OK;        // (no rays: the pointers are not looked at, as in hnrf_cloud_nn for Na = 0)
+    HNRF_REQUIRE(weights && xyz && bmw && wxyz && wmax && lbs, HNRF_E_ARG, "hnrf_surface_points: null pointer");
     const int64_t blocks = (R + 3) / 4;
     HNRF_REQUIRE(blocks < (int64_t)2147483647, HNRF_E_ARG, "hnrf_surface_points: too many rays");
     hipLaunchKernelGGL(surface_points_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, weights, xyz, bmw, R,

@@ -405,13 +405,13 @@ extern "C" int hnrf_mesh_emit(const float* density, int N, float level, const fl
 extern "C" int hnrf_forward_skin(const float* verts, int64_t V, const float* motion_Rs, const float* motion_Ts,
                                  const float* vol, int B, int G, const float* bbox_min, const float* bbox_scale,
                                  float* out, void* stream) {
-    HNRF_REQUIRE(verts && motion_Rs && motion_Ts && vol && bbox_min && bbox_scale && out, HNRF_E_ARG,
-                 "hnrf_forward_skin: null pointer");
     HNRF_REQUIRE(V >= 0 && (V + kThreads - 1) / kThreads < 2147483647LL, HNRF_E_ARG, "hnrf_forward_skin: bad V=%lld",
                  (long long)V);
     HNRF_REQUIRE(B >= 1 && B <= kMaxSkinBones && G >= 2 && G <= 1024, HNRF_E_ARG,
                  "hnrf_forward_skin: bad dims B=%d G=%d (B <= %d)", B, G, kMaxSkinBones);
-    if (V == 0) return HNRF_OK;
+    if (V == 0) return HNRF_OK;        // (no vertices: the pointers are not looked at, as in hnrf_skin.h)
+    HNRF_REQUIRE(verts && motion_Rs && motion_Ts && vol && bbox_min && bbox_scale && out, HNRF_E_ARG,
+                 "hnrf_forward_skin: null pointer");
     hipLaunchKernelGGL(forward_skin_kernel, dim3((unsigned)((V + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        (hipStream_t)stream, verts, V, motion_Rs, motion_Ts, vol, B, G, bbox_min, bbox_scale, out);
     return check_launch("hnrf_forward_skin");

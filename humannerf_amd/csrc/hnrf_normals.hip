@@ -246,10 +246,10 @@ extern "C" int hnrf_ray_normals(const float* weights, const float* bmw, const fl
     HNRF_REQUIRE(n_max == 0 || (idx && g), HNRF_E_ARG, "hnrf_ray_normals: null pointer (idx, g)");
     HNRF_REQUIRE(normal && nvalid, HNRF_E_ARG, "hnrf_ray_normals: null pointer (normal, nvalid)");
     HNRF_REQUIRE(workspace, HNRF_E_ARG, "hnrf_ray_normals: null pointer (workspace)");
-    HNRF_REQUIRE(((uintptr_t)workspace & 3) == 0, HNRF_E_ARG, "hnrf_ray_normals: workspace must be 4-byte aligned");
+    HNRF_REQUIRE(((uintptr_t)workspace & 255) == 0, HNRF_E_ARG, "hnrf_ray_normals: workspace must be 256-byte aligned");
     const size_t need = hnrf_ray_normals_workspace_bytes(R, S);
-    HNRF_REQUIRE(workspace_bytes >= need, HNRF_E_ARG, "hnrf_ray_normals: workspace of %zu bytes, %zu needed", workspace_bytes,
-                 need);
+    HNRF_REQUIRE(workspace_bytes >= need, HNRF_E_WORKSPACE, "hnrf_ray_normals: workspace of %zu bytes, %zu needed",
+                 workspace_bytes, need);
     hipStream_t st = (hipStream_t)stream;
     int* slot = (int*)workspace;
     if (hipMemsetAsync(slot, 0xff, need, st) != hipSuccess) {

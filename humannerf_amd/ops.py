@@ -1807,8 +1807,8 @@ def density_gradient(xyz, cnl_packed, cnl_weights, mode='f32', warp=None, worksp
 def ray_normals(weights, bmw, motion_Rs, idx, count, g, alpha, alpha_min=0.5, workspace=None, out=None):
     """hnrf_ray_normals (include/hnrf_normals.h): weights (R, S), bmw (R, S, B), motion_Rs (B, 3, 3), idx / count from
     compact_samples(weights, weight_min), g (n, 3) the gradient at the first n kept samples, alpha (R,) -> (normal (R, 3),
-    nvalid (R,) uint8).  ``workspace``: an int32 tensor of R S elements to use as the slot table; ``out``: (normal,
-    nvalid) to write into."""
+    nvalid (R,) uint8).  ``workspace``: an int32 tensor of R S elements, 256-byte aligned, to use as the slot table (one
+    that is too small or misaligned is replaced by a fresh one); ``out``: (normal, nvalid) to write into."""
     lib = _lib.load_normals()
     _chk(weights, bmw, motion_Rs, g, alpha)
     _chk_dev(idx, torch.int32, 'ray_normals: idx')
@@ -1822,7 +1822,7 @@ def ray_normals(weights, bmw, motion_Rs, idx, count, g, alpha, alpha_min=0.5, wo
     dev = weights.device
     n_max = min(int(g.shape[0]), int(idx.numel()))
     need = lib.hnrf_ray_normals_workspace_bytes(R, S)
-    if workspace is None or workspace.numel() * 4 < need:
+    if workspace is None or workspace.numel() * 4 < need or workspace.data_ptr() % 256:      # (a slice may be misaligned)
         workspace = torch.empty(max((need + 3) // 4, 1), dtype=torch.int32, device=dev)
     _chk_dev(workspace, torch.int32, 'ray_normals: workspace')
     normal, nvalid = out if out is not None else (torch.empty(R, 3, device=dev), torch.empty(R, dtype=torch.uint8, device=dev))

@@ -541,7 +541,8 @@ int hnrf_mesh_emit(const float* density, int N, float level, const float* bbox_m
  *  x_o = sum_b w_b(x_c) A_b^-1(x_c) / max(sum_b w_b, 1e-4), A_b(x) = R_b x + T_b the frame's motion basis
  *  (motion_Rs [B,3,3], motion_Ts [B,3], B <= 128), w_b = the trilinear weight of bone b of vol at the canonical
  *  vertex (bbox_min / bbox_scale as K1).  The forward counterpart of K1's inverse warp; the non-rigid offsets are not
- *  inverted. */
+ *  inverted.  vol [>= B,G,G,G]: the first B channels are read.  V >= 0 (V = 0: nothing is launched and the pointers are
+ *  not looked at). */
 int hnrf_forward_skin(const float* verts, int64_t V, const float* motion_Rs, const float* motion_Ts, const float* vol,
                       int B, int G, const float* bbox_min, const float* bbox_scale, float* out, void* stream);
 

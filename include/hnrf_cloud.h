@@ -21,7 +21,8 @@
  *   One wave per ray.  fp32 sums in one fixed order: lane l adds the samples l, l + 64, l + 128, ... ascending
  *   (acc = fl(acc + fl(w x)) from 0), then the 64 lanes are added by a butterfly over the lane distances 32, 16, 8, 4,
  *   2, 1 -- a ray's values depend on S alone, not on R, its row or the launch.
- *   R >= 0 (0 launches nothing), 1 <= S <= 512, 1 <= B <= 32 (HNRF_E_UNSUPPORTED beyond; HNRF_E_ARG below).
+ *   R >= 0 (0 launches nothing and the pointers are not looked at), 1 <= S <= 512, 1 <= B <= 32 (HNRF_E_UNSUPPORTED
+ *   beyond; HNRF_E_ARG below).
  *
  * ---- hnrf_cloud_nn: brute force, the counterpart of find_nearest_pair_gpu's argmin and the oracle of the windowed entry.
  *   a [Na,3], b [Nb,3] -> idx [Na] int32 = the nearest neighbour in b, d2 [Na] its d2.  Cloud b goes through LDS in

@@ -29,7 +29,10 @@
  *     where the ray is not valid.
  *   One wave per ray, four per workgroup.  A wave finds its kept samples through a slot table [R,S] int32 in the
  *   workspace (-1 = not kept, else the row of g), cleared and written from idx by two launches in front.
- *   workspace: hnrf_ray_normals_workspace_bytes(R, S) bytes (0 for sizes refused), 4-byte aligned.
+ *   workspace: hnrf_ray_normals_workspace_bytes(R, S) bytes (0 for sizes refused), 256-byte aligned like every other
+ *   workspace (a misaligned one is HNRF_E_ARG, a smaller one HNRF_E_WORKSPACE; either way nothing is written).  What it
+ *   held before the call does not matter, and normal [R,3] / nvalid [R] are written whole: R floats x 3 and R bytes.
+ *   idx and g are read on their first min(*count, n_max) rows only.
  *   R >= 0 (0 launches nothing), 1 <= S <= 512, 1 <= B <= 32, R S < 2^31, 0 <= n_max; alpha_min must not be NaN.
  *
  * ---- hnrf_normal_panels: the 8-bit panels from per-ray normals, one lane per pixel, lanes along x.

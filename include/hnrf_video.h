@@ -22,12 +22,16 @@
  *   image at `quality`, into host_out[0 .. cap); returns their number (613), or a negative error code (sizes outside
  *   1 .. 65535, quality outside 1 .. 100, cap too small).  The caller uploads them once per (H, W, quality).
  * ---- hnrf_jpeg_encode: rgb = device pointer of pixel (0, 0), pixel (y, x) at rgb + y row_stride + 3 x (row_stride >= 3 W
- *   bytes); header / header_len = the uploaded header (device memory, header_len <= 1024).  Three launches on `stream`:
+ *   bytes); only the 3 W bytes of each of the H rows are read, so a buffer of (H - 1) row_stride + 3 W bytes is enough:
+ *   the padding behind the last row need not exist.  header / header_len = the uploaded header (device memory,
+ *   header_len <= 1024; exactly header_len bytes are read).  Three launches on `stream`:
  *   one wave per MCU (colour transform, six DCTs through LDS, quantisation, Huffman coding by ballot and wave prefix
  *   sum into an LDS bit buffer, byte stuffing) writes the MCU's fixed slot of HNRF_JPEG_SLOT_BYTES in the workspace
  *   and its length; one block scans the lengths; the third kernel copies header, slots and markers into `out` and
  *   writes the stream's length to *out_len.  Nothing beyond out[0 .. *out_len) and *out_len is written outside the
- *   workspace.  Refused before any launch: sizes outside 1 .. 65535, quality outside 1 .. 100, null pointers (HNRF_E_ARG);
+ *   workspace: the bytes of out from *out_len on keep what they held, and out_len is one uint32 (4 bytes).  What the
+ *   workspace held before the call does not matter.  Refused before any launch (nothing is written then): sizes
+ *   outside 1 .. 65535, quality outside 1 .. 100, null pointers (HNRF_E_ARG);
  *   an image whose hnrf_jpeg_max_bytes does not fit the uint32 length word (HNRF_E_UNSUPPORTED: about 1.7 million MCUs);
  *   workspace_bytes < hnrf_jpeg_workspace_bytes or out_cap < hnrf_jpeg_max_bytes (HNRF_E_WORKSPACE).  workspace must be
  *   256-byte aligned, out_len 4-byte aligned.

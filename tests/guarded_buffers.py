@@ -9,7 +9,8 @@ guards, a multiple of 4.)  Afterwards
   - ``same_bits(a, b)`` compares the interiors of two buffers that went through the same call under the two FILLS: an
     element the call never wrote keeps each fill and differs, and so does a result that depends on what a buffer held
     before the call or on bytes behind an input's end (inputs sit in guarded buffers too: ``place``);
-  - ``rows_hold_fill(rows, ...)`` asserts that rows a contract calls "not written" still hold the pattern.
+  - ``rows_hold_fill(rows, ...)`` asserts that rows a contract calls "not written" still hold the pattern, and
+    ``bytes_hold_fill(offset, nbytes)`` the same of any byte range (uint8 outputs of odd sizes, a stream's tail).
 
 The two patterns: 0xFFFFFFFF is a NaN as a float and -1 as an index or a count, 0x00000000 is zero.  There is no large
 positive pattern on purpose: a stale positive count would drive a kernel off its buffers, and these tests are there to
@@ -134,6 +135,16 @@ class GuardedBuffer:
         if b is not None:
             raise GuardViolation('%s: interior written at byte %d: it must keep the fill 0x%08X'
                                  % (self.name, b - self.start, self.fill))
+
+    def bytes_hold_fill(self, offset=0, nbytes=None):
+        """Bytes [offset, offset + nbytes) of the interior (default: to its end) still hold the pattern -- any byte
+        offset and count: the tail of a byte stream behind its stated length, rows of an odd number of bytes."""
+        nbytes = self.nbytes - offset if nbytes is None else nbytes
+        assert 0 <= offset and 0 <= nbytes and offset + nbytes <= self.nbytes
+        b = self._first_bad(self.start + offset, self.start + offset + nbytes)
+        if b is not None:
+            raise GuardViolation('%s: byte %d of the interior was written: bytes %d .. %d must keep the fill 0x%08X'
+                                 % (self.name, b - self.start, offset, offset + nbytes, self.fill))
 
 
 def place(tensor, fill, device=None, name='input', guard=GUARD):

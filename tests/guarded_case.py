@@ -29,15 +29,17 @@ def bits(t):
 class Case:
     """The buffers of one call under one fill: inputs (``put``: a copy of the array in a buffer of exactly its size),
     packed images (``packed``) and outputs / workspaces (``new``).  ``done`` synchronises and checks (a) and (e).
-    ``guard``: bytes of every buffer's guards."""
+    ``guard``: bytes of every buffer's guards.  ``device``: where the buffers live (default: the GPU; the CPU for the
+    self-tests of tests/test_guarded_buffers_cpu.py)."""
 
-    def __init__(self, fill, guard=gb.GUARD):
+    def __init__(self, fill, guard=gb.GUARD, device=None):
         self.fill, self.guard, self.g, self.orig, self.status = fill, guard, {}, {}, {}
+        self.device = dev() if device is None else torch.device(device)
 
     def put(self, name, a):
         if a is None:
             return None
-        t = (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(dev()).contiguous()
+        t = (a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))).to(self.device).contiguous()
         self.g[name] = gb.place(t, self.fill, name=name, guard=self.guard)
         self.orig[name] = self.g[name].interior_bytes().clone()
         return self.g[name].ptr
@@ -50,7 +52,7 @@ class Case:
         return ptr
 
     def new(self, name, nbytes, misalign=0):
-        self.g[name] = gb.GuardedBuffer(nbytes, self.fill, dev(), name, misalign, guard=self.guard)
+        self.g[name] = gb.GuardedBuffer(nbytes, self.fill, self.device, name, misalign, guard=self.guard)
         return self.g[name].ptr
 
     def f(self, name, *shape):
@@ -59,8 +61,18 @@ class Case:
     def i(self, name, *shape):
         return self.g[name].view(torch.int32, *shape)
 
+    def u8(self, name, *shape):
+        return self.g[name].view(torch.uint8, *shape)
+
+    def i64(self, name, *shape):
+        return self.g[name].view(torch.int64, *shape)
+
+    def d(self, name, *shape):
+        return self.g[name].view(torch.float64, *shape)
+
     def done(self):
-        torch.cuda.synchronize()
+        if self.device.type == 'cuda':
+            torch.cuda.synchronize()
         for g in self.g.values():
             g.check()
         for name, was in self.orig.items():
@@ -75,12 +87,15 @@ class Case:
         return self
 
 
-def both(fn, guard=gb.GUARD):
-    """fn(case) under each fill -> the two finished cases."""
+def both(fn, guard=gb.GUARD, check=False):
+    """fn(case) under each fill -> the two finished cases.  ``check``: fn returns the entry's return code (None = 0), and
+    one that is not 0 raises."""
     out = []
     for fill in gb.FILLS:
         c = Case(fill, guard)
-        fn(c)
+        rc = fn(c)
+        if check:
+            ok(rc or 0, getattr(fn, '__name__', 'call'))
         out.append(c.done())
     return out
 
@@ -92,6 +107,15 @@ def same(a, b, names, rows=None, n_rows=None, row_bytes=None, offset=0):
 
 def eq(c, name, t):
     assert torch.equal(bits(c.g[name].view(torch.uint8 if t.element_size() == 1 else torch.int32)), bits(t)), name
+
+
+def eqb(c, name, t, nbytes=None):
+    """The interior of buffer ``name`` holds exactly the bytes of tensor ``t`` (its first ``nbytes``), whatever the
+    element type: uint8 images of odd sizes, int64 counts, float64 results."""
+    want = t.contiguous().reshape(-1).view(torch.uint8)
+    want = want if nbytes is None else want[:nbytes]
+    got = c.g[name].interior_bytes()
+    assert got.numel() == want.numel() and torch.equal(got, want.to(got.device)), name
 
 
 def ok(rc, what):

@@ -129,6 +129,12 @@ def test_ray_normals_refusals():
                      (dict(amin=float('nan')), 'alpha_min'), (dict(n_max=-1), 'n_max')):
         assert call(**kw) != 0, kw
         assert word in lib.hnrf_last_error().decode(), (kw, lib.hnrf_last_error())
+    # the workspace rule of include/hnrf.h: 256-byte aligned (HNRF_E_ARG = -1), a short one is HNRF_E_WORKSPACE = -4
+    for kw, code, word in ((dict(wsp=odd.ptr + 4), -1, '256-byte aligned'), (dict(wsp=odd.ptr + 2), -1, '256-byte aligned'),
+                           (dict(wsb=ws.nbytes - 1), -4, 'workspace'), (dict(wsb=ws.nbytes - 4), -4, 'workspace'),
+                           (dict(wsb=0), -4, 'workspace')):
+        assert call(**kw) == code, kw
+        assert word in lib.hnrf_last_error().decode(), (kw, lib.hnrf_last_error())
     torch.cuda.synchronize()
     out_n.holds_fill(), out_v.holds_fill(), bad_ws.holds_fill()
     assert lib.hnrf_ray_normals_workspace_bytes(3, 0) == 0 and lib.hnrf_ray_normals_workspace_bytes(3, 513) == 0

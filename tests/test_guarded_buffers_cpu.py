@@ -191,3 +191,56 @@ def test_misaligned_interior_for_the_refusal_cases():
     g = gb.GuardedBuffer(1024, gb.FILLS[0], misalign=128)
     assert g.ptr % 256 == 128
     g.check()
+
+
+# ------------------------------------------------------------- what tests/test_gpu_aux_buffer_bounds.py added
+@pytest.mark.parametrize('fill', gb.FILLS)
+def test_a_byte_range_that_must_stay_untouched(fill):
+    """A byte stream of 1001 bytes whose first 613 are written: the tail holds the fill; a byte written at the stated
+    length, or the last one, is named."""
+    g = gb.GuardedBuffer(1001, fill, name='stream')
+    g.interior_bytes()[:613] = 0x5A
+    g.bytes_hold_fill(613)
+    g.bytes_hold_fill(613, 0), g.bytes_hold_fill(1001), g.bytes_hold_fill(700, 3)
+    with pytest.raises(gb.GuardViolation, match='stream: byte 612 of the interior was written'):
+        g.bytes_hold_fill(612)
+    g.interior_bytes()[1000] = 0x5A
+    with pytest.raises(gb.GuardViolation, match='stream: byte 1000 of the interior was written'):
+        g.bytes_hold_fill(613)
+    g.bytes_hold_fill(613, 1000 - 613)
+    g.check()
+    gb.GuardedBuffer(0, fill).bytes_hold_fill()                     # a zero-byte buffer holds it trivially
+
+
+@pytest.mark.parametrize('fill', gb.FILLS)
+def test_case_views_of_bytes_int64_and_float64(fill):
+    """Case on CPU tensors: inputs of an odd number of bytes sit in exactly that many, int64 and float64 views address
+    the interior, eqb compares bytes of any type, and done() sees a written input and a written guard."""
+    from tests.guarded_case import Case, eqb
+    c = Case(fill, guard=1024, device='cpu')
+    img = np.arange(5 * 7 * 3, dtype=np.uint8).reshape(5, 7, 3)                 # 105 bytes
+    c.put('img', img)
+    c.put('off', np.array([0, 3, 1 << 40], np.int64))
+    c.put('empty', np.zeros((0, 3), np.float32))
+    c.new('out8', 35), c.new('cnt', 16), c.new('D', 24)
+    assert c.g['img'].nbytes == 105 and c.g['empty'].nbytes == 0 and c.g['img'].ptr % 256 == 0
+    assert torch.equal(c.u8('img', 5, 7, 3), torch.from_numpy(img)) and int(c.i64('off')[2]) == 1 << 40
+    c.u8('out8', 5, 7).copy_(torch.arange(35, dtype=torch.uint8).view(5, 7))
+    c.i64('cnt').copy_(torch.tensor([7, -1]))
+    c.d('D').copy_(torch.tensor([0.5, float('inf'), float('nan')], dtype=torch.float64))
+    c.done()
+    eqb(c, 'out8', torch.arange(35, dtype=torch.uint8))
+    eqb(c, 'cnt', torch.tensor([7, -1]))
+    eqb(c, 'D', torch.tensor([0.5, float('inf'), float('nan')], dtype=torch.float64))          # bytes: a NaN equals itself
+    eqb(c, 'cnt', torch.tensor([7, -1, 9]), nbytes=16)                                         # (the first bytes of a longer one)
+    with pytest.raises(AssertionError, match='cnt'):
+        eqb(c, 'cnt', torch.tensor([7, 5]))
+    with pytest.raises(AssertionError, match='out8'):
+        eqb(c, 'out8', torch.arange(36, dtype=torch.uint8))                                   # another size
+    c.u8('img')[104] ^= 1                                                                     # the last byte of an input
+    with pytest.raises(AssertionError, match='input img was written'):
+        c.done()
+    c.u8('img')[104] ^= 1
+    c.g['out8'].bytes[c.g['out8'].start + 35] ^= 0xFF                                         # one byte behind an odd-sized output
+    with pytest.raises(gb.GuardViolation, match=r"out8: back guard written at byte \+0 "):
+        c.done()
