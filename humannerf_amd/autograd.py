@@ -29,30 +29,37 @@ def _head_grads(dY, width, dw):
     return gW, gb
 
 
+def _layer_grads(dw, dZ, acts, pe, npe, dY, weights, skip_layer, skip_order):
+    """The walk over the layers that _weight_grads and _weight_grads_h share: the head, layer 0 from the PE matrix (``npe``
+    real columns), the skip layer's two column blocks, the rest.  ``dw(dz, x, l, kind, **out)``: the dW operator of layer
+    l for the operand format; kind 'head' | 'pe' | 'h' names what x is."""
+    n_hidden = acts.shape[0]
+    gW, gb = [None] * (n_hidden + 1), [None] * (n_hidden + 1)
+    gW[n_hidden], gb[n_hidden] = _head_grads(dY, acts.shape[-1], lambda dy, **out: dw(dy, acts[n_hidden - 1], n_hidden, 'head', **out))
+    for l in range(n_hidden):
+        if l == 0:
+            gW[l], gb[l] = dw(dZ[l], pe, l, 'pe')
+        elif l == skip_layer:
+            gW[l] = torch.empty_like(weights[l])
+            pe_cols = gW[l][:, :npe] if skip_order == 'pe_first' else gW[l][:, -npe:]
+            h_cols = gW[l][:, npe:] if skip_order == 'pe_first' else gW[l][:, :-npe]
+            dw(dZ[l], pe, l, 'pe', dW_out=pe_cols, want_db=False)
+            _, gb[l] = dw(dZ[l], acts[l - 1], l, 'h', dW_out=h_cols)
+        else:
+            gW[l], gb[l] = dw(dZ[l], acts[l - 1], l, 'h')
+    return gW, gb
+
+
 def _weight_grads(dZ, acts, pe, dY, weights, skip_layer, skip_order, amax=None, mode='f32'):
     """dW / db of every layer from the chain kernel's dZ [L][P][W], the saved activations and PE matrix.
     dY: gradient at the (3- / 4-wide) head output, or [H][P][4] head-major planes of a multi-head canonical MLP.
     mode 'f16x3' (with amax from the chain kernel) runs the matrix-shaped layers on the split-f16 kernel; PE blocks
     and heads stay fp32."""
-    n_hidden = acts.shape[0]
-    npe = pe.shape[1]
-    gW, gb = [None] * (n_hidden + 1), [None] * (n_hidden + 1)
-    am = (lambda l: amax[l]) if amax is not None else (lambda l: None)
-    if amax is None:
-        mode = 'f32'
-    gW[n_hidden], gb[n_hidden] = _head_grads(dY, acts.shape[-1], lambda dy, **out: ops.mlp_dw(dy, acts[n_hidden - 1], **out))
-    for l in range(n_hidden):
-        if l == 0:
-            gW[l], gb[l] = ops.mlp_dw(dZ[l], pe)
-        elif l == skip_layer:
-            gW[l] = torch.empty_like(weights[l])
-            pe_cols = gW[l][:, :npe] if skip_order == 'pe_first' else gW[l][:, -npe:]
-            h_cols = gW[l][:, npe:] if skip_order == 'pe_first' else gW[l][:, :-npe]
-            ops.mlp_dw(dZ[l], pe, pe_cols, want_db=False)
-            _, gb[l] = ops.mlp_dw(dZ[l], acts[l - 1], h_cols, mode=mode, dz_amax=am(l))
-        else:
-            gW[l], gb[l] = ops.mlp_dw(dZ[l], acts[l - 1], mode=mode, dz_amax=am(l))
-    return gW, gb
+    def dw(dz, x, l, kind, **out):
+        if kind != 'h' or amax is None:
+            return ops.mlp_dw(dz, x, **out)
+        return ops.mlp_dw(dz, x, mode=mode, dz_amax=amax[l], **out)
+    return _layer_grads(dw, dZ, acts, pe, pe.shape[1], dY, weights, skip_layer, skip_order)
 
 
 def _weight_grads_h(dZ, scale, acts, pe, dY, weights, skip_layer, skip_order, npe):
@@ -60,23 +67,14 @@ def _weight_grads_h(dZ, scale, acts, pe, dY, weights, skip_layer, skip_order, np
     with ``scale`` [L], acts f16 -- both in the blocked layout the training kernels write -- pe row-major f16 [P][64]
     (``npe`` real columns), dY fp32 [P, 3|4] at the head output.  Every layer runs on hnrf_mlp_dw_h (transposed LDS reads,
     one f16 MFMA per product, fp32 accumulation)."""
-    n_hidden = acts.shape[0]
     P = dY.shape[-2]
-    gW, gb = [None] * (n_hidden + 1), [None] * (n_hidden + 1)
-    gW[n_hidden], gb[n_hidden] = _head_grads(dY, acts.shape[-1], lambda dy, **out: ops.mlp_dw_h(dy, acts[n_hidden - 1], P=P, x_blocked=True, **out))
-    for l in range(n_hidden):
-        sc = scale[l:l + 1]
-        if l == 0:
-            gW[l], gb[l] = ops.mlp_dw_h(dZ[l], pe, dz_scale=sc, n_in=npe, P=P, z_blocked=True)
-        elif l == skip_layer:
-            gW[l] = torch.empty_like(weights[l])
-            pe_cols = gW[l][:, :npe] if skip_order == 'pe_first' else gW[l][:, -npe:]
-            h_cols = gW[l][:, npe:] if skip_order == 'pe_first' else gW[l][:, :-npe]
-            ops.mlp_dw_h(dZ[l], pe, pe_cols, want_db=False, dz_scale=sc, n_in=npe, P=P, z_blocked=True)
-            _, gb[l] = ops.mlp_dw_h(dZ[l], acts[l - 1], h_cols, dz_scale=sc, P=P, z_blocked=True, x_blocked=True)
-        else:
-            gW[l], gb[l] = ops.mlp_dw_h(dZ[l], acts[l - 1], dz_scale=sc, P=P, z_blocked=True, x_blocked=True)
-    return gW, gb
+    def dw(dz, x, l, kind, **out):
+        if kind == 'head':
+            return ops.mlp_dw_h(dz, x, P=P, x_blocked=True, **out)
+        if kind == 'pe':
+            return ops.mlp_dw_h(dz, x, dz_scale=scale[l:l + 1], n_in=npe, P=P, z_blocked=True, **out)
+        return ops.mlp_dw_h(dz, x, dz_scale=scale[l:l + 1], P=P, z_blocked=True, x_blocked=True, **out)
+    return _layer_grads(dw, dZ, acts, pe, npe, dY, weights, skip_layer, skip_order)
 
 
 ACT_MIN, ACT_MAX = 2.0 ** -8, 60000.0

@@ -120,6 +120,12 @@ static inline int launch_lds(const char* what, dim3 grid, dim3 block, size_t lds
     hipLaunchKernelGGL(K, grid, block, lds, st, args...);
     return check_launch(what);
 }
+// A kernel instance as a value, for a generic lambda that states one launch's arguments once and is called with the
+// instance chosen at run time: launch_lds<decltype(k)::value>(...).
+template <auto K>
+struct Kernel {
+    static constexpr auto value = K;
+};
 
 // The N^3 lattice of hnrf_density_grid and hnrf_bake_canonical (hnrf_mesh.hip): positions of the lattice points
 // p0 .. p0 + cnt - 1 ([z][y][x], x fastest) -> xyz [cnt,3]; both walk it in chunks of kLatticeChunk points per
@@ -149,30 +155,22 @@ size_t canonical16_status_offset();
 size_t nonrigid16_status_offset();
 int canonical16_pack(const float* const* w, const float* const* b, void* packed, hipStream_t st, int n_heads = 1);
 int nonrigid16_pack(const float* const* w, const float* const* b, const float* cond, void* packed, hipStream_t st);
+// n_heads >= 2: the all-heads instances on a multi-head image, raw / d_raw [n_heads][P][4]
 int canonical16_fwd(const float* xyz, const void* packed, int64_t P, float* raw, const int* idx, const int* count,
-                    bool guard, hipStream_t st);
-int canonical16_heads_fwd(const float* xyz, const void* packed, int64_t P, int n_heads, float* raw, const int* idx,
-                          const int* count, bool guard, hipStream_t st);
+                    bool guard, hipStream_t st, int n_heads = 1);
 int canonical16_fwd_train(const float* xyz, const void* packed, int64_t P, float* raw, float* pe_out, float* acts,
-                          uint32_t* relu_bits, int half, hipStream_t st);
-int canonical16_heads_fwd_train(const float* xyz, const void* packed, int64_t P, int n_heads, float* raw, float* pe_out,
-                                float* acts, uint32_t* relu_bits, int half, hipStream_t st);
+                          uint32_t* relu_bits, int half, hipStream_t st, int n_heads = 1);
 int nonrigid16_fwd(const float* x_skel, const float* hann_w, const void* packed, int64_t P, float* xyz,
                    float* offsets, const int* idx, const int* count, bool guard, hipStream_t st);
 
 int nonrigid16_fwd_train(const float* x_skel, const float* hann_w, const void* packed, int64_t P, float* xyz,
                          float* offsets, float* pe_out, float* acts, uint32_t* relu_bits, int half, hipStream_t st);
 
-size_t canonical16_bwd_bytes();
-int canonical16_bwd_pack(const float* const* w, void* packed, hipStream_t st);
+size_t canonical16_bwd_bytes(int n_heads = 1);
+int canonical16_bwd_pack(const float* const* w, void* packed, hipStream_t st, int n_heads = 1);
 int canonical16_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed, int64_t P,
-                    const float* d_raw_amax, float* dZ, float* d_xyz, float* dz_amax, int half, hipStream_t st);
-
-size_t canonical16_heads_bwd_bytes();
-int canonical16_heads_bwd_pack(const float* const* w, int n_heads, void* packed, hipStream_t st);
-int canonical16_heads_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed, int64_t P,
-                          int n_heads, const float* d_raw_amax, float* dZ, float* d_xyz, float* dz_amax, int half,
-                          hipStream_t st);
+                    const float* d_raw_amax, float* dZ, float* d_xyz, float* dz_amax, int half, hipStream_t st,
+                    int n_heads = 1);
 
 size_t nonrigid16_bwd_bytes();
 int nonrigid16_bwd_pack(const float* const* w, void* packed, hipStream_t st);

@@ -474,88 +474,75 @@ extern "C" int hnrf_nonrigid_pack(const float* const* weights, const float* cons
     return launch_pack(d, cond, out, st);
 }
 
+// The forward entries, dense and sparse, for one head (heads = false, n_heads = 1) or all heads of a multi-head image
+static int canonical_fwd(const char* who, bool heads, const float* xyz, const void* packed, int mode, int64_t P, int n_heads,
+                         const int* idx, const int* count, float* raw, void* stream) {
+    const bool guard = !(mode & HNRF_MLP_NO_RANGE_GUARD);         // (HNRF_MLP_GUARD_ONE_CHUNK concerns hnrf_render_frame_fwd only)
+    mode &= HNRF_MLP_ARITH_MASK;
+    HNRF_REQUIRE(xyz && packed && raw, HNRF_E_ARG, "%s: null pointer", who);
+    HNRF_REQUIRE(!heads || (n_heads >= 2 && n_heads <= 8), HNRF_E_ARG, "%s: n_heads=%d outside 2..8", who, n_heads);
+    HNRF_REQUIRE((idx == nullptr) == (count == nullptr), HNRF_E_ARG, "%s: idx and count go together", who);
+    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3, HNRF_E_UNSUPPORTED, "%s: mode %d not built", who, mode);
+    HNRF_REQUIRE(P >= 0 && (P + 127) / 128 < 2147483647LL, HNRF_E_ARG, "%s: bad P=%lld", who, (long long)P);
+    HNRF_REQUIRE((((uintptr_t)packed | (uintptr_t)raw) & 15) == 0, HNRF_E_ARG, "%s: packed/raw must be 16-byte aligned", who);
+    if (P == 0) return HNRF_OK;
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == HNRF_MLP_F16X3) return canonical16_fwd(xyz, packed, P, raw, idx, count, guard, st, n_heads);
+    auto go = [&](auto k) {
+        hipLaunchKernelGGL(decltype(k)::value, dim3((unsigned)((P + 127) / 128)), dim3(256), 0, st, xyz, (const float*)packed, P,
+                           (float4*)raw, nullptr, nullptr, nullptr, idx, count, n_heads);
+    };
+    heads ? go(Kernel<canonical_f32_kernel<false, true>>{}) : go(Kernel<canonical_f32_kernel<false>>{});
+    return check_launch(who);
+}
+
 extern "C" int hnrf_canonical_fwd(const float* xyz, const void* packed, int mode, int64_t P, float* raw,
                                   void* stream) {
-    return hnrf_canonical_fwd_sparse(xyz, packed, mode, P, nullptr, nullptr, raw, stream);
+    return canonical_fwd("hnrf_canonical_fwd", false, xyz, packed, mode, P, 1, nullptr, nullptr, raw, stream);
 }
 extern "C" int hnrf_canonical_fwd_sparse(const float* xyz, const void* packed, int mode, int64_t P, const int* idx,
                                          const int* count, float* raw, void* stream) {
-    const bool guard = !(mode & HNRF_MLP_NO_RANGE_GUARD);         // (HNRF_MLP_GUARD_ONE_CHUNK concerns hnrf_render_frame_fwd only)
-    mode &= HNRF_MLP_ARITH_MASK;
-    HNRF_REQUIRE(xyz && packed && raw, HNRF_E_ARG, "hnrf_canonical_fwd: null pointer");
-    HNRF_REQUIRE((idx == nullptr) == (count == nullptr), HNRF_E_ARG, "hnrf_canonical_fwd: idx and count go together");
-    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3, HNRF_E_UNSUPPORTED,
-                 "hnrf_canonical_fwd: mode %d not built", mode);
-    HNRF_REQUIRE(P >= 0 && (P + 127) / 128 < 2147483647LL, HNRF_E_ARG, "hnrf_canonical_fwd: bad P=%lld", (long long)P);
-    HNRF_REQUIRE((((uintptr_t)packed | (uintptr_t)raw) & 15) == 0, HNRF_E_ARG,
-                 "hnrf_canonical_fwd: packed/raw must be 16-byte aligned");
-    if (P == 0) return HNRF_OK;
-    if (mode == HNRF_MLP_F16X3) return canonical16_fwd(xyz, packed, P, raw, idx, count, guard, (hipStream_t)stream);
-    hipLaunchKernelGGL(canonical_f32_kernel<false>, dim3((unsigned)((P + 127) / 128)), dim3(256), 0,
-                       (hipStream_t)stream, xyz, (const float*)packed, P, (float4*)raw, nullptr, nullptr, nullptr, idx, count, 1);
-    return check_launch("hnrf_canonical_fwd");
+    return canonical_fwd("hnrf_canonical_fwd", false, xyz, packed, mode, P, 1, idx, count, raw, stream);
 }
-
 extern "C" int hnrf_canonical_heads_fwd(const float* xyz, const void* packed, int mode, int64_t P, int n_heads, float* raw,
                                         void* stream) {
-    return hnrf_canonical_heads_fwd_sparse(xyz, packed, mode, P, n_heads, nullptr, nullptr, raw, stream);
+    return canonical_fwd("hnrf_canonical_heads_fwd", true, xyz, packed, mode, P, n_heads, nullptr, nullptr, raw, stream);
 }
 extern "C" int hnrf_canonical_heads_fwd_sparse(const float* xyz, const void* packed, int mode, int64_t P, int n_heads,
                                                const int* idx, const int* count, float* raw, void* stream) {
-    const bool guard = !(mode & HNRF_MLP_NO_RANGE_GUARD);
-    mode &= HNRF_MLP_ARITH_MASK;
-    HNRF_REQUIRE(xyz && packed && raw, HNRF_E_ARG, "hnrf_canonical_heads_fwd: null pointer");
-    HNRF_REQUIRE(n_heads >= 2 && n_heads <= 8, HNRF_E_ARG, "hnrf_canonical_heads_fwd: n_heads=%d outside 2..8", n_heads);
-    HNRF_REQUIRE((idx == nullptr) == (count == nullptr), HNRF_E_ARG, "hnrf_canonical_heads_fwd: idx and count go together");
-    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3, HNRF_E_UNSUPPORTED,
-                 "hnrf_canonical_heads_fwd: mode %d not built", mode);
-    HNRF_REQUIRE(P >= 0 && (P + 127) / 128 < 2147483647LL, HNRF_E_ARG, "hnrf_canonical_heads_fwd: bad P=%lld", (long long)P);
-    HNRF_REQUIRE((((uintptr_t)packed | (uintptr_t)raw) & 15) == 0, HNRF_E_ARG,
-                 "hnrf_canonical_heads_fwd: packed/raw must be 16-byte aligned");
+    return canonical_fwd("hnrf_canonical_heads_fwd", true, xyz, packed, mode, P, n_heads, idx, count, raw, stream);
+}
+
+// The activation-saving forward of the training step, in the same two forms
+static int canonical_fwd_train(const char* who, bool heads, const float* xyz, const void* packed, int mode, int64_t P,
+                               int n_heads, float* raw, float* pe_out, float* acts, uint32_t* relu_bits, void* stream) {
+    HNRF_REQUIRE(xyz && packed && raw && pe_out && acts && relu_bits, HNRF_E_ARG, "%s: null pointer", who);
+    HNRF_REQUIRE(!heads || (n_heads >= 2 && n_heads <= 8), HNRF_E_ARG, "%s: n_heads=%d outside 2..8", who, n_heads);
+    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3 || mode == HNRF_MLP_F16X3_H, HNRF_E_UNSUPPORTED,
+                 "%s: mode %d not built", who, mode);
+    HNRF_REQUIRE(P >= 0 && (P + 127) / 128 < 2147483647LL, HNRF_E_ARG, "%s: bad P", who);
+    HNRF_REQUIRE((((uintptr_t)packed | (uintptr_t)raw | (uintptr_t)acts) & 15) == 0, HNRF_E_ARG,
+                 "%s: packed/raw/acts must be 16-byte aligned", who);
     if (P == 0) return HNRF_OK;
-    if (mode == HNRF_MLP_F16X3)
-        return canonical16_heads_fwd(xyz, packed, P, n_heads, raw, idx, count, guard, (hipStream_t)stream);
-    hipLaunchKernelGGL((canonical_f32_kernel<false, true>), dim3((unsigned)((P + 127) / 128)), dim3(256), 0,
-                       (hipStream_t)stream, xyz, (const float*)packed, P, (float4*)raw, nullptr, nullptr, nullptr, idx, count,
-                       n_heads);
-    return check_launch("hnrf_canonical_heads_fwd");
+    hipStream_t st = (hipStream_t)stream;
+    if (mode != HNRF_MLP_F32)
+        return canonical16_fwd_train(xyz, packed, P, raw, pe_out, acts, relu_bits, mode == HNRF_MLP_F16X3_H, st, n_heads);
+    auto go = [&](auto k) {
+        hipLaunchKernelGGL(decltype(k)::value, dim3((unsigned)((P + 127) / 128)), dim3(256), 0, st, xyz, (const float*)packed, P,
+                           (float4*)raw, pe_out, acts, relu_bits, nullptr, nullptr, n_heads);
+    };
+    heads ? go(Kernel<canonical_f32_kernel<true, true>>{}) : go(Kernel<canonical_f32_kernel<true>>{});
+    return check_launch(who);
 }
 
 extern "C" int hnrf_canonical_fwd_train(const float* xyz, const void* packed, int mode, int64_t P, float* raw,
                                         float* pe_out, float* acts, uint32_t* relu_bits, void* stream) {
-    HNRF_REQUIRE(xyz && packed && raw && pe_out && acts && relu_bits, HNRF_E_ARG,
-                 "hnrf_canonical_fwd_train: null pointer");
-    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3 || mode == HNRF_MLP_F16X3_H, HNRF_E_UNSUPPORTED,
-                 "hnrf_canonical_fwd_train: mode %d not built", mode);
-    HNRF_REQUIRE(P >= 0 && (P + 127) / 128 < 2147483647LL, HNRF_E_ARG, "hnrf_canonical_fwd_train: bad P");
-    HNRF_REQUIRE((((uintptr_t)packed | (uintptr_t)raw | (uintptr_t)acts) & 15) == 0, HNRF_E_ARG,
-                 "hnrf_canonical_fwd_train: packed/raw/acts must be 16-byte aligned");
-    if (P == 0) return HNRF_OK;
-    if (mode != HNRF_MLP_F32)
-        return canonical16_fwd_train(xyz, packed, P, raw, pe_out, acts, relu_bits, mode == HNRF_MLP_F16X3_H, (hipStream_t)stream);
-    hipLaunchKernelGGL(canonical_f32_kernel<true>, dim3((unsigned)((P + 127) / 128)), dim3(256), 0,
-                       (hipStream_t)stream, xyz, (const float*)packed, P, (float4*)raw, pe_out, acts, relu_bits, nullptr, nullptr, 1);
-    return check_launch("hnrf_canonical_fwd_train");
+    return canonical_fwd_train("hnrf_canonical_fwd_train", false, xyz, packed, mode, P, 1, raw, pe_out, acts, relu_bits, stream);
 }
-
 extern "C" int hnrf_canonical_heads_fwd_train(const float* xyz, const void* packed, int mode, int64_t P, int n_heads,
                                               float* raw, float* pe_out, float* acts, uint32_t* relu_bits, void* stream) {
-    HNRF_REQUIRE(xyz && packed && raw && pe_out && acts && relu_bits, HNRF_E_ARG,
-                 "hnrf_canonical_heads_fwd_train: null pointer");
-    HNRF_REQUIRE(n_heads >= 2 && n_heads <= 8, HNRF_E_ARG, "hnrf_canonical_heads_fwd_train: n_heads=%d outside 2..8", n_heads);
-    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3 || mode == HNRF_MLP_F16X3_H, HNRF_E_UNSUPPORTED,
-                 "hnrf_canonical_heads_fwd_train: mode %d not built", mode);
-    HNRF_REQUIRE(P >= 0 && (P + 127) / 128 < 2147483647LL, HNRF_E_ARG, "hnrf_canonical_heads_fwd_train: bad P");
-    HNRF_REQUIRE((((uintptr_t)packed | (uintptr_t)raw | (uintptr_t)acts) & 15) == 0, HNRF_E_ARG,
-                 "hnrf_canonical_heads_fwd_train: packed/raw/acts must be 16-byte aligned");
-    if (P == 0) return HNRF_OK;
-    if (mode != HNRF_MLP_F32)
-        return canonical16_heads_fwd_train(xyz, packed, P, n_heads, raw, pe_out, acts, relu_bits, mode == HNRF_MLP_F16X3_H,
-                                           (hipStream_t)stream);
-    hipLaunchKernelGGL((canonical_f32_kernel<true, true>), dim3((unsigned)((P + 127) / 128)), dim3(256), 0,
-                       (hipStream_t)stream, xyz, (const float*)packed, P, (float4*)raw, pe_out, acts, relu_bits, nullptr, nullptr,
-                       n_heads);
-    return check_launch("hnrf_canonical_heads_fwd_train");
+    return canonical_fwd_train("hnrf_canonical_heads_fwd_train", true, xyz, packed, mode, P, n_heads, raw, pe_out, acts,
+                               relu_bits, stream);
 }
 
 extern "C" int hnrf_nonrigid_fwd(const float* x_skel, const float* hann_w, const void* packed, int mode, int64_t P,

@@ -1349,29 +1349,41 @@ extern "C" int hnrf_mlp_dw_h(const void* dZ, int64_t ldz, const void* X, int64_t
     return check_launch("hnrf_mlp_dw_h (reduce)");
 }
 
-extern "C" size_t hnrf_canonical_bwd_packed_bytes(int mode) {
-    if (mode == HNRF_MLP_F16X3) return canonical16_bwd_bytes();
-    return mode == HNRF_MLP_F32 ? (size_t)CB_FLOATS * sizeof(float) : 0;
+// The canonical backward image for one head (heads = false, n_heads = 1) or all heads (hnrf_heads_train.h): the head
+// stage contracts 4 n_heads outputs, and the blocks behind it lie CBH_SHIFT floats further
+static size_t canonical_bwd_packed_bytes(int mode, int n_heads) {
+    if (mode == HNRF_MLP_F16X3) return canonical16_bwd_bytes(n_heads);
+    return mode == HNRF_MLP_F32 ? (size_t)(CB_FLOATS + (n_heads > 1 ? CBH_SHIFT : 0)) * sizeof(float) : 0;
+}
+extern "C" size_t hnrf_canonical_bwd_packed_bytes(int mode) { return canonical_bwd_packed_bytes(mode, 1); }
+extern "C" size_t hnrf_canonical_heads_bwd_packed_bytes(int mode, int n_heads) {
+    return n_heads < 2 || n_heads > 8 ? 0 : canonical_bwd_packed_bytes(mode, n_heads);
 }
 extern "C" size_t hnrf_nonrigid_bwd_packed_bytes(int mode) {
     if (mode == HNRF_MLP_F16X3) return nonrigid16_bwd_bytes();
     return mode == HNRF_MLP_F32 ? (size_t)NB_FLOATS * sizeof(float) : 0;
 }
 
-extern "C" int hnrf_canonical_bwd_pack(const float* const* weights, int mode, void* packed, void* stream) {
-    HNRF_REQUIRE(weights && packed, HNRF_E_ARG, "hnrf_canonical_bwd_pack: null pointer");
-    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3, HNRF_E_UNSUPPORTED,
-                 "hnrf_canonical_bwd_pack: mode %d not built", mode);
-    for (int i = 0; i < 9; ++i) HNRF_REQUIRE(weights[i], HNRF_E_ARG, "hnrf_canonical_bwd_pack: null layer %d", i);
+static int canonical_bwd_pack(const char* who, bool heads, const float* const* weights, int n_heads, int mode, void* packed,
+                              void* stream) {
+    HNRF_REQUIRE(weights && packed, HNRF_E_ARG, "%s: null pointer", who);
+    HNRF_REQUIRE(!heads || (n_heads >= 2 && n_heads <= 8), HNRF_E_ARG, "%s: n_heads=%d outside 2..8", who, n_heads);
+    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3, HNRF_E_UNSUPPORTED, "%s: mode %d not built", who, mode);
+    for (int i = 0; i < 9; ++i) HNRF_REQUIRE(weights[i], HNRF_E_ARG, "%s: null layer %d", who, i);
+    HNRF_REQUIRE(!heads || ((uintptr_t)packed & 15) == 0, HNRF_E_ARG, "%s: packed must be 16-byte aligned", who);
     hipStream_t st = (hipStream_t)stream;
-    if (mode == HNRF_MLP_F16X3) return canonical16_bwd_pack(weights, packed, st);
+    if (mode == HNRF_MLP_F16X3) return canonical16_bwd_pack(weights, packed, st, n_heads);
     float* out = (float*)packed;
-    if (hipMemsetAsync(out + CB_END, 0, PF * 256 * sizeof(float), st) != hipSuccess) {
-        set_error("hnrf_canonical_bwd_pack: memset failed");
+    const int64_t sh = heads ? CBH_SHIFT : 0;
+    if (hipMemsetAsync(out + sh + CB_END, 0, PF * 256 * sizeof(float), st) != hipSuccess) {
+        set_error("%s: memset failed", who);
         return HNRF_E_LAUNCH;
     }
     int rc;
-    if ((rc = launch_pack_bwd(PackBwd{weights[8], 4, 256, 8, 1, PE_NONE, 0, 1, CB_HEAD}, out, st))) return rc;
+    // the head record: 4 k-steps of kind 2 for all heads, 1 of kind 1 for one; it alone stays in front of the shift
+    if ((rc = launch_pack_bwd(PackBwd{weights[8], 4 * n_heads, 256, 8, heads ? 4 : 1, PE_NONE, 0, heads ? 2 : 1, CB_HEAD}, out, st)))
+        return rc;
+    out += sh;
     for (int l = 7; l >= 6; --l)
         if ((rc = launch_pack_bwd(PackBwd{weights[l], 256, 256, 8, 32, PE_NONE, 0, 0, CB_L7 + (7 - l) * CB_MID}, out, st)))
             return rc;
@@ -1381,6 +1393,14 @@ extern "C" int hnrf_canonical_bwd_pack(const float* const* weights, int mode, vo
         if ((rc = launch_pack_bwd(PackBwd{weights[l], 256, 256, 8, 32, PE_NONE, 0, 0, CB_L4 + (4 - l) * CB_MID}, out, st)))
             return rc;
     return launch_pack_bwd(PackBwd{weights[0], 256, 63, 2, 32, PE_CANONICAL, 0, 0, CB_L0P}, out, st);
+}
+
+extern "C" int hnrf_canonical_bwd_pack(const float* const* weights, int mode, void* packed, void* stream) {
+    return canonical_bwd_pack("hnrf_canonical_bwd_pack", false, weights, 1, mode, packed, stream);
+}
+extern "C" int hnrf_canonical_heads_bwd_pack(const float* const* weights, int n_heads, int mode, void* packed,
+                                             void* stream) {
+    return canonical_bwd_pack("hnrf_canonical_heads_bwd_pack", true, weights, n_heads, mode, packed, stream);
 }
 
 extern "C" int hnrf_nonrigid_bwd_pack(const float* const* weights, int mode, void* packed, void* stream) {
@@ -1422,93 +1442,49 @@ static int init_dz_amax(float* dz_amax, int layers, const float* amax_in, hipStr
     return check_launch(what);
 }
 
+// The backward chain in the same two forms: d_raw [P,4], or [n_heads][P][4] on the all-heads image
+static int canonical_bwd(const char* who, bool heads, const float* xyz, const float* d_raw, const uint32_t* relu_bits,
+                         const void* packed, int mode, const float* d_raw_amax, int64_t P, int n_heads, float* dZ, float* d_xyz,
+                         float* dz_amax, void* stream) {
+    HNRF_REQUIRE(xyz && d_raw && relu_bits && packed && dZ && d_xyz, HNRF_E_ARG, "%s: null pointer", who);
+    HNRF_REQUIRE(!heads || (n_heads >= 2 && n_heads <= 8), HNRF_E_ARG, "%s: n_heads=%d outside 2..8", who, n_heads);
+    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3 || mode == HNRF_MLP_F16X3_H, HNRF_E_UNSUPPORTED,
+                 "%s: mode %d not built", who, mode);
+    HNRF_REQUIRE(mode == HNRF_MLP_F32 || d_raw_amax, HNRF_E_ARG,
+                 "%s: HNRF_MLP_F16X3 needs d_raw_amax (device scalar >= max |d_raw|%s)", who, heads ? " over all planes" : "");
+    HNRF_REQUIRE(mode != HNRF_MLP_F16X3_H || dz_amax, HNRF_E_ARG, "%s: HNRF_MLP_F16X3_H needs dz_amax ([8] scales out)", who);
+    HNRF_REQUIRE(P >= 0, HNRF_E_ARG, "%s: bad P", who);
+    HNRF_REQUIRE((((uintptr_t)d_raw | (uintptr_t)relu_bits | (uintptr_t)dZ | (uintptr_t)packed) & 15) == 0, HNRF_E_ARG,
+                 "%s: d_raw, relu_bits, dZ, packed must be 16-byte aligned", who);
+    if (P == 0) return HNRF_OK;
+    const int64_t blocks = (P + 127) / 128;
+    HNRF_REQUIRE(blocks < 2147483647LL, HNRF_E_ARG, "%s: too many samples", who);
+    hipStream_t st = (hipStream_t)stream;
+    if (mode == HNRF_MLP_F16X3_H) return canonical16_bwd(xyz, d_raw, relu_bits, packed, P, d_raw_amax, dZ, d_xyz, dz_amax, 1, st, n_heads);
+    if (dz_amax)
+        if (int rc = init_dz_amax(dz_amax, 8, mode == HNRF_MLP_F16X3 ? d_raw_amax : nullptr, st,
+                                  heads ? "hnrf_canonical_heads_bwd (maxima)" : "hnrf_canonical_bwd (maxima)"))
+            return rc;
+    if (mode == HNRF_MLP_F16X3) return canonical16_bwd(xyz, d_raw, relu_bits, packed, P, d_raw_amax, dZ, d_xyz, dz_amax, 0, st, n_heads);
+    auto go = [&](auto k) {
+        hipLaunchKernelGGL(decltype(k)::value, dim3((unsigned)blocks), dim3(256), 0, st, xyz, (const float4*)d_raw, relu_bits,
+                           (const float*)packed, P, dZ, d_xyz, dz_amax, n_heads);
+    };
+    heads ? go(Kernel<canonical_bwd_kernel<true>>{}) : go(Kernel<canonical_bwd_kernel<false>>{});
+    return check_launch(who);
+}
+
 extern "C" int hnrf_canonical_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed,
                                   int mode, const float* d_raw_amax, int64_t P, float* dZ, float* d_xyz,
                                   float* dz_amax, void* stream) {
-    HNRF_REQUIRE(xyz && d_raw && relu_bits && packed && dZ && d_xyz, HNRF_E_ARG, "hnrf_canonical_bwd: null pointer");
-    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3 || mode == HNRF_MLP_F16X3_H, HNRF_E_UNSUPPORTED,
-                 "hnrf_canonical_bwd: mode %d not built", mode);
-    HNRF_REQUIRE(mode == HNRF_MLP_F32 || d_raw_amax, HNRF_E_ARG,
-                 "hnrf_canonical_bwd: HNRF_MLP_F16X3 needs d_raw_amax (device scalar >= max |d_raw|)");
-    HNRF_REQUIRE(mode != HNRF_MLP_F16X3_H || dz_amax, HNRF_E_ARG, "hnrf_canonical_bwd: HNRF_MLP_F16X3_H needs dz_amax ([8] scales out)");
-    HNRF_REQUIRE(P >= 0, HNRF_E_ARG, "hnrf_canonical_bwd: bad P");
-    HNRF_REQUIRE((((uintptr_t)d_raw | (uintptr_t)relu_bits | (uintptr_t)dZ | (uintptr_t)packed) & 15) == 0, HNRF_E_ARG,
-                 "hnrf_canonical_bwd: d_raw, relu_bits, dZ, packed must be 16-byte aligned");
-    if (P == 0) return HNRF_OK;
-    const int64_t blocks = (P + 127) / 128;
-    HNRF_REQUIRE(blocks < 2147483647LL, HNRF_E_ARG, "hnrf_canonical_bwd: too many samples");
-    if (mode == HNRF_MLP_F16X3_H)
-        return canonical16_bwd(xyz, d_raw, relu_bits, packed, P, d_raw_amax, dZ, d_xyz, dz_amax, 1, (hipStream_t)stream);
-    if (dz_amax)
-        if (int rc = init_dz_amax(dz_amax, 8, mode == HNRF_MLP_F16X3 ? d_raw_amax : nullptr, (hipStream_t)stream, "hnrf_canonical_bwd (maxima)")) return rc;
-    if (mode == HNRF_MLP_F16X3)
-        return canonical16_bwd(xyz, d_raw, relu_bits, packed, P, d_raw_amax, dZ, d_xyz, dz_amax, 0, (hipStream_t)stream);
-    hipLaunchKernelGGL(canonical_bwd_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, xyz,
-                       (const float4*)d_raw, relu_bits, (const float*)packed, P, dZ, d_xyz, dz_amax, 1);
-    return check_launch("hnrf_canonical_bwd");
+    return canonical_bwd("hnrf_canonical_bwd", false, xyz, d_raw, relu_bits, packed, mode, d_raw_amax, P, 1, dZ, d_xyz, dz_amax,
+                         stream);
 }
-
-// ---- all heads (hnrf_heads_train.h)
-extern "C" size_t hnrf_canonical_heads_bwd_packed_bytes(int mode, int n_heads) {
-    if (n_heads < 2 || n_heads > 8) return 0;
-    if (mode == HNRF_MLP_F16X3) return canonical16_heads_bwd_bytes();
-    return mode == HNRF_MLP_F32 ? (size_t)(CB_FLOATS + CBH_SHIFT) * sizeof(float) : 0;
-}
-
-extern "C" int hnrf_canonical_heads_bwd_pack(const float* const* weights, int n_heads, int mode, void* packed,
-                                             void* stream) {
-    HNRF_REQUIRE(weights && packed, HNRF_E_ARG, "hnrf_canonical_heads_bwd_pack: null pointer");
-    HNRF_REQUIRE(n_heads >= 2 && n_heads <= 8, HNRF_E_ARG, "hnrf_canonical_heads_bwd_pack: n_heads=%d outside 2..8", n_heads);
-    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3, HNRF_E_UNSUPPORTED,
-                 "hnrf_canonical_heads_bwd_pack: mode %d not built", mode);
-    for (int i = 0; i < 9; ++i) HNRF_REQUIRE(weights[i], HNRF_E_ARG, "hnrf_canonical_heads_bwd_pack: null layer %d", i);
-    HNRF_REQUIRE(((uintptr_t)packed & 15) == 0, HNRF_E_ARG, "hnrf_canonical_heads_bwd_pack: packed must be 16-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    if (mode == HNRF_MLP_F16X3) return canonical16_heads_bwd_pack(weights, n_heads, packed, st);
-    float* out = (float*)packed;
-    if (hipMemsetAsync(out + CBH_SHIFT + CB_END, 0, PF * 256 * sizeof(float), st) != hipSuccess) {
-        set_error("hnrf_canonical_heads_bwd_pack: memset failed");
-        return HNRF_E_LAUNCH;
-    }
-    int rc;
-    if ((rc = launch_pack_bwd(PackBwd{weights[8], 4 * n_heads, 256, 8, 4, PE_NONE, 0, 2, CB_HEAD}, out, st))) return rc;
-    out += CBH_SHIFT;
-    for (int l = 7; l >= 6; --l)
-        if ((rc = launch_pack_bwd(PackBwd{weights[l], 256, 256, 8, 32, PE_NONE, 0, 0, CB_L7 + (7 - l) * CB_MID}, out, st)))
-            return rc;
-    if ((rc = launch_pack_bwd(PackBwd{weights[5], 256, 319, 8, 32, PE_NONE, 63, 0, CB_L5H}, out, st))) return rc;
-    if ((rc = launch_pack_bwd(PackBwd{weights[5], 256, 319, 2, 32, PE_CANONICAL, 0, 0, CB_L5P}, out, st))) return rc;
-    for (int l = 4; l >= 1; --l)
-        if ((rc = launch_pack_bwd(PackBwd{weights[l], 256, 256, 8, 32, PE_NONE, 0, 0, CB_L4 + (4 - l) * CB_MID}, out, st)))
-            return rc;
-    return launch_pack_bwd(PackBwd{weights[0], 256, 63, 2, 32, PE_CANONICAL, 0, 0, CB_L0P}, out, st);
-}
-
 extern "C" int hnrf_canonical_heads_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed,
                                         int mode, const float* d_raw_amax, int64_t P, int n_heads, float* dZ, float* d_xyz,
                                         float* dz_amax, void* stream) {
-    HNRF_REQUIRE(xyz && d_raw && relu_bits && packed && dZ && d_xyz, HNRF_E_ARG, "hnrf_canonical_heads_bwd: null pointer");
-    HNRF_REQUIRE(n_heads >= 2 && n_heads <= 8, HNRF_E_ARG, "hnrf_canonical_heads_bwd: n_heads=%d outside 2..8", n_heads);
-    HNRF_REQUIRE(mode == HNRF_MLP_F32 || mode == HNRF_MLP_F16X3 || mode == HNRF_MLP_F16X3_H, HNRF_E_UNSUPPORTED,
-                 "hnrf_canonical_heads_bwd: mode %d not built", mode);
-    HNRF_REQUIRE(mode == HNRF_MLP_F32 || d_raw_amax, HNRF_E_ARG,
-                 "hnrf_canonical_heads_bwd: HNRF_MLP_F16X3 needs d_raw_amax (device scalar >= max |d_raw| over all planes)");
-    HNRF_REQUIRE(mode != HNRF_MLP_F16X3_H || dz_amax, HNRF_E_ARG, "hnrf_canonical_heads_bwd: HNRF_MLP_F16X3_H needs dz_amax ([8] scales out)");
-    HNRF_REQUIRE(P >= 0, HNRF_E_ARG, "hnrf_canonical_heads_bwd: bad P");
-    HNRF_REQUIRE((((uintptr_t)d_raw | (uintptr_t)relu_bits | (uintptr_t)dZ | (uintptr_t)packed) & 15) == 0, HNRF_E_ARG,
-                 "hnrf_canonical_heads_bwd: d_raw, relu_bits, dZ, packed must be 16-byte aligned");
-    if (P == 0) return HNRF_OK;
-    const int64_t blocks = (P + 127) / 128;
-    HNRF_REQUIRE(blocks < 2147483647LL, HNRF_E_ARG, "hnrf_canonical_heads_bwd: too many samples");
-    if (mode == HNRF_MLP_F16X3_H)
-        return canonical16_heads_bwd(xyz, d_raw, relu_bits, packed, P, n_heads, d_raw_amax, dZ, d_xyz, dz_amax, 1, (hipStream_t)stream);
-    if (dz_amax)
-        if (int rc = init_dz_amax(dz_amax, 8, mode == HNRF_MLP_F16X3 ? d_raw_amax : nullptr, (hipStream_t)stream, "hnrf_canonical_heads_bwd (maxima)")) return rc;
-    if (mode == HNRF_MLP_F16X3)
-        return canonical16_heads_bwd(xyz, d_raw, relu_bits, packed, P, n_heads, d_raw_amax, dZ, d_xyz, dz_amax, 0, (hipStream_t)stream);
-    hipLaunchKernelGGL(canonical_bwd_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, xyz,
-                       (const float4*)d_raw, relu_bits, (const float*)packed, P, dZ, d_xyz, dz_amax, n_heads);
-    return check_launch("hnrf_canonical_heads_bwd");
+    return canonical_bwd("hnrf_canonical_heads_bwd", true, xyz, d_raw, relu_bits, packed, mode, d_raw_amax, P, n_heads, dZ, d_xyz,
+                         dz_amax, stream);
 }
 
 extern "C" int hnrf_nonrigid_bwd(const float* x_skel, const float* hann_w, const float* d_xyz,

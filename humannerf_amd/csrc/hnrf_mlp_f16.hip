@@ -1285,7 +1285,7 @@ constexpr int64_t CB16_L5P = CB16_L7 + 3 * CB16_FULL;
 constexpr int64_t CB16_L4 = CB16_L5P + CB16_PE;
 constexpr int64_t CB16_L0P = CB16_L4 + 4 * CB16_FULL;
 constexpr int64_t CB16_BYTES = CB16_L0P + CB16_PE;            // followed by float amax[9] (layer_amax_kernel), 256 bytes
-// all-heads image (canonical16_heads_bwd_pack): the head stage has K = 4 H <= 32 = TWO k-steps (8 tiles x 4 blocks, for
+// all-heads image (canonical16_bwd_pack, n_heads >= 2): the head stage has K = 4 H <= 32 = TWO k-steps (8 tiles x 4 blocks, for
 // every H: the second k-step of H <= 4 is zeros, 24 of the chain's 6 528 MFMAs per wave, and the head slab is then a
 // 32-block slab like every other); everything behind it is the single-head image moved by 16 KiB
 constexpr int64_t CB16H_SHIFT = 16 * KB;
@@ -1300,7 +1300,7 @@ __device__ __forceinline__ void chain_amax(SaveCtx& sc, float* __restrict__ slot
 
 // HALF: dZ is an f16 matrix holding the chain's SCALED values (dz_scale[l] = the power of two dZ_l was multiplied by, for
 // hnrf_mlp_dw_h); otherwise fp32, un-scaled, with the per-layer maxima in dz_amax.
-// HEADS (hnrf_canonical_heads_bwd, image of canonical16_heads_bwd_pack): d_raw is n_heads planes [n_heads][P][4], the head
+// HEADS (hnrf_canonical_heads_bwd, image of canonical16_bwd_pack with n_heads): d_raw is n_heads planes [n_heads][P][4], the head
 // stage contracts all of them (two k-steps from the stash); d_raw_amax bounds every plane.
 template <bool HALF, bool HEADS = false>
 __global__ __launch_bounds__(256) void canonical_bwd16_kernel(const float* __restrict__ xyz,
@@ -1616,58 +1616,35 @@ int nonrigid16_pack(const float* const* w, const float* const* b, const float* c
     return launch_pack16(d, 7, cond, out, st);
 }
 
+// The canonical launchers take n_heads: 1 launches the single-head instance (HEADS off, kernel argument 1), >= 2 the
+// all-heads instance on a multi-head image (raw / d_raw [n_heads][P][4]).  `what` names the entry the call came from.
 int canonical16_fwd(const float* xyz, const void* packed, int64_t P, float* raw, const int* idx, const int* count,
-                    bool guard, hipStream_t st) {
+                    bool guard, hipStream_t st, int n_heads) {
     constexpr int lds = CNL16_BIAS_LDS + PE_STASH + RING * CNL16_SLAB;
     const dim3 grid((unsigned)((P + 127) / 128));
-    const char* what = "hnrf_canonical_fwd (f16x3)";
-    if (guard)
-        return launch_lds<canonical_f16x3_kernel<SV_NONE, true>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
-                                                                 (float4*)raw, idx, count, nullptr, nullptr, nullptr, 1);
-    return launch_lds<canonical_f16x3_kernel<SV_NONE, false>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
-                                                              (float4*)raw, idx, count, nullptr, nullptr, nullptr, 1);
+    const bool heads = n_heads > 1;
+    const char* what = heads ? "hnrf_canonical_heads_fwd (f16x3)" : "hnrf_canonical_fwd (f16x3)";
+    auto go = [&](auto k) {
+        return launch_lds<decltype(k)::value>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P, (float4*)raw, idx,
+                                              count, nullptr, nullptr, nullptr, n_heads);
+    };
+    if (heads) return guard ? go(Kernel<canonical_f16x3_kernel<SV_NONE, true, true>>{}) : go(Kernel<canonical_f16x3_kernel<SV_NONE, false, true>>{});
+    return guard ? go(Kernel<canonical_f16x3_kernel<SV_NONE, true>>{}) : go(Kernel<canonical_f16x3_kernel<SV_NONE, false>>{});
 }
 
-// all heads of a multi-head image: raw [n_heads][P][4]
-int canonical16_heads_fwd(const float* xyz, const void* packed, int64_t P, int n_heads, float* raw, const int* idx,
-                          const int* count, bool guard, hipStream_t st) {
-    constexpr int lds = CNL16_BIAS_LDS + PE_STASH + RING * CNL16_SLAB;
-    const dim3 grid((unsigned)((P + 127) / 128));
-    const char* what = "hnrf_canonical_heads_fwd (f16x3)";
-    if (guard)
-        return launch_lds<canonical_f16x3_kernel<SV_NONE, true, true>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed,
-                                                                       P, (float4*)raw, idx, count, nullptr, nullptr, nullptr,
-                                                                       n_heads);
-    return launch_lds<canonical_f16x3_kernel<SV_NONE, false, true>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
-                                                                    (float4*)raw, idx, count, nullptr, nullptr, nullptr,
-                                                                    n_heads);
-}
-
+// (what SAVE writes does not depend on the heads)
 int canonical16_fwd_train(const float* xyz, const void* packed, int64_t P, float* raw, float* pe_out, float* acts,
-                          uint32_t* relu_bits, int half, hipStream_t st) {
+                          uint32_t* relu_bits, int half, hipStream_t st, int n_heads) {
     constexpr int lds = CNL16_BIAS_LDS + PE_STASH + RING * CNL16_SLAB;
     const dim3 grid((unsigned)((P + 127) / 128));
-    const char* what = "hnrf_canonical_fwd_train (f16x3)";
-    if (half)
-        return launch_lds<canonical_f16x3_kernel<SV_ACT_H>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
-                                                            (float4*)raw, nullptr, nullptr, pe_out, acts, relu_bits, 1);
-    return launch_lds<canonical_f16x3_kernel<SV_ACT>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P, (float4*)raw,
-                                                      nullptr, nullptr, pe_out, acts, relu_bits, 1);
-}
-
-// all heads on the activation-saving instances: what SAVE writes does not depend on the heads
-int canonical16_heads_fwd_train(const float* xyz, const void* packed, int64_t P, int n_heads, float* raw, float* pe_out,
-                                float* acts, uint32_t* relu_bits, int half, hipStream_t st) {
-    constexpr int lds = CNL16_BIAS_LDS + PE_STASH + RING * CNL16_SLAB;
-    const dim3 grid((unsigned)((P + 127) / 128));
-    const char* what = "hnrf_canonical_heads_fwd_train (f16x3)";
-    if (half)
-        return launch_lds<canonical_f16x3_kernel<SV_ACT_H, false, true>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed,
-                                                                         P, (float4*)raw, nullptr, nullptr, pe_out, acts,
-                                                                         relu_bits, n_heads);
-    return launch_lds<canonical_f16x3_kernel<SV_ACT, false, true>>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P,
-                                                                   (float4*)raw, nullptr, nullptr, pe_out, acts, relu_bits,
-                                                                   n_heads);
+    const bool heads = n_heads > 1;
+    const char* what = heads ? "hnrf_canonical_heads_fwd_train (f16x3)" : "hnrf_canonical_fwd_train (f16x3)";
+    auto go = [&](auto k) {
+        return launch_lds<decltype(k)::value>(what, grid, dim3(256), lds, st, xyz, (const char*)packed, P, (float4*)raw, nullptr,
+                                              nullptr, pe_out, acts, relu_bits, n_heads);
+    };
+    if (heads) return half ? go(Kernel<canonical_f16x3_kernel<SV_ACT_H, false, true>>{}) : go(Kernel<canonical_f16x3_kernel<SV_ACT, false, true>>{});
+    return half ? go(Kernel<canonical_f16x3_kernel<SV_ACT_H>>{}) : go(Kernel<canonical_f16x3_kernel<SV_ACT>>{});
 }
 
 int nonrigid16_fwd(const float* x_skel, const float* hann_w, const void* packed, int64_t P, float* xyz,
@@ -1702,7 +1679,9 @@ int nonrigid16_fwd_train(const float* x_skel, const float* hann_w, const void* p
                                                      offsets, nullptr, nullptr, pe_out, acts, relu_bits);
 }
 
-size_t canonical16_bwd_bytes() { return (size_t)CB16_BYTES + 256; }
+// all heads: the transposed image whose head stage contracts 4 n_heads outputs; its full blocks lie CB16H_SHIFT further
+static int64_t cb16_shift(int n_heads) { return n_heads > 1 ? CB16H_SHIFT : 0; }
+size_t canonical16_bwd_bytes(int n_heads) { return (size_t)(CB16_BYTES + cb16_shift(n_heads)) + 256; }
 
 static int launch_layer_amax(const float* const* w, const int* n, int count, float* out, hipStream_t st) {
     LayerSet ls;
@@ -1728,42 +1707,11 @@ static int launch_pack_bwd16(const PackBwd16* ds, int count, char* out, hipStrea
     return check_launch("hnrf pack (backward, f16x3)");
 }
 
-int canonical16_bwd_pack(const float* const* w, void* packed, hipStream_t st) {
+int canonical16_bwd_pack(const float* const* w, void* packed, hipStream_t st, int n_heads) {
     char* out = (char*)packed;
-    float* kexp = reinterpret_cast<float*>(out + CB16_BYTES);
-    const int sizes[9] = {256 * 63, 256 * 256, 256 * 256, 256 * 256, 256 * 256, 256 * 319, 256 * 256, 256 * 256, 4 * 256};
-    int rc;
-    if ((rc = launch_layer_amax(w, sizes, 9, kexp, st))) return rc;
-    PackBwd16 d[10];
-    int n = 0;
-    d[n++] = PackBwd16{w[8], 4, 256, 8, 1, PE16_NONE, 0, 1, CB16_HEAD, kexp + 8};
-    for (int l = 7; l >= 6; --l) d[n++] = PackBwd16{w[l], 256, 256, 8, 16, PE16_NONE, 0, 0, CB16_L7 + (7 - l) * CB16_FULL, kexp + l};
-    d[n++] = PackBwd16{w[5], 256, 319, 8, 16, PE16_NONE, 63, 0, CB16_L7 + 2 * CB16_FULL, kexp + 5};
-    d[n++] = PackBwd16{w[5], 256, 319, 2, 16, PE16_CANONICAL, 0, 0, CB16_L5P, kexp + 5};
-    for (int l = 4; l >= 1; --l) d[n++] = PackBwd16{w[l], 256, 256, 8, 16, PE16_NONE, 0, 0, CB16_L4 + (4 - l) * CB16_FULL, kexp + l};
-    d[n++] = PackBwd16{w[0], 256, 63, 2, 16, PE16_CANONICAL, 0, 0, CB16_L0P, kexp};
-    return launch_pack_bwd16(d, n, out, st);
-}
-
-// half != 0: dZ is an f16 matrix in the chain's scaled domain and dz_amax receives the [8] scales instead of maxima
-int canonical16_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed, int64_t P,
-                    const float* d_raw_amax, float* dZ, float* d_xyz, float* dz_amax, int half, hipStream_t st) {
-    constexpr int lds = CNL16_BIAS_LDS + PE_STASH + RING * CNL16_SLAB;
-    const dim3 grid((unsigned)((P + 127) / 128));
-    const char* what = "hnrf_canonical_bwd (f16x3)";
-    if (half)
-        return launch_lds<canonical_bwd16_kernel<true>>(what, grid, dim3(256), lds, st, xyz, (const float4*)d_raw, relu_bits,
-                                                        (const char*)packed, P, d_raw_amax, dZ, d_xyz, dz_amax, 1);
-    return launch_lds<canonical_bwd16_kernel<false>>(what, grid, dim3(256), lds, st, xyz, (const float4*)d_raw, relu_bits,
-                                                     (const char*)packed, P, d_raw_amax, dZ, d_xyz, dz_amax, 1);
-}
-
-// ---- all heads: the transposed image whose head stage contracts 4 n_heads outputs, and the chain on it
-size_t canonical16_heads_bwd_bytes() { return (size_t)(CB16_BYTES + CB16H_SHIFT) + 256; }
-
-int canonical16_heads_bwd_pack(const float* const* w, int n_heads, void* packed, hipStream_t st) {
-    char* out = (char*)packed;
-    float* kexp = reinterpret_cast<float*>(out + CB16H_SHIFT + CB16_BYTES);
+    const int64_t sh = cb16_shift(n_heads);
+    const int head = n_heads > 1 ? 2 : 1;       // the head record's kind and its k-steps
+    float* kexp = reinterpret_cast<float*>(out + sh + CB16_BYTES);
     // (the head layer's maximum is taken over all heads: one exponent for the stage that sums them)
     const int sizes[9] = {256 * 63, 256 * 256, 256 * 256, 256 * 256, 256 * 256, 256 * 319, 256 * 256, 256 * 256,
                           4 * n_heads * 256};
@@ -1771,8 +1719,7 @@ int canonical16_heads_bwd_pack(const float* const* w, int n_heads, void* packed,
     if ((rc = launch_layer_amax(w, sizes, 9, kexp, st))) return rc;
     PackBwd16 d[10];
     int n = 0;
-    const int64_t sh = CB16H_SHIFT;
-    d[n++] = PackBwd16{w[8], 4 * n_heads, 256, 8, 2, PE16_NONE, 0, 2, CB16_HEAD, kexp + 8};
+    d[n++] = PackBwd16{w[8], 4 * n_heads, 256, 8, head, PE16_NONE, 0, head, CB16_HEAD, kexp + 8};
     for (int l = 7; l >= 6; --l) d[n++] = PackBwd16{w[l], 256, 256, 8, 16, PE16_NONE, 0, 0, sh + CB16_L7 + (7 - l) * CB16_FULL, kexp + l};
     d[n++] = PackBwd16{w[5], 256, 319, 8, 16, PE16_NONE, 63, 0, sh + CB16_L7 + 2 * CB16_FULL, kexp + 5};
     d[n++] = PackBwd16{w[5], 256, 319, 2, 16, PE16_CANONICAL, 0, 0, sh + CB16_L5P, kexp + 5};
@@ -1781,18 +1728,19 @@ int canonical16_heads_bwd_pack(const float* const* w, int n_heads, void* packed,
     return launch_pack_bwd16(d, n, out, st);
 }
 
-int canonical16_heads_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed, int64_t P,
-                          int n_heads, const float* d_raw_amax, float* dZ, float* d_xyz, float* dz_amax, int half,
-                          hipStream_t st) {
+// half != 0: dZ is an f16 matrix in the chain's scaled domain and dz_amax receives the [8] scales instead of maxima
+int canonical16_bwd(const float* xyz, const float* d_raw, const uint32_t* relu_bits, const void* packed, int64_t P,
+                    const float* d_raw_amax, float* dZ, float* d_xyz, float* dz_amax, int half, hipStream_t st, int n_heads) {
     constexpr int lds = CNL16_BIAS_LDS + PE_STASH + RING * CNL16_SLAB;
     const dim3 grid((unsigned)((P + 127) / 128));
-    const char* what = "hnrf_canonical_heads_bwd (f16x3)";
-    if (half)
-        return launch_lds<canonical_bwd16_kernel<true, true>>(what, grid, dim3(256), lds, st, xyz, (const float4*)d_raw,
-                                                              relu_bits, (const char*)packed, P, d_raw_amax, dZ, d_xyz,
-                                                              dz_amax, n_heads);
-    return launch_lds<canonical_bwd16_kernel<false, true>>(what, grid, dim3(256), lds, st, xyz, (const float4*)d_raw, relu_bits,
-                                                           (const char*)packed, P, d_raw_amax, dZ, d_xyz, dz_amax, n_heads);
+    const bool heads = n_heads > 1;
+    const char* what = heads ? "hnrf_canonical_heads_bwd (f16x3)" : "hnrf_canonical_bwd (f16x3)";
+    auto go = [&](auto k) {
+        return launch_lds<decltype(k)::value>(what, grid, dim3(256), lds, st, xyz, (const float4*)d_raw, relu_bits,
+                                              (const char*)packed, P, d_raw_amax, dZ, d_xyz, dz_amax, n_heads);
+    };
+    if (heads) return half ? go(Kernel<canonical_bwd16_kernel<true, true>>{}) : go(Kernel<canonical_bwd16_kernel<false, true>>{});
+    return half ? go(Kernel<canonical_bwd16_kernel<true>>{}) : go(Kernel<canonical_bwd16_kernel<false>>{});
 }
 
 size_t nonrigid16_bwd_bytes() { return (size_t)NB16_BYTES + 256; }

@@ -159,15 +159,31 @@ def status_word(packed, which, mode):
 STATUS_F16_RANGE = 1
 
 
-def canonical(xyz, packed, mode='f32'):
-    """K3 (fourier.py:9-38 + mlp_rgb_sigma.py:132-198).  xyz (...,3) -> raw (...,4)."""
-    lib = _lib.load()
+def _mlp_entry(lib, net, stem, n_heads=None):
+    """The entry hnrf_<net>_<stem>, or for every head of a multi-head image (``n_heads`` given: 'canonical' only)
+    hnrf_canonical_heads_<stem>: (function, name, the n_heads argument that follows P in its list: () or (H,))."""
+    name = 'hnrf_%s_%s%s' % (net, '' if n_heads is None else 'heads_', stem)
+    return getattr(lib, name), name, () if n_heads is None else (_chk_heads(n_heads),)
+
+
+def _canonical_fwd(lib, n_heads, xyz, packed, mode, sparse=None, raw=None):
+    """K3 (fourier.py:9-38 + mlp_rgb_sigma.py:132-198), and with ``n_heads`` for every head of one trunk pass
+    (mlp_rgb_sigma.py:180-193, head_id = -1): xyz (...,3) -> raw (...,4) or (H,...,4).  ``sparse`` = (idx, count): only the
+    samples idx[0 .. *count) are written, into ``raw`` or a zeroed tensor."""
     _chk(xyz, packed)
+    fn, name, H = _mlp_entry(lib, 'canonical', 'fwd' if sparse is None else 'fwd_sparse', n_heads)
     P = xyz.numel() // 3
-    raw = torch.empty(*xyz.shape[:-1], 4, device=xyz.device)
-    _lib.check(lib.hnrf_canonical_fwd(_ptr(xyz), _ptr(packed), _mode_arg(mode), P, _ptr(raw), _stream()),
-               'hnrf_canonical_fwd')
+    if raw is None:
+        raw = (torch.empty if sparse is None else torch.zeros)(*H, *xyz.shape[:-1], 4, device=xyz.device)
+    _chk(raw)
+    assert raw.numel() == P * 4 * (H[0] if H else 1)
+    _lib.check(fn(_ptr(xyz), _ptr(packed), _mode_arg(mode), P, *H, *[_ptr(t) for t in sparse or ()], _ptr(raw), _stream()),
+               name)
     return raw
+
+
+def canonical(xyz, packed, mode='f32'):
+    return _canonical_fwd(_lib.load(), None, xyz, packed, mode)
 
 
 def output_shapes(S, B, diagnostics=True):
@@ -411,41 +427,62 @@ def render_rays_term(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vo
 
 
 # ----------------------------------------------------------------------------- training
-def canonical_train(xyz, packed, mode='f32'):
-    """hnrf_canonical_fwd_train: raw (...,4), pe (P,63), acts (8,P,256), relu sign masks (8,P,8) int32.
-    ``packed`` must have been made for the same arithmetic (the 'f16x3' image serves 'f16x3h').  mode 'f16x3h':
-    acts is float16 in the BLOCKED layout of hnrf_mlp_dw_h, (8, P rounded up to 128, 256) -- opaque, for mlp_dw_h(...,
-    x_blocked=True) -- and pe a row-major float16 (P,64) matrix whose last column is zero."""
-    lib = _lib.load()
-    _chk(xyz, packed)
-    P = xyz.numel() // 3
-    dev = xyz.device
+# The buffers the training kernels save, stated once per network: layers, width, PE columns, sign-mask words per sample
+_NET = {'canonical': (8, 256, 63, 8), 'nonrigid': (6, 128, 36, 4)}
+
+
+def _train_buffers(net, names, P, mode, dev, out=None, lead=()):
+    """The buffers ``names`` of a *_train / *_bwd call over P samples:
+      pe         (P, PE columns); mode 'f16x3h': row-major float16 (P, 64), the columns behind the PE zero
+      acts, dZ   (layers, P, width); 'f16x3h': float16 in the BLOCKED layout of hnrf_mlp_dw_h, (layers, P rounded up to
+                 128, width) -- opaque, for mlp_dw_h(..., x_blocked / z_blocked=True)
+      bits       (layers, P, words) int32, the relu sign masks
+      amax       (layers, 64), max over row l bounds |dZ_l|; 'f16x3h': scale (layers,), the power of two dZ_l was multiplied by
+      raw; xyz, offsets; d_xyz, d_x_skel   (*lead, 4); (*lead, 3); (P, 3)
+    ``out``: a dict of buffers the caller owns (flat and larger ones will do), taken where it names one -- None = the
+    entry's null pointer -- in the place of a fresh tensor."""
+    L, W, C, words = _NET[net]
     half = mode == 'f16x3h'
-    raw = torch.empty(*xyz.shape[:-1], 4, device=dev)
-    pe = torch.empty(P, 64, device=dev, dtype=torch.float16) if half else torch.empty(P, 63, device=dev)
-    acts = torch.empty(8, (P + 127) // 128 * 128, 256, device=dev, dtype=torch.float16) if half else torch.empty(8, P, 256, device=dev)
-    bits = torch.empty(8, P, 8, dtype=torch.int32, device=dev)
-    _lib.check(lib.hnrf_canonical_fwd_train(_ptr(xyz), _ptr(packed), TRAIN_MODES[mode], P, _ptr(raw), _ptr(pe),
-                                            _ptr(acts), bits.data_ptr(), _stream()), 'hnrf_canonical_fwd_train')
-    return raw, pe, acts, bits
+    f = torch.float16 if half else torch.float32
+    rows = (P + 127) // 128 * 128 if half else P
+    spec = {'pe': ((P, 64 if half else C), f), 'acts': ((L, rows, W), f), 'dZ': ((L, rows, W), f),
+            'bits': ((L, P, words), torch.int32), 'amax': ((L,) if half else (L, 64), torch.float32),
+            'raw': ((*lead, 4), torch.float32), 'xyz': ((*lead, 3), torch.float32), 'offsets': ((*lead, 3), torch.float32),
+            'd_xyz': ((P, 3), torch.float32), 'd_x_skel': ((P, 3), torch.float32)}
+    out = out or {}
+    return [out[k] if k in out else torch.empty(spec[k][0], dtype=spec[k][1], device=dev) for k in names]
 
 
-def nonrigid_train(x_skel, hann_w, packed, mode='f32'):
+def _mlp_train(lib, net, n_heads, x, hann_w, packed, mode, out, P):
+    """canonical_train, nonrigid_train (``hann_w`` given) and canonical_heads_train (``n_heads`` given)."""
+    _chk(x, hann_w, packed)
+    fn, name, H = _mlp_entry(lib, net, 'fwd_train', n_heads)
+    P = x.numel() // 3 if P is None else int(P)
+    names = (('raw',) if hann_w is None else ('xyz', 'offsets')) + ('pe', 'acts', 'bits')
+    res = _train_buffers(net, names, P, mode, x.device, out, (*H, *x.shape[:-1]))
+    _lib.check(fn(_ptr(x), *(() if hann_w is None else (_ptr(hann_w),)), _ptr(packed), TRAIN_MODES[mode], P, *H,
+                  *[_ptr(t) for t in res], _stream()), name)
+    return tuple(res)
+
+
+def canonical_train(xyz, packed, mode='f32', *, out=None, P=None):
+    """hnrf_canonical_fwd_train: raw (...,4), pe (P,63), acts (8,P,256), relu sign masks (8,P,8) int32 (_train_buffers:
+    there also mode 'f16x3h').  ``packed`` must have been made for the same arithmetic (the 'f16x3' image serves
+    'f16x3h').  ``out``: buffers of the caller's among raw / pe / acts / bits to write into; ``P``: the sample count
+    where xyz is such a larger buffer too."""
+    return _mlp_train(_lib.load(), 'canonical', None, xyz, None, packed, mode, out, P)
+
+
+def canonical_heads_train(xyz, packed, n_heads, mode='f32', *, out=None, P=None):
+    """hnrf_canonical_heads_fwd_train: canonical_train on the image of canonical_heads_pack.  raw (H,...,4) head-major;
+    pe, acts and the sign masks are canonical_train's (the trunk does not know the heads)."""
+    return _mlp_train(_lib.load_heads_train(), 'canonical', n_heads, xyz, None, packed, mode, out, P)
+
+
+def nonrigid_train(x_skel, hann_w, packed, mode='f32', *, out=None, P=None):
     """hnrf_nonrigid_fwd_train: xyz, offsets, pe (P,36), acts (6,P,128), relu sign masks (6,P,4) int32; mode 'f16x3h':
-    float16 acts and a float16 pe (P,64) with columns 36.. zero."""
-    lib = _lib.load()
-    _chk(x_skel, hann_w, packed)
-    P = x_skel.numel() // 3
-    dev = x_skel.device
-    half = mode == 'f16x3h'
-    xyz, offsets = torch.empty_like(x_skel), torch.empty_like(x_skel)
-    pe = torch.empty(P, 64, device=dev, dtype=torch.float16) if half else torch.empty(P, 36, device=dev)
-    acts = torch.empty(6, (P + 127) // 128 * 128, 128, device=dev, dtype=torch.float16) if half else torch.empty(6, P, 128, device=dev)
-    bits = torch.empty(6, P, 4, dtype=torch.int32, device=dev)
-    _lib.check(lib.hnrf_nonrigid_fwd_train(_ptr(x_skel), _ptr(hann_w), _ptr(packed), TRAIN_MODES[mode], P, _ptr(xyz),
-                                           _ptr(offsets), _ptr(pe), _ptr(acts), bits.data_ptr(), _stream()),
-               'hnrf_nonrigid_fwd_train')
-    return xyz, offsets, pe, acts, bits
+    float16 acts and a float16 pe (P,64) with columns 36.. zero.  ``out`` / ``P``: as in canonical_train."""
+    return _mlp_train(_lib.load(), 'nonrigid', None, x_skel, hann_w, packed, mode, out, P)
 
 
 def composite_bwd(raw, fg_mask, z_vals, rays_d, bgcolor, g_rgb, g_alpha=None, g_depth=None, d_raw_out=None):
@@ -475,51 +512,89 @@ def pe_bwd(x, g, hann_w, n_bands, include_input, out=None):
     return out
 
 
-def canonical_bwd(xyz, d_raw, bits, weights, mode='f32'):
+def _mlp_bwd_pack(lib, net, n_heads, weights, mode, out):
+    _chk(*weights)
+    fn, name, H = _mlp_entry(lib, net, 'bwd_pack', n_heads)
+    assert len(weights) == _NET[net][0] + 1 and (not H or tuple(weights[8].shape) == (4 * H[0], 256))
+    m = MLP_MODES[mode]
+    nbytes = _mlp_entry(lib, net, 'bwd_packed_bytes', n_heads)[0](m, *H)
+    if out is None or out.numel() * 4 < nbytes:
+        out = torch.empty((nbytes + 3) // 4, device=weights[0].device)
+    _lib.check(fn(_ptr_array(weights), *H, m, _ptr(out), _stream()), name)
+    return out
+
+
+def canonical_bwd_pack(weights, mode='f32', out=None):
+    """hnrf_canonical_bwd_pack: the transposed image of the 9 canonical nn.Linear weights the dX chain reads, for a
+    caller that keeps it (canonical_bwd packs one per call).  ``out``: a buffer of a former pack to write into."""
+    return _mlp_bwd_pack(_lib.load(), 'canonical', None, weights, mode, out)
+
+
+def canonical_heads_bwd_pack(weights, n_heads, mode='f32', out=None):
+    """hnrf_canonical_heads_bwd_pack: as canonical_bwd_pack, with weights[8] (4 H, 256)."""
+    return _mlp_bwd_pack(_lib.load_heads_train(), 'canonical', n_heads, weights, mode, out)
+
+
+def nonrigid_bwd_pack(weights, mode='f32', out=None):
+    """hnrf_nonrigid_bwd_pack: as canonical_bwd_pack, of the 7 non-rigid nn.Linear weights."""
+    return _mlp_bwd_pack(_lib.load(), 'nonrigid', None, weights, mode, out)
+
+
+def _mlp_bwd(lib, net, n_heads, x, hann_w, d_in, bits, weights, mode, out, bound, P):
+    """canonical_bwd, nonrigid_bwd (``hann_w`` given) and canonical_heads_bwd (``n_heads`` given): -> dZ, d_x, amax."""
+    _chk(x, hann_w, d_in, bound)
+    fn, name, H = _mlp_entry(lib, net, 'bwd', n_heads)
+    exact = P is None                   # else the operands may be larger buffers of which P samples count
+    P = x.numel() // 3 if exact else int(P)
+    L, _, _, words = _NET[net]
+    n_bits, n_in = L * P * words, (3 if hann_w is not None else 4 * (H[0] if H else 1)) * P
+    assert bits.dtype == torch.int32 and bits.is_contiguous()
+    assert (bits.shape == (L, P, words) and d_in.numel() == n_in) if exact else (bits.numel() >= n_bits and d_in.numel() >= n_in)
+    if torch.is_tensor(weights):
+        packed = weights
+        _chk(packed)
+    else:
+        packed = _mlp_bwd_pack(lib, net, n_heads, weights, 'f16x3' if mode == 'f16x3h' else mode, None)
+    if bound is None and mode != 'f32':
+        bound = d_in.abs().amax().reshape(1)
+    dZ, d_x, amax = _train_buffers(net, ('dZ', 'd_xyz' if hann_w is None else 'd_x_skel', 'amax'), P, mode, x.device, out)
+    _lib.check(fn(_ptr(x), *(() if hann_w is None else (_ptr(hann_w),)), _ptr(d_in), _ptr(bits), _ptr(packed),
+                  TRAIN_MODES[mode], _ptr(bound), P, *H, _ptr(dZ), _ptr(d_x), _ptr(amax), _stream()), name)
+    return dZ, d_x, amax
+
+
+def canonical_bwd(xyz, d_raw, bits, weights, mode='f32', *, out=None, d_raw_amax=None, P=None):
     """dX chain of the canonical MLP: returns dZ (8,P,256), d_xyz (P,3) and amax (8,64) (max over row l bounds
     |dZ_l|).  bits: sign masks from canonical_train.  mode 'f16x3h': dZ is float16 in the chain's scaled domain and the
-    third result is scale (8,): the power of two dZ_l was multiplied by (mlp_dw_h divides it out)."""
-    lib = _lib.load()
-    _chk(xyz, d_raw, *weights)
-    P = xyz.numel() // 3
-    assert bits.shape == (8, P, 8) and bits.dtype == torch.int32 and bits.is_contiguous()
-    assert d_raw.numel() == 4 * P and len(weights) == 9
-    half = mode == 'f16x3h'
-    m = MLP_MODES['f16x3' if half else mode]
-    packed = torch.empty((lib.hnrf_canonical_bwd_packed_bytes(m) + 3) // 4, device=xyz.device)
-    _lib.check(lib.hnrf_canonical_bwd_pack(_ptr_array(weights), m, _ptr(packed), _stream()), 'hnrf_canonical_bwd_pack')
-    d_raw_amax = d_raw.abs().amax().reshape(1) if mode != 'f32' else None
-    dZ = torch.empty(8, (P + 127) // 128 * 128, 256, device=xyz.device, dtype=torch.float16) if half else torch.empty(8, P, 256, device=xyz.device)
-    d_xyz = torch.empty(P, 3, device=xyz.device)
-    amax = torch.empty(8, device=xyz.device) if half else torch.empty(8, 64, device=xyz.device)
-    _lib.check(lib.hnrf_canonical_bwd(_ptr(xyz), _ptr(d_raw), bits.data_ptr(), _ptr(packed), TRAIN_MODES[mode],
-                                      _ptr(d_raw_amax), P, _ptr(dZ), _ptr(d_xyz), _ptr(amax), _stream()), 'hnrf_canonical_bwd')
-    return dZ, d_xyz, amax
+    third result is scale (8,): the power of two dZ_l was multiplied by (mlp_dw_h divides it out).  ``weights``: the 9
+    nn.Linear weights, packed here, or the backward image (canonical_bwd_pack: one tensor).  ``out``: buffers of the
+    caller's among dZ / d_xyz / amax (_train_buffers); ``d_raw_amax``: a device scalar >= max |d_raw|, taken here
+    otherwise; ``P``: the sample count where the operands are larger buffers."""
+    return _mlp_bwd(_lib.load(), 'canonical', None, xyz, None, d_raw, bits, weights, mode, out, d_raw_amax, P)
 
 
-def nonrigid_bwd(x_skel, hann_w, d_xyz, bits, weights, mode='f32'):
+def canonical_heads_bwd(xyz, d_raw, bits, weights, n_heads, mode='f32', *, out=None, d_raw_amax=None, P=None):
+    """canonical_bwd seeded with every head's gradient: d_raw (H,P,4) head-major, weights[8] (4 H, 256) or the image of
+    canonical_heads_bwd_pack.  Returns what canonical_bwd returns; the bound of the incoming gradient is taken over all
+    planes."""
+    return _mlp_bwd(_lib.load_heads_train(), 'canonical', n_heads, xyz, None, d_raw, bits, weights, mode, out, d_raw_amax, P)
+
+
+def nonrigid_bwd(x_skel, hann_w, d_xyz, bits, weights, mode='f32', *, out=None, d_xyz_amax=None, P=None):
     """dX chain of the non-rigid MLP: returns dZ (6,P,128), d_x_skel (P,3) (identity path included), amax (6,64)
-    (mode 'f16x3h': float16 dZ and scale (6,), see canonical_bwd)."""
-    lib = _lib.load()
-    _chk(x_skel, hann_w, d_xyz, *weights)
-    P = x_skel.numel() // 3
-    assert bits.shape == (6, P, 4) and bits.dtype == torch.int32 and bits.is_contiguous()
-    assert d_xyz.numel() == 3 * P and len(weights) == 7
-    half = mode == 'f16x3h'
-    m = MLP_MODES['f16x3' if half else mode]
-    packed = torch.empty((lib.hnrf_nonrigid_bwd_packed_bytes(m) + 3) // 4, device=x_skel.device)
-    _lib.check(lib.hnrf_nonrigid_bwd_pack(_ptr_array(weights), m, _ptr(packed), _stream()), 'hnrf_nonrigid_bwd_pack')
-    d_amax = d_xyz.abs().amax().reshape(1) if mode != 'f32' else None
-    dZ = torch.empty(6, (P + 127) // 128 * 128, 128, device=x_skel.device, dtype=torch.float16) if half else torch.empty(6, P, 128, device=x_skel.device)
-    d_x_skel = torch.empty(P, 3, device=x_skel.device)
-    amax = torch.empty(6, device=x_skel.device) if half else torch.empty(6, 64, device=x_skel.device)
-    _lib.check(lib.hnrf_nonrigid_bwd(_ptr(x_skel), _ptr(hann_w), _ptr(d_xyz), bits.data_ptr(), _ptr(packed),
-                                     TRAIN_MODES[mode], _ptr(d_amax), P, _ptr(dZ), _ptr(d_x_skel), _ptr(amax), _stream()),
-               'hnrf_nonrigid_bwd')
-    return dZ, d_x_skel, amax
+    (mode 'f16x3h': float16 dZ and scale (6,)); the keyword arguments as in canonical_bwd."""
+    return _mlp_bwd(_lib.load(), 'nonrigid', None, x_skel, hann_w, d_xyz, bits, weights, mode, out, d_xyz_amax, P)
 
 
 _dw_ws = {}
+
+
+def _dw_workspace(need, device):
+    """The device's weight-gradient workspace of at least ``need`` bytes: kept between calls, grown when too small."""
+    ws = _dw_ws.get(device.index)
+    if ws is None or ws.numel() < need:
+        ws = _dw_ws[device.index] = torch.empty(need, dtype=torch.uint8, device=device)
+    return ws
 
 
 def _db_buffer(db_out, n_out, want_db, device):
@@ -547,10 +622,7 @@ def mlp_dw(dZ, X, dW_out=None, want_db=True, mode='f32', dz_amax=None, db_out=No
     need = lib.hnrf_mlp_dw_workspace_bytes(P, n_out, n_in)
     if need == 0:
         raise _lib.HnrfError('hnrf_mlp_dw: shape (%d, %d, %d) not built' % (P, n_out, n_in))
-    key = dZ.device.index
-    ws = _dw_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _dw_ws[key] = torch.empty(need, dtype=torch.uint8, device=dZ.device)
+    ws = _dw_workspace(need, dZ.device)
     if mode == 'f16x3' and dz_amax is None:
         dz_amax = dZ.abs().amax().reshape(1)
     _lib.check(lib.hnrf_mlp_dw(dZ.data_ptr(), dZ.stride(0), X.data_ptr(), X.stride(0), P, n_out, n_in,
@@ -583,10 +655,7 @@ def mlp_dw_h(dZ, X, dW_out=None, want_db=True, dz_scale=None, n_in=None, P=None,
     need = lib.hnrf_mlp_dw_h_workspace_bytes(P, n_out, n_in)
     if need == 0:
         raise _lib.HnrfError('hnrf_mlp_dw_h: shape (%d, %d, %d) not built' % (P, n_out, n_in))
-    key = dZ.device.index
-    ws = _dw_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = _dw_ws[key] = torch.empty(need, dtype=torch.uint8, device=dZ.device)
+    ws = _dw_workspace(need, dZ.device)
     layout = (1 if z_blocked else 0) | (2 if x_blocked else 0)
     _lib.check(lib.hnrf_mlp_dw_h(dZ.data_ptr(), dZ.stride(0), X.data_ptr(), X.stride(0), P, n_out, n_in, layout,
                                  _ptr(dz_scale), dW_out.data_ptr(), dW_out.stride(0), _ptr(db), ws.data_ptr(), ws.numel(),
@@ -696,14 +765,7 @@ def compact_samples(fg_mask, eps):
 
 
 def canonical_sparse(xyz, packed, idx, count, mode='f32', raw=None):
-    lib = _lib.load()
-    _chk(xyz, packed)
-    P = xyz.numel() // 3
-    if raw is None:
-        raw = torch.zeros(*xyz.shape[:-1], 4, device=xyz.device)
-    _lib.check(lib.hnrf_canonical_fwd_sparse(_ptr(xyz), _ptr(packed), _mode_arg(mode), P, _ptr(idx), _ptr(count),
-                                             _ptr(raw), _stream()), 'hnrf_canonical_fwd_sparse')
-    return raw
+    return _canonical_fwd(_lib.load(), None, xyz, packed, mode, (idx, count), raw)
 
 
 # ----------------------------------------------------------------------------- multi-head canonical MLP
@@ -726,27 +788,11 @@ def canonical_heads_pack(weights, biases, n_heads, mode='f32', out=None):
 
 
 def canonical_heads(xyz, packed, n_heads, mode='f32'):
-    """K3 for every head of one trunk pass (mlp_rgb_sigma.py:180-193, head_id = -1).  xyz (...,3) -> raw (H,...,4)."""
-    lib = _lib.load_heads()
-    _chk(xyz, packed)
-    H, P = _chk_heads(n_heads), xyz.numel() // 3
-    raw = torch.empty(H, *xyz.shape[:-1], 4, device=xyz.device)
-    _lib.check(lib.hnrf_canonical_heads_fwd(_ptr(xyz), _ptr(packed), _mode_arg(mode), P, H, _ptr(raw), _stream()),
-               'hnrf_canonical_heads_fwd')
-    return raw
+    return _canonical_fwd(_lib.load_heads(), n_heads, xyz, packed, mode)
 
 
 def canonical_heads_sparse(xyz, packed, n_heads, idx, count, mode='f32', raw=None):
-    lib = _lib.load_heads()
-    _chk(xyz, packed)
-    H, P = _chk_heads(n_heads), xyz.numel() // 3
-    if raw is None:
-        raw = torch.zeros(H, *xyz.shape[:-1], 4, device=xyz.device)
-    _chk(raw)
-    assert raw.numel() == H * P * 4
-    _lib.check(lib.hnrf_canonical_heads_fwd_sparse(_ptr(xyz), _ptr(packed), _mode_arg(mode), P, H, _ptr(idx), _ptr(count),
-                                                   _ptr(raw), _stream()), 'hnrf_canonical_heads_fwd_sparse')
-    return raw
+    return _canonical_fwd(_lib.load_heads(), n_heads, xyz, packed, mode, (idx, count), raw)
 
 
 def render_frame_heads(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w,
@@ -1669,33 +1715,6 @@ def geometry_maps(rays_o, rays_d, surf, pix2ray, H, W, want, surface=0, alpha=No
 
 
 # ------------------------------------------------------------------------------------------ density-gradient normals
-def canonical_bwd_pack(weights, mode='f32', out=None):
-    """hnrf_canonical_bwd_pack: the transposed image of the 9 canonical nn.Linear weights the dX chain reads, for a
-    caller that keeps it (canonical_bwd packs one per call).  ``out``: a buffer of a former pack to write into."""
-    lib = _lib.load()
-    _chk(*weights)
-    assert len(weights) == 9
-    m = MLP_MODES[mode]
-    nbytes = lib.hnrf_canonical_bwd_packed_bytes(m)
-    if out is None or out.numel() * 4 < nbytes:
-        out = torch.empty((nbytes + 3) // 4, device=weights[0].device)
-    _lib.check(lib.hnrf_canonical_bwd_pack(_ptr_array(weights), m, _ptr(out), _stream()), 'hnrf_canonical_bwd_pack')
-    return out
-
-
-def nonrigid_bwd_pack(weights, mode='f32', out=None):
-    """hnrf_nonrigid_bwd_pack: as canonical_bwd_pack, of the 7 non-rigid nn.Linear weights."""
-    lib = _lib.load()
-    _chk(*weights)
-    assert len(weights) == 7
-    m = MLP_MODES[mode]
-    nbytes = lib.hnrf_nonrigid_bwd_packed_bytes(m)
-    if out is None or out.numel() * 4 < nbytes:
-        out = torch.empty((nbytes + 3) // 4, device=weights[0].device)
-    _lib.check(lib.hnrf_nonrigid_bwd_pack(_ptr_array(weights), m, _ptr(out), _stream()), 'hnrf_nonrigid_bwd_pack')
-    return out
-
-
 GRADIENT_CHUNK = 16384
 # bytes of workspace per sample of a chunk, 'f32' and 'f16x3' alike (both save fp32 activations):
 #   canonical  raw 16 + pe 252 + acts 8192 + relu_bits 256 + d_raw 16 + dZ 8192
@@ -1708,16 +1727,15 @@ def _gradient_workspace(ws, C, with_warp, dev):
     if ws.get('key') != key:
         ws.clear()
         ws['key'] = key
-        f = lambda n: torch.empty(n, device=dev)
-        i = lambda n: torch.empty(n, dtype=torch.int32, device=dev)
         d_raw = torch.zeros(C, 4, device=dev)
         d_raw[:, 3] = 1.0
-        ws.update(raw=f(C * 4), pe=f(C * 63), acts=f(8 * C * 256), bits=i(8 * C * 8), dZ=f(8 * C * 256), d_raw=d_raw,
+        names = ('raw', 'pe', 'acts', 'bits', 'dZ')
+        ws.update(zip(names, _train_buffers('canonical', names, C, 'f32', dev, lead=(C,))), d_raw=d_raw,
                   one=torch.ones(1, device=dev), amax=torch.zeros(1, device=dev))
     if with_warp and 'nr_acts' not in ws:
-        f = lambda n: torch.empty(n, device=dev)
-        ws.update(nr_xyz=f(C * 3), nr_off=f(C * 3), nr_pe=f(C * 36), nr_acts=f(6 * C * 128),
-                  nr_bits=torch.empty(6 * C * 4, dtype=torch.int32, device=dev), nr_dZ=f(6 * C * 128))
+        names = ('xyz', 'offsets', 'pe', 'acts', 'bits', 'dZ')
+        ws.update(zip(('nr_xyz', 'nr_off', 'nr_pe', 'nr_acts', 'nr_bits', 'nr_dZ'),
+                      _train_buffers('nonrigid', names, C, 'f32', dev, lead=(C,))))
     return ws
 
 
@@ -1741,10 +1759,8 @@ def density_gradient(xyz, cnl_packed, cnl_weights, mode='f32', warp=None, worksp
     samples at a time through ``workspace``, a dict the caller keeps (filled here; {} or None = a fresh one).  It takes
     GRADIENT_BYTES_CANONICAL = 16924 bytes per sample of a chunk in either mode, and GRADIENT_BYTES_NONRIGID = 6408 more
     with ``warp`` (277 MB and 382 MB at the default chunk of 16384).  Nothing synchronises."""
-    lib = _lib.load()
     if mode not in MLP_MODES:
         raise _lib.HnrfError("density_gradient: mode must be 'f32' or 'f16x3', got %r" % (mode,))
-    m = TRAIN_MODES[mode]
     C = int(chunk)
     if C < 1:
         raise _lib.HnrfError('density_gradient: chunk must be >= 1, got %r' % (chunk,))
@@ -1771,36 +1787,29 @@ def density_gradient(xyz, cnl_packed, cnl_weights, mode='f32', warp=None, worksp
     ws = _gradient_workspace({} if workspace is None else workspace, min(C, max(P, 1)) if workspace is None else C,
                              warp is not None, dev)
     C = ws['key'][0]
-    st = _stream()
+    # the chunks' saved buffers are the workspace's (a last, shorter chunk uses their front: hence P = n)
+    if warp is not None:
+        nr_out = {'xyz': ws['nr_xyz'], 'offsets': ws['nr_off'], 'pe': ws['nr_pe'], 'acts': ws['nr_acts'], 'bits': ws['nr_bits']}
     with torch.cuda.device(dev):
         for i in range(0, P, C):
             n = min(C, P - i)
             if warp is not None:
-                _lib.check(lib.hnrf_nonrigid_fwd_train(_ptr(x_skel[i:i + n]), _ptr(hann_w), _ptr(nr_packed), m, n,
-                                                       _ptr(ws['nr_xyz']), _ptr(ws['nr_off']), _ptr(ws['nr_pe']),
-                                                       _ptr(ws['nr_acts']), ws['nr_bits'].data_ptr(), st),
-                           'hnrf_nonrigid_fwd_train')
+                nonrigid_train(x_skel[i:i + n], hann_w, nr_packed, mode, out=nr_out)
                 pts = ws['nr_xyz']
             else:
                 pts = xyz[i:i + n]
-            _lib.check(lib.hnrf_canonical_fwd_train(_ptr(pts), _ptr(cnl_packed), m, n, _ptr(ws['raw']), _ptr(ws['pe']),
-                                                    _ptr(ws['acts']), ws['bits'].data_ptr(), st), 'hnrf_canonical_fwd_train')
-            _lib.check(lib.hnrf_canonical_bwd(_ptr(pts), _ptr(ws['d_raw']), ws['bits'].data_ptr(), _ptr(cnl_weights), m,
-                                              _ptr(ws['one']), n, _ptr(ws['dZ']), _ptr(g[i:i + n]), 0, st),
-                       'hnrf_canonical_bwd')
-            sigma[i:i + n].copy_(ws['raw'][:4 * n].view(n, 4)[:, 3])
+            canonical_train(pts, cnl_packed, mode, out=ws, P=n)
+            canonical_bwd(pts, ws['d_raw'], ws['bits'], cnl_weights, mode, out={'dZ': ws['dZ'], 'd_xyz': g[i:i + n], 'amax': None},
+                          d_raw_amax=ws['one'], P=n)
+            sigma[i:i + n].copy_(ws['raw'][:n, 3])
         if warp is not None:
             d_xyz = g.clone()
             torch.amax(d_xyz.abs().reshape(-1), dim=0, keepdim=True, out=ws['amax'])
             for i in range(0, P, C):
                 n = min(C, P - i)
-                _lib.check(lib.hnrf_nonrigid_fwd_train(_ptr(x_skel[i:i + n]), _ptr(hann_w), _ptr(nr_packed), m, n,
-                                                       _ptr(ws['nr_xyz']), _ptr(ws['nr_off']), _ptr(ws['nr_pe']),
-                                                       _ptr(ws['nr_acts']), ws['nr_bits'].data_ptr(), st),
-                           'hnrf_nonrigid_fwd_train')
-                _lib.check(lib.hnrf_nonrigid_bwd(_ptr(x_skel[i:i + n]), _ptr(hann_w), _ptr(d_xyz[i:i + n]),
-                                                 ws['nr_bits'].data_ptr(), _ptr(nr_weights), m, _ptr(ws['amax']), n,
-                                                 _ptr(ws['nr_dZ']), _ptr(g[i:i + n]), 0, st), 'hnrf_nonrigid_bwd')
+                nonrigid_train(x_skel[i:i + n], hann_w, nr_packed, mode, out=nr_out)
+                nonrigid_bwd(x_skel[i:i + n], hann_w, d_xyz[i:i + n], ws['nr_bits'], nr_weights, mode,
+                             out={'dZ': ws['nr_dZ'], 'd_x_skel': g[i:i + n], 'amax': None}, d_xyz_amax=ws['amax'], P=n)
     return g, sigma
 
 
@@ -1897,56 +1906,3 @@ def field_normals(verts, g, sigma, vol, n_bones, bbox_min, bbox_scale):
         _lib.check(lib.hnrf_field_normals(_ptr(verts), _ptr(g), _ptr(sigma), V, _ptr(vol), int(n_bones), G, _ptr(bbox_min),
                                           _ptr(bbox_scale), _ptr(normal), _stream()), 'hnrf_field_normals')
     return normal
-
-
-# -------------------------------------------------------------------------- training the multi-head canonical MLP
-def canonical_heads_train(xyz, packed, n_heads, mode='f32'):
-    """hnrf_canonical_heads_fwd_train: canonical_train on the image of canonical_heads_pack.  raw (H,...,4) head-major;
-    pe, acts and the sign masks are canonical_train's (the trunk does not know the heads)."""
-    lib = _lib.load_heads_train()
-    _chk(xyz, packed)
-    H, P = _chk_heads(n_heads), xyz.numel() // 3
-    dev = xyz.device
-    half = mode == 'f16x3h'
-    raw = torch.empty(H, *xyz.shape[:-1], 4, device=dev)
-    pe = torch.empty(P, 64, device=dev, dtype=torch.float16) if half else torch.empty(P, 63, device=dev)
-    acts = torch.empty(8, (P + 127) // 128 * 128, 256, device=dev, dtype=torch.float16) if half else torch.empty(8, P, 256, device=dev)
-    bits = torch.empty(8, P, 8, dtype=torch.int32, device=dev)
-    _lib.check(lib.hnrf_canonical_heads_fwd_train(_ptr(xyz), _ptr(packed), TRAIN_MODES[mode], P, H, _ptr(raw), _ptr(pe),
-                                                  _ptr(acts), bits.data_ptr(), _stream()), 'hnrf_canonical_heads_fwd_train')
-    return raw, pe, acts, bits
-
-
-def canonical_heads_bwd_pack(weights, n_heads, mode='f32', out=None):
-    """hnrf_canonical_heads_bwd_pack: as canonical_bwd_pack, with weights[8] (4 H, 256)."""
-    lib = _lib.load_heads_train()
-    _chk(*weights)
-    H = _chk_heads(n_heads)
-    assert len(weights) == 9 and tuple(weights[8].shape) == (4 * H, 256)
-    m = MLP_MODES[mode]
-    nbytes = lib.hnrf_canonical_heads_bwd_packed_bytes(m, H)
-    if out is None or out.numel() * 4 < nbytes:
-        out = torch.empty((nbytes + 3) // 4, device=weights[0].device)
-    _lib.check(lib.hnrf_canonical_heads_bwd_pack(_ptr_array(weights), H, m, _ptr(out), _stream()),
-               'hnrf_canonical_heads_bwd_pack')
-    return out
-
-
-def canonical_heads_bwd(xyz, d_raw, bits, weights, n_heads, mode='f32'):
-    """canonical_bwd seeded with every head's gradient: d_raw (H,P,4) head-major, weights[8] (4 H, 256).  Returns what
-    canonical_bwd returns; the bound of the incoming gradient is taken over all planes."""
-    lib = _lib.load_heads_train()
-    _chk(xyz, d_raw, *weights)
-    H, P = _chk_heads(n_heads), xyz.numel() // 3
-    assert bits.shape == (8, P, 8) and bits.dtype == torch.int32 and bits.is_contiguous()
-    assert d_raw.numel() == 4 * P * H and len(weights) == 9 and tuple(weights[8].shape) == (4 * H, 256)
-    half = mode == 'f16x3h'
-    packed = canonical_heads_bwd_pack(weights, H, 'f16x3' if half else mode)
-    d_raw_amax = d_raw.abs().amax().reshape(1) if mode != 'f32' else None
-    dZ = torch.empty(8, (P + 127) // 128 * 128, 256, device=xyz.device, dtype=torch.float16) if half else torch.empty(8, P, 256, device=xyz.device)
-    d_xyz = torch.empty(P, 3, device=xyz.device)
-    amax = torch.empty(8, device=xyz.device) if half else torch.empty(8, 64, device=xyz.device)
-    _lib.check(lib.hnrf_canonical_heads_bwd(_ptr(xyz), _ptr(d_raw), bits.data_ptr(), _ptr(packed), TRAIN_MODES[mode],
-                                            _ptr(d_raw_amax), P, H, _ptr(dZ), _ptr(d_xyz), _ptr(amax), _stream()),
-               'hnrf_canonical_heads_bwd')
-    return dZ, d_xyz, amax

@@ -106,6 +106,66 @@ def test_bad_head_counts_and_null_pointers_are_refused_before_any_launch():
     assert lib.hnrf_canonical_heads_fwd_train(p, p, 0, 0, 3, p, p, p, p, None) == 0                  # P = 0: nothing to do
 
 
+def test_single_head_entries_refuse_what_they_refused_and_name_themselves():
+    """The same table for hnrf_canonical_fwd_train, hnrf_canonical_bwd_pack and hnrf_canonical_bwd, which share their
+    bodies with the _heads entries: the codes are those the library gave while each entry still had a body of its own,
+    and the message names the entry that was called, never its twin.  No GPU: nothing may be launched."""
+    from humannerf_amd import _lib
+    lib = _lib.load_heads_train()
+    E_ARG, E_UNSUPPORTED = -1, -2
+    buf = (ctypes.c_float * 64)()
+    p = (ctypes.addressof(buf) + 15) // 16 * 16
+    ptrs9 = (ctypes.c_void_p * 9)(*[p] * 9)
+
+    def refused(entry, code, *args, word=b''):
+        assert getattr(lib, entry)(*args) == code, (entry, args)
+        msg = lib.hnrf_last_error()
+        assert msg.startswith(entry.encode() + b':') and word in msg, msg
+
+    for k in (0, 1, 4, 5, 6, 7):                                    # xyz, packed, raw, pe_out, acts, relu_bits
+        args = [p, p, 0, 128, p, p, p, p, None]
+        args[k] = None
+        refused('hnrf_canonical_fwd_train', E_ARG, *args, word=b'null pointer')
+    for k in (0, 1, 2, 3, 7, 8):                                    # xyz, d_raw, relu_bits, packed, dZ, d_xyz
+        args = [p, p, p, p, 0, None, 128, p, p, None, None]
+        args[k] = None
+        refused('hnrf_canonical_bwd', E_ARG, *args, word=b'null pointer')
+    refused('hnrf_canonical_bwd_pack', E_ARG, None, 0, p, None, word=b'null pointer')
+    refused('hnrf_canonical_bwd_pack', E_ARG, ptrs9, 0, None, None, word=b'null pointer')
+    holed = (ctypes.c_void_p * 9)(*[p] * 9)
+    holed[5] = None
+    refused('hnrf_canonical_bwd_pack', E_ARG, holed, 0, p, None, word=b'null layer 5')
+    # split-f16 without its bound (the single-head wording: no "over all planes"), f16 dZ without its scales
+    refused('hnrf_canonical_bwd', E_ARG, p, p, p, p, 1, None, 128, p, p, None, None, word=b'>= max |d_raw|)')
+    refused('hnrf_canonical_bwd', E_ARG, p, p, p, p, 2, p, 128, p, p, None, None, word=b'needs dz_amax')
+    assert lib.hnrf_canonical_heads_bwd(p, p, p, p, 1, None, 128, 3, p, p, None, None) == E_ARG
+    assert lib.hnrf_last_error().startswith(b'hnrf_canonical_heads_bwd:') and b'over all planes' in lib.hnrf_last_error()
+    # a mode that is not built; two faults at once report the earlier check (null before mode, mode before alignment)
+    refused('hnrf_canonical_fwd_train', E_UNSUPPORTED, p, p, 7, 128, p, p, p, p, None, word=b'mode 7 not built')
+    refused('hnrf_canonical_bwd', E_UNSUPPORTED, p, p, p, p, 7, None, 128, p, p, None, None, word=b'mode 7 not built')
+    refused('hnrf_canonical_bwd_pack', E_UNSUPPORTED, ptrs9, 2, p, None, word=b'mode 2 not built')
+    refused('hnrf_canonical_fwd_train', E_ARG, None, p + 4, 7, 128, p, p, p, p, None, word=b'null pointer')
+    refused('hnrf_canonical_fwd_train', E_UNSUPPORTED, p, p + 4, 7, 128, p, p, p, p, None, word=b'not built')
+    refused('hnrf_canonical_bwd', E_ARG, p, p, p, p + 4, 1, None, 128, p, p, None, None, word=b'd_raw_amax')
+    # misaligned images and buffers; negative P
+    refused('hnrf_canonical_fwd_train', E_ARG, p, p + 4, 0, 128, p, p, p, p, None, word=b'16-byte aligned')
+    refused('hnrf_canonical_fwd_train', E_ARG, p, p, 0, 128, p, p, p + 4, p, None, word=b'16-byte aligned')
+    refused('hnrf_canonical_bwd', E_ARG, p, p, p, p + 4, 0, None, 128, p, p, None, None, word=b'16-byte aligned')
+    refused('hnrf_canonical_fwd_train', E_ARG, p, p, 0, -1, p, p, p, p, None, word=b'bad P')
+    refused('hnrf_canonical_bwd', E_ARG, p, p, p, p, 0, None, -1, p, p, None, None, word=b'bad P')
+    # (the 16-byte check of the image is the _heads pack's alone; that the single-head pack makes none cannot be shown
+    # here without letting it go on to a launch)
+    refused('hnrf_canonical_heads_bwd_pack', E_ARG, ptrs9, 3, 0, p + 4, None, word=b'16-byte aligned')
+    # P = 0: nothing to do, in every mode; these calls carry no n_heads
+    for mode in (0, 1, 2):
+        assert lib.hnrf_canonical_fwd_train(p, p, mode, 0, p, p, p, p, None) == 0
+        assert lib.hnrf_canonical_bwd(p, p, p, p, mode, p, 0, p, p, p, None) == 0
+    assert lib.hnrf_canonical_bwd(p, p, p, p, 0, None, 0, p, p, None, None) == 0
+    for mode in (0, 1):
+        assert lib.hnrf_canonical_bwd_packed_bytes(mode) > 0
+    assert lib.hnrf_canonical_bwd_packed_bytes(2) == 0
+
+
 # ---------------------------------------------------------------------------------------------------- 'argmin' loss
 def reference_argmin_loss(rgbs, target, lossweights, selector, unselected):
     """trainer.py:124-160 restated line by line for mse / l1 terms (numpy, float64)."""
