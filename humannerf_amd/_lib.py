@@ -40,6 +40,7 @@ OPEN_GROUPS = {
     'heads_shared': ('hnrf_heads_shared.h', 'the shared evaluation for all heads'),
     'normals': ('hnrf_normals.h', 'the density-gradient normals'),
     'heads_train': ('hnrf_heads_train.h', 'the multi-head training kernels'),
+    'view': ('hnrf_view.h', 'view-dependent colour'),
 }
 
 _SCALARS = {'int': ctypes.c_int, 'int64_t': ctypes.c_int64, 'size_t': ctypes.c_size_t, 'float': ctypes.c_float,
@@ -107,6 +108,7 @@ _OPEN_HEADERS = {group: _header(group, OPEN_GROUPS) for group in OPEN_GROUPS}
 HEADS_SHARED_HEADER_PATH, HEADS_SHARED_SIGNATURES = _OPEN_HEADERS['heads_shared']
 NORMALS_HEADER_PATH, NORMALS_SIGNATURES = _OPEN_HEADERS['normals']
 HEADS_TRAIN_HEADER_PATH, HEADS_TRAIN_SIGNATURES = _OPEN_HEADERS['heads_train']
+VIEW_HEADER_PATH, VIEW_SIGNATURES = _OPEN_HEADERS['view']
 
 _lib = None
 
@@ -203,6 +205,10 @@ def load_normals(lib=None):
 
 def load_heads_train(lib=None):
     return _bind_table('heads_train', lib, OPEN_GROUPS, _OPEN_HEADERS)
+
+
+def load_view(lib=None):
+    return _bind_table('view', lib, OPEN_GROUPS, _OPEN_HEADERS)
 
 
 def load_open():

@@ -156,8 +156,29 @@ def training_modes():
     return fwd, chain, dw, half
 
 
+class ViewBias(torch.autograd.Function):
+    """bias (R, 3) = ViewBias.apply(dirs, B, c): the per-ray colour bias B e(d) + c of view-dependent colour
+    (hnrf_view_bias_fwd), with gradients for B (3, 3 + 6 L) and c (3,) from hnrf_view_bias_bwd.  The directions are data."""
+
+    @staticmethod
+    def forward(ctx, dirs, B, c):
+        dirs, B, c = dirs.contiguous(), B.contiguous(), c.contiguous()
+        ctx.save_for_backward(dirs)
+        ctx.bands = (B.shape[1] - 3) // 6
+        return ops.view_bias(dirs, B, c)
+
+    @staticmethod
+    def backward(ctx, g):
+        dB, dc = ops.view_bias_bwd(ctx.saved_tensors[0], g.contiguous(), ctx.bands)
+        return None, dB, dc
+
+
 class RenderRays(torch.autograd.Function):
-    """rgb, alpha, depth[, 8 diagnostic outputs] = RenderRays.apply(consts..., motion_Rs, motion_Ts, vol, *mlp_params)
+    """rgb, alpha, depth[, 8 diagnostic outputs] = RenderRays.apply(consts..., motion_Rs, motion_Ts, vol, *mlp_params
+    [, view_bias])
+
+    ``view_bias`` (R, 3), behind the 32 MLP parameters: view-dependent colour, one raw-colour bias per ray in K4 and K4'
+    (single head only); its gradient is the last one returned.
 
     With ``diag`` the other keys of the reference's return dict (network.py:776-789) come out too, as
     non-differentiable tensors, in OUTPUT_KEYS order.
@@ -178,6 +199,7 @@ class RenderRays(torch.autograd.Function):
         (differentiably, in fp32) and passes ``use_nonrigid = False``: xyz = x_skel + const_offset."""
         nr_w, nr_b = list(params[0:7]), list(params[7:14])
         cn_w, cn_b = list(params[14:23]), list(params[23:32])
+        view_bias = params[32].contiguous() if len(params) > 32 else None
         motion_Rs, motion_Ts, vol = motion_Rs.contiguous(), motion_Ts.contiguous(), vol.contiguous()
         z, x_skel, mask, bmw = ops.sample_warp(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min,
                                                bbox_scale, n_samples, want_bmw=bool(diag))
@@ -196,8 +218,11 @@ class RenderRays(torch.autograd.Function):
         if n == 1:
             cn_packed = ops.canonical_pack(cn_w, cn_b, mode)
             raw, pe_c, acts_c, bits_c = ops.canonical_train(xyz, cn_packed, tmode)
-            out = ops.composite(raw, mask, z, rays_d, xyz if diag else None, bg, diagnostics=bool(diag))
+            out = ops.composite(raw, mask, z, rays_d, xyz if diag else None, bg, diagnostics=bool(diag),
+                                **({} if view_bias is None else {'view_bias': view_bias}))
         else:
+            if view_bias is not None:
+                raise NotImplementedError('RenderRays: view-dependent colour with a multi-head canonical MLP is not built')
             cn_packed = ops.canonical_heads_pack(cn_w, cn_b, n, mode)
             raw, pe_c, acts_c, bits_c = ops.canonical_heads_train(xyz, cn_packed, n, tmode)      # raw [n, R, S, 4]
             R, S = z.shape
@@ -211,8 +236,10 @@ class RenderRays(torch.autograd.Function):
         ctx.const_offset = const_offset is not None
         ctx.half = half
         ctx.n_out = 11 if diag else 3
+        ctx.has_view_bias = view_bias is not None
         ctx.save_for_backward(rays_o, rays_d, z, x_skel, mask, xyz, raw, pe_c, acts_c, pe_n, acts_n, motion_Rs,
-                              motion_Ts, vol, bbox_min, bbox_scale, hann_w, cond, bg, bits_c, bits_n, *nr_w, *cn_w)
+                              motion_Ts, vol, bbox_min, bbox_scale, hann_w, cond, bg, bits_c, bits_n, *nr_w, *cn_w,
+                              *(() if view_bias is None else (view_bias,)))
         if not diag:
             return out['rgb'], out['alpha'], out['depth']
         out.update(xyz_on_rays=xyz.view_as(x_skel).clone(), backward_motion_weights=bmw, offsets=offsets)
@@ -229,7 +256,13 @@ class RenderRays(torch.autograd.Function):
         P = z.numel()
         c = lambda t: None if t is None else t.contiguous()
         n = ctx.n_planes
-        if n == 1:
+        d_bias = ()
+        if n == 1 and ctx.has_view_bias:
+            d_raw, d_mask, d_view = ops.composite_bwd(raw, mask, z, rays_d, bg, c(g_rgb), c(g_alpha), c(g_depth),
+                                                      view_bias=ctx.saved_tensors[37])
+            d_raw, d_bias = d_raw.view(P, 4), (d_view,)
+            chain = ops.canonical_bwd
+        elif n == 1:
             d_raw, d_mask = ops.composite_bwd(raw, mask, z, rays_d, bg, c(g_rgb), c(g_alpha), c(g_depth))
             d_raw = d_raw.view(P, 4)
             chain = ops.canonical_bwd
@@ -279,4 +312,4 @@ class RenderRays(torch.autograd.Function):
         d_vol, d_Rs, d_Ts = ops.sample_warp_bwd(rays_o, rays_d, z, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
                                                 x_skel, mask, d_x_skel.view_as(x_skel).contiguous(), d_mask)
         d_offset = d_xyz.reshape(P, 3).sum(dim=0) if ctx.const_offset else None
-        return (None,) * 13 + (d_offset, d_Rs, d_Ts, d_vol, *gWn, *gbn, *gWc, *gbc)
+        return (None,) * 13 + (d_offset, d_Rs, d_Ts, d_vol, *gWn, *gbn, *gWc, *gbc, *d_bias)

@@ -76,6 +76,7 @@ _DEFAULTS = {
     'canonical_mlp': {                         # default.yaml:51-57
         'mlp_depth': 8, 'mlp_width': 256, 'multires': 10, 'i_embed': 0,
         'view_dir': False, 'pose_color': 'wo', 'last_linear_scale': 1,
+        'view_embed': 'mlp', 'view_dir_camera_only': False, 'multires_dir': 4,      # default.yaml:58-64
     },
     'mweight_volume': {                        # default.yaml:133-137
         'embedding_size': 256, 'volume_size': 32, 'dst_voxel_size': 0.0625,
@@ -138,6 +139,12 @@ _DEFAULTS = {
         # get zero gradients), head_id = -1 renders and differentiates every head from one pass through both trunks
         # (include/hnrf_heads_train.h), and Trainer reads batch['head_id'] (dataset.FrameStream: multihead.split)
         'train_heads': False,
+        # view-dependent colour (canonical_mlp.view_dir = True, view_embed 'mlp', pose_color 'wo', single head).  False:
+        # such a configuration is refused, as every branch outside the default ones.  True: the view branch is built --
+        # it has no non-linearity behind the trunk, so it is folded into an ordinary canonical image plus three floats per
+        # ray that K4 adds in front of its sigmoid (DESIGN.md section 4 "View-dependent colour"); rendering, baking and
+        # training cost what they cost without it.  Network.fixed_view chooses the direction for colour without a ray
+        'view_dir': False,
         # inference in 'f16x3' is fp32-accurate for hidden activations below 128 (and clamps them at 65504, the f16
         # range).  The kernels flag any beyond (status word of
         # the packed weight image, read back one frame late without a synchronisation); what Network.forward does when

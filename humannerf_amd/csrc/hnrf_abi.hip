@@ -63,10 +63,13 @@ struct Share {
 // What K3 writes and K4 composites: the n planes raw [n][P][4] and the outputs o[g] of each.  n == 1: the chunk's own
 // raw (c.raw) and FrameOut; n >= 2: all heads of a multi-head canonical image (hnrf_render_frame_heads_fwd), written by
 // K3 in one launch.  Every o[g] carries the same xyz / bmw / offsets: those do not depend on the head.
+// view_bias: view-dependent colour (hnrf_view.h), the chunk's rows [R][3] added to every plane's raw colour in K4; null =
+// none, which is what every entry but hnrf_render_frame_view_fwd passes.
 struct Planes {
     int n;
     float* raw;
     const FrameOut* o;
+    const float* view_bias = nullptr;
 };
 
 // K2 -> K3 -> K4 of one ray chunk whose K1 results are in `c`: the whole of hnrf_render_rays_fwd after K1, and the body
@@ -119,9 +122,9 @@ int render_chunk(const RenderCarve& c, const float* rays_d, const float* hann_w,
     }
     for (int g = 0; g < pl.n; ++g) {
         const FrameOut& o = pl.o[g];
-        if ((rc = hnrf_composite_fwd(pl.raw + (size_t)g * P * 4, c.mask, c.z_vals, rays_d, diag ? cnl_in : nullptr, bgcolor,
-                                     R, S, cull ? cull_eps : 0.f, o.rgb, o.alpha, o.depth, o.weights, o.rgb_on_rays,
-                                     o.cnl_xyz, o.cnl_rgb, o.cnl_weight, st)))
+        if ((rc = hnrf_composite_view_fwd(pl.raw + (size_t)g * P * 4, c.mask, c.z_vals, rays_d, diag ? cnl_in : nullptr,
+                                          bgcolor, pl.view_bias, R, S, cull ? cull_eps : 0.f, o.rgb, o.alpha, o.depth,
+                                          o.weights, o.rgb_on_rays, o.cnl_xyz, o.cnl_rgb, o.cnl_weight, st)))
             return rc;
     }
     return HNRF_OK;
@@ -252,6 +255,7 @@ struct FrameOpts {
     int* live_counts = nullptr;           // shared underflowing inputs: the live count of every chunk (null = off)
     int n_heads = 0;                      // >= 2: every head of a multi-head canonical image, with
     const FrameOut* head_out = nullptr;   // the whole-frame outputs of head g (head_out[0] is `out`)
+    const float* view_bias = nullptr;     // view-dependent colour: the per-ray bias [N][3] of K4 (null = none)
 };
 
 int render_frame(const char* who, const Rays& rays, const WarpField& field, const float* hann_w, const void* nr_packed,
@@ -353,7 +357,7 @@ int render_frame(const char* who, const Rays& rays, const WarpField& field, cons
         FrameOut po[8] = {k.o};                                   // the planes' rows of this chunk
         for (int g = 1; g < n_planes; ++g) po[g] = opt.head_out[g].rows(i * chunk, S, field.B);
         if ((rc = render_chunk(k.c, k.rays.d, hann_w, nr_packed, off, cnl, bgcolor, cmode, cull_eps, k.R, S,
-                               Planes{n_planes, k.raw, po},
+                               Planes{n_planes, k.raw, po, opt.view_bias ? opt.view_bias + 3 * i * chunk : nullptr},
                                mlp_events ? mlp_events[2 * i] : nullptr, mlp_events ? mlp_events[2 * i + 1] : nullptr, st,
                                Share{share ? &k.sh : nullptr, fused}))) return rc;
         if (two) HNRF_HIP(hipEventRecord(ev_done[i & 1], st));
@@ -507,4 +511,36 @@ extern "C" int hnrf_render_frame_baked_nr_fwd(const float* rays_o, const float* 
                         FrameOut{rgb, alpha, depth, weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays,
                                  bmw, offsets},
                         side_stream, events, mlp_events, stream);
+}
+
+// The view path's one frame entry (hnrf_view.h): the frame of whichever of the four single-head entries above its nullable
+// arguments select, with the per-ray colour bias in every chunk's K4.
+extern "C" int hnrf_render_frame_view_fwd(const float* rays_o, const float* rays_d, const float* near, const float* far,
+                                          const float* t_rand, const float* motion_Rs, const float* motion_Ts,
+                                          const float* vol, const float* bbox_min, const float* bbox_scale,
+                                          const float* hann_w, const void* nr_packed, const void* cnl_packed,
+                                          const void* off_grid, int off_M, const float* off_bbox_min,
+                                          const float* off_bbox_max, const void* grid, int grid_N,
+                                          const float* grid_bbox_min, const float* grid_bbox_max, const float* view_bias,
+                                          const float* bgcolor, int mode, float cull_eps, int64_t N, int S, int B, int G,
+                                          int64_t chunk, void* workspace, size_t workspace_bytes, float* rgb, float* alpha,
+                                          float* depth, float* weights_on_rays, float* rgb_on_rays, float* cnl_xyz,
+                                          float* cnl_rgb, float* cnl_weight, float* xyz_on_rays, float* bmw, float* offsets,
+                                          int* live_counts, void* side_stream, void* const* events,
+                                          void* const* mlp_events, void* stream) {
+    const char* who = "hnrf_render_frame_view_fwd";
+    HNRF_REQUIRE(!off_grid || grid, HNRF_E_ARG, "%s: an offset grid needs a canonical grid", who);
+    FrameOpts opt;
+    opt.live_counts = live_counts;
+    opt.view_bias = view_bias;
+    return render_frame(who, Rays{rays_o, rays_d, near, far, t_rand},
+                        WarpField{motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, B, G}, off_grid ? nullptr : hann_w,
+                        off_grid ? nullptr : nr_packed,
+                        off_grid ? BakedGrid{off_grid, off_M, off_bbox_min, off_bbox_max} : kNoOffGrid,
+                        grid ? CnlSource{nullptr, grid, grid_N, grid_bbox_min, grid_bbox_max}
+                             : CnlSource{cnl_packed, nullptr, 0, nullptr, nullptr},
+                        bgcolor, mode, cull_eps, N, S, chunk, workspace, workspace_bytes,
+                        FrameOut{rgb, alpha, depth, weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, xyz_on_rays,
+                                 bmw, offsets},
+                        side_stream, events, mlp_events, stream, opt);
 }

@@ -19,9 +19,9 @@ namespace hnrf {
 template <int SPL>
 __global__ __launch_bounds__(256) void composite_bwd_kernel(
     const float4* __restrict__ raw, const float* __restrict__ fg_mask, const float* __restrict__ z_vals,
-    const float* __restrict__ rays_d, const float* __restrict__ bgcolor, const float* __restrict__ g_rgb,
-    const float* __restrict__ g_alpha, const float* __restrict__ g_depth, int64_t R, int S,
-    float4* __restrict__ d_raw, float* __restrict__ d_mask) {
+    const float* __restrict__ rays_d, const float* __restrict__ bgcolor, const float* __restrict__ view_bias,
+    const float* __restrict__ g_rgb, const float* __restrict__ g_alpha, const float* __restrict__ g_depth, int64_t R, int S,
+    float4* __restrict__ d_raw, float* __restrict__ d_mask, float* __restrict__ d_bias) {
     const int lane = threadIdx.x & 63;
     const int64_t ray = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     if (ray >= R) return;
@@ -31,6 +31,9 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
     const float bg0 = bgcolor[0] / 255.f, bg1 = bgcolor[1] / 255.f, bg2 = bgcolor[2] / 255.f;
     const float gr = g_rgb[ray * 3 + 0], gg = g_rgb[ray * 3 + 1], gb = g_rgb[ray * 3 + 2];
     const float ga = g_alpha ? g_alpha[ray] : 0.f, gd = g_depth ? g_depth[ray] : 0.f;
+    // view-dependent colour (hnrf_view.h): the forward's per-ray bias in the sigmoids; null (wave-uniform) = none
+    float vb0 = 0.f, vb1 = 0.f, vb2 = 0.f;
+    if (view_bias) { vb0 = view_bias[ray * 3 + 0]; vb1 = view_bias[ray * 3 + 1]; vb2 = view_bias[ray * 3 + 2]; }
 
     float zv[SPL], al[SPL], ee[SPL], dl[SPL], cr[SPL], cg[SPL], cb[SPL], mk[SPL];
     float4 rw[SPL];
@@ -39,6 +42,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
         const int s = lane * SPL + i;
         const int sc = s < S ? s : S - 1;
         rw[i] = raw[base + sc];
+        if (view_bias) { rw[i].x += vb0; rw[i].y += vb1; rw[i].z += vb2; }
         mk[i] = s < S ? fg_mask[base + sc] : 0.f;
         zv[i] = z_vals[base + sc];
     }
@@ -91,6 +95,7 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
     }
     float after = __shfl_down(suf, 1, 64);   // sum over later lanes
     if (lane == 63) after = 0.f;
+    float b0 = 0.f, b1 = 0.f, b2 = 0.f;      // d_bias: this lane's sum of d_raw.xyz
 #pragma unroll
     for (int i = SPL - 1; i >= 0; --i) {
         const int s = lane * SPL + i;
@@ -106,6 +111,22 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
             o.w = dsig;
             d_raw[base + s] = o;
             d_mask[base + s] = da * (1.0f - ee[i]);
+            b0 += o.x;
+            b1 += o.y;
+            b2 += o.z;
+        }
+    }
+    if (d_bias) {                             // (wave-uniform)
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            b0 += __shfl_xor(b0, off, 64);
+            b1 += __shfl_xor(b1, off, 64);
+            b2 += __shfl_xor(b2, off, 64);
+        }
+        if (lane == 0) {
+            d_bias[ray * 3 + 0] = b0;
+            d_bias[ray * 3 + 1] = b1;
+            d_bias[ray * 3 + 2] = b2;
         }
     }
 }
@@ -314,28 +335,46 @@ __global__ __launch_bounds__(NTH) void sample_warp_bwd_kernel(
 
 using namespace hnrf;
 
-extern "C" int hnrf_composite_bwd(const float* raw, const float* fg_mask, const float* z_vals, const float* rays_d,
-                                  const float* bgcolor, const float* g_rgb, const float* g_alpha,
-                                  const float* g_depth, int64_t R, int S, float* d_raw, float* d_mask,
-                                  void* stream) {
+// hnrf_composite_bwd and -- view_bias, d_bias -- hnrf_composite_view_bwd: one body, one launch
+static int composite_bwd(const char* who, const float* raw, const float* fg_mask, const float* z_vals, const float* rays_d,
+                         const float* bgcolor, const float* view_bias, const float* g_rgb, const float* g_alpha,
+                         const float* g_depth, int64_t R, int S, float* d_raw, float* d_mask, float* d_bias,
+                         void* stream) {
     HNRF_REQUIRE(raw && fg_mask && z_vals && rays_d && bgcolor && g_rgb && d_raw && d_mask, HNRF_E_ARG,
-                 "hnrf_composite_bwd: null pointer");
-    HNRF_REQUIRE(R >= 0 && S >= 2, HNRF_E_ARG, "hnrf_composite_bwd: bad dims");
-    HNRF_REQUIRE(S <= 512, HNRF_E_UNSUPPORTED, "hnrf_composite_bwd: S=%d > 512 not built", S);
-    HNRF_REQUIRE((((uintptr_t)raw | (uintptr_t)d_raw) & 15) == 0, HNRF_E_ARG, "hnrf_composite_bwd: raw/d_raw alignment");
+                 "%s: null pointer", who);
+    HNRF_REQUIRE(R >= 0 && S >= 2, HNRF_E_ARG, "%s: bad dims", who);
+    HNRF_REQUIRE(S <= 512, HNRF_E_UNSUPPORTED, "%s: S=%d > 512 not built", who, S);
+    HNRF_REQUIRE((((uintptr_t)raw | (uintptr_t)d_raw) & 15) == 0, HNRF_E_ARG, "%s: raw/d_raw alignment", who);
     if (R == 0) return HNRF_OK;
     const int64_t blocks = (R + 3) / 4;
     hipStream_t st = (hipStream_t)stream;
     const int spl = (S + 63) / 64;
 #define HNRF_LAUNCH_CB(N)                                                                                          \
     hipLaunchKernelGGL(composite_bwd_kernel<N>, dim3((unsigned)blocks), dim3(256), 0, st, (const float4*)raw,     \
-                       fg_mask, z_vals, rays_d, bgcolor, g_rgb, g_alpha, g_depth, R, S, (float4*)d_raw, d_mask)
+                       fg_mask, z_vals, rays_d, bgcolor, view_bias, g_rgb, g_alpha, g_depth, R, S, (float4*)d_raw, d_mask,   \
+                       d_bias)
     if (spl <= 1) HNRF_LAUNCH_CB(1);
     else if (spl <= 2) HNRF_LAUNCH_CB(2);
     else if (spl <= 4) HNRF_LAUNCH_CB(4);
     else HNRF_LAUNCH_CB(8);
 #undef HNRF_LAUNCH_CB
-    return check_launch("hnrf_composite_bwd");
+    return check_launch(who);
+}
+
+extern "C" int hnrf_composite_bwd(const float* raw, const float* fg_mask, const float* z_vals, const float* rays_d,
+                                  const float* bgcolor, const float* g_rgb, const float* g_alpha,
+                                  const float* g_depth, int64_t R, int S, float* d_raw, float* d_mask,
+                                  void* stream) {
+    return composite_bwd("hnrf_composite_bwd", raw, fg_mask, z_vals, rays_d, bgcolor, nullptr, g_rgb, g_alpha, g_depth, R,
+                         S, d_raw, d_mask, nullptr, stream);
+}
+
+extern "C" int hnrf_composite_view_bwd(const float* raw, const float* fg_mask, const float* z_vals, const float* rays_d,
+                                       const float* bgcolor, const float* view_bias, const float* g_rgb,
+                                       const float* g_alpha, const float* g_depth, int64_t R, int S, float* d_raw,
+                                       float* d_mask, float* d_bias, void* stream) {
+    return composite_bwd("hnrf_composite_view_bwd", raw, fg_mask, z_vals, rays_d, bgcolor, view_bias, g_rgb, g_alpha,
+                         g_depth, R, S, d_raw, d_mask, d_bias, stream);
 }
 
 extern "C" int hnrf_pe_bwd(const float* x, const float* g, const float* hann_w, int64_t P, int n_bands,

@@ -19,7 +19,7 @@ template <int SPL>
 __global__ __launch_bounds__(256) void composite_kernel(
     const float4* __restrict__ raw, const float* __restrict__ fg_mask, const float* __restrict__ z_vals,
     const float* __restrict__ rays_d, const float* __restrict__ xyz, const float* __restrict__ bgcolor,
-    int64_t R, int S, float cull_eps,
+    const float* __restrict__ view_bias, int64_t R, int S, float cull_eps,
     float* __restrict__ rgb_out, float* __restrict__ alpha_out, float* __restrict__ depth_out,
     float* __restrict__ weights_out, float* __restrict__ rgb_on_rays,
     float* __restrict__ cnl_xyz, float* __restrict__ cnl_rgb, float* __restrict__ cnl_weight) {
@@ -30,6 +30,9 @@ __global__ __launch_bounds__(256) void composite_kernel(
     const float dx = rays_d[ray * 3 + 0], dy = rays_d[ray * 3 + 1], dz = rays_d[ray * 3 + 2];
     const float dnorm = sqrtf(dx * dx + dy * dy + dz * dz);
     const int64_t base = ray * S;
+    // view-dependent colour (hnrf_view.h): three floats per ray in front of the sigmoid; null (wave-uniform) = none
+    float vb0 = 0.f, vb1 = 0.f, vb2 = 0.f;
+    if (view_bias) { vb0 = view_bias[ray * 3 + 0]; vb1 = view_bias[ray * 3 + 1]; vb2 = view_bias[ray * 3 + 2]; }
 
     float zv[SPL], al[SPL], cr[SPL], cg[SPL], cb[SPL];
     float4 rw[SPL];
@@ -40,6 +43,7 @@ __global__ __launch_bounds__(256) void composite_kernel(
         const bool ok = s < S;
         const int sc = ok ? s : S - 1;
         rw[i] = raw[base + sc];
+        if (view_bias) { rw[i].x += vb0; rw[i].y += vb1; rw[i].z += vb2; }
         mk[i] = ok ? fg_mask[base + sc] : 0.f;
         zv[i] = z_vals[base + sc];
     }
@@ -139,6 +143,38 @@ __global__ __launch_bounds__(256) void composite_kernel(
 
 }  // namespace hnrf
 
+// hnrf_composite_fwd and -- view_bias -- hnrf_composite_view_fwd: one body, one launch
+static int composite_fwd(const char* who, const float* raw, const float* fg_mask, const float* z_vals,
+                         const float* rays_d, const float* xyz, const float* bgcolor, const float* view_bias,
+                         int64_t R, int S, float cull_eps,
+                         float* rgb, float* alpha, float* depth,
+                         float* weights, float* rgb_on_rays,
+                         float* cnl_xyz, float* cnl_rgb, float* cnl_weight,
+                         void* stream) {
+    using namespace hnrf;
+    HNRF_REQUIRE(raw && fg_mask && z_vals && rays_d && bgcolor, HNRF_E_ARG, "%s: null input pointer", who);
+    HNRF_REQUIRE(rgb && alpha && depth, HNRF_E_ARG, "%s: null output pointer", who);
+    HNRF_REQUIRE(!(cnl_xyz && !xyz), HNRF_E_ARG, "%s: cnl_xyz requested without xyz", who);
+    HNRF_REQUIRE(R >= 0 && S >= 2, HNRF_E_ARG, "%s: bad dims R=%lld S=%d", who, (long long)R, S);
+    HNRF_REQUIRE(S <= 512, HNRF_E_UNSUPPORTED, "%s: S=%d > 512 samples per ray not built", who, S);
+    HNRF_REQUIRE(((uintptr_t)raw & 15) == 0, HNRF_E_ARG, "%s: raw must be 16-byte aligned", who);
+    if (R == 0) return HNRF_OK;
+    const int64_t blocks = (R + 3) / 4;
+    HNRF_REQUIRE(blocks < (int64_t)2147483647, HNRF_E_ARG, "%s: too many rays", who);
+    hipStream_t st = (hipStream_t)stream;
+    const int spl = (S + 63) / 64;
+#define HNRF_LAUNCH_COMPOSITE(N)                                                                                  \
+    hipLaunchKernelGGL(composite_kernel<N>, dim3((unsigned)blocks), dim3(256), 0, st, (const float4*)raw, fg_mask, \
+                       z_vals, rays_d, xyz, bgcolor, view_bias, R, S, cull_eps, rgb, alpha, depth, weights, rgb_on_rays, cnl_xyz,      \
+                       cnl_rgb, cnl_weight)
+    if (spl <= 1) HNRF_LAUNCH_COMPOSITE(1);
+    else if (spl <= 2) HNRF_LAUNCH_COMPOSITE(2);
+    else if (spl <= 4) HNRF_LAUNCH_COMPOSITE(4);
+    else HNRF_LAUNCH_COMPOSITE(8);
+#undef HNRF_LAUNCH_COMPOSITE
+    return check_launch(who);
+}
+
 extern "C" int hnrf_composite_fwd(const float* raw, const float* fg_mask, const float* z_vals,
                                   const float* rays_d, const float* xyz, const float* bgcolor,
                                   int64_t R, int S, float cull_eps,
@@ -146,26 +182,15 @@ extern "C" int hnrf_composite_fwd(const float* raw, const float* fg_mask, const 
                                   float* weights, float* rgb_on_rays,
                                   float* cnl_xyz, float* cnl_rgb, float* cnl_weight,
                                   void* stream) {
-    using namespace hnrf;
-    HNRF_REQUIRE(raw && fg_mask && z_vals && rays_d && bgcolor, HNRF_E_ARG, "hnrf_composite_fwd: null input pointer");
-    HNRF_REQUIRE(rgb && alpha && depth, HNRF_E_ARG, "hnrf_composite_fwd: null output pointer");
-    HNRF_REQUIRE(!(cnl_xyz && !xyz), HNRF_E_ARG, "hnrf_composite_fwd: cnl_xyz requested without xyz");
-    HNRF_REQUIRE(R >= 0 && S >= 2, HNRF_E_ARG, "hnrf_composite_fwd: bad dims R=%lld S=%d", (long long)R, S);
-    HNRF_REQUIRE(S <= 512, HNRF_E_UNSUPPORTED, "hnrf_composite_fwd: S=%d > 512 samples per ray not built", S);
-    HNRF_REQUIRE(((uintptr_t)raw & 15) == 0, HNRF_E_ARG, "hnrf_composite_fwd: raw must be 16-byte aligned");
-    if (R == 0) return HNRF_OK;
-    const int64_t blocks = (R + 3) / 4;
-    HNRF_REQUIRE(blocks < (int64_t)2147483647, HNRF_E_ARG, "hnrf_composite_fwd: too many rays");
-    hipStream_t st = (hipStream_t)stream;
-    const int spl = (S + 63) / 64;
-#define HNRF_LAUNCH_COMPOSITE(N)                                                                                  \
-    hipLaunchKernelGGL(composite_kernel<N>, dim3((unsigned)blocks), dim3(256), 0, st, (const float4*)raw, fg_mask, \
-                       z_vals, rays_d, xyz, bgcolor, R, S, cull_eps, rgb, alpha, depth, weights, rgb_on_rays, cnl_xyz,      \
-                       cnl_rgb, cnl_weight)
-    if (spl <= 1) HNRF_LAUNCH_COMPOSITE(1);
-    else if (spl <= 2) HNRF_LAUNCH_COMPOSITE(2);
-    else if (spl <= 4) HNRF_LAUNCH_COMPOSITE(4);
-    else HNRF_LAUNCH_COMPOSITE(8);
-#undef HNRF_LAUNCH_COMPOSITE
-    return check_launch("hnrf_composite_fwd");
+    return composite_fwd("hnrf_composite_fwd", raw, fg_mask, z_vals, rays_d, xyz, bgcolor, nullptr, R, S, cull_eps, rgb,
+                         alpha, depth, weights, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, stream);
+}
+
+extern "C" int hnrf_composite_view_fwd(const float* raw, const float* fg_mask, const float* z_vals, const float* rays_d,
+                                       const float* xyz, const float* bgcolor, const float* view_bias, int64_t R, int S,
+                                       float cull_eps, float* rgb, float* alpha, float* depth, float* weights,
+                                       float* rgb_on_rays, float* cnl_xyz, float* cnl_rgb, float* cnl_weight,
+                                       void* stream) {
+    return composite_fwd("hnrf_composite_view_fwd", raw, fg_mask, z_vals, rays_d, xyz, bgcolor, view_bias, R, S, cull_eps,
+                         rgb, alpha, depth, weights, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight, stream);
 }

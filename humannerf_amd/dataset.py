@@ -121,6 +121,20 @@ def apply_global_tfm_to_camera(E, Rh, Th):
     return np.asarray(E).dot(np.linalg.inv(g))
 
 
+def view_camera_only():
+    """True when view-dependent colour is built and asks for the camera's own directions (canonical_mlp.view_dir with
+    cfg.amd.view_dir, and view_dir_camera_only): the third row of a train / movement frame's ``rays`` is then the
+    reference's rays_d_camera (train.py:562-565), not a copy of row 1."""
+    cm, amd = cfg.get('canonical_mlp', {}), cfg.get('amd', {})
+    return bool(cm.get('view_dir', False)) and bool(amd.get('view_dir', False)) and bool(cm.get('view_dir_camera_only', False))
+
+
+def camera_turn(E_camera, E):
+    """The rotation M (3, 3) with d_camera = M d for the ray directions of one pixel under the extrinsics ``E_camera``
+    (before apply_global_tfm_to_camera) and ``E`` (after): get_rays_from_KRT gives d = R^T K^-1 pix, so M = R_camera^T R."""
+    return np.asarray(E_camera, dtype=np.float64)[:3, :3].T.dot(np.asarray(E, dtype=np.float64)[:3, :3])
+
+
 def rotate_camera_by_frame_idx(extrinsics, frame_idx, trans=None, rotate_axis='y', period=196, inv_angle=False):
     """Orbit of the free-viewpoint renderer (camera_util.py:6-48, 82-114)."""
     angle = 2 * np.pi * (frame_idx / period)
@@ -258,20 +272,29 @@ class Subject:
                 'cnl_bbox_min_xyz': mn, 'cnl_bbox_max_xyz': mx,           # renderer keeps it resident by identity
                 'cnl_bbox_scale_xyz': scale, 'dst_posevec': poses[3:] + 1e-2}
 
-    def _camera_entries(self, K, E, info, H, W, host_rays):
-        """K already scaled to the image size; E with the global transform applied."""
+    def _camera_entries(self, K, E, info, H, W, host_rays, E_camera=None):
+        """K already scaled to the image size; E with the global transform applied.  ``E_camera`` (train and movement
+        frames with view_camera_only()): the extrinsics BEFORE that transform -- the third row of ``rays`` is then the
+        directions under them (train.py:562-565), same pixels as rows 0 and 1; a camera-only frame carries the rotation
+        between the two instead (``camera_turn``: ops.gen_rays turns row 1 by it)."""
         bbox = info['bbox']
         out = {'img_width': int(W), 'img_height': int(H)}
         if not host_rays:
             out.update(K=K.astype('float32'), E=E.astype('float32'),
                        ray_bbox_min_xyz=np.asarray(bbox['min_xyz'], 'float32'),
                        ray_bbox_max_xyz=np.asarray(bbox['max_xyz'], 'float32'))
+            if E_camera is not None:
+                out['camera_turn'] = camera_turn(E_camera, E).astype('float32')
             return out
         rays_o, rays_d = scene.get_rays_from_KRT(H, W, K, E[:3, :3], E[:3, 3])
         rays_o, rays_d = rays_o.reshape(-1, 3).copy(), rays_d.reshape(-1, 3).copy()
         near, far, ray_mask = scene.rays_intersect_3d_bbox(bbox, rays_o, rays_d)
         rays_o, rays_d = rays_o[ray_mask], rays_d[ray_mask]
-        out.update(rays=np.stack([rays_o, rays_d, rays_d], axis=0).astype('float32'),      # [o, d, d_camera]: SURVEY 2.3
+        rays_d_camera = rays_d
+        if E_camera is not None:
+            E_camera = np.asarray(E_camera)
+            rays_d_camera = scene.get_rays_from_KRT(H, W, K, E_camera[:3, :3], E_camera[:3, 3])[1].reshape(-1, 3)[ray_mask]
+        out.update(rays=np.stack([rays_o, rays_d, rays_d_camera], axis=0).astype('float32'),   # [o, d, d_camera]: SURVEY 2.3
                    near=near[:, None].astype('float32'), far=far[:, None].astype('float32'), ray_mask=ray_mask)
         return out
 
@@ -300,7 +323,7 @@ class Subject:
         K = cam['intrinsics'][:3, :3].copy()
         K[:2] *= cfg.get('resize_img_scale', 1.0)
         E = apply_global_tfm_to_camera(cam['extrinsics'], info['Rh'].astype('float32'), info['Th'].astype('float32'))
-        out.update(self._camera_entries(K, E, info, H, W, host_rays))
+        out.update(self._camera_entries(K, E, info, H, W, host_rays, cam['extrinsics'] if view_camera_only() else None))
         out.update(self._skeleton_entries(info))
         if img is not None:
             out['raw_rgbs'] = img
@@ -358,7 +381,7 @@ class Subject:
         K = cam['intrinsics'][:3, :3].copy()
         K[:2] *= cfg.get('resize_img_scale', 1.0)
         E = apply_global_tfm_to_camera(cam['extrinsics'], info['Rh'].astype('float32'), info['Th'].astype('float32'))
-        ent = self._camera_entries(K, E, info, H, W, host_rays=True)
+        ent = self._camera_entries(K, E, info, H, W, True, cam['extrinsics'] if view_camera_only() else None)
         ray_mask = ent['ray_mask']
         sel, pinfo, div = scene.sample_patch_rays(ray_mask, alpha[:, :, 0] > 0., ray_mask.reshape(H, W),
                                                   int(cfg.patch.N_patches), int(cfg.patch.size), H, W,
@@ -477,6 +500,8 @@ class DeviceFrameCache:
                'ray_mask': g['ray_mask'], 'orig': o, 'alpha': a,
                'parity': 'exact' if lens is None and scale == 1.0 else 'unpinned',
                'sampler': scene.PatchSampler(ray_mask, subject_mask, ray_mask.reshape(H, W), H, W),
+               # d_camera = M d (camera_turn): the camera's own directions for view_camera_only(), per item from row 1
+               'camera_turn': up(camera_turn(cam['extrinsics'], E).astype('float32')),
                'skeleton': {k: torch.as_tensor(np.ascontiguousarray(v)).to(dev)
                             for k, v in subj._skeleton_entries(info).items()}}
         ent['bytes'] = sum(v.numel() * v.element_size() for v in ent.values() if torch.is_tensor(v))
@@ -519,7 +544,8 @@ class DeviceFrameCache:
         size = int(cfg.patch.size)
         targets = ops.composite_windows(ent['orig'], ent['alpha'], bg_d, pinfo['xy_min'], size, size, scale=ent['scale'])
         out = {'frame_name': ent['name'], 'bgcolor': bg_d, 'img_width': ent['W'], 'img_height': ent['H'],
-               'ray_mask': ent['ray_mask'], 'rays': torch.stack([o, d, d], 0),
+               'ray_mask': ent['ray_mask'],
+               'rays': torch.stack([o, d, d @ ent['camera_turn'].t() if view_camera_only() else d], 0),
                'near': ent['near'].index_select(0, sel_d), 'far': ent['far'].index_select(0, sel_d),
                'patch_div_indices': torch.from_numpy(div), 'patch_masks': masks_d, 'target_patches': targets,
                'target_rgbs': targets.reshape(-1, 3).index_select(0, flat_d), 'resize_parity': ent['parity']}

@@ -26,7 +26,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
-from .autograd import RenderRays
+from .autograd import RenderRays, ViewBias
 from .config import cfg, amd_option, check_amd_options
 from .kept import Kept, _resident, _still_resident     # noqa: F401  (the rule keeps its name here for its importers)
 from .range_guard import ActivationRangeError, InferenceRangeGuard     # noqa: F401  (the error's importers look here)
@@ -115,7 +115,10 @@ class _NonRigidParams(nn.Module):
 class _CanonicalParams(nn.Module):
     """Parameters of CanonicalMLP default branch (canonical_mlps/mlp_rgb_sigma.py:64-99)."""
 
-    def __init__(self, input_ch, mlp_depth, mlp_width, skips, n_heads=1):
+    def __init__(self, input_ch, mlp_depth, mlp_width, skips, n_heads=1, view_ch=0):
+        """``view_ch`` > 0: the view branch (mlp_rgb_sigma.py:85-96) on a direction embedding of that many columns --
+        output_linear_density, output_linear_rgb_1, output_linear_rgb_2 in the place of output_linear, under the
+        reference's names and with nn.Linear's default initialisation (initseq touches pts_linears only there)."""
         super().__init__()
         if not (input_ch == 63 and mlp_depth == 8 and mlp_width == 256 and list(skips) == [4]):
             raise NotImplementedError('only the default canonical MLP (8x256, skip 4, PE63) is built')
@@ -125,12 +128,59 @@ class _CanonicalParams(nn.Module):
             mods += [nn.Linear(n_in, mlp_width), nn.ReLU()]
         self.pts_linears = nn.ModuleList(mods)
         _init_sequence(self.pts_linears)
+        self.view_ch = int(view_ch)
+        if self.view_ch:
+            assert n_heads == 1, 'Unsupported multihead+view-dependent rgb'          # (mlp_rgb_sigma.py:86)
+            self.output_linear_density = nn.Sequential(nn.Linear(mlp_width, 1))
+            self.output_linear_rgb_1 = nn.Sequential(nn.Linear(mlp_width, mlp_width))
+            self.output_linear_rgb_2 = nn.Sequential(nn.Linear(mlp_width + self.view_ch, mlp_width), nn.Linear(mlp_width, 3))
+            return
         # multihead, head_depth 1 (mlp_rgb_sigma.py:114-115): head g is rows 4g .. 4g+3
         self.output_linear = nn.Sequential(nn.Linear(mlp_width, 4 * n_heads))
         _init_sequence(self.output_linear)
 
+    def trunk(self):
+        return [m for m in self.pts_linears if isinstance(m, nn.Linear)]
+
     def linears(self):
-        return [m for m in self.pts_linears if isinstance(m, nn.Linear)] + [self.output_linear[0]]
+        """The nine layers every kernel knows.  With the view branch there is no ninth: its place is taken by the folded
+        head (fold_view_branch), which Network states once (_cnl_layers)."""
+        if self.view_ch:
+            raise RuntimeError('the canonical MLP has a view branch: its head is folded from view_layers() '
+                               '(network.fold_view_branch), there is no output_linear')
+        return self.trunk() + [self.output_linear[0]]
+
+    def view_layers(self):
+        """output_linear_density.0, output_linear_rgb_1.0, output_linear_rgb_2.0, output_linear_rgb_2.1"""
+        return [self.output_linear_density[0], self.output_linear_rgb_1[0], self.output_linear_rgb_2[0],
+                self.output_linear_rgb_2[1]]
+
+
+def fold_view_branch(density, rgb_1, rgb_2a, rgb_2b, dtype=None):
+    """The view branch of the reference's CanonicalMLP has no non-linearity behind the trunk output h
+    (mlp_rgb_sigma.py:168-178):  density = Wd h + bd,  rgb = W3 (W2 [W1 h + b1 ; e(d)] + b2) + b3.  So
+        raw = [A ; Wd] h + [c ; bd] + (B e(d), 0),   A = W3 W2[:, :n] W1,  B = W3 W2[:, n:],  c = W3 (W2[:, :n] b1 + b2) + b3.
+    Returns (head weight (4, n) = A | Wd, head bias (4,) = c | bd, B (3, view_ch)) from the four layers (modules, or
+    (weight, bias) pairs), in plain torch ops: under autograd the gradient goes back to the four layers.  ``dtype``: the
+    arithmetic (inference folds in float64 and rounds once); None = the parameters' own."""
+    pair = lambda l: (l.weight, l.bias) if hasattr(l, 'weight') else l
+    cast = (lambda t: t) if dtype is None else (lambda t: t.to(dtype))
+    (Wd, bd), (W1, b1), (W2, b2), (W3, b3) = [tuple(cast(t) for t in pair(l)) for l in (density, rgb_1, rgb_2a, rgb_2b)]
+    n = W1.shape[0]
+    W32 = W3 @ W2[:, :n]
+    A, B = W32 @ W1, W3 @ W2[:, n:]
+    c = W32 @ b1 + W3 @ b2 + b3
+    return torch.cat([A, Wd], dim=0), torch.cat([c, bd.reshape(1)], dim=0), B.contiguous()
+
+
+def view_embedding(dirs, bands):
+    """e(d) of the reference (network.py:499-507 + fourier.py): normalize(d), then per band sin(2^k n), cos(2^k n).
+    dirs (..., 3) -> (..., 3 + 6 bands), in dirs' dtype: the host statement of what hnrf_view_bias_fwd embeds."""
+    n = F.normalize(dirs, dim=-1)
+    parts = [n]
+    for k in range(bands):
+        parts += [torch.sin(n * (2.0 ** k)), torch.cos(n * (2.0 ** k))]
+    return torch.cat(parts, dim=-1)
 
 
 _POINT_CONV = True       # (A/B switch of the 1x1x1 special case, profiles/tools/ab_pose.py)
@@ -464,6 +514,17 @@ _BUILT_BRANCHES = (
 )
 
 
+VIEW_BANDS_MIN, VIEW_BANDS_MAX = 1, 10   # multires_dir of the view branch (hnrf_view.h)
+
+
+def view_dir_bands(config):
+    """Bands L of the direction embedding (3 + 6 L columns) when ``config`` selects view-dependent colour AND opts in
+    (``canonical_mlp.view_dir`` with ``amd.view_dir``), else 0.  check_config_is_built says which values are built."""
+    if not (bool(_node(config, 'canonical_mlp.view_dir', False)) and bool(_node(config, 'amd.view_dir', False))):
+        return 0
+    return _node(config, 'canonical_mlp.multires_dir', 4)
+
+
 HEADS_MIN, HEADS_MAX = 2, 8         # the canonical MLP's head layer is one 32-row MFMA tile: up to 8 heads x 4 outputs
 
 
@@ -490,14 +551,29 @@ def check_config_is_built(config):
         depth = _node(config, 'canonical_mlp.multihead.head_depth', 1)
         if depth != 1:
             bad.append('canonical_mlp.multihead.head_depth = %r (built: 1)' % (depth,))
+    # view-dependent colour: built behind the opt-in amd.view_dir (DESIGN.md section 4 "View-dependent colour")
+    view = bool(_node(config, 'canonical_mlp.view_dir', False)) and bool(_node(config, 'amd.view_dir', False))
+    if view:
+        if bool(_node(config, 'canonical_mlp.multihead.enable', False)):
+            bad.append('canonical_mlp.view_dir = True with canonical_mlp.multihead.enable = True (the reference refuses '
+                       'multihead + view-dependent rgb itself)')
+        embed = _node(config, 'canonical_mlp.view_embed', 'mlp')
+        if embed != 'mlp':
+            bad.append("canonical_mlp.view_embed = %r (built: 'mlp'; 'vocab' is not)" % (embed,))
+        L = view_dir_bands(config)
+        if isinstance(L, bool) or not isinstance(L, int) or not VIEW_BANDS_MIN <= L <= VIEW_BANDS_MAX:
+            bad.append('canonical_mlp.multires_dir = %r (built: an int in %d..%d)' % (L, VIEW_BANDS_MIN, VIEW_BANDS_MAX))
     for path, want in _BUILT_BRANCHES:
+        if view and path == 'canonical_mlp.view_dir':
+            continue
         have = _node(config, path, want)
         if path.endswith('.module'):
             have = str(have).split('.')[-1]
         if isinstance(want, bool):
             have = bool(have)
         if have != want:
-            bad.append('%s = %r (built: %r)' % (path, have, want))
+            bad.append('%s = %r (built: %r%s)' % (path, have, want, ', or True with the opt-in cfg.amd.view_dir = True'
+                                                  if path == 'canonical_mlp.view_dir' else ''))
     if bad:
         raise NotImplementedError('configuration selects branches outside the hot path this build implements '
                                   '(SURVEY.md section 2.1): ' + '; '.join(bad))
@@ -519,9 +595,11 @@ class Network(nn.Module):
             mlp_width=nr.mlp_width, mlp_depth=nr.mlp_depth, skips=nr.skips))
         # heads of the canonical MLP: 0 = the single-head network, else 2..8 (select_head / forward's head_id)
         self.head_num = canonical_head_num(cfg)
+        # bands of the view branch's direction embedding: 0 = colour does not depend on the view (fixed_view / forward)
+        self.view_bands = view_dir_bands(cfg)
         self.cnl_mlp = _Replicated(_CanonicalParams(
             input_ch=3 + 6 * cm.multires, mlp_depth=cm.mlp_depth, mlp_width=cm.mlp_width, skips=[4],
-            n_heads=max(self.head_num, 1)))
+            n_heads=max(self.head_num, 1), view_ch=3 + 6 * self.view_bands if self.view_bands else 0))
         if not cfg.get('pose_decoder_off', False):
             self.pose_decoder = BodyPoseRefiner(
                 embedding_size=cfg.pose_decoder.embedding_size, mlp_width=cfg.pose_decoder.mlp_width,
@@ -539,6 +617,8 @@ class Network(nn.Module):
         self._weights_gen = 0
         # the head that _canonical_packed() packs outside forward (select_head), None = not chosen
         self._head = None
+        # the direction fixed_view chose for colour evaluated without a ray (a tuple of three floats), None = not chosen
+        self._view = None
         self._nr_pack_buf = None
         self.f16_guard = InferenceRangeGuard()
         # the bakes this network ran, and the resident workspace of the offset grid's bake
@@ -609,13 +689,14 @@ class Network(nn.Module):
             self._drop(lambda e: e.packed is not None)          # (a fresh pack clears the canonical image's word)
         return self.f16_guard.act(*hit)
 
-    def _canonical_pass(self, op):
-        """``op(packed canonical image, mode)`` of a canonical-MLP pass outside forward, with its status word acted on
+    def _canonical_pass(self, op, colour=None):
+        """``op(packed canonical image, mode)`` of a canonical-MLP pass outside forward (``colour``: _canonical_packed's),
+        with its status word acted on
         exactly as forward does (cfg.amd.on_f16_range: raise, warn and switch to 'f32', or ignore): after a hit that
         forced another mode the pass runs again in that mode, so the result returned is one of _mlp_mode().  Waits
         for the device."""
         while True:
-            mode, packed = self._mlp_mode(), self._canonical_packed()
+            mode, packed = self._mlp_mode(), self._canonical_packed(colour)
             res = op(packed, mode)
             if mode != 'f16x3':
                 return res
@@ -664,20 +745,80 @@ class Network(nn.Module):
             raise ValueError('head_id %d outside -1..%d' % (h, self.head_num - 1))
         return h
 
-    def _canonical_packed(self):
+    def fixed_view(self, direction):
+        """Choose the viewing direction (3 numbers, any length; observation space) of a view-dependent canonical MLP for
+        everything that evaluates colour without a ray -- mesh and glTF vertex colours, the raster preview, bake_canonical
+        called directly -- in the manner of select_head; None drops the choice.  B e(direction) is folded into the colour
+        bias of the packed image (a host-side add), so every kernel works on it unchanged.  forward never uses it: there
+        every ray brings its own direction."""
+        if direction is not None:
+            if not self.view_bands:
+                raise ValueError('fixed_view: the canonical MLP has no view branch (canonical_mlp.view_dir with '
+                                 'cfg.amd.view_dir is off)')
+            d = torch.as_tensor(direction, dtype=torch.float64).detach().cpu().reshape(-1)
+            if d.numel() != 3 or not bool(torch.isfinite(d).all()):
+                raise ValueError('fixed_view: a direction of three finite numbers, got %r' % (direction,))
+            direction = tuple(float(x) for x in d)
+        self._view = direction
+        return self
+
+    def _cnl_params(self, biases=True):
+        """The canonical MLP's parameters, trunk first, weights then (``biases``) biases: what every entry derived from
+        it is keyed on (the RAW parameters, with the view branch its four layers, never the folded tensors)."""
+        cm = self.cnl_mlp.module
+        lin = cm.trunk() + (cm.view_layers() if self.view_bands else [cm.output_linear[0]])
+        return [l.weight for l in lin] + ([l.bias for l in lin] if biases else [])
+
+    def _view_fold(self):
+        """(head weight (4, 256), head bias (4,), B (3, 3 + 6 L), zeros (3,)) of the view branch for inference: folded in
+        float64 from the detached layers, rounded to fp32 once, kept until the four layers change."""
+        layers = self.cnl_mlp.module.view_layers()
+        params = [t for l in layers for t in (l.weight, l.bias)]
+        ent = self._kept.get('view_fold')
+        if ent is None or not ent.built_from(None, self._weights_gen, params):
+            with torch.no_grad():
+                hw, hb, B = fold_view_branch(*[(l.weight.detach(), l.bias.detach()) for l in layers], dtype=torch.float64)
+                value = (hw.float().contiguous(), hb.float().contiguous(), B.float().contiguous(), hb.new_zeros(3).float())
+            ent = self._kept['view_fold'] = Kept(None, self._weights_gen, params, value=value)
+        return ent.value
+
+    def _cnl_layers(self, colour=None):
+        """(weights, biases) of the nine layers the kernels know, detached: the parameters themselves, or with the view
+        branch the trunk and the folded head -- ``colour`` 'fixed': with B e(fixed_view's direction) in its colour bias."""
+        cm = self.cnl_mlp.module
+        if not self.view_bands:
+            lin = cm.linears()
+            return [l.weight.detach() for l in lin], [l.bias.detach() for l in lin]
+        hw, hb, B, _ = self._view_fold()
+        if colour == 'fixed':
+            e = view_embedding(torch.tensor(self._view, dtype=torch.float64), self.view_bands)
+            hb = hb.clone()
+            hb[:3] += (B.double().cpu() @ e).float().to(hb.device)
+        lin = cm.trunk()
+        return [l.weight.detach() for l in lin] + [hw], [l.bias.detach() for l in lin] + [hb]
+
+    def _canonical_packed(self, colour=None):
         """The packed canonical image: of all rows on the single-head network (no head: None in the key), else of the
         selected head (ops.canonical_pack on its four rows) or with head -1 the all-heads image
-        (ops.canonical_heads_pack); one kept image per head, the head in its key."""
+        (ops.canonical_heads_pack); one kept image per head, the head in its key.  With a view branch the image is the
+        folded one, and ``colour`` says what its colour rows are for: 'fixed' = read as they are (vertex colours, a bake
+        outside forward) -- needs fixed_view's direction, none is used silently; 'ray' = a per-ray bias follows in K4
+        (forward); None = not read at all (density only).  The last two share one image."""
         h = self._head if self.head_num else None
         if self.head_num and h is None:
             raise RuntimeError('multi-head canonical MLP (%d heads): call select_head(h) before evaluating it outside '
                                'forward (no head is used silently)' % self.head_num)
-        lin = self.cnl_mlp.module.linears()
-        ws, bs = [l.weight for l in lin], [l.bias for l in lin]
-        mode, name = self._mlp_mode(), ('pack', h)
+        view = None
+        if self.view_bands and colour == 'fixed':
+            if self._view is None:
+                raise RuntimeError('view-dependent colour: call fixed_view(direction) before evaluating colour without a '
+                                   'ray (no direction is used silently)')
+            view = self._view
+        ws = self._cnl_params()
+        mode, name = self._mlp_mode(), ('pack', h) + ((view,) if self.view_bands else ())
         ent = self._kept.get(name)
-        if ent is None or not ent.built_from((mode, h), self._weights_gen, ws + bs):
-            W, B = [w.detach() for w in ws], [b.detach() for b in bs]
+        if ent is None or not ent.built_from((mode, h), self._weights_gen, ws):
+            W, B = self._cnl_layers(colour)
             buf = None if ent is None else ent.packed                   # (a stale image's buffer is packed into again)
             if h is not None and h < 0:
                 packed = ops.canonical_heads_pack(W, B, self.head_num, mode, out=buf)
@@ -686,7 +827,7 @@ class Network(nn.Module):
                     W[8], B[8] = W[8][4 * h:4 * h + 4], B[8][4 * h:4 * h + 4]    # (whole rows: contiguous views)
                 packed = ops.canonical_pack(W, B, mode, out=buf)
             self._pack_serial += 1                                      # (every pack takes the next serial)
-            ent = self._kept[name] = Kept((mode, h), self._weights_gen, ws + bs, packed=packed, serial=self._pack_serial)
+            ent = self._kept[name] = Kept((mode, h), self._weights_gen, ws, packed=packed, serial=self._pack_serial)
         self._pack_last = name                                          # (_guard_plan: the serial of the image used last)
         return ent.packed
 
@@ -792,7 +933,7 @@ class Network(nn.Module):
             vol = self.grad_sync.volume_hook(vol, priors)
         nr_packed, cnl_packed = None, None
         if not train_path:
-            cnl_packed = self._canonical_packed()
+            cnl_packed = self._canonical_packed('ray')
             if not ignore_nr and not nr_from_grid:
                 nr_packed = self._nonrigid_packed(cond)
 
@@ -812,6 +953,27 @@ class Network(nn.Module):
         bg = f32(bgcolor).contiguous()
         diag = bool(amd_option('diagnostics', True))
         term_eps = float(amd_option('term_eps', 0.0))
+        view_bias = view_train = None
+        if self.view_bands:
+            # view-dependent colour: every sample of a ray shares the ray's direction (network.py:499-507), so the branch
+            # leaves three floats per ray, computed once per frame here and added to the raw colour in K4
+            camera_only = bool(cfg.canonical_mlp.get('view_dir_camera_only', False))
+            if camera_only and len(rays) < 3:
+                raise ValueError('canonical_mlp.view_dir_camera_only = True needs the camera directions as the third row '
+                                 'of rays (rays_d_camera), got %d rows' % len(rays))
+            if term_eps > 0.0 and not train_path:
+                raise NotImplementedError('cfg.amd.term_eps > 0 with view-dependent colour (canonical_mlp.view_dir): the '
+                                          'slab compositor of early ray termination does not take the per-ray bias')
+            view_dirs = f32(rays[2]).reshape(-1, 3).contiguous() if camera_only else rays_d
+            if view_dirs.shape[0] != N:
+                raise ValueError('rays: %d directions for the view branch, %d rays' % (view_dirs.shape[0], N))
+            if train_path:
+                # the fold in fp32 under autograd, once per step: torch carries the gradient back to the four layers
+                hw, hb, Bv = fold_view_branch(*self.cnl_mlp.module.view_layers())
+                view_train = (hw, hb, ViewBias.apply(view_dirs, Bv, hb.new_zeros(3)) if N else None)
+            elif N:
+                _, _, Bv, zero3 = self._view_fold()
+                view_bias = ops.view_bias(view_dirs, Bv, zero3)
         if N == 0:
             # a camera that does not see the subject's bbox (the reference's chunk loop, network.py:330-352, has nothing
             # to concatenate then and raises; a render loop should get its background image): the 11 keys, empty
@@ -835,7 +997,7 @@ class Network(nn.Module):
         elif train_path:
             # (cfg.amd.train_heads: head h >= 0 trains on the single-head kernels, -1 on the all-heads ones)
             out = self._forward_chunks(per_ray, per_frame, bg, S, mode, diag,
-                                       train=(cond, not ignore_nr, nr_inputs_are_zero))
+                                       train=(cond, not ignore_nr, nr_inputs_are_zero), view=view_train)
             if all_heads:      # the reference's list shapes, like the inference path's
                 out = {k: list(v.unbind(0)) if k in ops.HEAD_KEYS else ([v] * self.head_num if k == 'xyz_on_rays' else v)
                        for k, v in out.items()}
@@ -852,7 +1014,7 @@ class Network(nn.Module):
                     baked_nr, nr_baked_on = self._baked_nr_for_frame(posevec_arg, iter_val, hann_host, baked[1], baked[2])
             if diag or term_eps == 0.0:    # (with diagnostics on, term_eps is ignored: early termination has no 11-output form)
                 out = self._forward_frame(per_ray, per_frame, nr_packed, cnl_packed, bg, S, mode, diag, hann_host,
-                                          baked, baked_nr, nr_baked_on)
+                                          baked, baked_nr, nr_baked_on, view_bias=view_bias)
             else:
                 out = self._forward_chunks(per_ray, per_frame, bg, S, mode, diag, packs=(nr_packed, cnl_packed),
                                            term_eps=term_eps)
@@ -871,13 +1033,13 @@ class Network(nn.Module):
         return self.f16_guard.plan(mode, -(-n_rays // int(cfg.chunk)), None if last is None else last.serial)
 
     def _forward_frame(self, per_ray, per_frame, nr_packed, cnl_packed, bg, S, mode, diag, hann_host=None, baked=None,
-                       baked_nr=None, nr_baked_on=None, all_heads=False):
+                       baked_nr=None, nr_baked_on=None, all_heads=False, view_bias=None):
         """Inference, the whole frame in one library call -- chunk loop of network.py:330-352, results straight into
         whole-frame tensors (the reference concatenates per-chunk results: one more pass over 17 KB per ray);
         optionally K1 of the next chunk on a side stream under the MLP kernels of the current one
         (cfg.amd.overlap_warp).  ``all_heads``: every head (hnrf_render_frame_heads_fwd, with the shared evaluation of
         underflowing inputs hnrf_render_frame_heads_shared_fwd) -- the trunks of both MLPs once per chunk, one compositing
-        pass per head."""
+        pass per head.  ``view_bias`` (N, 3): view-dependent colour, on every path (hnrf_render_frame_view_fwd)."""
         gmode, guarded = self._guard_plan(mode, per_ray[0].shape[0])
         cull_eps = 0.0 if diag else float(amd_option('cull_eps', 0.0))
         common = dict(diagnostics=diag, cull_eps=cull_eps, workspace=self._workspace,
@@ -893,16 +1055,18 @@ class Network(nn.Module):
                                                           **common)
         else:
             out, self._workspace = ops.render_frame(*per_ray, *per_frame, nr_packed, cnl_packed, bg, S, int(cfg.chunk),
-                                                    gmode, baked=baked, baked_nr=baked_nr, share_log=share_log, **common)
+                                                    gmode, baked=baked, baked_nr=baked_nr, share_log=share_log,
+                                                    **({} if view_bias is None else {'view_bias': view_bias}), **common)
         self._share_last = share_log[0] if share else None
         if mode == 'f16x3' and guarded != set():
             self.f16_guard.watch(cnl_packed, nr_packed if baked_nr is None else nr_baked_on, mode)
         return out
 
-    def _forward_chunks(self, per_ray, per_frame, bg, S, mode, diag, train=None, packs=None, term_eps=0.0):
+    def _forward_chunks(self, per_ray, per_frame, bg, S, mode, diag, train=None, packs=None, term_eps=0.0, view=None):
         """Per ray chunk (network.py:333): training (``train`` = (cond, use_nonrigid, nr_inputs_are_zero):
         autograd.RenderRays), or the lean inference path with early ray termination (``packs`` = (nr_packed,
-        cnl_packed): hnrf_render_rays_term_fwd, one workspace for every chunk)."""
+        cnl_packed): hnrf_render_rays_term_fwd, one workspace for every chunk).  ``view`` (training with view-dependent
+        colour): (folded head weight, folded head bias, the frame's per-ray bias), the bias cut into the chunks' rows."""
         N, chunk = per_ray[0].shape[0], int(cfg.chunk)
         self._share_last = None
         if train is None:
@@ -915,7 +1079,8 @@ class Network(nn.Module):
         for ci, i in enumerate(range(0, N, chunk)):
             part = [None if t is None else t[i:i + chunk] for t in per_ray]
             if train is not None:
-                chunks.append(self._render_rays_train(*part, *per_frame, train[0], bg, S, train[1], diag, train[2]))
+                chunks.append(self._render_rays_train(*part, *per_frame, train[0], bg, S, train[1], diag, train[2],
+                                                      view=None if view is None else view[:2] + (view[2][i:i + chunk],)))
                 continue
             chunks.append(ops.render_rays_term(*part, *per_frame, *packs, bg, S,
                                                mode if guarded is None or ci in guarded else mode + '+noguard',
@@ -951,16 +1116,22 @@ class Network(nn.Module):
         return F.linear(torch.relu(h), lin[-1].weight, lin[-1].bias)
 
     def _render_rays_train(self, rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale,
-                           hann_w, cond, bg, S, use_nonrigid, diag, nr_inputs_are_zero):
+                           hann_w, cond, bg, S, use_nonrigid, diag, nr_inputs_are_zero, view=None):
         """Differentiable chunk: autograd.RenderRays (activation-saving MLP kernels).  rgb / alpha / depth carry
         gradient (the trainer's loss reads rgb, trainer.py:121); with ``cfg.amd.diagnostics`` the other eight keys of
         the reference's return dict (network.py:776-789) are returned too, detached.  cfg.amd.canonical = 'baked' is
         ignored here: training always evaluates the canonical MLP (the grid has no gradient)."""
         nr = self.non_rigid_mlp.module.linears()
-        cn = self.cnl_mlp.module.linears()
         if hann_w is None:
             hann_w = torch.ones(6, device=rays_o.device)
-        cn_w, cn_b = [l.weight for l in cn], [l.bias for l in cn]
+        if view is not None:
+            # view-dependent colour: the folded head as layer 8 and the chunk's per-ray bias -- no kernel sees the
+            # unfolded branch
+            cn = self.cnl_mlp.module.trunk()
+            cn_w, cn_b = [l.weight for l in cn] + [view[0]], [l.bias for l in cn] + [view[1]]
+        else:
+            cn = self.cnl_mlp.module.linears()
+            cn_w, cn_b = [l.weight for l in cn], [l.bias for l in cn]
         if self.head_num and self._head >= 0:
             # one head of a multi-head MLP (cfg.amd.train_heads): views of its four rows, as select_head packs them --
             # autograd leaves zeros in the other heads' rows, like the reference's slice (mlp_rgb_sigma.py:189-191)
@@ -978,25 +1149,34 @@ class Network(nn.Module):
             use_nonrigid = False
         res = RenderRays.apply(rays_o, rays_d, near, far, t_rand, bbox_min, bbox_scale, hann_w,
                                cond.detach().contiguous(), bg, S, use_nonrigid, diag, const_offset, motion_Rs, motion_Ts, vol,
-                               *params)
+                               *params, *(() if view is None else (view[2],)))
         return dict(zip(RenderRays.OUTPUT_KEYS if diag else RenderRays.OUTPUT_KEYS[:3], res))
 
     # baked canonical grid (no counterpart in the reference; humannerf_amd/baked.py) --------------------------------
     def _cnl_tensors(self):
-        lin = self.cnl_mlp.module.linears()
+        cm = self.cnl_mlp.module
+        lin = cm.trunk() + cm.view_layers() if self.view_bands else cm.linears()
         return [t for l in lin for t in (l.weight, l.bias)]
+
+    def _view_key(self, colour):
+        """What a baked grid's key says about its colour rows: () without a view branch, else (fixed_view's direction,) or
+        (None,) for a grid whose colour waits for the per-ray bias."""
+        return ((self._view if colour == 'fixed' else None),) if self.view_bands else ()
 
     def canonical_weights_hash(self):
         """sha256 of the canonical MLP's weights (baked.weights_hash): what save_grid stores with a grid."""
         from . import baked
         return baked.weights_hash(self._cnl_tensors())
 
-    def bake_canonical(self, cnl_bbox_min_xyz, cnl_bbox_max_xyz=None, resolution=None, cnl_bbox_scale_xyz=None):
+    def bake_canonical(self, cnl_bbox_min_xyz, cnl_bbox_max_xyz=None, resolution=None, cnl_bbox_scale_xyz=None,
+                       colour='fixed'):
         """Tabulate the canonical MLP on a resolution^3 lattice (default cfg.amd.bake_resolution) over
         [cnl_bbox_min_xyz, cnl_bbox_max_xyz] (max absent: min + 2 / cnl_bbox_scale_xyz) with hnrf_bake_canonical, in
         the current mlp_mode, with the f16-range re-run of canonical_density_grid.  Returns the grid (N, N, N, 4)
         float16 on the device and caches it for forward (cfg.amd.canonical = 'baked').  Warns when an output left the
-        f16 range and was saturated.  One host synchronisation (the verdicts): call it once per checkpoint."""
+        f16 range and was saturated.  One host synchronisation (the verdicts): call it once per checkpoint.  With a view
+        branch ``colour`` = 'fixed' bakes fixed_view's direction into the colour (it raises without one); the baked
+        renderer bakes with 'ray': the grid stays a pure function of position and K4 adds the per-ray bias."""
         from . import baked as baked_mod
         with torch.no_grad():
             N = baked_mod.check_resolution(amd_option('bake_resolution', 256) if resolution is None else resolution)
@@ -1007,7 +1187,7 @@ class Network(nn.Module):
             bmax = _vec3(cnl_bbox_max_xyz, dev).clone() if cnl_bbox_max_xyz is not None \
                 else (bmin + 2.0 / _vec3(cnl_bbox_scale_xyz, dev)).contiguous()
             grid, sat = self._canonical_pass(
-                lambda packed, mode: ops.bake_canonical(packed, bmin, bmax, N, mode, want_saturated=True))
+                lambda packed, mode: ops.bake_canonical(packed, bmin, bmax, N, mode, want_saturated=True), colour)
             n_sat = int(sat)
             if n_sat:
                 import warnings
@@ -1015,7 +1195,8 @@ class Network(nn.Module):
                               'the baked render differs from the exact one there' % n_sat)
             self.bake_count += 1
             # key: mode, resolution, selected head.  No input objects remembered: the next frame compares its box by value once
-            self._kept['baked'] = Kept((self._mlp_mode(), N, self._head), self._weights_gen, self._cnl_tensors(),
+            self._kept['baked'] = Kept((self._mlp_mode(), N, self._head) + self._view_key(colour), self._weights_gen,
+                                       self._cnl_tensors(),
                                        grid=grid, bmin=bmin, bmax=bmax)
             return grid
 
@@ -1104,7 +1285,7 @@ class Network(nn.Module):
         b = self._kept.get('baked')
         if b is None or not b.injected:
             box = (bbox_min, bbox_max if bbox_max is not None else bbox_scale)
-            key = (self._mlp_mode(), int(amd_option('bake_resolution', 256)), self._head)
+            key = (self._mlp_mode(), int(amd_option('bake_resolution', 256)), self._head) + self._view_key('ray')
 
             def same_box():
                 bmin = _vec3(bbox_min, b.bmin.device)
@@ -1112,7 +1293,7 @@ class Network(nn.Module):
                 return torch.equal(bmin, b.bmin) and torch.equal(bmax, b.bmax)
 
             if b is None or not (b.built_from(key, self._weights_gen, self._cnl_tensors()) and b.fed_by(box, same_box)):
-                self.bake_canonical(bbox_min, bbox_max, key[1], bbox_scale)
+                self.bake_canonical(bbox_min, bbox_max, key[1], bbox_scale, colour='ray')
                 b = self._kept['baked']
                 b.remember(box)
         return b.grid, b.bmin, b.bmax
@@ -1147,12 +1328,13 @@ class Network(nn.Module):
                 packed, vol, bmin, bmax, scale, int(resolution), mode, want_parts=return_parts))
 
     def vertex_colors(self, verts):
-        """sigmoid(raw[:3]) of the canonical MLP at the vertices (V, 3) -- the activation of _raw2outputs."""
+        """sigmoid(raw[:3]) of the canonical MLP at the vertices (V, 3) -- the activation of _raw2outputs.  With a view
+        branch: seen from fixed_view's direction (it raises without one)."""
         with torch.no_grad():
             verts = verts.to(device=self._mesh_device(), dtype=torch.float32).contiguous()
             if verts.shape[0] == 0:
                 return verts.new_zeros(0, 3)
-            raw = self._canonical_pass(lambda packed, mode: ops.canonical(verts, packed, mode))
+            raw = self._canonical_pass(lambda packed, mode: ops.canonical(verts, packed, mode), 'fixed')
             return torch.sigmoid(raw[:, :3])
 
     def extract_canonical_mesh(self, cnl_bbox_min_xyz, cnl_bbox_max_xyz, motion_weights_priors, resolution=256,
@@ -1174,13 +1356,15 @@ class Network(nn.Module):
         mode = self._mlp_mode()
         if which == 'canonical':
             h = self._head if self.head_num else None
-            lin = self.cnl_mlp.module.linears()
+            # (with a view branch: the folded head, which like every weight of the chain depends on no bias)
+            ws, layers = self._cnl_params(biases=False), lambda: self._cnl_layers()[0]
         else:
             h, lin = None, self.non_rigid_mlp.module.linears()
-        ws, name = [l.weight for l in lin], ('pack_bwd', which, h)
+            ws, layers = [l.weight for l in lin], lambda: [l.weight.detach() for l in lin]
+        name = ('pack_bwd', which, h)
         ent = self._kept.get(name)
         if ent is None or not ent.built_from((mode, h), self._weights_gen, ws):
-            W = [w.detach() for w in ws]
+            W = layers()
             if h is not None:
                 W[8] = W[8][4 * h:4 * h + 4]
             pack = ops.canonical_bwd_pack if which == 'canonical' else ops.nonrigid_bwd_pack

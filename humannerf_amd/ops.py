@@ -197,11 +197,18 @@ def output_shapes(S, B, diagnostics=True):
     return shp
 
 
-def composite(raw, fg_mask, z_vals, rays_d, xyz, bgcolor, diagnostics=True, cull_eps=0.0, out=None):
+def _chk_view_bias(view_bias, R):
+    _chk(view_bias)
+    if tuple(view_bias.shape) != (R, 3):
+        raise _lib.HnrfError(f'view_bias must be ({R}, 3), one colour bias per ray, got {tuple(view_bias.shape)}')
+
+
+def composite(raw, fg_mask, z_vals, rays_d, xyz, bgcolor, diagnostics=True, cull_eps=0.0, out=None, view_bias=None):
     """K4 (network.py:355-388).  Returns dict with rgb/alpha/depth and, when
     ``diagnostics``, weights_on_rays, rgb_on_rays, cnl_xyz, cnl_rgb, cnl_weight.  ``out``: dict of contiguous
-    tensors of those shapes to write into (e.g. row ranges of whole-frame buffers)."""
-    lib = _lib.load()
+    tensors of those shapes to write into (e.g. row ranges of whole-frame buffers).  ``view_bias`` (R, 3): view-dependent
+    colour, added to raw[..., :3] of every sample of the ray in front of the sigmoid (hnrf_composite_view_fwd)."""
+    lib = _lib.load() if view_bias is None else _lib.load_view()
     _chk(raw, fg_mask, z_vals, rays_d, xyz, bgcolor)
     R, S = z_vals.shape
     dev = raw.device
@@ -214,6 +221,14 @@ def composite(raw, fg_mask, z_vals, rays_d, xyz, bgcolor, diagnostics=True, cull
             assert tuple(out[k].shape) == sh, (k, tuple(out[k].shape), sh)
         _chk(*out.values())
     g = out.get
+    if view_bias is not None:
+        _chk_view_bias(view_bias, R)
+        _lib.check(lib.hnrf_composite_view_fwd(_ptr(raw), _ptr(fg_mask), _ptr(z_vals), _ptr(rays_d), _ptr(xyz),
+                                               _ptr(bgcolor), _ptr(view_bias), R, S, float(cull_eps), _ptr(out['rgb']),
+                                               _ptr(out['alpha']), _ptr(out['depth']), _ptr(g('weights_on_rays')),
+                                               _ptr(g('rgb_on_rays')), _ptr(g('cnl_xyz')), _ptr(g('cnl_rgb')),
+                                               _ptr(g('cnl_weight')), _stream()), 'hnrf_composite_view_fwd')
+        return out
     _lib.check(lib.hnrf_composite_fwd(_ptr(raw), _ptr(fg_mask), _ptr(z_vals), _ptr(rays_d), _ptr(xyz),
                                       _ptr(bgcolor), R, S, float(cull_eps), _ptr(out['rgb']), _ptr(out['alpha']),
                                       _ptr(out['depth']), _ptr(g('weights_on_rays')), _ptr(g('rgb_on_rays')),
@@ -329,7 +344,7 @@ def _frame_sync_args(dev, N, chunk, overlap, want_mlp_events):
 
 def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min, bbox_scale, hann_w, nr_packed,
                  cnl_packed, bgcolor, n_samples, chunk, mode='f16x3', diagnostics=True, cull_eps=0.0, workspace=None,
-                 overlap=True, mlp_event_log=None, baked=None, baked_nr=None, share_log=None):
+                 overlap=True, mlp_event_log=None, baked=None, baked_nr=None, share_log=None, view_bias=None):
     """The whole frame in one call (hnrf_render_frame_fwd): all ray chunks through K1..K4, results in whole-frame tensors;
     K1 of the next chunk on a side stream while the MLP kernels of the current one run.  Returns (dict of outputs,
     workspace).  ``mlp_event_log``: list that receives one (start, stop) torch.cuda.Event pair per chunk.  ``baked``:
@@ -339,15 +354,18 @@ def render_frame(rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, b
     (hnrf_render_frame_baked_nr_fwd; xyz_on_rays / offsets are the interpolated values) and ``hann_w`` / ``nr_packed``
     are not used (may be None).  ``share_log``: a list selects hnrf_render_frame_shared_fwd (f16x3, both MLPs, cull_eps == 0;
     the caller has checked that every Hann weight is <= 1) and receives (live_counts, samples): the device int32 tensor
-    of the samples per chunk that went through the MLPs, and the frame's sample count."""
-    lib = _lib.load()
+    of the samples per chunk that went through the MLPs, and the frame's sample count.  ``view_bias`` (N, 3): view-dependent
+    colour, one raw-colour bias per ray added in K4 -- the frame then goes through hnrf_render_frame_view_fwd, the one entry
+    that takes the grids and the shared evaluation as nullable arguments."""
+    lib = _lib.load() if view_bias is None else _lib.load_view()
     _chk_baked_nr(baked, baked_nr)
     share = share_log is not None
     if share and (baked is not None or baked_nr is not None):
         raise _lib.HnrfError('render_frame: shared inputs exist with both MLPs only, not with a baked grid')
     out, workspace, live = _frame_call(lib, (rays_o, rays_d, near, far, t_rand, motion_Rs, motion_Ts, vol, bbox_min,
                                              bbox_scale, hann_w, nr_packed, cnl_packed, bgcolor), n_samples, chunk, mode,
-                                       diagnostics, cull_eps, workspace, overlap, mlp_event_log, baked, baked_nr, share)
+                                       diagnostics, cull_eps, workspace, overlap, mlp_event_log, baked, baked_nr, share,
+                                       view_bias=view_bias)
     if share:
         share_log.append((live, rays_o.shape[0] * int(n_samples)))
     return out, workspace
@@ -357,12 +375,13 @@ HEAD_KEYS = ('rgb', 'alpha', 'depth', 'weights_on_rays', 'rgb_on_rays', 'cnl_xyz
 
 
 def _frame_call(lib, operands, n_samples, chunk, mode, diagnostics, cull_eps, workspace, overlap, mlp_event_log,
-                baked=None, baked_nr=None, share=False, n_heads=None):
+                baked=None, baked_nr=None, share=False, n_heads=None, view_bias=None):
     """The one call of a frame entry, for render_frame and -- ``n_heads`` -- render_frame_heads: the workspace, the
     whole-frame output tensors (with ``n_heads`` one allocation per HEAD_KEYS key, head-major: out[k][h] is a contiguous
     whole-frame tensor), the stream and event arguments, the call, and what the side stream and the event log need
     afterwards.  ``share`` with ``n_heads``: hnrf_render_frame_heads_shared_fwd (``lib`` has its header bound).  Returns
-    (out, workspace, the live counts of ``share`` or None)."""
+    (out, workspace, the live counts of ``share`` or None).  ``view_bias`` (single head): hnrf_render_frame_view_fwd
+    (``lib`` has its header bound), the grids, the bias and the live counts as its nullable arguments."""
     H = n_heads
     N, S, B, G = operands[0].shape[0], int(n_samples), operands[5].shape[0], operands[7].shape[-1]
     dev = operands[0].device
@@ -385,13 +404,19 @@ def _frame_call(lib, operands, n_samples, chunk, mode, diagnostics, cull_eps, wo
     side, ev_arr, mlp_arr, pairs = _frame_sync_args(dev, N, chunk, overlap, mlp_event_log is not None)
     if H:
         fn, name, ptrs = getattr(lib, stem + '_fwd'), stem + '_fwd', list(map(_ptr, args))
+    elif view_bias is not None:
+        _chk_view_bias(view_bias, N)
+        no_grid = [None, 0, None, None]
+        fn, name, ptrs = lib.hnrf_render_frame_view_fwd, 'hnrf_render_frame_view_fwd', list(map(_ptr, args))
+        ptrs[13:13] = (no_grid if baked_nr is None else _baked_args(baked_nr, dev)) + \
+            (no_grid if baked is None else _baked_args(baked, dev)) + [_ptr(view_bias)]
     else:
         fn, name, ptrs = _render_entry(lib, 'frame', args, baked, baked_nr, share)
     live = torch.empty(max(1, -(-N // chunk)), dtype=torch.int32, device=dev) if share else None
     _lib.check(fn(
         *ptrs, _mode_arg(mode), float(cull_eps), N, S, B, G, chunk, *([H] if H else []), _ptr(workspace),
         workspace.numel() * workspace.element_size(), *[ptr(k) for k in output_shapes(S, B)],
-        *([_ptr(live)] if share else []), side.cuda_stream if side is not None else None, ev_arr, mlp_arr, _stream()), name)
+        *([_ptr(live)] if share or view_bias is not None else []), side.cuda_stream if side is not None else None, ev_arr, mlp_arr, _stream()), name)
     if side is not None:
         # the side stream read the inputs and wrote backward_motion_weights / the workspace: keep the allocator from
         # handing those blocks out again before it is done (everything it did is also ordered on the main stream)
@@ -485,17 +510,59 @@ def nonrigid_train(x_skel, hann_w, packed, mode='f32', *, out=None, P=None):
     return _mlp_train(_lib.load(), 'nonrigid', None, x_skel, hann_w, packed, mode, out, P)
 
 
-def composite_bwd(raw, fg_mask, z_vals, rays_d, bgcolor, g_rgb, g_alpha=None, g_depth=None, d_raw_out=None):
-    """K4'.  ``d_raw_out``: a contiguous tensor of raw's size to write d_raw into (one plane of a multi-head d_raw)."""
-    lib = _lib.load()
+def composite_bwd(raw, fg_mask, z_vals, rays_d, bgcolor, g_rgb, g_alpha=None, g_depth=None, d_raw_out=None,
+                  view_bias=None):
+    """K4'.  ``d_raw_out``: a contiguous tensor of raw's size to write d_raw into (one plane of a multi-head d_raw).
+    ``view_bias`` (R, 3): the forward's view-dependent colour bias; then (d_raw, d_mask, d_bias (R, 3)) is returned
+    (hnrf_composite_view_bwd)."""
+    lib = _lib.load() if view_bias is None else _lib.load_view()
     _chk(raw, fg_mask, z_vals, rays_d, bgcolor, g_rgb, g_alpha, g_depth, d_raw_out)
     R, S = z_vals.shape
     assert d_raw_out is None or d_raw_out.numel() == raw.numel()
     d_raw, d_mask = torch.empty_like(raw) if d_raw_out is None else d_raw_out, torch.empty_like(fg_mask)
+    if view_bias is not None:
+        _chk_view_bias(view_bias, R)
+        d_bias = torch.empty_like(view_bias)
+        _lib.check(lib.hnrf_composite_view_bwd(_ptr(raw), _ptr(fg_mask), _ptr(z_vals), _ptr(rays_d), _ptr(bgcolor),
+                                               _ptr(view_bias), _ptr(g_rgb), _ptr(g_alpha), _ptr(g_depth), R, S, _ptr(d_raw),
+                                               _ptr(d_mask), _ptr(d_bias), _stream()), 'hnrf_composite_view_bwd')
+        return d_raw, d_mask, d_bias
     _lib.check(lib.hnrf_composite_bwd(_ptr(raw), _ptr(fg_mask), _ptr(z_vals), _ptr(rays_d), _ptr(bgcolor), _ptr(g_rgb),
                                       _ptr(g_alpha), _ptr(g_depth), R, S, _ptr(d_raw), _ptr(d_mask), _stream()),
                'hnrf_composite_bwd')
     return d_raw, d_mask
+
+
+def view_bias(dirs, B, c):
+    """The per-ray colour bias of view-dependent colour (hnrf_view_bias_fwd): dirs (R, 3) of any length, B (3, 3 + 6 L),
+    c (3,) -> B e(d) + c (R, 3), e the reference's direction embedding of normalize(d)."""
+    lib = _lib.load_view()
+    c = c.reshape(-1)
+    _chk(dirs, B, c)
+    R, L = dirs.shape[0], (B.shape[1] - 3) // 6
+    if dirs.shape != (R, 3) or tuple(B.shape) != (3, 3 + 6 * L) or c.numel() != 3:
+        raise _lib.HnrfError(f'view_bias: dirs (R, 3), B (3, 3 + 6 L), c (3,), got {tuple(dirs.shape)}, {tuple(B.shape)}, '
+                             f'{tuple(c.shape)}')
+    out = torch.empty(R, 3, device=dirs.device)
+    _lib.check(lib.hnrf_view_bias_fwd(_ptr(dirs), _ptr(B), _ptr(c), L, R, _ptr(out), _stream()), 'hnrf_view_bias_fwd')
+    return out
+
+
+def view_bias_bwd(dirs, d_bias, L):
+    """Backward of view_bias with respect to B and c (hnrf_view_bias_bwd, a fixed-order two-stage sum): (dB (3, 3 + 6 L),
+    dc (3,))."""
+    lib = _lib.load_view()
+    _chk(dirs, d_bias)
+    R, L = dirs.shape[0], int(L)
+    assert dirs.shape == (R, 3) and d_bias.shape == (R, 3)
+    need = lib.hnrf_view_bias_bwd_workspace_bytes(R, L)
+    if need == 0:
+        raise _lib.HnrfError(f'view_bias_bwd: L={L} outside 1..10')
+    ws = torch.empty(need // 4 + 64, device=dirs.device)
+    dB, dc = torch.empty(3, 3 + 6 * L, device=dirs.device), torch.empty(3, device=dirs.device)
+    _lib.check(lib.hnrf_view_bias_bwd(_ptr(dirs), _ptr(d_bias), L, R, _ptr(ws), ws.numel() * 4, _ptr(dB), _ptr(dc),
+                                      _stream()), 'hnrf_view_bias_bwd')
+    return dB, dc
 
 
 def pe_bwd(x, g, hann_w, n_bands, include_input, out=None):
@@ -827,12 +894,14 @@ def nonrigid_sparse(x_skel, hann_w, packed, idx, count, mode='f32'):
     return xyz
 
 
-def gen_rays(K, E, bbox_min, bbox_max, H, W, device=None):
+def gen_rays(K, E, bbox_min, bbox_max, H, W, device=None, camera_turn=None):
     """Rays of one camera that cross the bbox, generated on the device in pixel order.
 
     K (3,3), E (4,4) float32 arrays / tensors (intrinsics, world->camera extrinsics), bbox_min / bbox_max (3,).
     Returns dict(rays (3,N,3) = [o, d, d], near (N,1), far (N,1), ray_mask (H*W,) bool) -- the per-frame entries a
-    reference dataset yields (freeview.py:232-242).  One host sync (the ray count sizes the views)."""
+    reference dataset yields (freeview.py:232-242).  One host sync (the ray count sizes the views).  ``camera_turn`` (3,3):
+    the third row is M d instead of d -- the directions under the camera's extrinsics before the body's global transform
+    (dataset.camera_turn; view-dependent colour with view_dir_camera_only)."""
     lib = _lib.load()
     import numpy as np
     device = device or torch.device('cuda', torch.cuda.current_device())
@@ -853,7 +922,11 @@ def gen_rays(K, E, bbox_min, bbox_max, H, W, device=None):
                                  _stream()), 'hnrf_gen_rays')
     N = int(count.item())
     o, d = rays_o[:N], rays_d[:N]
-    return {'rays': torch.stack([o, d, d], 0), 'near': near[:N, None], 'far': far[:N, None], 'ray_mask': mask.bool()}
+    dc = d
+    if camera_turn is not None:
+        dc = d @ torch.as_tensor(np.asarray(camera_turn.cpu() if torch.is_tensor(camera_turn) else camera_turn, dtype=np.float32),
+                                 device=device).t()
+    return {'rays': torch.stack([o, d, dc], 0), 'near': near[:N, None], 'far': far[:N, None], 'ray_mask': mask.bool()}
 
 
 # ------------------------------------------------------------------------------------------------ image pre-processing

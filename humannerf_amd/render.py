@@ -482,7 +482,8 @@ def with_rays(frame, device):
     from . import ops
     return dict(frame, **ops.gen_rays(frame['K'], frame['E'], frame.get('ray_bbox_min_xyz', frame['cnl_bbox_min_xyz']),
                                       frame.get('ray_bbox_max_xyz', frame['cnl_bbox_max_xyz']),
-                                      int(frame['img_height']), int(frame['img_width']), device=device))
+                                      int(frame['img_height']), int(frame['img_width']), device=device,
+                                      camera_turn=frame.get('camera_turn')))
 
 
 class FramePrefetcher:

@@ -77,6 +77,18 @@ def with_density(state, bias_delta=0.0, gain=1.0):
     return out
 
 
+def view_shapes(bands=4, volume_size=32, total_bones=24):
+    """default_shapes of a network with view-dependent colour (canonical_mlp.view_dir, multires_dir = ``bands``): the
+    reference's view branch (mlp_rgb_sigma.py:85-96) in the place of output_linear."""
+    s = {k: v for k, v in default_shapes(volume_size, total_bones).items() if '.output_linear.' not in k}
+    view = {'output_linear_density.0': (1, 256), 'output_linear_rgb_1.0': (256, 256),
+            'output_linear_rgb_2.0': (256, 256 + 3 + 6 * bands), 'output_linear_rgb_2.1': (3, 256)}
+    for name, sh in view.items():
+        s[f'cnl_mlp.module.{name}.weight'] = sh
+        s[f'cnl_mlp.module.{name}.bias'] = (sh[0],)
+    return s
+
+
 def default_shapes(volume_size=32, total_bones=24):
     """Parameter names/shapes of the reference Network in its default config
     (SURVEY.md section 5 key-name contract; Appendix A.4 census = 64 417 381 at 32^3)."""

@@ -814,6 +814,11 @@ int hnrf_image_metrics(const uint8_t* pred, const uint8_t* target, const uint8_t
  * 13; contracts and declarations in hnrf_heads_train.h. */
 #include "hnrf_heads_train.h"
 
+/* ---- view-dependent colour (canonical_mlp.view_dir): the per-ray colour bias the folded view branch leaves, K4 and K4'
+ * with it, and the one frame entry that carries it through every inference path.  Additive to ABI version 13; contracts
+ * and declarations in hnrf_view.h. */
+#include "hnrf_view.h"
+
 #ifdef __cplusplus
 }
 #endif
